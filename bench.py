@@ -21,7 +21,14 @@ launch's HIP-event time measured in this run, against per-clock peaks measured
 by tools/ubench.hip (profiles/ubench.json); "bound" is the ceiling with the
 largest fraction.
 
-Run: python bench.py [--gpus N --steps K --warmup W]
+A plain run does what the headline figure needs and no more: set up, warm up,
+time the steps, hash (and with --dump-outputs DIR write) the last timed frame,
+print the line.  --full adds what takes launches or CPU time of its own: the
+untimed ZRT_FLAG_STATS launch and everything derived from it (roofline, simd,
+accel, order_replays), the REFERENCE-traversal launch of the same frame and the
+one-core CPU baseline (--no-reference-check / --no-cpu-baseline drop those two).
+
+Run: python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR]
      N > 1, one process per GPU: python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
      N > 1, one process for all GPUs (no launcher, WORLD_SIZE unset): python bench.py --gpus N
        - zrt_multi_* over devices 0..N-1: one context per GPU, ncclCommInitAll
@@ -378,6 +385,32 @@ def fail(msg, code=2):
     sys.exit(code)
 
 
+PROGRESS_COUNTERS = ("recursion_depth_hits", "reflections", "background_hits", "pixels_processed",
+                     "samples_processed", "rays_processed")
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, frame, st):
+    """--dump-outputs: what a caller of the timed path receives from its last timed
+    step, as .npy files under `dirname` - frame.npy, the assembled framebuffer
+    (f32 [H, W, 3], row 0 = bottom), and counters.npy, the Progress counters of
+    that step (f64, PROGRESS_COUNTERS order; exact below 2^53).  A frame that
+    would take the files past 64 MB is written as a fixed sample of its values
+    instead (flat indices drawn by numpy's default_rng(0), so two builds sample
+    the same positions).  The scene, camera and RNG seed are fixed by the
+    arguments: the same arguments give the same inputs on every run."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    counters = np.array([st[k] for k in PROGRESS_COUNTERS], dtype=np.float64)
+    a = np.ascontiguousarray(frame, dtype=np.float32)
+    room = DUMP_LIMIT_BYTES - counters.nbytes - 4096  # (4096: the two .npy headers)
+    if a.nbytes > room:
+        idx = np.random.default_rng(0).integers(0, a.size, size=room // 4)
+        a = a.reshape(-1)[idx]
+    np.save(os.path.join(dirname, "frame.npy"), a)
+    np.save(os.path.join(dirname, "counters.npy"), counters)
+
+
 def main_multi(args, devices):
     """--gpus N without a launcher: every GPU driven from this one process through
     zrt_multi_* (per-device contexts, ncclCommInitAll, one ncclGather to
@@ -414,10 +447,16 @@ def main_multi(args, devices):
     for d in distinct:
         torch.cuda.synchronize(d)
     elapsed = time.perf_counter() - t0
-    frame_sha1 = hashlib.sha1(m.frame().tobytes()).hexdigest()
-    _, diag = m.render(scene.camera, z.RenderParams(**{**params.__dict__, "flags": params.flags | z.ZRT_FLAG_STATS}),
-                       copy_out=False)
-    assert diag["rays_processed"] == st["rays_processed"], "diagnostic launch diverged"
+    frame = m.frame()
+    frame_sha1 = hashlib.sha1(frame.tobytes()).hexdigest()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, frame, st)
+    diag = None
+    if args.full:
+        _, diag = m.render(scene.camera,
+                           z.RenderParams(**{**params.__dict__, "flags": params.flags | z.ZRT_FLAG_STATS}),
+                           copy_out=False)
+        assert diag["rays_processed"] == st["rays_processed"], "diagnostic launch diverged"
     m.close()
 
     n = len(devices)
@@ -426,14 +465,16 @@ def main_multi(args, devices):
     n_units = sum(counts) * ((args.spp + chunk - 1) // chunk)
     per_rank = [sum(r[k] for r in rank_ms) / len(rank_ms) for k in range(n)]
     slowest_s = max(per_rank) / 1e3
-    algo = algorithmic_bytes(diag, n_units, diag["pixels_processed"])
-    # the ceilings are priced from PMC passes at N=1 only; here the frame's
-    # algorithmic bytes spread over the ranks against the slowest rank's kernel
-    roof = {"bound": None, "achieved": None, "peak": None, "unit": None, "frac": None, "traffic": None,
-            "reason": "PMC passes are taken at N=1 only", "kernel_s": round(slowest_s, 6),
-            "algorithmic": {"bytes_per_launch": int(algo), "gbs_per_gpu": round(algo / n / slowest_s / 1e9, 1),
-                            "per_ray": {"node_visits": round(diag["node_visits"] / max(1, diag["rays_processed"]), 2),
-                                        "bytes": round(algo / max(1, diag["rays_processed"]), 1)}}}
+    roof = None
+    if diag is not None:
+        algo = algorithmic_bytes(diag, n_units, diag["pixels_processed"])
+        # the ceilings are priced from PMC passes at N=1 only; here the frame's
+        # algorithmic bytes spread over the ranks against the slowest rank's kernel
+        roof = {"bound": None, "achieved": None, "peak": None, "unit": None, "frac": None, "traffic": None,
+                "reason": "PMC passes are taken at N=1 only", "kernel_s": round(slowest_s, 6),
+                "algorithmic": {"bytes_per_launch": int(algo), "gbs_per_gpu": round(algo / n / slowest_s / 1e9, 1),
+                                "per_ray": {"node_visits": round(diag["node_visits"] / max(1, diag["rays_processed"]), 2),
+                                            "bytes": round(algo / max(1, diag["rays_processed"]), 1)}}}
     key = {"scene": args.scene, "width": args.width, "height": args.height, "spp": args.spp,
            "max_depth": args.depth, "traversal": args.traversal, "sample_chunk": chunk}
     ref_hash = n1_frame_hash(key)
@@ -467,7 +508,8 @@ def main_multi(args, devices):
         "samples_per_step": int(st["samples_processed"]),
         "rays_per_sample": round(st["rays_processed"] / max(1, st["samples_processed"]), 4),
         "kernel_ms_slowest_rank": round(max(per_rank), 2),
-        "roofline": roof,
+        "full": bool(args.full),
+        "roofline": roof,  # (--full: it takes a ZRT_FLAG_STATS launch of its own)
         "parity": "bit-exact vs oracle (tests/test_gpu_parity.py); frame vs the committed N=1 frame below",
         "frame_sha1": frame_sha1,
         "frame_sha1_n1": ref_hash,
@@ -477,12 +519,91 @@ def main_multi(args, devices):
         "per_rank_ms": {"kernel": [round(x, 3) for x in per_rank],
                         "gather_assemble": round(sum(gather_ms) / len(gather_ms), 3)},
     }
+    if roof is None:
+        del out["roofline"]
     if len(distinct) < n:
         out["scaling_note"] = (f"{n} ranks share {len(distinct)} GPU(s): value rehearses the N-rank path (launches, "
                                "gather, assemble, frame equality) and is not a scaling figure; the ranks' kernels "
                                "run concurrently on the same CUs, so per_rank_ms.kernel is each rank's share of "
                                "one GPU, not its time alone")
     print(json.dumps(out), flush=True)
+
+
+def stats_report(args, z, fr, st, diag, diag_kernel_ms, avg_kernel_s, chunk, pmc_key, bid, world):
+    """--full, rank 0: (roofline, simd) of the timed launch from the untimed
+    ZRT_FLAG_STATS launch of the same frame (`diag`: its zrt_stats; its debug
+    counters are still in the context) and the committed PMC entry of this config
+    and build, if there is one."""
+    n_units = fr.counts[0] * ((args.spp + chunk - 1) // chunk)
+    algo = algorithmic_bytes(diag, n_units, diag["pixels_processed"])
+    if world == 1:
+        pe, why = pmc_entry(pmc_key, bid)
+    else:
+        pe, why = None, "PMC passes are taken at N=1 only"
+    if bid.split("-")[0] != z.build_id_of_sources():
+        pe, why = None, f"libzrt.so ({bid}) is stale against its sources ({z.build_id_of_sources()})"
+    dc = fr.ctx.debug_counters(48)  # the STATS launch's counters (shapes, SIMD efficiency, writes)
+    roof = roofline(pe, avg_kernel_s, algo, diag, why, model_in=(dc, n_units))
+    # what the render launch writes to memory (DESIGN.md section 4): each work unit's
+    # 64 chunk sums (float4), the attenuation rows past the LDS ones (float4; STATS
+    # counter kAttWrites of the diagnostic launch) and, on deep trees, the traversal
+    # stack entries past the LDS rows (u32; kStackOvfWrites)
+    wb = {"chunk_sums_B": 16 * 64 * n_units, "att_rows_B": 4 * int(dc[28]),  # 4-B att codes
+          "stack_rows_B": 4 * int(dc[30])}  # FAST stack entries past the LDS rows (kStackOvfWrites)
+    wb["payload_B"] = wb["chunk_sums_B"] + wb["att_rows_B"] + wb["stack_rows_B"]
+    # what memory sees: a chunk-sum store is 1 KiB of whole lines; a row or stack
+    # store is 4 B, and where the wave's lanes store to unrelated paths (every loop
+    # but lockstep, whose lanes push the same row together) each is written back as
+    # a 32-B sector of its own (L2 keeps no line long enough to merge a path's pushes
+    # under the C5 fetch stream: profiles/r04/r04o, path-major rows)
+    loop_id = int(st.get("sampling_loop", -1))
+    granule = 4 if loop_id == 3 else 32
+    wb["row_store_granule_B"] = granule
+    wb["predicted_B"] = wb["chunk_sums_B"] + (granule // 4) * (wb["att_rows_B"] + wb["stack_rows_B"])
+    if pe and pe.get("write_size_kb"):
+        wb["pmc_write_B"] = int(pe["write_size_kb"] * 1024)
+        wb["predicted_over_pmc"] = round(wb["predicted_B"] / wb["pmc_write_B"], 3)
+        c = pe.get("cache") or {}
+        if c.get("TCC_EA0_WRREQ_sum"):
+            # L2 -> memory write requests: 64-B (whole line) and 32-B (partial) ones;
+            # WRITE_SIZE = 64 x WRREQ_64B + 32 x the rest on gfx950
+            n64 = c.get("TCC_EA0_WRREQ_64B_sum", 0.0)
+            n32 = c["TCC_EA0_WRREQ_sum"] - n64
+            wb["pmc_wrreq_64B"] = int(n64)
+            wb["pmc_wrreq_32B"] = int(n32)
+            wb["pmc_wrreq_bytes"] = int(64 * n64 + 32 * n32)
+    roof["write_budget"] = wb
+    # the STATS launch's vector-load shape counts (data_return_model's inputs), kept in
+    # the line so the model can be recomputed against any PMC entry (tools/dr_model.py)
+    roof["stats_shapes"] = {k: int(dc[i]) for k, i in DC_SHAPES.items()} if len(dc) > 43 else None
+    if pe and pe.get("fetch_size_kb") is not None:
+        # HBM bytes the sampling loop needs, apart from what spilled registers cost:
+        # the measured reads (2 x FETCH_SIZE KiB, MI355X_MICROARCH.md's gfx950
+        # correction) plus the predicted payload writes (chunk sums, global att and
+        # stack rows at the store granule), never the scratch lines of spills
+        useful = 2 * pe["fetch_size_kb"] * 1024 + wb["predicted_B"]
+        roof["useful_hbm"] = {"bytes_per_launch": int(useful),
+                              "gbs": round(useful / avg_kernel_s / 1e9, 1),
+                              "frac": round(useful / avg_kernel_s / (HBM_PEAK_GBS * 1e9), 4),
+                              "note": "2 FETCH_SIZE (PMC) + predicted payload writes; hbm_frac also counts "
+                                      "spill scratch lines written back (WRITE_SIZE)"}
+    # SIMD efficiency of the loop (STATS launch, zrt_ctx_debug_counters slots 4 / 21-23):
+    # lane node visits / (64 x the wave's traversal trips), and the lanes that ran a
+    # rayColor step / (64 x loop iterations that ran one)
+    loops = {0: "list", 1: "binary", 2: "reference", 3: "lockstep", 4: "wavefront", 5: "path pool",
+             6: "list, per-lane items"}
+    # (an A/B variant built before zrt_stats.sampling_loop existed leaves it zero: "unknown", not "list")
+    simd = {"sampling_loop": loops.get(int(st.get("sampling_loop", -1)), "unknown") if bid != "unknown"
+            else "unknown"}
+    if int(dc[21]):
+        simd["traversal_lane_eff"] = round(int(dc[4]) / (64.0 * int(dc[21])), 4)
+    if int(dc[22]):
+        # (the path pool's lanes own two paths each and may shade both in one
+        # loop iteration: there the ratio runs up to 2)
+        simd["shade_lane_eff"] = round(int(dc[23]) / (64.0 * int(dc[22])), 4)
+    roof["kernel"] = f"render_kernel (BVH {args.traversal} traversal)"
+    roof["counters_from"] = f"one untimed ZRT_FLAG_STATS launch (kernel {diag_kernel_ms:.1f} ms)"
+    return roof, simd
 
 
 def main():
@@ -497,11 +618,16 @@ def main():
     ap.add_argument("--depth", type=int, default=20)
     ap.add_argument("--chunk", type=int, default=0)
     ap.add_argument("--traversal", choices=["fast", "reference", "binary"], default="fast")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the ZRT_FLAG_STATS launch and the roofline "
+                         "built on it, the REFERENCE-traversal launch of the same frame, the one-core CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's frame and counters to DIR/frame.npy and DIR/counters.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the one-core CPU baseline")
     ap.add_argument("--guard", action="store_true",
                     help="render with ZRT_FLAG_GUARD (the grazing-triangle guard; the path-pool loop carries it)")
     ap.add_argument("--no-reference-check", action="store_true",
-                    help="skip the untimed REFERENCE-traversal launch of the same frame (N=1 only)")
+                    help="with --full: skip the untimed REFERENCE-traversal launch of the same frame (N=1 only)")
     ap.add_argument("--dist-backend", default="nccl",
                     help="nccl (RCCL, one GPU per rank) or gloo (rehearsal: ranks may share a GPU)")
     ap.add_argument("--device", type=int, default=None, help="GPU index (default: LOCAL_RANK)")
@@ -510,6 +636,8 @@ def main():
     args = ap.parse_args()
     if args.gpus < 1:
         fail("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        fail("--steps must be >= 1 and --warmup >= 0")
     if "WORLD_SIZE" not in os.environ and (args.gpus > 1 or args.devices):
         devices = [int(x) for x in args.devices.split(",")] if args.devices else list(range(args.gpus))
         if len(devices) < 1 or min(devices) < 0:
@@ -573,12 +701,20 @@ def main():
     # (gather_ms holds the timed steps' gathers; None rather than a fake 0 if it has none)
     my_times = [sum(kernel_ms) / len(kernel_ms),
                 sum(fr.gather_ms) / len(fr.gather_ms) if fr.gather_ms else float("nan")]
-    frame_sha1 = hashlib.sha1(fr.image().tobytes()).hexdigest() if rank == 0 else None
-    # Traffic diagnostics (node visits, primitive tests, ...) come from one extra,
-    # untimed launch of the diagnostic kernel flavour: same traversal, same image.
-    diag_kernel_ms = fr.step(z.RenderParams(**{**params.__dict__, "flags": params.flags | z.ZRT_FLAG_STATS}))
-    diag = fr.ctx.stats()
-    assert diag["rays_processed"] == st["rays_processed"], "diagnostic launch diverged"
+    frame_sha1 = None
+    if rank == 0:
+        frame = fr.image()  # the last timed step's frame
+        frame_sha1 = hashlib.sha1(frame.tobytes()).hexdigest()
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, frame, st)
+        del frame
+    diag = None
+    if args.full:
+        # Traffic diagnostics (node visits, primitive tests, ...) come from one extra,
+        # untimed launch of the diagnostic kernel flavour: same traversal, same image.
+        diag_kernel_ms = fr.step(z.RenderParams(**{**params.__dict__, "flags": params.flags | z.ZRT_FLAG_STATS}))
+        diag = fr.ctx.stats()
+        assert diag["rays_processed"] == st["rays_processed"], "diagnostic launch diverged"
     red = "cuda" if args.dist_backend == "nccl" else "cpu"
     rays = torch.tensor([float(st["rays_processed"]), float(st["samples_processed"])], dtype=torch.float64,
                         device=red)
@@ -599,78 +735,9 @@ def main():
         value = total_rays * args.steps / elapsed / 1e6
         avg_kernel_s = sum(kernel_ms) / len(kernel_ms) / 1e3
         chunk = args.chunk or 32  # ZRT_DEFAULT_SAMPLE_CHUNK
-        n_units = fr.counts[rank] * ((args.spp + chunk - 1) // chunk)
-        algo = algorithmic_bytes(diag, n_units, diag["pixels_processed"])
         pmc_key = {"scene": args.scene, "width": args.width, "height": args.height, "spp": args.spp,
                    "max_depth": args.depth, "traversal": args.traversal, "sample_chunk": chunk}
         bid = z.build_id()
-        if world == 1:
-            pe, why = pmc_entry(pmc_key, bid)
-        else:
-            pe, why = None, "PMC passes are taken at N=1 only"
-        if bid.split("-")[0] != z.build_id_of_sources():
-            pe, why = None, f"libzrt.so ({bid}) is stale against its sources ({z.build_id_of_sources()})"
-        dc = fr.ctx.debug_counters(48)  # the STATS launch's counters (shapes, SIMD efficiency, writes)
-        roof = roofline(pe, avg_kernel_s, algo, diag, why, model_in=(dc, n_units))
-        # what the render launch writes to memory: each work unit's
-        # 64 chunk sums (float4), the attenuation rows past the LDS ones (float4; STATS
-        # counter kAttWrites of the diagnostic launch) and, on deep trees, the traversal
-        # stack entries past the LDS rows (u32; kStackOvfWrites)
-        wb = {"chunk_sums_B": 16 * 64 * n_units, "att_rows_B": 4 * int(dc[28]),  # 4-B att codes
-              "stack_rows_B": 4 * int(dc[30])}  # FAST stack entries past the LDS rows (kStackOvfWrites)
-        wb["payload_B"] = wb["chunk_sums_B"] + wb["att_rows_B"] + wb["stack_rows_B"]
-        # what memory sees: a chunk-sum store is 1 KiB of whole lines; a row or stack
-        # store is 4 B, and where the wave's lanes store to unrelated paths (every loop
-        # but lockstep, whose lanes push the same row together) each is written back as
-        # a 32-B sector of its own (L2 keeps no line long enough to merge a path's pushes
-        # under the C5 fetch stream: profiles/r04/r04o, path-major rows)
-        loop_id = int(st.get("sampling_loop", -1))
-        granule = 4 if loop_id == 3 else 32
-        wb["row_store_granule_B"] = granule
-        wb["predicted_B"] = wb["chunk_sums_B"] + (granule // 4) * (wb["att_rows_B"] + wb["stack_rows_B"])
-        if pe and pe.get("write_size_kb"):
-            wb["pmc_write_B"] = int(pe["write_size_kb"] * 1024)
-            wb["predicted_over_pmc"] = round(wb["predicted_B"] / wb["pmc_write_B"], 3)
-            c = pe.get("cache") or {}
-            if c.get("TCC_EA0_WRREQ_sum"):
-                # L2 -> memory write requests: 64-B (whole line) and 32-B (partial) ones;
-                # WRITE_SIZE = 64 x WRREQ_64B + 32 x the rest on gfx950
-                n64 = c.get("TCC_EA0_WRREQ_64B_sum", 0.0)
-                n32 = c["TCC_EA0_WRREQ_sum"] - n64
-                wb["pmc_wrreq_64B"] = int(n64)
-                wb["pmc_wrreq_32B"] = int(n32)
-                wb["pmc_wrreq_bytes"] = int(64 * n64 + 32 * n32)
-        roof["write_budget"] = wb
-        # the STATS launch's vector-load shape counts (data_return_model's inputs), kept in
-        # the line so the model can be recomputed against any PMC entry (tools/dr_model.py)
-        roof["stats_shapes"] = {k: int(dc[i]) for k, i in DC_SHAPES.items()} if len(dc) > 43 else None
-        if pe and pe.get("fetch_size_kb") is not None:
-            # HBM bytes the sampling loop needs, apart from what spilled registers cost:
-            # the measured reads (2 x FETCH_SIZE KiB, MI355X_MICROARCH.md's gfx950
-            # correction) plus the predicted payload writes (chunk sums, global att and
-            # stack rows at the store granule), never the scratch lines of spills
-            useful = 2 * pe["fetch_size_kb"] * 1024 + wb["predicted_B"]
-            roof["useful_hbm"] = {"bytes_per_launch": int(useful),
-                                  "gbs": round(useful / avg_kernel_s / 1e9, 1),
-                                  "frac": round(useful / avg_kernel_s / (HBM_PEAK_GBS * 1e9), 4),
-                                  "note": "2 FETCH_SIZE (PMC) + predicted payload writes; hbm_frac also counts "
-                                          "spill scratch lines written back (WRITE_SIZE)"}
-        # SIMD efficiency of the loop (STATS launch, zrt_ctx_debug_counters slots 4 / 21-23):
-        # lane node visits / (64 x the wave's traversal trips), and the lanes that ran a
-        # rayColor step / (64 x loop iterations that ran one)
-        loops = {0: "list", 1: "binary", 2: "reference", 3: "lockstep", 4: "wavefront", 5: "path pool",
-                 6: "list, per-lane items"}
-        # (an A/B variant built before zrt_stats.sampling_loop existed leaves it zero: "unknown", not "list")
-        simd = {"sampling_loop": loops.get(int(st.get("sampling_loop", -1)), "unknown") if bid != "unknown"
-                else "unknown"}
-        if int(dc[21]):
-            simd["traversal_lane_eff"] = round(int(dc[4]) / (64.0 * int(dc[21])), 4)
-        if int(dc[22]):
-            # (the path pool's lanes own two paths each and may shade both in one
-            # loop iteration: there the ratio runs up to 2)
-            simd["shade_lane_eff"] = round(int(dc[23]) / (64.0 * int(dc[22])), 4)
-        roof["kernel"] = f"render_kernel (BVH {args.traversal} traversal)"
-        roof["counters_from"] = f"one untimed ZRT_FLAG_STATS launch (kernel {diag_kernel_ms:.1f} ms)"
         out = {
             "metric": METRIC,
             "value": round(value, 2),
@@ -696,29 +763,36 @@ def main():
             "samples_per_step": int(total_samples),
             "rays_per_sample": round(total_rays / max(1.0, total_samples), 4),
             "kernel_ms_avg": round(avg_kernel_s * 1e3, 2),
-            "order_replays": diag["order_replays"],
-            "simd": simd,
-            "roofline": roof,
-            "accel": {"reference_bvh_nodes": diag["bvh_nodes"], "reference_bvh_depth": diag["bvh_max_depth"],
-                      "wide_nodes": diag["wide_nodes"], "node_bytes": diag["node_bytes"]},
+            "full": bool(args.full),
+        }
+        if args.full:  # what the ZRT_FLAG_STATS launch counted
+            roof, simd = stats_report(args, z, fr, st, diag, diag_kernel_ms, avg_kernel_s, chunk, pmc_key, bid, world)
+            out.update({
+                "order_replays": diag["order_replays"],
+                "simd": simd,
+                "roofline": roof,
+                "accel": {"reference_bvh_nodes": diag["bvh_nodes"], "reference_bvh_depth": diag["bvh_max_depth"],
+                          "wide_nodes": diag["wide_nodes"], "node_bytes": diag["node_bytes"]}})
+        out.update({
             "parity": "bit-exact vs oracle (tests/test_gpu_parity.py)",
             "frame_sha1": frame_sha1,
             "build_id": bid,
             "abi_version": z.lib().zrt_abi_version(),
             "per_rank_ms": {"kernel": [round(x[0], 3) for x in per_rank],
                             "gather": [round(x[1], 3) if x[1] == x[1] else None for x in per_rank]},
-        }
+        })
         ref_hash = n1_frame_hash(pmc_key)
         out["frame_sha1_n1"] = ref_hash
         out["frame_equal_to_n1"] = (frame_sha1 == ref_hash) if ref_hash else None
-        if world == 1 and args.traversal == "fast" and st["used_bvh"] and not args.no_reference_check:
+        if (args.full and world == 1 and args.traversal == "fast" and st["used_bvh"]
+                and not args.no_reference_check):
             if scene.n_prims <= 100_000:
                 log("[rank 0] reference-traversal launch of the same frame ...")
                 out["reference_traversal"] = reference_check(fr, params, frame_sha1, z)
             else:  # the reference's loose test visits most of a million-triangle tree per ray
                 out["reference_traversal"] = {"skipped": f"{scene.n_prims} primitives: the reference's loose slab "
                                                          "test visits most of the tree per ray (hours per frame)"}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             log("[rank 0] cpu baseline (oracle, 1 core) ...")
             out["cpu_baseline"] = cpu_baseline(scene, args.scene, args.depth)
         print(json.dumps(out), flush=True)

@@ -56,3 +56,34 @@ def test_rehearsal_devices_need_a_gpu():
 def test_bad_device_list_refused():
     r = run_bench(["--devices", "0,-1"])
     assert r.returncode == 2 and "non-negative" in r.stderr
+
+
+def test_zero_steps_refused():
+    r = run_bench(["--steps", "0"])
+    assert r.returncode == 2 and "--steps" in r.stderr
+
+
+def test_dump_outputs_files(tmp_path, monkeypatch):
+    """--dump-outputs: the frame as f32 and the Progress counters as f64; a frame past
+    the size limit is written as the same seeded sample of its values every time."""
+    import numpy as np
+    sys.path.insert(0, REPO)
+    import bench
+    st = {k: 3_000_000_000 + i for i, k in enumerate(bench.PROGRESS_COUNTERS)}
+    frame = np.arange(5 * 7 * 3, dtype=np.float32).reshape(5, 7, 3)
+    frame[0, 0, 0] = np.nan
+    bench.dump_outputs(str(tmp_path / "a"), frame, st)
+    got = np.load(tmp_path / "a" / "frame.npy")
+    assert got.dtype == np.float32 and got.shape == frame.shape
+    assert got.tobytes() == frame.tobytes()
+    c = np.load(tmp_path / "a" / "counters.npy")
+    assert c.dtype == np.float64 and [int(x) for x in c] == [st[k] for k in bench.PROGRESS_COUNTERS]
+    # past the limit: a fixed sample of the values, within the limit, the same on every run
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 4096 + 48 + 64)
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), frame, st)
+    b, c = np.load(tmp_path / "b" / "frame.npy"), np.load(tmp_path / "c" / "frame.npy")
+    assert b.dtype == np.float32 and b.shape == (16,) and b.tobytes() == c.tobytes()
+    flat = frame.reshape(-1)
+    assert all(np.isnan(x) or x in flat for x in b)
+    assert sum(os.path.getsize(tmp_path / "b" / f) for f in os.listdir(tmp_path / "b")) <= 4096 + 48 + 64

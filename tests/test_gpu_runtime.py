@@ -153,6 +153,61 @@ def test_bench_one_process_rehearsal(scenes):
     assert line["value"] > 0
 
 
+def test_bench_plain_run_dumps_its_frame(scenes, tmp_path):
+    """A plain bench.py run (no --full) times its steps and stops: no STATS launch, so
+    no roofline, reference-traversal or CPU-baseline fields; --dump-outputs writes the
+    last timed frame and its counters, equal to zrt_render's bit for bit."""
+    import json
+    import subprocess
+    import sys
+    s = scenes(2)
+    one, st1 = z.render(s, s.camera, z.RenderParams(96, 80, 8, 20))
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    r = subprocess.run([sys.executable, os.path.join(os.path.dirname(os.path.dirname(__file__)), "bench.py"),
+                        "--gpus", "1", "--steps", "3", "--warmup", "1", "--width", "96", "--height", "80",
+                        "--spp", "8", "--dump-outputs", str(tmp_path)], env=env, capture_output=True, text=True,
+                       timeout=240)
+    assert r.returncode == 0, r.stderr[-2000:]
+    line = json.loads([x for x in r.stdout.splitlines() if x.startswith("{")][-1])
+    assert line["steps"] == 3 and r.stderr.count("/3: kernel ") == 3
+    assert line["ms_per_step"] > 0 and line["value"] > 0 and line["unit"] == "Mrays/s" and line["dtype"] == "f32"
+    assert line["rays_per_step"] == st1["rays_processed"]
+    assert line["full"] is False
+    assert not {"roofline", "simd", "reference_traversal", "cpu_baseline"} & set(line)
+    assert sorted(os.listdir(tmp_path)) == ["counters.npy", "frame.npy"]
+    frame = np.load(tmp_path / "frame.npy")
+    assert frame.dtype == np.float32 and same_bits(frame, one)
+    counters = np.load(tmp_path / "counters.npy")
+    order = ("recursion_depth_hits", "reflections", "background_hits", "pixels_processed", "samples_processed",
+             "rays_processed")  # bench.PROGRESS_COUNTERS
+    assert counters.dtype == np.float64 and [int(x) for x in counters] == [st1[k] for k in order]
+
+
+def test_bench_full_adds_the_stats_report(scenes):
+    """bench.py --full: the same line plus what the untimed ZRT_FLAG_STATS launch
+    counted (roofline with its algorithmic bytes, simd, accel) and the REFERENCE-
+    traversal frame, equal to FAST's (the CPU baseline, ~15 s of one core, left out)."""
+    import json
+    import subprocess
+    import sys
+    s = scenes(2)
+    _, st1 = z.render(s, s.camera, z.RenderParams(96, 80, 8, 20))
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    r = subprocess.run([sys.executable, os.path.join(os.path.dirname(os.path.dirname(__file__)), "bench.py"),
+                        "--gpus", "1", "--steps", "1", "--warmup", "0", "--width", "96", "--height", "80",
+                        "--spp", "8", "--full", "--no-cpu-baseline"], env=env, capture_output=True, text=True,
+                       timeout=240)
+    assert r.returncode == 0, r.stderr[-2000:]
+    line = json.loads([x for x in r.stdout.splitlines() if x.startswith("{")][-1])
+    assert line["full"] is True and line["rays_per_step"] == st1["rays_processed"]
+    assert line["roofline"]["algorithmic"]["bytes_per_launch"] > 0
+    assert "ZRT_FLAG_STATS" in line["roofline"]["counters_from"]
+    assert line["simd"]["sampling_loop"] != "unknown" and line["accel"]["wide_nodes"] > 0
+    assert line["reference_traversal"]["frame_equal_to_fast"] is True
+    assert line["reference_traversal"]["rays"] == st1["rays_processed"]
+    assert "cpu_baseline" not in line
+
+
 def test_multi_render_surfaces_device_error(scenes, monkeypatch):
     monkeypatch.setenv("ZRT_DEBUG_STACK_CAP", "4")
     s = scenes(3)

@@ -7,7 +7,7 @@ TAG=$1; shift
 R=${GRAFT_REPO_ROOT:-$(pwd)}; O=$R/gpurun_out/$TAG; mkdir -p $O
 export TMPDIR=/tmp
 cd /tmp
-P="$* --steps 1 --warmup 0 --no-cpu-baseline"
+P="$* --steps 1 --warmup 0 --full --no-cpu-baseline"
 i=0
 for grp in "TCP_UTCL1_TRANSLATION_MISS_sum TCP_UTCL1_REQUEST_sum TCP_TOTAL_CACHE_ACCESSES_sum TCP_TCC_READ_REQ_sum" \
            "TCC_HIT_sum TCC_MISS_sum" "TCC_EA0_RDREQ_sum"; do

@@ -11,7 +11,7 @@ for r in $(seq 1 $ROUNDS); do
   i=0
   for e in "${ENVS[@]}"; do
     i=$((i + 1))
-    env $e timeout -k 10 300 python $R/bench.py --no-cpu-baseline "$@" > $OUT/e$i.$r.json 2> $OUT/e$i.$r.err || { echo "env '$e' failed"; tail -5 $OUT/e$i.$r.err; exit 1; }
+    env $e timeout -k 10 300 python $R/bench.py --full --no-cpu-baseline "$@" > $OUT/e$i.$r.json 2> $OUT/e$i.$r.err || { echo "env '$e' failed"; tail -5 $OUT/e$i.$r.err; exit 1; }
     python -c "import json; d=json.load(open('$OUT/e$i.$r.json')); print('$e', $r, d['value'], 'Mrays/s', d['kernel_ms_avg'], 'ms')"
   done
 done

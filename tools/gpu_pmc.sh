@@ -11,7 +11,7 @@ TAG=$1; shift
 R=${GRAFT_REPO_ROOT:-$(pwd)}; O=$R/gpurun_out/$TAG; mkdir -p $O
 export TMPDIR=/tmp
 cd /tmp
-B="$R/bench.py $* --no-cpu-baseline --no-reference-check"
+B="$R/bench.py $* --full --no-cpu-baseline --no-reference-check"
 echo "bench args: $*" > $O/args.txt
 timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -o run -- python $B > $O/bench_traced.json 2> $O/trace.err || { echo "trace pass failed"; tail -3 $O/trace.err; exit 1; }
 i=0

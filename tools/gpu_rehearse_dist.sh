@@ -8,8 +8,8 @@ set -o pipefail
 R=${GRAFT_REPO_ROOT:-$(pwd)}; O=$R/gpurun_out/${1:-dist}; mkdir -p $O
 export MASTER_ADDR=127.0.0.1
 case ${2:-c3} in
-  4k) A="--scene 2 --width 4096 --height 4096 --spp 64 --depth 20 --no-cpu-baseline --no-reference-check" ;;
-  *)  A="--scene 3 --width 1024 --height 1024 --spp 256 --depth 20 --no-cpu-baseline" ;;
+  4k) A="--scene 2 --width 4096 --height 4096 --spp 64 --depth 20 --full --no-cpu-baseline --no-reference-check" ;;
+  *)  A="--scene 3 --width 1024 --height 1024 --spp 256 --depth 20 --full --no-cpu-baseline" ;;
 esac
 # (gloo prints its connection lines to stdout too: the bench line is the last '{' line)
 show() { python -c "import json; d=json.loads([l for l in open('$1') if l.startswith('{')][-1]); print(d['n_gpus'], d['value'], d['frame_sha1'][:12], d['frame_equal_to_n1'], d['per_rank_ms'])"; }

@@ -37,17 +37,17 @@ if [ "$1" == "--no-tests" ]; then shift; else
   tail -3 $O/tests.log; [ $rc -eq 0 ] || exit $rc
 fi
 if [ "$1" == "--no-bench" ]; then shift; else
-  (cd $R && timeout -k 10 600 python bench.py > $O/c4.json 2> $O/c4.err) || { echo "bench failed"; tail -5 $O/c4.err; exit 1; }
+  (cd $R && timeout -k 10 600 python bench.py --full > $O/c4.json 2> $O/c4.err) || { echo "bench failed"; tail -5 $O/c4.err; exit 1; }
   python -c "import json; d=json.load(open('$O/c4.json')); r=d['roofline']; print('C4', d['value'], d['ms_per_step'], r.get('bound'), r.get('frac'), r.get('reason'))"
 fi
 for step in "$@"; do
   IFS=: read -r kind c a3 a4 <<< "$step"
   case $kind in
     pmc) bash $R/tools/gpu_pmc.sh $TAG/pmc_$c $(cfg_args $c) || exit 1 ;;
-    bench) (cd $R && timeout -k 10 900 python bench.py $(cfg_args $c) --no-cpu-baseline > $O/$c.json 2> $O/$c.err) || { echo "bench $c failed"; tail -5 $O/$c.err; exit 1; }
+    bench) (cd $R && timeout -k 10 900 python bench.py --full $(cfg_args $c) --no-cpu-baseline > $O/$c.json 2> $O/$c.err) || { echo "bench $c failed"; tail -5 $O/$c.err; exit 1; }
            python -c "import json; d=json.load(open('$O/$c.json')); print('$c', d['value'], d['ms_per_step'], d['frame_sha1'][:12], d['roofline'].get('bound'), d['roofline'].get('frac'))" ;;
     multi) f=$O/multi_${c}_${a3//,/_}.json
-           (cd $R && timeout -k 10 900 python bench.py $(cfg_args $c) --devices $a3 > $f 2> ${f%.json}.err) || { echo "multi $c $a3 failed"; tail -5 ${f%.json}.err; exit 1; }
+           (cd $R && timeout -k 10 900 python bench.py --full $(cfg_args $c) --devices $a3 > $f 2> ${f%.json}.err) || { echo "multi $c $a3 failed"; tail -5 ${f%.json}.err; exit 1; }
            python -c "import json; d=json.load(open('$f')); print('multi $c $a3', d['value'], d['ms_per_step'], d['frame_equal_to_n1'], d['per_rank_ms'])" ;;
     rehearse) bash $R/tools/gpu_rehearse_dist.sh $TAG/dist_$c $c "${a3//,/ }" || exit 1 ;;
     ab) bash $R/tools/ab.sh $TAG/ab_$c $a3 ${a4//,/ } -- --no-reference-check $(cfg_args $c) || exit 1 ;;
