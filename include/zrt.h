@@ -499,8 +499,9 @@ int zrt_debug_division(uint64_t n, uint64_t* counts, uint32_t device);
  * max depths - is checked region by region (stack rows, top wide nodes, pool
  * queues, lane state, attenuation rows, materials: in the block's LDS, disjoint,
  * float4 regions 16-B aligned; the lockstep loop's plan within its 6-block
- * share).  n_checked: the number of plans checked.  ZRT_E_UNSUPPORTED names the
- * first violation. */
+ * share), the FAST loops' 16-bit plans also with their LDS stack rows capped at
+ * 1, 2 and 4 (as ZRT_STACK_LDS_ROWS16 caps them).  n_checked: the number of plans
+ * checked.  ZRT_E_UNSUPPORTED names the first violation. */
 int zrt_debug_lds_plans(const zrt_scene* scene, uint32_t* n_checked);
 /* Host-side check of the global buffers the launches of a FAST frame share (no
  * device needed): for every sampling loop, stack width, PRNG, node format, a
@@ -511,8 +512,32 @@ int zrt_debug_lds_plans(const zrt_scene* scene, uint32_t* n_checked);
  * instead of a device fault).  legacy = 1 applies the sizing before the round-5
  * fix (the probe shared the render's attenuation rows without growing them):
  * it must fail where a loop keeps more rows in LDS than the probe's 4.
+ * The 16-bit stacks are checked with their LDS rows capped at 1, 2 and 4 too.
  * n_checked: configurations checked. */
 int zrt_debug_buffer_plans(const zrt_scene* scene, uint32_t legacy, uint32_t* n_checked);
+/* The launch decision zrt_ctx_render_tiles would take for this scene and these
+ * params, with no device: the scene is flattened as zrt_ctx_create does, then
+ * the function the render path itself calls decides the sampling loop, the stack
+ * width and the block's LDS plan, under the same environment knobs (ZRT_WF,
+ * ZRT_POOL, ZRT_LIST_LANES, ZRT_QNODES, ZRT_ATT_LDS_ROWS, ZRT_STACK_LDS_ROWS,
+ * ZRT_STACK_LDS_ROWS16, ...).  Only max_depth, traversal, prng, flags and
+ * bounded_volume_hierarchy of the params are read (tests only). */
+typedef struct zrt_launch_plan {
+  uint32_t mode;               /* 0 list, 1 BINARY, 2 REFERENCE, 3 FAST */
+  uint32_t kmode;              /* the kernel's loop: mode, or 4 wavefront, 5 / 7 (guarded) path pool,
+                                  8 / 9 (guarded) path pool over compressed nodes, 6 list with per-lane items */
+  uint32_t sampling_loop;      /* what zrt_stats.sampling_loop reports for it (7, 8, 9 -> 5) */
+  uint32_t stk16;              /* 16-bit stack entries (else 32-bit) */
+  uint32_t wf, pool, qnodes, guard_on;
+  uint32_t stack_depth;        /* stack rows the traversal may use */
+  uint32_t stack_rows;         /* of them in LDS; the rest are global overflow rows */
+  uint32_t att_rows;           /* attenuation rows in LDS */
+  uint32_t att_rows_per_path;  /* global attenuation rows allocated per path (lane) */
+  uint32_t mats_in_lds;        /* the material table has a region in the plan */
+  uint32_t lds_bytes;          /* the block's dynamic LDS */
+  uint64_t ovf_bytes_per_lane; /* global stack overflow rows allocated per lane, in bytes */
+} zrt_launch_plan;
+int zrt_debug_launch_plan(const zrt_scene* scene, const zrt_params* params, zrt_launch_plan* out);
 /* Host-side check of the compressed wide nodes built for this scene (no device
  * needed): every plane of every node's eight octant copies decodes exactly to
  * an f32, every slot's decoded box contains the full node's box of that slot,

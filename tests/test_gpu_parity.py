@@ -443,56 +443,63 @@ def test_texel_stores_bit_exact():
     assert gs["texel_bytes"] == 12  # one f32 image in the scene
 
 
-def _many_materials_scene(n_side=24):
-    """A grid of n_side^2 small spheres over a ground sphere, every one with a material
-    of its own (lambertian / metal / dielectric in turn, each with a color texture):
-    n_side^2 + 1 materials, 48 B each on the device - past the lockstep and list-lane
-    loops' LDS share (~26 KiB per block) at n_side = 24."""
-    from zraytrace_amd import _ffi
-    import ctypes as C
-    n = n_side * n_side + 1
-    rng = np.random.default_rng(5)
-    cols = rng.random((n, 3), dtype=np.float32)
-    texs = (_ffi.Texture * n)(*[_ffi.Texture(_ffi.ZRT_TEX_COLOR, 0, _ffi.Vec3(*map(float, cols[i])), 0.0, 0.0)
-                                for i in range(n)])
-    kinds = (_ffi.ZRT_MAT_LAMBERTIAN, _ffi.ZRT_MAT_METAL, _ffi.ZRT_MAT_DIELECTRIC)
-    mats = (_ffi.Material * n)(*[_ffi.Material(kinds[i % 3], i, 0.3 if kinds[i % 3] == _ffi.ZRT_MAT_METAL
-                                               else 1.5 if kinds[i % 3] == _ffi.ZRT_MAT_DIELECTRIC else 0.0)
-                                 for i in range(n)])
-    prims = (_ffi.Prim * n)()
-    for i in range(n - 1):
-        gx, gy = i % n_side, i // n_side
-        prims[i].kind = _ffi.ZRT_PRIM_SPHERE
-        prims[i].material = i
-        prims[i].center = _ffi.Vec3(-2.3 + 0.2 * gx, -0.35, 2.0 + 0.2 * gy)
-        prims[i].radius = 0.08
-    prims[n - 1].kind = _ffi.ZRT_PRIM_SPHERE
-    prims[n - 1].material = n - 1
-    prims[n - 1].center = _ffi.Vec3(0.0, -100.5, 3.0)
-    prims[n - 1].radius = 100.0
-    scene = _ffi.Scene(prims, n, n, mats, texs, n, 0, C.cast(None, C.POINTER(_ffi.Image)))
-    scene._keep = (prims, mats, texs)
-    return scene
+_MM_ORACLE = {}  # (bvh, max_depth, prng) -> the oracle's frame of the many-materials scene
 
 
-@pytest.mark.parametrize("bvh", [True, False])
-def test_material_table_past_lds_share(bvh):
+def _mm_cases():
+    """(bvh, max_depth, pool, prng); the two cases this test had before it covered the
+    shallow depths (depth 6, default PRNG, no ZRT_POOL) keep their ids, "True" and "False"."""
+    combos = [(b, d, False) for b in (True, False) for d in (0, 1, 2, 6)] + [(True, 1, True), (True, 6, True)]
+    out = []
+    for bvh, depth, pool in combos:
+        for name, prng in (("xoroshiro", z.ZRT_PRNG_XOROSHIRO128), ("xoshiro", z.ZRT_PRNG_XOSHIRO256)):
+            first = depth == 6 and not pool and name == "xoroshiro"
+            out.append(pytest.param(bvh, depth, pool, prng,
+                                    id=str(bvh) if first else f"{bvh}-{depth}-{'pool-' if pool else ''}{name}"))
+    return out
+
+
+@pytest.mark.parametrize("bvh,max_depth,pool,prng", _mm_cases())
+def test_material_table_past_lds_share(bvh, max_depth, pool, prng, monkeypatch):
     """The lockstep and list-lane loops read the material table from LDS only
     (ZRT_MATS_LDS_ONLY); a table past their LDS share renders on the loop that reads
     it from global memory (FAST: the wavefront loop; list: the wave-unit loop), with
-    no tile schedule (its probe is the lockstep loop) - the oracle's frame either way."""
+    no tile schedule (its probe is the lockstep loop) - the oracle's frame either way.
+    At max_depth 0 no loop shades and the wavefront loop (written for max_depth >= 1:
+    it would trace, and its first scatter would write attenuation row 1 of a one-row
+    buffer) must not be chosen: the lockstep loop renders the black frame.  With
+    ZRT_POOL=1 the path pool, which reads the table from global memory too, renders it."""
     import ctypes as C
-    s = _many_materials_scene()
-    cam = z.camera_init((0, 0.6, -1.0), (0, -0.3, 3.0), (0, 1, 0), 50.0, 1.0)
-    p = z.RenderParams(16, 16, 128 if bvh else 4, 6, bounded_volume_hierarchy=bvh)
+    import many_materials as M
+    if pool:
+        monkeypatch.setenv("ZRT_POOL", "1")
+    s = M.many_materials_scene()
+    cam = M.camera()
+    p = z.RenderParams(16, 16, 128 if bvh else 4, max_depth, bounded_volume_hierarchy=bvh, prng=prng)
+    if (bvh, max_depth, prng) not in _MM_ORACLE:
+        _MM_ORACLE[bvh, max_depth, prng] = O.render(C.pointer(s), cam, p)
+    ref, rs = _MM_ORACLE[bvh, max_depth, prng]
+    # (the shallow cases are not vacuous: paths reach the depth limit at every depth rendered)
+    assert rs["recursion_depth_hits"] > 0
+    if max_depth == 0:
+        assert rs["recursion_depth_hits"] == rs["samples_processed"] and rs["rays_processed"] == 0
     gpu, gs = z.render(C.pointer(s), cam, p)
-    ref, rs = O.render(C.pointer(s), cam, p)
     assert_bit_exact(gpu, ref)
     for k in COUNTERS:
         assert gs[k] == rs[k], k
-    assert gs["sampling_loop"] == (4 if bvh else 0)
+    if max_depth == 0:
+        assert not gpu.any() and gs["rays_processed"] == 0
+        assert gs["sampling_loop"] != 4
+        assert gs["sampling_loop"] == (3 if bvh else 0)
+    else:
+        assert gs["sampling_loop"] == ((5 if pool else 4) if bvh else 0)
     if bvh:
         assert gs["schedule_ms"] == 0  # the probe cannot hold the table: tiles in order
+    ps = z.RenderParams(**{**p.__dict__, "flags": z.ZRT_FLAG_STATS})
+    gpu2, gs2 = z.render(C.pointer(s), cam, ps)
+    assert same_bits(gpu, gpu2).all()
+    for k in COUNTERS:
+        assert gs2[k] == rs[k], k
 
 
 def test_eight_bit_texels_selected(scenes):
@@ -616,8 +623,18 @@ def test_trace_mesh_rays_bit_exact(scenes, scene_index, rows, monkeypatch):
     its order-hazard replay (the vertex rays have some) run on the global rows."""
     if rows:
         monkeypatch.setenv("ZRT_STACK_LDS_ROWS", rows)
-    from zraytrace_amd import _ffi
     s = scenes(scene_index)
+    origins, dirs = mesh_rays(s, scene_index)
+    t_ref, p_ref = O.trace(s.view, True, origins, dirs)
+    assert (p_ref >= 0).mean() > 0.3
+    for trav in TRAVERSALS:
+        t, p = z.trace(s, z.RenderParams(1, 1, 1, 1, traversal=trav), origins, dirs)
+        assert_same_hits(t, p, t_ref, p_ref)
+
+
+def mesh_rays(s, scene_index):
+    """test_trace_mesh_rays_bit_exact's rays for a mesh scene: (origins, directions)."""
+    from zraytrace_amd import _ffi
     v = s.view.contents
     pr = prim_array(v)
     tri = pr[pr["kind"] == _ffi.ZRT_PRIM_TRIANGLE]
@@ -641,11 +658,7 @@ def test_trace_mesh_rays_bit_exact(scenes, scene_index, rows, monkeypatch):
     o3 = (verts[kv] - axis * np.float32(0.25)).astype(np.float32)
     origins = np.concatenate([o, o2, o3]).astype(np.float32)
     dirs = np.concatenate([d, targets - o2, axis]).astype(np.float32)
-    t_ref, p_ref = O.trace(s.view, True, origins, dirs)
-    assert (p_ref >= 0).mean() > 0.3
-    for trav in TRAVERSALS:
-        t, p = z.trace(s, z.RenderParams(1, 1, 1, 1, traversal=trav), origins, dirs)
-        assert_same_hits(t, p, t_ref, p_ref)
+    return origins, dirs
 
 
 def prim_array(v):

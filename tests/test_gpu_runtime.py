@@ -456,21 +456,31 @@ def test_scheduled_launch_of_other_loops(scenes, loop, monkeypatch):
         assert st[k] == rs[k], k
 
 
-@pytest.mark.parametrize("loop", ["lockstep", "pool"])
-def test_device_row_bounds_check_reports(scenes, loop, monkeypatch):
+@pytest.mark.parametrize("loop,hook", [("lockstep", "ZRT_STACK_LDS_ROWS"), ("pool", "ZRT_STACK_LDS_ROWS"),
+                                       ("wavefront", "ZRT_STACK_LDS_ROWS16"), ("pool", "ZRT_STACK_LDS_ROWS16")],
+                         ids=["lockstep", "pool", "wavefront-rows16", "pool-rows16"])
+def test_device_row_bounds_check_reports(scenes, loop, hook, monkeypatch):
     """VERDICT r05 next #4, the device half: the STATS flavour checks every global
     attenuation-row and stack-overflow-row index against its buffer (render.hip
     row_ok, KArgs::att_cap / ovf_cap).  Told the buffers hold nothing
     (ZRT_DEBUG_ROW_CAP=0, honoured by STATS launches only; the real buffers stay
     full size, so nothing is read or written out of bounds either way), a depth-20
     frame whose paths push attenuation rows past the LDS ones and whose traversal
-    stack is forced into its global rows (ZRT_STACK_LDS_ROWS=2) must fail with
+    stack is forced into its global rows (ZRT_STACK_LDS_ROWS=2: a 32-bit stack;
+    ZRT_STACK_LDS_ROWS16=2: the 16-bit stack this tree gets, in the wavefront and
+    path-pool loops) must fail with
     the bounds error - not fault, not pass; the same launch without the cap passes
     and equals the timed flavour's frame."""
     s = scenes(3)
     p = z.RenderParams(128, 128, 4, 20, flags=z.ZRT_FLAG_STATS)
     monkeypatch.setenv("ZRT_POOL", "1" if loop == "pool" else "0")
-    monkeypatch.setenv("ZRT_STACK_LDS_ROWS", "2")
+    if loop == "wavefront":
+        monkeypatch.setenv("ZRT_WF", "1")
+    monkeypatch.setenv(hook, "2")
+    plan = z.debug_launch_plan(s, p)
+    assert plan["stk16"] == (1 if hook == "ZRT_STACK_LDS_ROWS16" else 0) and plan["stack_rows"] == 2
+    if hook == "ZRT_STACK_LDS_ROWS16":
+        assert plan["sampling_loop"] == {"wavefront": 4, "pool": 5}[loop]
     img, st = z.render(s, s.camera, p)
     ref, _ = z.render(s, s.camera, z.RenderParams(128, 128, 4, 20))
     assert same_bits(img, ref)

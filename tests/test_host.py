@@ -327,7 +327,9 @@ def test_lds_plans_disjoint(scenes, index):
     # modes 0-2 one loop each, mode 3 lockstep / wavefront / pool (full nodes, and compressed
     # ones where the scene has a tree: their real top levels); x stk16 x prng x depth
     comp = 0 if index == 1 else 1
-    assert n == (1 + 1 + 1 + 1 + 1 + 1 + comp) * 2 * 2 * 6
+    # + the FAST loops' 16-bit plans with their LDS stack rows capped at 1, 2 and 4
+    # (ZRT_STACK_LDS_ROWS16), x prng x depth
+    assert n == (1 + 1 + 1 + 1 + 1 + 1 + comp) * 2 * 2 * 6 + (1 + 1 + 1 + comp) * 3 * 2 * 6
 
 
 @pytest.mark.parametrize("index", [0, 2, 3, 4])
@@ -342,9 +344,153 @@ def test_shared_buffer_sizing_covers_every_launch(scenes, index):
     probe's 4: the wavefront loop's 12 - the round-5 GPU fault of ZRT_WF=1 on C3."""
     s = scenes(index)
     n = z.debug_buffer_plans(s)
-    assert n >= 3 * 2 * 2 * 9 * 3  # lockstep, wavefront, pool (+ compressed) x stk16 x prng x depth x grid
+    # lockstep, wavefront, pool (+ compressed) x stk16 x prng x depth x grid, + the 16-bit
+    # stacks with their LDS rows capped at 1, 2 and 4 (ZRT_STACK_LDS_ROWS16)
+    assert n >= 3 * 2 * 2 * 9 * 3 + 3 * 3 * 2 * 9 * 3
     with pytest.raises(z.ZrtError, match="scheduling probe: needs .* attenuation-row entries.*loop 1"):
         z.debug_buffer_plans(s, legacy=True)
+
+
+TRAVERSALS = (z.ZRT_TRAVERSAL_FAST, z.ZRT_TRAVERSAL_BINARY, z.ZRT_TRAVERSAL_REFERENCE)
+PRNGS = (z.ZRT_PRNG_XOROSHIRO128, z.ZRT_PRNG_XOSHIRO256)
+NEEDS_DEPTH = (4, 5, 7, 8, 9)  # the wavefront and path-pool kernels: written for max_depth >= 1
+LOOP_KNOBS = ("ZRT_WF", "ZRT_POOL", "ZRT_LIST_LANES")
+
+
+def _plan_scene(scenes, which):
+    if which == "many-materials":
+        import many_materials as M
+        s = M.many_materials_scene()
+        return s, C.pointer(s)
+    s = scenes(which)
+    return s, s.view
+
+
+def _check_plan(d, depth, where):
+    """The invariants of one launch decision (zrt_debug_launch_plan)."""
+    assert d["sampling_loop"] == (5 if d["kmode"] in (7, 8, 9) else d["kmode"]), where
+    # 1. a loop whose kernel assumes max_depth >= 1 is chosen only there
+    if d["kmode"] in NEEDS_DEPTH:
+        assert depth >= 1, where
+    # 2. the loops that read the material table from LDS only have it there, or shade nothing
+    if d["kmode"] in (3, 6):
+        assert d["mats_in_lds"] or depth == 0, where
+    # 3. every attenuation row a kernel can index is allocated: rows 0 .. max_depth-2 are
+    #    pushed, the first att_rows of them live in LDS
+    assert d["att_rows_per_path"] >= max(1, depth - 1 - d["att_rows"]), where
+    # 4. the stack rows past the LDS ones are allocated, at the stack's width
+    assert d["stack_rows"] <= max(d["stack_depth"], 1), where
+    ovf_rows = max(0, d["stack_depth"] - d["stack_rows"])
+    assert d["ovf_bytes_per_lane"] >= ovf_rows * (2 if d["stk16"] else 4), where
+    assert d["lds_bytes"] <= 160 << 10, where
+
+
+@pytest.mark.parametrize("which", [0, 1, 2, 3, 4, "many-materials"])
+def test_launch_plan_invariants(scenes, which, monkeypatch):
+    """The launch decision of zrt_ctx_render_tiles (render.hip plan_launch, reported
+    with no device by zrt_debug_launch_plan) over traversal x max_depth x PRNG x the
+    loop knobs (ZRT_WF, ZRT_POOL, ZRT_LIST_LANES: unset, 0, 1) x ZRT_FLAG_GUARD x the
+    16-bit stack-row cap (ZRT_STACK_LDS_ROWS16): the invariants of _check_plan.
+
+    The knobs are crossed in full on the many-materials grid, where the material-table
+    fallback is taken (and which flattens in a millisecond).  The reference scenes
+    flatten in 10 - 40 ms a call: there ZRT_WF x ZRT_POOL are crossed for FAST (the
+    only traversal that reads them) with ZRT_LIST_LANES varied alone - on the seven
+    spheres, a list scene, ZRT_LIST_LANES is crossed and the other two varied alone -
+    and the other traversals run with every knob unset and with every knob set."""
+    keep, view = _plan_scene(scenes, which)
+    vals = (None, "0", "1")
+    unset = dict.fromkeys(LOOP_KNOBS)
+    if which == "many-materials":
+        fast = [dict(zip(LOOP_KNOBS, (a, b, c))) for a in vals for b in vals for c in vals]
+        other = fast
+    elif which == 1:
+        fast = [{**unset, "ZRT_LIST_LANES": c} for c in vals] + [{**unset, "ZRT_WF": "1"}, {**unset, "ZRT_POOL": "1"}]
+        other = [unset, {"ZRT_WF": "1", "ZRT_POOL": "1", "ZRT_LIST_LANES": "0"}]
+    else:
+        fast = [{**unset, "ZRT_WF": a, "ZRT_POOL": b} for a in vals for b in vals]
+        fast += [{**unset, "ZRT_LIST_LANES": c} for c in ("0", "1")]
+        other = [unset, {"ZRT_WF": "1", "ZRT_POOL": "1", "ZRT_LIST_LANES": "0"}]
+    n = 0
+    for trav in TRAVERSALS:
+        for knobs in (fast if trav == z.ZRT_TRAVERSAL_FAST else other):
+            for k, v in knobs.items():
+                monkeypatch.setenv(k, v) if v is not None else monkeypatch.delenv(k, raising=False)
+            for depth in (0, 1, 2, 5, 20):
+                for prng in PRNGS:
+                    for flags in (0, z.ZRT_FLAG_GUARD):
+                        p = z.RenderParams(24, 24, 4, depth, prng=prng, traversal=trav, flags=flags)
+                        where = f"scene {which} traversal {trav} depth {depth} prng {prng} flags {flags} {knobs}"
+                        monkeypatch.delenv("ZRT_STACK_LDS_ROWS16", raising=False)
+                        plain = z.debug_launch_plan(view, p)
+                        _check_plan(plain, depth, where)
+                        monkeypatch.setenv("ZRT_STACK_LDS_ROWS16", "2")
+                        capped = z.debug_launch_plan(view, p)
+                        _check_plan(capped, depth, where + " rows16=2")
+                        # the cap takes the FAST stack's rows out of LDS and never its 16-bit width
+                        assert capped["kmode"] == plain["kmode"] and capped["stk16"] >= plain["stk16"], where
+                        if plain["mode"] == 3:
+                            assert capped["stack_rows"] == min(2, plain["stack_rows"]), where
+                        else:
+                            assert capped["stack_rows"] == plain["stack_rows"], where
+                        if depth == 0:  # nothing shades: ZRT_WF=1 / ZRT_POOL=1 / the guard keep the lockstep loop
+                            assert plain["sampling_loop"] in (0, 1, 2, 3, 6), where
+                        n += 2
+    assert n == (len(fast) + 2 * len(other)) * 5 * 2 * 2 * 2
+
+
+def test_launch_plan_material_table_fallback(monkeypatch):
+    """A material table past the lockstep loop's LDS share (the many-materials grid):
+    FAST falls back to the wavefront loop, which reads the table from global memory -
+    but not at max_depth 0, where the wavefront loop would trace and its first
+    scatter write attenuation row 1 of a one-row buffer.  There the
+    lockstep loop stays, without the table; the list scene falls back to the
+    wave-unit loop at every depth."""
+    import many_materials as M
+    s = M.many_materials_scene()
+    for k in LOOP_KNOBS:
+        monkeypatch.delenv(k, raising=False)
+    for depth, kmode in ((0, 3), (1, 4), (2, 4), (6, 4)):
+        for prng in PRNGS:
+            d = z.debug_launch_plan(C.pointer(s), z.RenderParams(16, 16, 4, depth, prng=prng))
+            assert (d["kmode"], d["mats_in_lds"]) == (kmode, 0), (depth, d)
+            assert d["att_rows_per_path"] >= max(1, depth - 1 - d["att_rows"])
+            d = z.debug_launch_plan(C.pointer(s), z.RenderParams(16, 16, 4, depth, prng=prng,
+                                                                 bounded_volume_hierarchy=False))
+            assert (d["mode"], d["kmode"]) == (0, 0), (depth, d)
+    # a grid whose table fits keeps the lockstep loop with the table in LDS
+    d = z.debug_launch_plan(C.pointer(M.many_materials_scene(M.N_SIDE_LOCKSTEP)), z.RenderParams(16, 16, 4, 6))
+    assert (d["kmode"], d["mats_in_lds"]) == (3, 1), d
+
+
+@pytest.mark.parametrize("index", [2, 3, 4])
+def test_launch_plan_stack_row_hooks(scenes, index, monkeypatch):
+    """ZRT_STACK_LDS_ROWS=<n> caps the FAST stack's LDS rows and forces the 32-bit
+    stack; ZRT_STACK_LDS_ROWS16=<n> caps them the same way and keeps the 16-bit stack
+    these trees (< 65 536 nodes) get, in the lockstep, wavefront and path-pool loops
+    (full and compressed nodes); BINARY / REFERENCE keep their whole stack in LDS."""
+    s = scenes(index)
+    for env in ({"ZRT_WF": "0", "ZRT_POOL": "0"}, {"ZRT_WF": "1", "ZRT_POOL": "0"}, {"ZRT_WF": "0", "ZRT_POOL": "1"},
+                {"ZRT_WF": "0", "ZRT_POOL": "1", "ZRT_QNODES": "1"}):
+        for k, v in env.items():
+            monkeypatch.setenv(k, v)
+        for rows in (1, 2, 4):
+            p = z.RenderParams(24, 16, 4, 8)
+            monkeypatch.setenv("ZRT_STACK_LDS_ROWS16", str(rows))
+            d = z.debug_launch_plan(s, p)
+            assert (d["stk16"], d["stack_rows"]) == (1, rows), (env, rows, d)
+            assert d["qnodes"] == (1 if "ZRT_QNODES" in env else 0)
+            assert d["ovf_bytes_per_lane"] == 2 * (d["stack_depth"] - rows)
+            for trav in (z.ZRT_TRAVERSAL_BINARY, z.ZRT_TRAVERSAL_REFERENCE):
+                b = z.debug_launch_plan(s, z.RenderParams(24, 16, 4, 8, traversal=trav))
+                assert b["stack_rows"] == b["stack_depth"] and b["ovf_bytes_per_lane"] == 0
+            monkeypatch.delenv("ZRT_STACK_LDS_ROWS16")
+            monkeypatch.setenv("ZRT_STACK_LDS_ROWS", str(rows))
+            d = z.debug_launch_plan(s, p)
+            assert (d["stk16"], d["stack_rows"]) == (0, rows), (env, rows, d)
+            assert d["ovf_bytes_per_lane"] == 4 * (d["stack_depth"] - rows)
+            monkeypatch.delenv("ZRT_STACK_LDS_ROWS")
+        monkeypatch.delenv("ZRT_QNODES", raising=False)
 
 
 @pytest.mark.parametrize("index", [0, 2, 3, 4])

@@ -453,6 +453,18 @@ def debug_buffer_plans(scene, legacy: bool = False) -> int:
     return n.value
 
 
+def debug_launch_plan(scene, params) -> dict:
+    """The launch decision a render of this scene with these params would take
+    (zrt_debug_launch_plan; no device), under the environment knobs a real launch
+    reads: the zrt_launch_plan fields as a dict (kmode, stk16, stack_rows,
+    stack_depth, att_rows, att_rows_per_path, mats_in_lds, ...)."""
+    view = scene.view if isinstance(scene, LoadedScene) else scene
+    out = _ffi.LaunchPlan()
+    p = params.abi()
+    check(lib().zrt_debug_launch_plan(view, C.byref(p), C.byref(out)))
+    return out.as_dict()
+
+
 def debug_qnodes(scene) -> int:
     """Host-side check of the scene's compressed wide nodes (zrt_debug_qnodes; no
     device): returns the number of slots checked, raises ZrtError on a violation."""

@@ -112,6 +112,17 @@ class Scanline(C.Structure):
 SCANLINE_FIELDS = [name for name, _ in Scanline._fields_]
 
 
+class LaunchPlan(C.Structure):
+    _fields_ = [("mode", C.c_uint32), ("kmode", C.c_uint32), ("sampling_loop", C.c_uint32),
+                ("stk16", C.c_uint32), ("wf", C.c_uint32), ("pool", C.c_uint32), ("qnodes", C.c_uint32),
+                ("guard_on", C.c_uint32), ("stack_depth", C.c_uint32), ("stack_rows", C.c_uint32),
+                ("att_rows", C.c_uint32), ("att_rows_per_path", C.c_uint32), ("mats_in_lds", C.c_uint32),
+                ("lds_bytes", C.c_uint32), ("ovf_bytes_per_lane", C.c_uint64)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
 class BvhNode(C.Structure):
     _fields_ = [("min", Vec3), ("left", C.c_int32), ("max", Vec3), ("right", C.c_int32)]
 
@@ -179,6 +190,7 @@ SIGNATURES = [
     ("zrt_debug_division", C.c_int, [C.c_uint64, C.POINTER(C.c_uint64), C.c_uint32]),
     ("zrt_debug_lds_plans", C.c_int, [C.POINTER(Scene), C.POINTER(C.c_uint32)]),
     ("zrt_debug_buffer_plans", C.c_int, [C.POINTER(Scene), C.c_uint32, C.POINTER(C.c_uint32)]),
+    ("zrt_debug_launch_plan", C.c_int, [C.POINTER(Scene), C.POINTER(Params), C.POINTER(LaunchPlan)]),
     ("zrt_debug_qnodes", C.c_int, [C.POINTER(Scene), C.POINTER(C.c_uint64)]),
 ]
 

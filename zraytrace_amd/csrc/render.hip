@@ -4653,9 +4653,8 @@ void upload_scene(zrt_ctx* c, const HostScene& h) {
 // little time: C5 +2.6 %, C3 -3 .. +1 %, and on the bunny, whose lockstep
 // camera rays share cache lines, it costs a third.  Default:
 // trees too large for the 16-bit stack (million-triangle meshes, C5).
-bool use_wavefront(const zrt_ctx* c, bool stk16) {
+bool use_wavefront(bool stk16) {
   if (const char* e = std::getenv("ZRT_WF")) return std::atoi(e) != 0;
-  (void)c;
   return !stk16;
 }
 // Per-axis margins (wide_iter) in waves with a lane whose max_k |1/d_k| exceeds
@@ -4669,9 +4668,8 @@ float paxis_threshold() {
 // 16-bit stack), where it is 4 % faster at C5's full size (8.30 -> 8.65 Gray/s,
 // profiles/r03/ab5); on the teapot (C3) and the bunny (C4) the lockstep loop
 // stays ahead (14.7 vs 14.3, 50.5 vs 29.4 Gray/s).
-bool use_pool(const zrt_ctx* c, bool stk16) {
+bool use_pool(bool stk16) {
   if (const char* e = std::getenv("ZRT_POOL")) return std::atoi(e) != 0;
-  (void)c;
   return !stk16;
 }
 // Compressed wide nodes (wide_iter_q, MODE 8 / 9) for this tree?  ZRT_QNODES=1
@@ -4783,12 +4781,27 @@ uint32_t lane_state_words(uint32_t prng) {
   return (prng == ZRT_PRNG_XOSHIRO256 ? LaneState<ZRT_PRNG_XOSHIRO256>::kWords
                                       : LaneState<ZRT_PRNG_XOROSHIRO128>::kWords);
 }
+// tests: a cap on the FAST stack's LDS rows, so that the global overflow rows come
+// into use.  ZRT_STACK_LDS_ROWS=<n> also forces the 32-bit stack (fast_stk16);
+// ZRT_STACK_LDS_ROWS16=<n> caps the rows the same way and leaves the stack's width
+// alone, so a 16-bit stack reads its overflow rows too.
+constexpr uint32_t kNoRowsCap = 0xffffffffu;
+uint32_t stack_rows_cap() {
+  const char* f = std::getenv("ZRT_STACK_LDS_ROWS");
+  if (!f) f = std::getenv("ZRT_STACK_LDS_ROWS16");
+  return f ? uint32_t(std::atoi(f)) : kNoRowsCap;
+}
+// FAST: a 16-bit stack when node indices fit (either width keeps its first rows in
+// LDS and deeper ones in global memory, plan_lds)
+bool fast_stk16(uint32_t n_wide, uint32_t n_nodes) {
+  return n_wide < 65536 && n_nodes < 65536 && !std::getenv("ZRT_STACK_LDS_ROWS");
+}
 // pool: the path-pool loop (MODE 5): its attenuation rows are per path
 // (kBlockPaths per block), and its rays / hits / queues follow them.
 // The lockstep FAST loop (mode 3, neither wf nor pool) also holds its lane state
 // (ZRT_LANE_LDS) and keeps at most ZRT_STACK_ROWS_LOCK stack rows in LDS.
 LdsPlan plan_lds(uint32_t n_top, uint32_t n_mats, int mode, bool stk16, uint32_t stack_depth, uint32_t max_depth,
-                 bool wf, bool pool, uint32_t prng, uint32_t node_f4 = 8) {
+                 bool wf, bool pool, uint32_t prng, uint32_t node_f4 = 8, uint32_t rows_cap = stack_rows_cap()) {
   const uint32_t waves = mode == 3 ? (pool ? ZRT_WAVES_POOL : wf ? ZRT_WAVES_WF : ZRT_WAVES_WIDE)
                          : mode == 0 ? ZRT_WAVES_LIST : ZRT_WAVES_PER_SIMD;
   // 256-thread blocks: `waves` blocks per CU; 1 KiB below the even share (a
@@ -4828,8 +4841,8 @@ LdsPlan plan_lds(uint32_t n_top, uint32_t n_mats, int mode, bool stk16, uint32_t
   } else {
     L.stack_rows = stack_depth;  // BINARY / REFERENCE: the whole stack in LDS (check_plan: within a block's LDS)
   }
-  if (const char* f = std::getenv("ZRT_STACK_LDS_ROWS"))  // tests: force the overflow rows into use
-    if (mode == 3) L.stack_rows = std::max<uint32_t>(1, std::min<uint32_t>(L.stack_rows, uint32_t(std::atoi(f))));
+  if (rows_cap != kNoRowsCap && mode == 3)  // tests: force the overflow rows into use
+    L.stack_rows = std::max<uint32_t>(1, std::min<uint32_t>(L.stack_rows, rows_cap));
   const size_t stack = (size_t(L.stack_rows) * kBlock * entry + 15) & ~size_t(15);
   const size_t used = stack + top + pool_b + state;
   // loops that read the material table from LDS only (ZRT_MATS_LDS_ONLY): the table
@@ -4882,10 +4895,14 @@ struct BufNeed {
   uint64_t att_elems = 0;  // u32 attenuation codes
   uint64_t ovf_bytes = 0;  // stack entries (StackT) past the LDS rows
 };
+// global attenuation rows a path (a lane; the path pool: a path) is given
+uint32_t att_rows_per_path(const LdsPlan& lp, uint32_t max_depth) {
+  return std::max<uint32_t>(1, max_depth - std::min(max_depth, lp.att_rows));
+}
 BufNeed buffer_need(const LdsPlan& lp, uint32_t max_depth, uint32_t stack_depth, uint64_t n_paths, uint64_t n_lanes,
                     bool stk16) {
   BufNeed n;
-  n.att_elems = std::max<uint64_t>(1, max_depth - std::min(max_depth, lp.att_rows)) * n_paths;
+  n.att_elems = uint64_t(att_rows_per_path(lp, max_depth)) * n_paths;
   if (stack_depth > lp.stack_rows)
     n.ovf_bytes = uint64_t(stack_depth - lp.stack_rows) * n_lanes * (stk16 ? sizeof(uint16_t) : sizeof(uint32_t));
   return n;
@@ -4902,6 +4919,115 @@ void check_buffers(const char* launch, const BufNeed& need, uint64_t att_elems, 
 // elements), in the STATS flavour: a row index past its buffer sets kErrBounds and
 // the access is skipped (tests/test_gpu_runtime.py shrinks the capacity it is told)
 uint64_t ovf_cap_elems(uint64_t ovf_bytes, bool stk16) { return ovf_bytes / (stk16 ? 2u : 4u); }
+
+// What the launch decision reads of a scene: a context's copy of it, or (no
+// device: zrt_debug_launch_plan) the flattened scene itself.
+struct SceneShape {
+  bool use_bvh = false, q_ok = false;
+  uint32_t n_nodes = 0, n_wide = 0, wide_stack = 0, stack_depth = 0, n_top = 0, q_top = 0, n_mats = 0;
+  float guard = 0.0f;
+};
+SceneShape shape_of(const zrt_ctx* c) {
+  SceneShape s;
+  s.use_bvh = c->use_bvh;
+  s.q_ok = c->q_ok;
+  s.n_nodes = c->n_nodes;
+  s.n_wide = c->n_wide;
+  s.wide_stack = c->wide_stack;
+  s.stack_depth = c->stack_depth;
+  s.n_top = c->n_top;
+  s.q_top = c->q_top;
+  s.n_mats = c->n_mats;
+  s.guard = c->guard;
+  return s;
+}
+SceneShape shape_of(const HostScene& h) {  // (as upload_scene fills the context)
+  SceneShape s;
+  s.use_bvh = h.use_bvh;
+  s.q_ok = h.q_ok;
+  s.n_nodes = h.n_nodes;
+  s.n_wide = h.n_wide;
+  s.wide_stack = h.wide_stack;
+  s.stack_depth = h.use_bvh ? h.bvh_depth + 2 : 0;
+  s.n_top = h.n_top;
+  s.q_top = h.q_top;
+  s.n_mats = uint32_t(h.mats.size());
+  s.guard = h.guard;
+  return s;
+}
+
+// The launch decision of a render (zrt_ctx_render_tiles; zrt_debug_launch_plan
+// reports it with no device): traversal mode, stack width and depth, sampling
+// loop (kmode: the kernel's MODE), node format and the block's LDS plan.  Pure:
+// it reads the scene's shape, the params and the environment knobs only.
+struct LaunchPlan {
+  int mode = 0;   // 0 list, 1 binary, 2 reference, 3 FAST
+  int kmode = 0;  // the kernel: mode, or 4 wavefront, 5 / 7 / 8 / 9 path pool, 6 list with per-lane items
+  bool stk16 = false, wf = false, pool = false, qn = false, guard_on = false;
+  uint32_t node_f4 = 8, stack_depth = 0;
+  LdsPlan lp;
+};
+// zrt_stats::sampling_loop of a kernel: the path pool's flavours report as the pool
+uint32_t reported_loop(int kmode) { return kmode == 7 || kmode == 8 || kmode == 9 ? 5u : uint32_t(kmode); }
+LaunchPlan plan_launch(const SceneShape& s, const zrt_params* p) {
+  LaunchPlan P;
+  P.mode = !s.use_bvh ? 0 : p->traversal == ZRT_TRAVERSAL_REFERENCE ? 2 : p->traversal == ZRT_TRAVERSAL_BINARY ? 1 : 3;
+  const int mode = P.mode;
+  // (FAST also holds the reference traversal's rows for its order-hazard replay)
+  P.stack_depth = mode == 3 ? std::max(s.wide_stack, s.stack_depth) : s.stack_depth;
+  if (const char* cap = std::getenv("ZRT_DEBUG_STACK_CAP"))  // tests: a stack too small for the tree
+    P.stack_depth = std::max<uint32_t>(4, std::min<uint32_t>(P.stack_depth, uint32_t(std::atoi(cap))));
+  P.stk16 = mode == 3 ? fast_stk16(s.n_wide, s.n_nodes) : s.n_nodes < 65536;
+  // no loop shades at max_depth 0 (every sample ends at the depth limit before it
+  // traces): the lockstep / list loops return black there; the wavefront and
+  // path-pool loops assume max_depth >= 1 and are never chosen
+  const bool shades = p->max_depth >= 1;
+  // FAST: the wavefront loop (MODE 4) where lanes' traversal lengths diverge
+  P.wf = mode == 3 && shades && use_wavefront(P.stk16);
+  // the grazing-triangle guard (ZRT_FLAG_GUARD): carried by the path-pool loop's traversal
+  P.guard_on = mode == 3 && (p->flags & ZRT_FLAG_GUARD) != 0 && s.guard > 0.0f;
+  // the path-pool loop (MODE 5) for the same cases, when asked for; a 16-bit stack
+  // must fit beside its rays and queues in the block's LDS share, else the 32-bit
+  // stack with overflow rows
+  P.pool = mode == 3 && shades && (use_pool(P.stk16) || P.guard_on);
+  // the path pool over compressed nodes (MODE 8 / 9) where the context built them (and
+  // the lockstep loop in the ZRT_LOCK_QN A/B build, which has no other traversal)
+  const bool lock_qn = ZRT_LOCK_QN && mode == 3 && !P.pool && !P.wf;
+  if (lock_qn && !s.q_ok) throw Error(ZRT_E_UNSUPPORTED, "ZRT_LOCK_QN build: no compressed nodes for this tree");
+  P.qn = (P.pool || lock_qn) && s.q_ok;
+  P.node_f4 = P.qn ? kQuantNodeF4 : 8u;
+  const uint32_t n_top = P.qn ? s.q_top : s.n_top;
+  if (P.pool && P.stk16) {
+    const size_t budget = (160u << 10) / ZRT_WAVES_POOL - (1u << 10);
+    const size_t top = ZRT_LDS_TOP ? size_t(n_top) * P.node_f4 * sizeof(float4) * kOctCopies : 0;
+    // (rows the tests' cap keeps out of LDS need not fit it)
+    const uint32_t rows = std::min(P.stack_depth, stack_rows_cap());
+    if (size_t(rows) * kBlock * sizeof(uint16_t) + top + kPoolLdsBytes > budget) P.stk16 = false;
+  }
+  const bool list_lanes = mode == 0 && use_list_lanes();
+  // (the guard's branch costs the path pool 0.7 % on C5, so a guarded render has a
+  // kernel of its own, MODE 7; profiles/r04/r04n)
+  P.kmode = P.pool ? (P.qn ? (P.guard_on ? 9 : 8) : (P.guard_on ? 7 : 5)) : P.wf ? 4 : list_lanes ? 6 : mode;
+  // FAST: deep trees keep their last stack rows in global memory (rarely
+  // touched) so the LDS never caps the occupancy the registers allow; the
+  // other traversals keep the whole stack in LDS (plan_lds)
+  P.lp = plan_lds(n_top, s.n_mats, mode, P.stk16, P.stack_depth, p->max_depth, P.wf, P.pool, p->prng, P.node_f4);
+  if (ZRT_MATS_LDS_ONLY && (P.kmode == 3 || P.kmode == 6) && !P.lp.mats_in_lds) {
+    // a material table past the loop's LDS share: the loop that reads it from global
+    // memory (the wavefront loop for FAST, the wave-unit list loop; same images).
+    // At max_depth 0 the lockstep loop stays (the wavefront loop would trace, and its
+    // first scatter would write attenuation row 1 of a one-row buffer): it reads no
+    // material there, and the launch copies no table into LDS (KArgs::n_mats = 0)
+    if (P.kmode == 6) {
+      P.kmode = 0;
+    } else if (shades) {
+      P.wf = true;
+      P.kmode = 4;
+    }
+    P.lp = plan_lds(n_top, s.n_mats, mode, P.stk16, P.stack_depth, p->max_depth, P.wf, P.pool, p->prng, P.node_f4);
+  }
+  return P;
+}
 
 // Longest-processing-time-first order of this rank's tiles (zrt.h,
 // ZRT_FLAG_NO_SCHEDULE): the probe renders kProbeSpp samples of every tile as
@@ -5244,56 +5370,13 @@ int zrt_ctx_render_tiles(zrt_ctx* c, const zrt_camera* cam, const zrt_params* p,
     hipStream_t st = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
     const zrt::Geometry g = zrt::geometry(p);
     const uint32_t my_tiles = zrt::rank_tiles(g, p->rank, p->world_size);
-    const int mode = !c->use_bvh ? 0
-                     : p->traversal == ZRT_TRAVERSAL_REFERENCE ? 2
-                     : p->traversal == ZRT_TRAVERSAL_BINARY ? 1 : 3;
+    // the launch decision (zrt::plan_launch; zrt_debug_launch_plan reports the same)
+    const zrt::LaunchPlan plan = zrt::plan_launch(zrt::shape_of(c), p);
+    const int mode = plan.mode, kmode = plan.kmode;
     const bool diag = (p->flags & ZRT_FLAG_STATS) != 0;
-    // FAST: a 16-bit stack when node indices fit (either flavour keeps its first
-    // rows in LDS and deeper ones in global memory, zrt::plan_lds)
-    const char* force_rows = std::getenv("ZRT_STACK_LDS_ROWS");  // tests: force the overflow rows into use
-    // (FAST also holds the reference traversal's rows for its order-hazard replay)
-    uint32_t stack_depth = mode == 3 ? std::max(c->wide_stack, c->stack_depth) : c->stack_depth;
-    if (const char* cap = std::getenv("ZRT_DEBUG_STACK_CAP"))  // tests: a stack too small for the tree
-      stack_depth = std::max<uint32_t>(4, std::min<uint32_t>(stack_depth, uint32_t(std::atoi(cap))));
-    bool stk16 = mode == 3 ? c->n_wide < 65536 && c->n_nodes < 65536 && !force_rows : c->n_nodes < 65536;
-    // FAST: the wavefront loop (MODE 4) where lanes' traversal lengths diverge
-    bool wf = mode == 3 && p->max_depth >= 1 && zrt::use_wavefront(c, stk16);
-    // the path-pool loop (MODE 5) for the same cases, when asked for; a 16-bit stack
-    // must fit beside its rays and queues in the block's LDS share, else the 32-bit
-    // stack with overflow rows
-    // the grazing-triangle guard (ZRT_FLAG_GUARD): carried by the path-pool loop's traversal
-    const bool guard_on = mode == 3 && (p->flags & ZRT_FLAG_GUARD) != 0 && c->guard > 0.0f;
-    const bool pool = mode == 3 && p->max_depth >= 1 && (zrt::use_pool(c, stk16) || guard_on);
-    // the path pool over compressed nodes (MODE 8 / 9) where the context built them (and
-    // the lockstep loop in the ZRT_LOCK_QN A/B build, which has no other traversal)
-    const bool lock_qn = ZRT_LOCK_QN && mode == 3 && !pool && !wf;
-    if (lock_qn && !c->q_ok) return fail(ZRT_E_UNSUPPORTED, "ZRT_LOCK_QN build: no compressed nodes for this tree");
-    const bool qn = (pool || lock_qn) && c->q_ok;
-    const uint32_t node_f4 = qn ? zrt::kQuantNodeF4 : 8u;
-    if (pool && stk16) {
-      const size_t budget = (160u << 10) / ZRT_WAVES_POOL - (1u << 10);
-      const size_t top = ZRT_LDS_TOP ? size_t(qn ? c->q_top : c->n_top) * node_f4 * sizeof(float4) * zrt::kOctCopies : 0;
-      if (size_t(stack_depth) * zrt::kBlock * sizeof(uint16_t) + top + zrt::kPoolLdsBytes > budget) stk16 = false;
-    }
-    const bool list_lanes = mode == 0 && zrt::use_list_lanes();
-    // (the guard's branch costs the path pool 0.7 % on C5, so a guarded render has a
-    // kernel of its own, MODE 7; profiles/r04/r04n)
-    int kmode = pool ? (qn ? (guard_on ? 9 : 8) : (guard_on ? 7 : 5)) : wf ? 4 : list_lanes ? 6 : mode;
-    // FAST: deep trees keep their last stack rows in global memory (rarely
-    // touched) so the LDS never caps the occupancy the registers allow; the
-    // other traversals keep the whole stack in LDS (zrt::plan_lds)
-    zrt::LdsPlan lp = zrt::plan_lds(c, mode, stk16, stack_depth, p->max_depth, wf, pool, p->prng, node_f4);
-    if (ZRT_MATS_LDS_ONLY && (kmode == 3 || kmode == 6) && !lp.mats_in_lds) {
-      // a material table past the loop's LDS share: the loop that reads it from global
-      // memory (the wavefront loop for FAST, the wave-unit list loop; same images)
-      if (kmode == 6) {
-        kmode = 0;
-      } else {
-        wf = true;
-        kmode = 4;
-      }
-      lp = zrt::plan_lds(c, mode, stk16, stack_depth, p->max_depth, wf, pool, p->prng, node_f4);
-    }
+    const bool stk16 = plan.stk16, pool = plan.pool, qn = plan.qn, guard_on = plan.guard_on;
+    const uint32_t stack_depth = plan.stack_depth, node_f4 = plan.node_f4;
+    const zrt::LdsPlan& lp = plan.lp;
     void* kfn = zrt::select_kernel(kmode, p->prng, diag, stk16);
     const uint32_t lds_rows = lp.stack_rows;
     const size_t lds = lp.bytes;
@@ -5397,7 +5480,9 @@ int zrt_ctx_render_tiles(zrt_ctx* c, const zrt_camera* cam, const zrt_params* p,
     a.lds_pool_off = lp.pool_off;
     a.lds_state_off = lp.state_off;
     a.n_paths = uint32_t(n_paths);
-    a.n_mats = c->n_mats;
+    // (a loop that reads the table from LDS only and has none there - the lockstep loop
+    // at max_depth 0, which shades nothing - copies none: its plan holds no region for it)
+    a.n_mats = ZRT_MATS_LDS_ONLY && kmode == 3 && !lp.mats_in_lds ? 0u : c->n_mats;
     a.mats_in_lds = lp.mats_in_lds;
     a.seed_mix = p->seed * 0x9E3779B97F4A7C15ULL;
     if (std::getenv("ZRT_DEBUG_LAUNCH"))
@@ -5490,7 +5575,7 @@ int zrt_ctx_render_tiles(zrt_ctx* c, const zrt_camera* cam, const zrt_params* p,
     c->last_xbound = g.xbound;
     c->last_stats = diag;
     c->last_mode = mode;
-    c->last_loop = kmode == 7 || kmode == 8 || kmode == 9 ? 5 : kmode;
+    c->last_loop = int(zrt::reported_loop(kmode));
     c->last_qn = qn;
     c->last_guard = a.guard;
     c->launched = 1;
@@ -5968,9 +6053,8 @@ int zrt_trace(const zrt_scene* scene, const zrt_params* params, const float* ray
     const int mode = !c->use_bvh ? 0
                      : params->traversal == ZRT_TRAVERSAL_REFERENCE ? 2
                      : params->traversal == ZRT_TRAVERSAL_BINARY ? 1 : 3;
-    const char* force_rows = std::getenv("ZRT_STACK_LDS_ROWS");  // tests: force the overflow rows into use
     const uint32_t stack_depth = mode == 3 ? std::max(c->wide_stack, c->stack_depth) : c->stack_depth;
-    const bool stk16 = mode == 3 ? c->n_wide < 65536 && c->n_nodes < 65536 && !force_rows : c->n_nodes < 65536;
+    const bool stk16 = mode == 3 ? zrt::fast_stk16(c->n_wide, c->n_nodes) : c->n_nodes < 65536;
     // FAST over compressed nodes (wide_iter_q, MODE 8) where the context built them
     const bool qn = mode == 3 && c->q_ok;
     const uint32_t node_f4 = qn ? zrt::kQuantNodeF4 : 8u;
@@ -6109,17 +6193,24 @@ int zrt_debug_lds_plans(const zrt_scene* scene, uint32_t* n_checked) {
             for (uint32_t depth : {0u, 1u, 2u, 5u, 20u, 50u}) {
               for (uint32_t nf4 : {8u, 4u}) {  // full / compressed wide nodes (the path pool only)
                 if (nf4 == 4u && (loop != 2 || !h.q_ok)) continue;
-                const uint32_t sd = mode == 3 ? std::max(h.wide_stack, ref_depth) : ref_depth;
-                where = "mode " + std::to_string(mode) + " loop " + std::to_string(loop) + " stk16 " +
-                        std::to_string(int(stk16)) + " prng " + std::to_string(prng) + " depth " +
-                        std::to_string(depth) + " node_f4 " + std::to_string(nf4);
-                try {
-                  (void)zrt::plan_lds(nf4 == 4u ? h.q_top : h.n_top, n_mats, mode, stk16, sd, depth, loop == 1,
-                                      loop == 2, prng, nf4);
-                } catch (const zrt::Error& e) {
-                  throw zrt::Error(e.code, std::string(e.what()) + " (" + where + ")");
+                // the plan as the environment has it, and (FAST, 16-bit stack) with the LDS
+                // rows capped as ZRT_STACK_LDS_ROWS16 caps them
+                for (uint32_t cap : {zrt::stack_rows_cap(), 1u, 2u, 4u}) {
+                  const bool capped = cap != zrt::stack_rows_cap();
+                  if (capped && !(mode == 3 && stk16)) continue;
+                  const uint32_t sd = mode == 3 ? std::max(h.wide_stack, ref_depth) : ref_depth;
+                  where = "mode " + std::to_string(mode) + " loop " + std::to_string(loop) + " stk16 " +
+                          std::to_string(int(stk16)) + " prng " + std::to_string(prng) + " depth " +
+                          std::to_string(depth) + " node_f4 " + std::to_string(nf4) +
+                          (capped ? " stack rows capped at " + std::to_string(cap) : std::string());
+                  try {
+                    (void)zrt::plan_lds(nf4 == 4u ? h.q_top : h.n_top, n_mats, mode, stk16, sd, depth, loop == 1,
+                                        loop == 2, prng, nf4, cap);
+                  } catch (const zrt::Error& e) {
+                    throw zrt::Error(e.code, std::string(e.what()) + " (" + where + ")");
+                  }
+                  ++*n_checked;
                 }
-                ++*n_checked;
               }
             }
           }
@@ -6149,17 +6240,23 @@ int zrt_debug_buffer_plans(const zrt_scene* scene, uint32_t legacy, uint32_t* n_
             for (uint32_t nf4 : {8u, 4u}) {
               if (nf4 == 4u && (loop != 2 || !h.q_ok)) continue;
               for (uint32_t grid : {64u, 1536u, 2048u}) {  // blocks (the probe: at most the render's)
+               // the plans as the environment has them, and (16-bit stack) with the LDS rows
+               // capped as ZRT_STACK_LDS_ROWS16 caps them: more overflow rows for both launches
+               for (uint32_t cap : {zrt::stack_rows_cap(), 1u, 2u, 4u}) {
+                const bool capped = cap != zrt::stack_rows_cap();
+                if (capped && !stk16) continue;
                 const std::string where = "loop " + std::to_string(loop) + " stk16 " + std::to_string(int(stk16)) +
                                           " prng " + std::to_string(prng) + " depth " + std::to_string(depth) +
-                                          " node_f4 " + std::to_string(nf4) + " grid " + std::to_string(grid);
+                                          " node_f4 " + std::to_string(nf4) + " grid " + std::to_string(grid) +
+                                          (capped ? " stack rows capped at " + std::to_string(cap) : std::string());
                 // zrt_render's sizing: the render launch's need, then (schedule_tiles) the
                 // probe's, the buffers grown to the larger of the two
                 const zrt::LdsPlan lp = zrt::plan_lds(nf4 == 4u ? h.q_top : h.n_top, n_mats, 3, stk16, sd, depth,
-                                                      loop == 1, loop == 2, prng, nf4);
+                                                      loop == 1, loop == 2, prng, nf4, cap);
                 const uint64_t n_lanes = uint64_t(grid) * zrt::kBlock;
                 const uint64_t n_paths = loop == 2 ? uint64_t(grid) * zrt::kBlockPaths : n_lanes;
                 const zrt::BufNeed rn = zrt::buffer_need(lp, depth, sd, n_paths, n_lanes, stk16);
-                const zrt::LdsPlan pp = zrt::plan_lds(h.n_top, n_mats, 3, stk16, sd, depth, false, false, prng, 8);
+                const zrt::LdsPlan pp = zrt::plan_lds(h.n_top, n_mats, 3, stk16, sd, depth, false, false, prng, 8, cap);
                 const zrt::BufNeed pn = zrt::buffer_need(pp, depth, sd, n_lanes, n_lanes, stk16);
                 uint64_t att = rn.att_elems, ovf = std::max(rn.ovf_bytes, pn.ovf_bytes);
                 // legacy = 1: the sizing before commit 4072f5f, where the probe shared the
@@ -6172,12 +6269,44 @@ int zrt_debug_buffer_plans(const zrt_scene* scene, uint32_t legacy, uint32_t* n_
                   throw zrt::Error(e.code, std::string(e.what()) + " (" + where + ")");
                 }
                 ++*n_checked;
+               }
               }
             }
           }
         }
       }
     }
+    return ZRT_OK;
+  }
+  ZRT_CATCH_ALL
+}
+
+int zrt_debug_launch_plan(const zrt_scene* scene, const zrt_params* params, zrt_launch_plan* out) {
+  if (!params || !out) return fail(ZRT_E_INVALID, "null argument");
+  std::memset(out, 0, sizeof(*out));
+  int rc = zrt::validate_scene(scene);
+  if (rc) return rc;
+  if (params->traversal > ZRT_TRAVERSAL_BINARY) return fail(ZRT_E_INVALID, "unknown traversal");
+  try {
+    const bool use_bvh = params->bounded_volume_hierarchy != 0 && scene->n_prims > 10;  // (zrt_ctx_create)
+    zrt::HostScene h;
+    zrt::flatten_scene(&h, scene, use_bvh, -1);
+    const zrt::LaunchPlan P = zrt::plan_launch(zrt::shape_of(h), params);
+    out->mode = uint32_t(P.mode);
+    out->kmode = uint32_t(P.kmode);
+    out->sampling_loop = zrt::reported_loop(P.kmode);
+    out->stk16 = P.stk16;
+    out->wf = P.wf;
+    out->pool = P.pool;
+    out->qnodes = P.qn;
+    out->guard_on = P.guard_on;
+    out->stack_depth = P.stack_depth;
+    out->stack_rows = P.lp.stack_rows;
+    out->att_rows = P.lp.att_rows;
+    out->att_rows_per_path = zrt::att_rows_per_path(P.lp, params->max_depth);
+    out->mats_in_lds = P.lp.mats_in_lds;
+    out->lds_bytes = uint32_t(P.lp.bytes);
+    out->ovf_bytes_per_lane = zrt::buffer_need(P.lp, params->max_depth, P.stack_depth, 1, 1, P.stk16).ovf_bytes;
     return ZRT_OK;
   }
   ZRT_CATCH_ALL
