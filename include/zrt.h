@@ -538,6 +538,18 @@ typedef struct zrt_launch_plan {
   uint64_t ovf_bytes_per_lane; /* global stack overflow rows allocated per lane, in bytes */
 } zrt_launch_plan;
 int zrt_debug_launch_plan(const zrt_scene* scene, const zrt_params* params, zrt_launch_plan* out);
+/* Whether zrt_ctx_render_tiles would launch the lean kernel for this scene, camera
+ * and params, with no device (decided by the functions the render path calls).
+ * The lean kernel is the timed lockstep FAST kernel compiled without image
+ * textures, dielectrics, the ray-origin check, the IEEE 1/det fallback and the
+ * scanline rows.  *lean is 1 only when all of this holds: the launch plan's loop is
+ * the lockstep FAST loop with max_depth >= 1 and the material table in LDS; the
+ * scene has no dielectric and no image-textured material and every triangle is under
+ * the fast 1/det bound; ZRT_FLAG_SCANLINES and ZRT_FLAG_STATS are clear; the camera
+ * lies inside the scene's ray-origin bound; the environment does not say ZRT_LEAN=0.
+ * (tests only) */
+int zrt_debug_lean_kernel(const zrt_scene* scene, const zrt_camera* camera, const zrt_params* params,
+                          uint32_t* lean);
 /* Host-side check of the compressed wide nodes built for this scene (no device
  * needed): every plane of every node's eight octant copies decodes exactly to
  * an f32, every slot's decoded box contains the full node's box of that slot,

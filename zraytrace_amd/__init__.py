@@ -465,6 +465,17 @@ def debug_launch_plan(scene, params) -> dict:
     return out.as_dict()
 
 
+def debug_lean_kernel(scene, camera, params) -> bool:
+    """Whether a render of this scene from this camera with these params would launch
+    the lean lockstep kernel (zrt_debug_lean_kernel; no device), under the
+    environment knobs a real launch reads (ZRT_LEAN among them)."""
+    view = scene.view if isinstance(scene, LoadedScene) else scene
+    out = C.c_uint32()
+    p = params.abi()
+    check(lib().zrt_debug_lean_kernel(view, C.byref(camera), C.byref(p), C.byref(out)))
+    return bool(out.value)
+
+
 def debug_qnodes(scene) -> int:
     """Host-side check of the scene's compressed wide nodes (zrt_debug_qnodes; no
     device): returns the number of slots checked, raises ZrtError on a violation."""

@@ -191,6 +191,8 @@ SIGNATURES = [
     ("zrt_debug_lds_plans", C.c_int, [C.POINTER(Scene), C.POINTER(C.c_uint32)]),
     ("zrt_debug_buffer_plans", C.c_int, [C.POINTER(Scene), C.c_uint32, C.POINTER(C.c_uint32)]),
     ("zrt_debug_launch_plan", C.c_int, [C.POINTER(Scene), C.POINTER(Params), C.POINTER(LaunchPlan)]),
+    ("zrt_debug_lean_kernel", C.c_int, [C.POINTER(Scene), C.POINTER(Camera), C.POINTER(Params),
+                                        C.POINTER(C.c_uint32)]),
     ("zrt_debug_qnodes", C.c_int, [C.POINTER(Scene), C.POINTER(C.c_uint64)]),
 ]
 

@@ -247,6 +247,39 @@ constexpr int kBlock = 256;
 #ifndef ZRT_SYNC_SAMPLES
 #define ZRT_SYNC_SAMPLES 1  // the lanes of a wave wait for each other every this many samples
 #endif
+// The lean lockstep kernel (render_kernel<3, PRNG, false, StackT, true>, DESIGN.md §3
+// "The lean kernel"): the timed FAST lockstep loop compiled for a scene of
+// solid-colour Lambertian and metal materials only, whose triangles all pass the
+// tri_rcp_fast bound, rendered from a camera inside the origin bound, without
+// scanline rows (zrt::plan_launch's `lean` and the launch's own check_origins
+// decide on the host; ZRT_LEAN=0 forces the general kernel).  One switch per
+// feature it leaves out, so each can be measured on its own (0: the lean kernel
+// keeps that feature's code, as the general kernel has it):
+#ifndef ZRT_LEAN_TEX
+#define ZRT_LEAN_TEX 1  // no image textures: no (u, v), no texel codes, no texel stores in att_value
+#endif
+#ifndef ZRT_LEAN_DIEL
+#define ZRT_LEAN_DIEL 1  // no dielectric: no refraction branch, no (1, 1, 1) attenuation code
+#endif
+#ifndef ZRT_LEAN_ORIGIN
+#define ZRT_LEAN_ORIGIN 1  // every ray origin inside the bound: ray_origin_ok is true
+#endif
+#ifndef ZRT_LEAN_DET
+#define ZRT_LEAN_DET 0  // 1: no IEEE 1/det behind dev::rcp_core (every triangle is under the tri_rcp_fast
+                        // bound).  Exact, but off: alone it spills 30 VGPRs for 26, and the other four
+                        // without it ran C4 0.4 % faster than all five in every A/B round
+#endif
+#ifndef ZRT_LEAN_EPI
+#define ZRT_LEAN_EPI 1  // no scanline rows and no probe cost at the end of a unit
+#endif
+#ifndef ZRT_LEAN_DEFAULT
+#define ZRT_LEAN_DEFAULT 1  // an eligible launch takes the lean kernel unless ZRT_LEAN=0 (0: only with ZRT_LEAN=1)
+#endif
+template <bool LEAN>
+struct Lean {
+  static constexpr bool tex = LEAN && ZRT_LEAN_TEX, diel = LEAN && ZRT_LEAN_DIEL, origin = LEAN && ZRT_LEAN_ORIGIN,
+                        det = LEAN && ZRT_LEAN_DET, epi = LEAN && ZRT_LEAN_EPI;
+};
 
 // ---------------------------------------------------------------------------
 // RNG: std.rand DefaultPrng restated per (pixel, sample)
@@ -1684,13 +1717,14 @@ __device__ __forceinline__ bool wide_iter(const KArgs& a, const RayT& r, const W
 
 // The end of a FAST traversal: the order hazard of DESIGN.md §3 (1e-8..1e-5
 // of rays) re-traced the reference's way.
-template <bool STATS, class StackT>
+template <bool STATS, class StackT, bool LEAN = false>
 __device__ __forceinline__ void wide_finish(const KArgs& a, const RayT& r, StackT* __restrict__ stk, uint32_t gl,
                                             float& best_t, int& best, uint32_t& c_replays) {
   // an origin farther out than the sphere growth was sized for: the reference's
   // way alone (narrow = false).  One call site for both cases: the replay is
   // inlined, and a second copy cost the lockstep loop 2.8 % on C4 (registers).
-  const bool far = __builtin_expect(!ray_origin_ok(a, r) || ray_degenerate(r), 0);
+  // (the lean kernel is launched only where the host found check_origins 0)
+  const bool far = __builtin_expect((!Lean<LEAN>::origin && !ray_origin_ok(a, r)) || ray_degenerate(r), 0);
   if (__builtin_expect((ZRT_ORDER_EXACT && order_hazard<false>(a, r, best_t, best)) || far, 0)) {
     if (STATS) ++c_replays;
 #if ZRT_REPLAY_OFF
@@ -1984,7 +2018,7 @@ __device__ __forceinline__ void traverse_wide_q(const KArgs& a, const RayT& r, S
   wide_finish<STATS, StackT>(a, r, stk, gl, best_t, best, c_replays);
 }
 
-template <bool STATS, class StackT, bool PAXIS = ZRT_PAXIS_LOCK>
+template <bool STATS, class StackT, bool PAXIS = ZRT_PAXIS_LOCK, bool LEAN = false>
 __device__ __forceinline__ void traverse_wide(const KArgs& a, const RayT& r, StackT* __restrict__ stk,
                                               const float4* __restrict__ lds_top, uint32_t gl, float& best_t,
                                               int& best, uint32_t& c_nodes, uint32_t& c_leaves, uint32_t& c_tri,
@@ -1998,7 +2032,7 @@ __device__ __forceinline__ void traverse_wide(const KArgs& a, const RayT& r, Sta
   while (wide_iter<STATS, StackT, ZRT_SCALAR_NODES, PAXIS, true, ZRT_Q_GLOBAL != 0>(
       a, r, v, stk, gl, w, q, sp, best_t, best, c_nodes, c_leaves, c_tri, c_sph, coh)) {
   }
-  wide_finish<STATS, StackT>(a, r, stk, gl, best_t, best, c_replays);
+  wide_finish<STATS, StackT, LEAN>(a, r, stk, gl, best_t, best, c_replays);
 }
 
 // ---------------------------------------------------------------------------
@@ -2063,15 +2097,18 @@ __device__ __forceinline__ uint32_t image_texel_code(const MatReg& mr, float u, 
 }
 
 // The albedo of a lambertian / metal hit (texture.zig:20-74) as an att code
+template <bool LEAN = false>
 __device__ __forceinline__ uint32_t albedo_code(const MatReg& mr, uint32_t mat, float u, float v) {
-  if (mr.tex_kind() == ZRT_TEX_COLOR) return (1u << 31) | mat;
+  if (Lean<LEAN>::tex || mr.tex_kind() == ZRT_TEX_COLOR) return (1u << 31) | mat;
   return image_texel_code(mr, u, v);
 }
 
-// The attenuation an att code stands for
+// The attenuation an att code stands for (the lean kernel's paths push one class
+// of code only, a material's solid color)
+template <bool LEAN = false>
 __device__ __forceinline__ V3 att_value(const KArgs& a, const DevMaterial* __restrict__ mats, uint32_t code) {
-  if (code == kAttOne) return mk(1.0f, 1.0f, 1.0f);
-  if (code >> 31) {
+  if (!Lean<LEAN>::diel && code == kAttOne) return mk(1.0f, 1.0f, 1.0f);
+  if (Lean<LEAN>::tex || code >> 31) {
     const float4 c = reinterpret_cast<const float4*>(mats + (code & 0x7fffffffu))[0];
     return mk(c.x, c.y, c.z);
   }
@@ -2225,7 +2262,7 @@ __device__ __forceinline__ uint32_t att_row(const KArgs& a, const AttRows& ar, u
 #ifndef ZRT_ATT_PAIRS
 #define ZRT_ATT_PAIRS 1  // att_product decodes two rows at a time (their texel loads in flight together)
 #endif
-template <bool STATS>
+template <bool STATS, bool LEAN = false>
 __device__ __forceinline__ V3 att_product(const KArgs& a, const DevMaterial* __restrict__ mats, const AttRows& ar,
                                           uint32_t n, V3 col, Coh& coh) {
   uint32_t i = n;
@@ -2234,20 +2271,20 @@ __device__ __forceinline__ V3 att_product(const KArgs& a, const DevMaterial* __r
   // the order of the multiplications are the recursion's, as below)
   if (ZRT_ATT_PAIRS) {
     for (; i >= 2; i -= 2) {
-      const V3 hi = att_value(a, mats, att_row<STATS>(a, ar, i - 1, coh));
-      const V3 lo = att_value(a, mats, att_row<STATS>(a, ar, i - 2, coh));
+      const V3 hi = att_value<LEAN>(a, mats, att_row<STATS>(a, ar, i - 1, coh));
+      const V3 lo = att_value<LEAN>(a, mats, att_row<STATS>(a, ar, i - 2, coh));
       col = mk(hi.x * col.x, hi.y * col.y, hi.z * col.z);
       col = mk(lo.x * col.x, lo.y * col.y, lo.z * col.z);
     }
   }
   for (; i-- > 0;) {
-    const V3 at = att_value(a, mats, att_row<STATS>(a, ar, i, coh));
+    const V3 at = att_value<LEAN>(a, mats, att_row<STATS>(a, ar, i, coh));
     col = mk(at.x * col.x, at.y * col.y, at.z * col.z);
   }
   return col;
 }
 
-template <bool STATS, class R>
+template <bool STATS, class R, bool LEAN = false>
 __device__ __forceinline__ void shade_step(const KArgs& a, const DevMaterial* __restrict__ mats,
                                            const AttRows& ar, R& rng, int best, float best_t,
                                            V3& o, V3& d, uint32_t& depth_left, bool& path_end, bool& sky, V3& L,
@@ -2276,7 +2313,7 @@ __device__ __forceinline__ void shade_step(const KArgs& a, const DevMaterial* __
     const uint32_t tag = __float_as_uint(sh.w);
     const MatReg mat = load_material(mats, tag & 0x7fffffffu);
     const uint32_t mkind = mat.kind();
-    const bool need_uv = mkind != ZRT_MAT_DIELECTRIC && mat.tex_kind() == ZRT_TEX_IMAGE;
+    const bool need_uv = !Lean<LEAN>::tex && mkind != ZRT_MAT_DIELECTRIC && mat.tex_kind() == ZRT_TEX_IMAGE;
     if (STATS) {
       ++c_shade;
       c_tex += need_uv ? 1u : 0u;
@@ -2447,10 +2484,10 @@ __device__ __forceinline__ void shade_step(const KArgs& a, const DevMaterial* __
       V3 hv = mk(cs * rr, sn * rr, r1);
       if (!rand_bool(rng)) hv.z = hv.z * -1.0f;
       nd = unit(add(normal, hv));
-      att = albedo_code(mat, tag & 0x7fffffffu, tu, tv);
-    } else if (mkind == ZRT_MAT_METAL) {
+      att = albedo_code<LEAN>(mat, tag & 0x7fffffffu, tu, tv);
+    } else if (Lean<LEAN>::diel || mkind == ZRT_MAT_METAL) {  // (lean: what is not Lambertian is metal)
       nd = unit(reflect(unit(d), normal));
-      if (dot(nd, normal) > 0.0f) att = albedo_code(mat, tag & 0x7fffffffu, tu, tv);
+      if (dot(nd, normal) > 0.0f) att = albedo_code<LEAN>(mat, tag & 0x7fffffffu, tu, tv);
       else absorbed = true;
     } else {
       const float ratio = front ? dev::rcp_rn(mat.ior()) : mat.ior();
@@ -2571,8 +2608,9 @@ __device__ __forceinline__ uint32_t auto_sync(const KArgs& a) {
 #define ZRT_PROBE_STATIC 1
 #endif
 template <int MODE /*0 list, 1 BVH binary, 2 BVH reference, 3 wide (FAST)*/, int PRNG, bool STATS, class StackT,
-          bool PROBE = false>
+          bool PROBE = false, bool LEAN = false /* MODE 3, timed flavour: the lean kernel (ZRT_LEAN_*) */>
 __device__ __forceinline__ void render_loop(const KArgs& a) {
+  static_assert(!LEAN || (MODE == 3 && !STATS && !PROBE), "the lean kernel is the timed lockstep FAST loop's");
   extern __shared__ __attribute__((aligned(16))) char lds_raw[];
   StackT* stk = reinterpret_cast<StackT*>(lds_raw) + threadIdx.x;  // LDS: the traversal stack
   float4* lds_top = reinterpret_cast<float4*>(lds_raw + a.lds_top_off);
@@ -2643,12 +2681,12 @@ __device__ __forceinline__ void render_loop(const KArgs& a) {
       } else {
         if (cur_lt != 0xffffffffu)  // the finished unit's chunk sums, [chunk][pixel slot]: one 1 KiB store per wave
           a.partial[chunk_j * a.n_slots + cur_lt * 64u + (uint32_t)lane] = make_float4(acc_r, acc_g, acc_b, 0.0f);
-        if (a.unit_cost && cur_lt != 0xffffffffu && lane == 0) {
+        if (!Lean<LEAN>::epi && a.unit_cost && cur_lt != 0xffffffffu && lane == 0) {
           a.unit_cost[cur_lt] = iters;
           // (the probe's units are one sample: one of the unit's iterations ran no step)
           atomicAdd(&a.counters[kProbeTrips], (unsigned long long)(iters - 1u));
         }
-        if (a.scanlines && cur_lt != 0xffffffffu) {  // the finished unit's counters, per frame row
+        if (!Lean<LEAN>::epi && a.scanlines && cur_lt != 0xffffffffu) {  // the finished unit's counters, per frame row
           flush_scanline(a.scanlines, y0 + ((uint32_t)lane >> 3), a.height, lane, c_depth, c_refl, c_bg);
           c_depth = c_refl = c_bg = 0;  // (so the launch totals are the rows' sums)
         }
@@ -2715,7 +2753,7 @@ __device__ __forceinline__ void render_loop(const KArgs& a) {
       RayT r;
       r.ox = o.x; r.oy = o.y; r.oz = o.z;
       r.dx = d.x; r.dy = d.y; r.dz = d.z;
-      r.rcp_det = a.tri_rcp_fast;
+      r.rcp_det = Lean<LEAN>::det ? 1u : a.tri_rcp_fast;
       r.gm = a.graze_m;
       r.gl = a.graze_leaf;
       r.gk = a.guard;
@@ -2751,7 +2789,8 @@ __device__ __forceinline__ void render_loop(const KArgs& a) {
           traverse_wide_q<STATS, StackT, true>(a, r, stk, lds_top, gl, best_t, best, c_nodes, c_leaves, c_tri, c_sph,
                                                c_replays, coh);
         else
-          traverse_wide<STATS>(a, r, stk, lds_top, gl, best_t, best, c_nodes, c_leaves, c_tri, c_sph, c_replays, coh);
+          traverse_wide<STATS, StackT, ZRT_PAXIS_LOCK != 0, LEAN>(a, r, stk, lds_top, gl, best_t, best, c_nodes, c_leaves,
+                                                                  c_tri, c_sph, c_replays, coh);
         if (kLaneLds) {
           LaneState<PRNG>::unpark(st_l, rng, acc_r, acc_g, acc_b, sample, depth_left);
           if (ZRT_LANE_OD) LaneState<PRNG>::unpark_od(st_l, o, d);
@@ -2760,15 +2799,15 @@ __device__ __forceinline__ void render_loop(const KArgs& a) {
         traverse_bvh<MODE == 1, STATS>(a, r, stk, best_t, best, c_nodes, c_tri, c_sph, &excess);
       }
       if (ZRT_PROFILE) { const uint64_t t = prof_stamp(); pf[2] += t - t0; t0 = t; }
-      shade_step<STATS>(a, mats, AttRows{att_l, kBlock, gl, a.n_lanes}, rng, best, best_t, o, d, depth_left, path_end,
-                        sky, L, c_bg, c_refl, c_shade, c_tex, coh);
+      shade_step<STATS, Rng<PRNG>, LEAN>(a, mats, AttRows{att_l, kBlock, gl, a.n_lanes}, rng, best, best_t, o, d, depth_left,
+                                         path_end, sky, L, c_bg, c_refl, c_shade, c_tex, coh);
     }
 
     if (ZRT_PROFILE) { const uint64_t t = prof_stamp(); pf[3] += t - t0; t0 = t; }
     if (path_end) {
       // a path that reached the sky traced at depth_left >= 1: all of its
       // max_depth - depth_left scatters were pushed
-      const V3 col = sky ? att_product<STATS>(a, mats, AttRows{att_l, kBlock, gl, a.n_lanes}, a.max_depth - depth_left, L, coh) : L;
+      const V3 col = sky ? att_product<STATS, LEAN>(a, mats, AttRows{att_l, kBlock, gl, a.n_lanes}, a.max_depth - depth_left, L, coh) : L;
       acc_r += col.x;
       acc_g += col.y;
       acc_b += col.z;
@@ -3767,7 +3806,7 @@ __device__ __forceinline__ void render_loop_list(const KArgs& a) {
 #define ZRT_ATT_ROWS_POOL 3  // path-pool loop: attenuation rows kept in LDS per path (2 KiB per row per block)
 #endif
 
-template <int MODE, int PRNG, bool STATS, class StackT>
+template <int MODE, int PRNG, bool STATS, class StackT, bool LEAN = false>
 __global__ void __launch_bounds__(kBlock, MODE == 5 || MODE == 7 || MODE == 8 || MODE == 9 ? ZRT_WAVES_POOL
                                           : MODE == 4 ? ZRT_WAVES_WF
                                           : MODE == 3 ? ZRT_WAVES_WIDE
@@ -3780,7 +3819,7 @@ __global__ void __launch_bounds__(kBlock, MODE == 5 || MODE == 7 || MODE == 8 ||
   else if constexpr (MODE == 8) render_loop_pool<PRNG, STATS, StackT, false, true>(a);  // compressed nodes
   else if constexpr (MODE == 9) render_loop_pool<PRNG, STATS, StackT, true, true>(a);   // compressed, guarded
   else if constexpr (MODE == 4) render_loop_wf<PRNG, STATS, StackT>(a);
-  else render_loop<MODE, PRNG, STATS, StackT>(a);
+  else render_loop<MODE, PRNG, STATS, StackT, false, LEAN>(a);
 }
 
 // The scheduling probe (FAST traversal): the same loop over a few samples per
@@ -4166,6 +4205,7 @@ struct zrt_ctx {
   float guard = 0.0f;                                // KArgs::guard
   uint32_t texel_bytes = 0;
   uint32_t tri_rcp_fast = 1;
+  uint32_t has_dielectric = 0, has_image_texture = 0;  // HostScene's
   float scene_extent = 1.0f;
   float tri_c[3] = {0.0f, 0.0f, 0.0f}, tri_h[3] = {0.0f, 0.0f, 0.0f};  // KArgs::tri_c / tri_h
   zrt::DevBuf<uint32_t> att;  // attenuation rows past the LDS ones (att codes)
@@ -4219,6 +4259,8 @@ struct HostScene {
   uint32_t n_wide = 0, n_leaves = 0, wide_stack = 0, wide_stride = 0, n_top = 0, n_mats = 0;
   uint32_t texel_bytes = 0;
   uint32_t tri_rcp_fast = 1;  // KArgs::tri_rcp_fast
+  // a dielectric / an image-textured material in the table (used or not): no lean kernel (plan_launch)
+  uint32_t has_dielectric = 0, has_image_texture = 0;
   float scene_extent = 0.0f;  // KArgs::scene_extent
   float tri_c[3] = {0.0f, 0.0f, 0.0f}, tri_h[3] = {0.0f, 0.0f, 0.0f};  // KArgs::tri_c / tri_h
   float root_c[3] = {0.0f, 0.0f, 0.0f}, origin_bound = 0.0f;  // KArgs::root_c / origin_bound
@@ -4549,9 +4591,12 @@ void flatten_scene(HostScene* c, const zrt_scene* s, bool use_bvh, int device, i
     dm.kind = m.kind;
     dm.ior = m.index_of_refraction;
     dm.tex_kind = ZRT_TEX_COLOR;
+    // (the kernels take every kind that is neither Lambertian nor metal as a dielectric)
+    if (m.kind != ZRT_MAT_LAMBERTIAN && m.kind != ZRT_MAT_METAL) c->has_dielectric = 1;
     if (m.kind != ZRT_MAT_DIELECTRIC) {
       const zrt_texture& t = s->textures[m.texture];
       dm.tex_kind = t.kind;
+      if (t.kind != ZRT_TEX_COLOR) c->has_image_texture = 1;
       dm.r = t.color.x;
       dm.g = t.color.y;
       dm.b = t.color.z;
@@ -4638,6 +4683,8 @@ void upload_scene(zrt_ctx* c, const HostScene& h) {
   c->wide_stride = h.wide_stride;
   c->texel_bytes = h.texel_bytes;
   c->tri_rcp_fast = h.tri_rcp_fast;
+  c->has_dielectric = h.has_dielectric;
+  c->has_image_texture = h.has_image_texture;
   c->scene_extent = h.scene_extent;
   for (int k = 0; k < 3; ++k) {
     c->tri_c[k] = h.tri_c[k];
@@ -4700,9 +4747,9 @@ bool use_list_lanes() {
 // LDS of the path-pool loop's rays, hits and queues per block (render_loop_pool)
 constexpr size_t kPoolLdsBytes = ((8 * sizeof(float) + 1) * kBlockPaths + 15) & ~size_t(15);
 
-template <int MODE, int PRNG, bool STATS, class StackT>
+template <int MODE, int PRNG, bool STATS, class StackT, bool LEAN = false>
 void* kernel_ptr() {
-  return reinterpret_cast<void*>(&render_kernel<MODE, PRNG, STATS, StackT>);
+  return reinterpret_cast<void*>(&render_kernel<MODE, PRNG, STATS, StackT, LEAN>);
 }
 
 template <int PRNG, bool STATS>
@@ -4720,10 +4767,19 @@ void* select_kernel_ps(int mode, bool stk16) {
 }
 #ifdef ZRT_ISA_KERNEL
 // tools/isa.sh: device assembly of ONE render kernel (register / spill probes in
-// seconds instead of minutes); ZRT_ISA_KERNEL = MODE, PRNG, STATS, StackT
-void* select_kernel(int, uint32_t, bool, bool) { return kernel_ptr<ZRT_ISA_KERNEL>(); }
+// seconds instead of minutes); ZRT_ISA_KERNEL = MODE, PRNG, STATS, StackT[, true: the lean kernel]
+void* select_kernel(int, uint32_t, bool, bool, bool) { return kernel_ptr<ZRT_ISA_KERNEL>(); }
 #else
-void* select_kernel(int mode, uint32_t prng, bool stats, bool stk16) {
+// lean: the lean kernel of the timed lockstep FAST loop (plan_launch decides; four kernels)
+void* select_kernel(int mode, uint32_t prng, bool stats, bool stk16, bool lean) {
+  if (lean) {
+    if (mode != 3 || stats) throw Error(ZRT_E_UNSUPPORTED, "no lean kernel for this loop");
+    if (prng == ZRT_PRNG_XOSHIRO256)
+      return stk16 ? kernel_ptr<3, ZRT_PRNG_XOSHIRO256, false, uint16_t, true>()
+                   : kernel_ptr<3, ZRT_PRNG_XOSHIRO256, false, uint32_t, true>();
+    return stk16 ? kernel_ptr<3, ZRT_PRNG_XOROSHIRO128, false, uint16_t, true>()
+                 : kernel_ptr<3, ZRT_PRNG_XOROSHIRO128, false, uint32_t, true>();
+  }
   if (prng == ZRT_PRNG_XOSHIRO256)
     return stats ? select_kernel_ps<ZRT_PRNG_XOSHIRO256, true>(mode, stk16)
                  : select_kernel_ps<ZRT_PRNG_XOSHIRO256, false>(mode, stk16);
@@ -4926,9 +4982,13 @@ struct SceneShape {
   bool use_bvh = false, q_ok = false;
   uint32_t n_nodes = 0, n_wide = 0, wide_stack = 0, stack_depth = 0, n_top = 0, q_top = 0, n_mats = 0;
   float guard = 0.0f;
+  bool tri_rcp_fast = false, has_dielectric = true, has_image_texture = true;  // (the lean kernel's conditions)
 };
 SceneShape shape_of(const zrt_ctx* c) {
   SceneShape s;
+  s.tri_rcp_fast = c->tri_rcp_fast != 0;
+  s.has_dielectric = c->has_dielectric != 0;
+  s.has_image_texture = c->has_image_texture != 0;
   s.use_bvh = c->use_bvh;
   s.q_ok = c->q_ok;
   s.n_nodes = c->n_nodes;
@@ -4943,6 +5003,9 @@ SceneShape shape_of(const zrt_ctx* c) {
 }
 SceneShape shape_of(const HostScene& h) {  // (as upload_scene fills the context)
   SceneShape s;
+  s.tri_rcp_fast = h.tri_rcp_fast != 0;
+  s.has_dielectric = h.has_dielectric != 0;
+  s.has_image_texture = h.has_image_texture != 0;
   s.use_bvh = h.use_bvh;
   s.q_ok = h.q_ok;
   s.n_nodes = h.n_nodes;
@@ -4964,9 +5027,27 @@ struct LaunchPlan {
   int mode = 0;   // 0 list, 1 binary, 2 reference, 3 FAST
   int kmode = 0;  // the kernel: mode, or 4 wavefront, 5 / 7 / 8 / 9 path pool, 6 list with per-lane items
   bool stk16 = false, wf = false, pool = false, qn = false, guard_on = false;
+  // the timed launch may take the lean kernel (ZRT_LEAN_*): the scene and the params
+  // allow it; the launch itself adds that its camera lies inside the origin bound
+  // and that it is not the STATS flavour (lean_launch)
+  bool lean = false;
   uint32_t node_f4 = 8, stack_depth = 0;
   LdsPlan lp;
 };
+// ZRT_LEAN=0 forces the general kernel; an ineligible launch never takes the lean one
+bool lean_wanted() {
+  if (const char* e = std::getenv("ZRT_LEAN")) return std::atoi(e) != 0;
+  return ZRT_LEAN_DEFAULT != 0;
+}
+// KArgs::check_origins of a render launch is 0: its camera lies inside the scene's origin bound
+bool camera_inside(const zrt_camera* cam, const float root_c[3], float origin_bound) {
+  const float m = std::max({std::fabs(cam->origin.x - root_c[0]), std::fabs(cam->origin.y - root_c[1]),
+                            std::fabs(cam->origin.z - root_c[2])});
+  return m <= origin_bound;
+}
+// The kernel of one launch: the lean one where the plan allows it, for the timed
+// flavour (the STATS flavour stays general) of a launch that checks no origin
+bool lean_launch(const LaunchPlan& P, bool stats, bool cam_inside) { return P.lean && !stats && cam_inside; }
 // zrt_stats::sampling_loop of a kernel: the path pool's flavours report as the pool
 uint32_t reported_loop(int kmode) { return kmode == 7 || kmode == 8 || kmode == 9 ? 5u : uint32_t(kmode); }
 LaunchPlan plan_launch(const SceneShape& s, const zrt_params* p) {
@@ -5026,6 +5107,10 @@ LaunchPlan plan_launch(const SceneShape& s, const zrt_params* p) {
     }
     P.lp = plan_lds(n_top, s.n_mats, mode, P.stk16, P.stack_depth, p->max_depth, P.wf, P.pool, p->prng, P.node_f4);
   }
+  // the lean kernel: the lockstep FAST loop over full nodes, shading (it reads the
+  // material table from LDS only), in a scene that has none of what it leaves out
+  P.lean = P.kmode == 3 && !ZRT_LOCK_QN && shades && P.lp.mats_in_lds != 0 && s.tri_rcp_fast && !s.has_dielectric &&
+           !s.has_image_texture && (p->flags & ZRT_FLAG_SCANLINES) == 0 && lean_wanted();
   return P;
 }
 
@@ -5377,7 +5462,9 @@ int zrt_ctx_render_tiles(zrt_ctx* c, const zrt_camera* cam, const zrt_params* p,
     const bool stk16 = plan.stk16, pool = plan.pool, qn = plan.qn, guard_on = plan.guard_on;
     const uint32_t stack_depth = plan.stack_depth, node_f4 = plan.node_f4;
     const zrt::LdsPlan& lp = plan.lp;
-    void* kfn = zrt::select_kernel(kmode, p->prng, diag, stk16);
+    // the camera inside the origin bound: so is every ray of the launch (scattered rays start at hits)
+    const bool cam_inside = zrt::camera_inside(cam, c->root_c, c->origin_bound);
+    void* kfn = zrt::select_kernel(kmode, p->prng, diag, stk16, zrt::lean_launch(plan, diag, cam_inside));
     const uint32_t lds_rows = lp.stack_rows;
     const size_t lds = lp.bytes;
     int per_cu = 0;
@@ -5455,11 +5542,7 @@ int zrt_ctx_render_tiles(zrt_ctx* c, const zrt_camera* cam, const zrt_params* p,
     a.graze_m = c->graze_m;
     a.graze_leaf = c->graze_leaf;
     a.guard = guard_on ? c->guard : 0.0f;
-    {  // the camera inside the bound: so is every ray of the launch (scattered rays start at hits)
-      const float m = std::max({std::fabs(a.org[0] - a.root_c[0]), std::fabs(a.org[1] - a.root_c[1]),
-                                std::fabs(a.org[2] - a.root_c[2])});
-      a.check_origins = m <= a.origin_bound ? 0u : 1u;
-    }
+    a.check_origins = cam_inside ? 0u : 1u;
     a.wnodes = qn ? c->qnodes.p : c->wnodes.p;
     a.wide_stride = qn ? c->q_stride : c->wide_stride;
     a.node_f4 = node_f4;
@@ -6307,6 +6390,27 @@ int zrt_debug_launch_plan(const zrt_scene* scene, const zrt_params* params, zrt_
     out->mats_in_lds = P.lp.mats_in_lds;
     out->lds_bytes = uint32_t(P.lp.bytes);
     out->ovf_bytes_per_lane = zrt::buffer_need(P.lp, params->max_depth, P.stack_depth, 1, 1, P.stk16).ovf_bytes;
+    return ZRT_OK;
+  }
+  ZRT_CATCH_ALL
+}
+
+int zrt_debug_lean_kernel(const zrt_scene* scene, const zrt_camera* camera, const zrt_params* params, uint32_t* lean) {
+  if (!camera || !params || !lean) return fail(ZRT_E_INVALID, "null argument");
+  *lean = 0;
+  int rc = zrt::validate_scene(scene);
+  if (rc) return rc;
+  if (params->traversal > ZRT_TRAVERSAL_BINARY) return fail(ZRT_E_INVALID, "unknown traversal");
+  try {
+    const bool use_bvh = params->bounded_volume_hierarchy != 0 && scene->n_prims > 10;  // (zrt_ctx_create)
+    zrt::HostScene h;
+    zrt::flatten_scene(&h, scene, use_bvh, -1);
+    const zrt::LaunchPlan P = zrt::plan_launch(zrt::shape_of(h), params);
+    // (as zrt_ctx_render_tiles decides)
+    *lean = zrt::lean_launch(P, (params->flags & ZRT_FLAG_STATS) != 0,
+                             zrt::camera_inside(camera, h.root_c, h.origin_bound))
+                ? 1u
+                : 0u;
     return ZRT_OK;
   }
   ZRT_CATCH_ALL
