@@ -31,6 +31,7 @@ import zraytrace_amd as z
 from oracle import oracle_py as O
 
 import many_materials as M
+import shading_scenes as SH
 import test_gpu_parity as P
 
 pytestmark = pytest.mark.gpu
@@ -73,8 +74,11 @@ _MM = {}
 
 
 def scene_of(scenes, which):
-    """(object to keep alive, zrt_scene pointer, camera) of a reference scene index or
-    "mm": the many-materials grid whose table fits the lockstep loop's LDS share."""
+    """(object to keep alive, zrt_scene pointer, camera) of a reference scene index,
+    "mm": the many-materials grid whose table fits the lockstep loop's LDS share, or a
+    name of tests/shading_scenes.py."""
+    if which in SH.NAMES:
+        return SH.get(which)
     if which == "mm":
         if not _MM:
             _MM["scene"] = M.many_materials_scene(M.N_SIDE_LOCKSTEP)
@@ -85,17 +89,18 @@ def scene_of(scenes, which):
     return s, s.view, s.camera
 
 
-_ORACLE = {}  # (scene, width, height, spp, max_depth, prng, seed, chunk) -> (image, stats, scanline rows)
+_ORACLE = {}  # (scene, width, height, spp, max_depth, prng, seed, chunk, bvh) -> (image, stats, scanline rows)
 
 
 def oracle_frame(scenes, which, p):
     """The oracle's frame, computed once and shared (never written to).  The loop,
     the traversal and the flags change nothing the oracle computes."""
-    key = (which, p.width, p.height, p.samples_per_pixel, p.max_depth, p.prng, p.seed, p.sample_chunk)
+    key = (which, p.width, p.height, p.samples_per_pixel, p.max_depth, p.prng, p.seed, p.sample_chunk,
+           p.bounded_volume_hierarchy)
     if key not in _ORACLE:
         _, view, cam = scene_of(scenes, which)
         plain = z.RenderParams(p.width, p.height, p.samples_per_pixel, p.max_depth, prng=p.prng, seed=p.seed,
-                               sample_chunk=p.sample_chunk)
+                               sample_chunk=p.sample_chunk, bounded_volume_hierarchy=p.bounded_volume_hierarchy)
         img, st, rows = O.render_scanlines(view, cam, plain)
         img.setflags(write=False)
         rows.setflags(write=False)

@@ -503,3 +503,103 @@ def test_compressed_nodes_encode_the_full_tree(scenes, index):
     s = scenes(index)
     n = z.debug_qnodes(s)
     assert n >= 8 * 4 * 100  # 8 octant copies x 4 slots x the tree's nodes
+
+
+# ---- validate_scene: every refusal, before the device check ----------------------------------
+
+def _valid_scene():
+    """A small valid scene with every kind in it: a sphere and a triangle; Lambertian
+    with an image texture, metal with a colour, a dielectric (its texture index is the
+    0xffffffff nobody reads).  Returns (scene, keep-alive)."""
+    px = np.linspace(0.0, 1.0, 2 * 3 * 3, dtype=np.float32)
+    imgs = (_ffi.Image * 1)(_ffi.Image(3, 2, px.ctypes.data_as(C.POINTER(C.c_float))))
+    texs = (_ffi.Texture * 2)(_ffi.Texture(_ffi.ZRT_TEX_IMAGE, 0, _ffi.Vec3(0, 0, 0), -0.3, 0.35),
+                              _ffi.Texture(_ffi.ZRT_TEX_COLOR, 0, _ffi.Vec3(0.5, 0.5, 0.5), 0.0, 0.0))
+    mats = (_ffi.Material * 3)(_ffi.Material(_ffi.ZRT_MAT_LAMBERTIAN, 0, 0.0),
+                               _ffi.Material(_ffi.ZRT_MAT_METAL, 1, 0.0),
+                               _ffi.Material(_ffi.ZRT_MAT_DIELECTRIC, 0xFFFFFFFF, 1.5))
+    prims = (_ffi.Prim * 3)()
+    prims[0].kind, prims[0].material = _ffi.ZRT_PRIM_SPHERE, 0
+    prims[0].center, prims[0].radius = _ffi.Vec3(0, 0, 3), 1.0
+    prims[1].kind, prims[1].material = _ffi.ZRT_PRIM_TRIANGLE, 1
+    prims[1].a, prims[1].b, prims[1].c = _ffi.Vec3(-1, -1, 2), _ffi.Vec3(0, 1, 2.5), _ffi.Vec3(1, -1, 2)
+    prims[2].kind, prims[2].material = _ffi.ZRT_PRIM_SPHERE, 2
+    prims[2].center, prims[2].radius = _ffi.Vec3(1, 0, 2), 0.5
+    s = _ffi.Scene(prims, 3, 3, mats, texs, 2, 1, imgs)
+    return s, (prims, mats, texs, imgs, px)
+
+
+def _set(path, value):
+    def mutate(s, keep):
+        obj = s
+        *head, last = path
+        for step in head:
+            obj = getattr(obj, step[0])[step[1]] if isinstance(step, tuple) else getattr(obj, step)
+        setattr(obj, last, value)
+    return mutate
+
+
+REFUSALS = [
+    ("prim-kind", _set([("prims", 1), "kind"], 2), "unknown primitive kind"),
+    ("prim-material", _set([("prims", 2), "material"], 3), "material index out of range"),
+    ("material-kind", _set([("materials", 1), "kind"], 3), "unknown material kind"),
+    ("material-texture", _set([("materials", 0), "texture"], 2), "texture index out of range"),
+    ("metal-texture-unset", _set([("materials", 1), "texture"], 0xFFFFFFFF), "texture index out of range"),
+    ("texture-kind", _set([("textures", 1), "kind"], 2), "unknown texture kind"),
+    ("texture-image", _set([("textures", 0), "image"], 1), "image index out of range"),
+    ("image-null-pixels", _set([("images", 0), "pixels"], C.POINTER(C.c_float)()), "empty image"),
+    ("image-width-0", _set([("images", 0), "width"], 0), "empty image"),
+    ("image-height-0", _set([("images", 0), "height"], 0), "empty image"),
+    ("null-prims", _set(["prims"], C.POINTER(_ffi.Prim)()), "prims is null"),
+    ("null-materials", _set(["materials"], C.POINTER(_ffi.Material)()), "materials is null"),
+    ("null-textures", _set(["textures"], C.POINTER(_ffi.Texture)()), "textures is null"),
+    ("null-images", _set(["images"], C.POINTER(_ffi.Image)()), "images is null"),
+]
+
+
+def _scene_calls(s):
+    """The three entry points of the issue, each on scene s: context creation, the
+    one-shot render and the device-free launch plan."""
+    view = C.pointer(s)
+    cam = z.camera_init((0, 0, -1), (0, 0, 3), (0, 1, 0), 45.0, 1.0)
+    p = z.RenderParams(8, 8, 1, 4)
+    return {"zrt_ctx_create": lambda: z.RenderContext(view, p),
+            "zrt_render": lambda: z.render(view, cam, p),
+            "zrt_debug_launch_plan": lambda: z.debug_launch_plan(view, p)}
+
+
+@pytest.mark.parametrize("name,mutate,message", REFUSALS, ids=[r[0] for r in REFUSALS])
+def test_validate_scene_refusals(name, mutate, message):
+    """render.hip validate_scene: each refusal, reached by changing one field of a valid
+    scene, comes back as ZRT_E_INVALID with its own message from zrt_ctx_create,
+    zrt_render and zrt_debug_launch_plan - before the device check, so with no GPU too."""
+    s, keep = _valid_scene()
+    mutate(s, keep)
+    for entry, call in _scene_calls(s).items():
+        with pytest.raises(z.ZrtError) as e:
+            call()
+        assert e.value.code == _ffi.ZRT_E_INVALID, (entry, str(e.value))
+        assert message in str(e.value), (entry, str(e.value))
+
+
+def test_validate_scene_accepts_the_unmutated_scene():
+    """The scene the refusals start from is valid - its dielectric's texture index is
+    0xffffffff, which validate_scene and the flattening skip.  Past validation a launch
+    plan is made and the LDS plans of the flattened scene are checked, and without a
+    GPU the entry points that need one report ZRT_E_NODEVICE, not ZRT_E_INVALID."""
+    s, keep = _valid_scene()
+    assert s.materials[2].kind == _ffi.ZRT_MAT_DIELECTRIC and s.materials[2].texture == 0xFFFFFFFF
+    calls = _scene_calls(s)
+    d = calls["zrt_debug_launch_plan"]()
+    assert d["mode"] == 0 and d["sampling_loop"] in (0, 6)  # (3 primitives: the surface list)
+    assert z.debug_lds_plans(C.pointer(s)) > 0
+    import torch
+    if not torch.cuda.is_available():
+        for entry in ("zrt_ctx_create", "zrt_render"):
+            with pytest.raises(z.ZrtError) as e:
+                calls[entry]()
+            assert e.value.code == _ffi.ZRT_E_NODEVICE, entry
+    # the same scene as the oracle reads it: a frame without NaN
+    cam = z.camera_init((0, 0, -1), (0, 0, 3), (0, 1, 0), 45.0, 1.0)
+    img, st = O.render(C.pointer(s), cam, z.RenderParams(8, 8, 2, 4))
+    assert np.isfinite(img).all() and st["reflections"] > 0

@@ -246,3 +246,108 @@ def test_transformed_prims_are_the_stated_map(scenes):
     exp = (t["a"].astype(np.float32) * np.float32(1e3) + np.float32(1e4)).astype(np.float32)
     assert np.array_equal(np.asarray(tri[0][0], np.float32), exp)
     assert sph[0][1] == float(np.float32(pr[pr["kind"] == 0][0]["radius"]) * np.float32(1e3))
+
+
+# ---- texture.zig:52-74, every arm of the wrap ------------------------------------------------
+
+def _zig_texel(w, h, u_off, v_off, u, v):
+    """ImageTexture.albedo (texture.zig:52-74) restated from the reference source: the
+    (x, y) of the texel it returns, arithmetic in f32.  @floatToInt(u64, f) truncates
+    toward zero; where the integer part of f is negative (f <= -1) Zig leaves it
+    undefined and the coordinate is returned as None."""
+    one = f32(1.0)
+    uu_first = f32(f32(one - f32(u)) + f32(u_off))
+    uu = uu_first
+    if uu_first > one:
+        uu = f32(uu_first - one)
+    elif uu_first < 0:
+        uu = f32(uu_first + one)
+    vv_first = f32(f32(v) + f32(v_off))
+    vv = vv_first
+    if vv_first > one:
+        vv = f32(vv_first - one)
+    elif uu_first < 0:  # (texture.zig:66 tests uu_first, not vv_first)
+        vv = f32(vv_first + one)
+
+    def index(f, n):
+        if f <= -1:
+            return None
+        return min(max(int(f), 0), n - 1)  # int() truncates toward zero, exactly
+    return index(f32(uu * f32(w)), w), index(f32(vv * f32(h)), h), f32(uu * f32(w)), f32(vv * f32(h))
+
+
+def _wrap_grid(n, off):
+    """Texture coordinates in [0, 1] for one axis of n texels with offset off: 0, 1, a
+    coarse sweep, and every value that puts the wrapped coordinate on a texel boundary
+    k / n (for both directions and every whole-number wrap), with its two f32 neighbours."""
+    vals = [f32(0.0), f32(1.0)] + list(np.linspace(0, 1, 23, dtype=np.float32))
+    for k in range(n + 1):
+        for j in (-1, 0, 1, 2):
+            kn = f32(k) / f32(n)
+            for c in (f32(kn - f32(off) + f32(j)), f32(f32(1.0) + f32(off) - kn + f32(j))):
+                vals += [c, np.nextafter(c, f32(-np.inf)), np.nextafter(c, f32(np.inf))]
+    return sorted({float(x) for x in vals if 0.0 <= x <= 1.0})
+
+
+def _wrap_cases():
+    import shading_scenes as S
+    return S.images(), S.OFFSETS
+
+
+def test_texture_wrap_arms_match_the_reference_source():
+    """texture.zig:52-74 on the four small images of tests/shading_scenes.py (1 x 1,
+    5 x 3, 1 x 7, 8 x 2) with its four offset pairs - negative offsets, offsets past 1
+    and (0, 0) - over (u, v) grids that sit on, one ulp under and one ulp over the texel
+    boundaries: the oracle returns exactly the texel the reference's source selects,
+    in every arm of the wrap, the V wrap that tests uu_first (:66) included.  The
+    inputs whose @floatToInt argument is <= -1 are left to the next test."""
+    images, offsets = _wrap_cases()
+    seen = dict.fromkeys(("uu>1", "uu<0", "vv>1", "quirk", "vv<0 kept", "on boundary", "clamped high", "total"), 0)
+    for img in images:
+        h, w = img.shape[:2]
+        for u_off, v_off in offsets:
+            for u in _wrap_grid(w, u_off):
+                for v in _wrap_grid(h, v_off):
+                    x, y, xf, yf = _zig_texel(w, h, u_off, v_off, u, v)
+                    if x is None or y is None:
+                        continue
+                    got = O.texture_albedo(img, u_off, v_off, u, v)
+                    assert got.tobytes() == img[y, x].tobytes(), (w, h, u_off, v_off, u, v, x, y)
+                    uu_first = f32(f32(f32(1.0) - f32(u)) + f32(u_off))
+                    vv_first = f32(f32(v) + f32(v_off))
+                    seen["total"] += 1
+                    seen["uu>1"] += uu_first > 1
+                    seen["uu<0"] += uu_first < 0
+                    seen["vv>1"] += vv_first > 1
+                    seen["quirk"] += (not vv_first > 1) and uu_first < 0
+                    seen["vv<0 kept"] += vv_first < 0 and not uu_first < 0
+                    seen["on boundary"] += (xf == np.floor(xf) and 0 < xf < w) or (yf == np.floor(yf) and 0 < yf < h)
+                    seen["clamped high"] += xf >= w or yf >= h
+    print(seen)
+    assert all(n > 100 for n in seen.values()), seen
+
+
+def test_texture_wrap_negative_float_to_int_is_the_x86_64_result():
+    """vv_first < 0 is kept when uu_first >= 0 (texture.zig:62-68), so vv * height can be
+    <= -1 - with offsets (-0.3, -0.2) on the 1 x 7 image, v < 0.057 - and the reference
+    hands @floatToInt(u64, ..) a value whose integer part is negative, which Zig leaves
+    undefined.  The oracle and the kernel both state what the reference's x86-64 build
+    computes: the conversion yields a value of 2^63 or more, which std.math.clamp
+    brings to the last texel (oracle.c float_to_u64, render.hip texel_index).  A value
+    in (-1, 0) truncates to 0 and is defined; the previous test covers it."""
+    images, offsets = _wrap_cases()
+    n = 0
+    for img in images:
+        h, w = img.shape[:2]
+        for u_off, v_off in offsets:
+            for u in _wrap_grid(w, u_off):
+                for v in _wrap_grid(h, v_off):
+                    x, y, xf, yf = _zig_texel(w, h, u_off, v_off, u, v)
+                    if x is not None and y is not None:
+                        continue
+                    x = w - 1 if x is None else x
+                    y = h - 1 if y is None else y
+                    got = O.texture_albedo(img, u_off, v_off, u, v)
+                    assert got.tobytes() == img[y, x].tobytes(), (w, h, u_off, v_off, u, v, x, y)
+                    n += 1
+    assert n > 100
