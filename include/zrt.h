@@ -408,6 +408,85 @@ int zrt_ctx_debug_wave_times(zrt_ctx* ctx, uint64_t* out, uint32_t cap, uint32_t
  * launch stream; synchronises). */
 int zrt_ctx_last_kernel_ms(zrt_ctx* ctx, double* ms);
 
+/* ---- progressive rendering: sample passes accumulated on a context --------- *
+ * A sample's random stream is keyed by (pixel, sample index, seed) and not by
+ * samples_per_pixel, and a pixel is the sequential sum of its chunk sums
+ * (raytrace.zig:177) times 1 / samples_per_pixel (raytrace.zig:157, 182).  So a
+ * frame can be rendered in passes of whole sample chunks, each added onto a
+ * resident per-pixel sum: after every pass the resolved frame (sum x 1 / samples
+ * done) equals, bit for bit, a full render with samples_per_pixel = samples
+ * done, and the chunk sums a launch parks in memory are the pass's, not the
+ * frame's.
+ *
+ * zrt_ctx_accum_begin starts a run: it fixes the camera and every param
+ * (validated as zrt_ctx_render_tiles validates them; samples_per_pixel is the
+ * run's cap, the planned total).  One run is live per context: a second begin
+ * restarts it, and any zrt_ctx_render_tiles on the context ends it (the
+ * scheduling probe's buffers belong to the context).
+ *
+ * zrt_ctx_accum_pass renders the next n_samples samples of every pixel through
+ * zrt_ctx_render_tiles' launch path and kernels, adds them to the accumulator
+ * and writes the resolved tiles (this rank's, as zrt_ctx_render_tiles lays them
+ * out) to dev_tiles.  Asynchronous; every pass of a run goes to one stream (or
+ * to streams the caller orders).  ZRT_E_INVALID: n_samples == 0, a pass past the
+ * cap, a pass that does not start on a sample chunk boundary (a ragged pass is
+ * allowed and is then the run's last, as the frame's ragged last chunk is), or
+ * no live run.  The run schedules once, by the rule of ZRT_FLAG_NO_SCHEDULE with
+ * the cap as samples_per_pixel: its first pass probes, later passes reuse the
+ * tile order (their schedule_ms is 0).  After a pass zrt_ctx_stats,
+ * zrt_ctx_scanlines report the run's counters so far - what a full render of
+ * samples_done samples counts - with render_ms / schedule_ms summed over the
+ * passes; zrt_ctx_last_kernel_ms is the last pass's.  A device error in a pass
+ * is sticky for the run: NaN tiles from then on, ZRT_E_UNSUPPORTED from
+ * zrt_ctx_sync / zrt_ctx_stats / zrt_ctx_accum_info and from later passes. */
+typedef struct zrt_pass_info {
+  uint32_t samples_done;    /* samples per pixel in the accumulator after the pass */
+  uint32_t pass_samples;    /* of them, this pass */
+  uint64_t changed_pixels;  /* this rank's pixels whose 8-bit PNG value changed in the pass */
+  float    max_abs_change;  /* largest |new - previous| over this rank's channels (previous = 0 before pass 1) */
+  float    render_ms;       /* this pass: probe (if any) + render kernel, as zrt_stats.render_ms */
+  float    schedule_ms;     /* this pass's probe + sort; 0 when the run's cached order was reused */
+  uint32_t reserved;
+} zrt_pass_info;
+
+int zrt_ctx_accum_begin(zrt_ctx* ctx, const zrt_camera* camera, const zrt_params* params);
+int zrt_ctx_accum_pass(zrt_ctx* ctx, uint32_t n_samples, float* dev_tiles, void* hip_stream);
+/* The last pass's metrics and times (waits for it). */
+int zrt_ctx_accum_info(zrt_ctx* ctx, zrt_pass_info* out);
+
+/* zrt_render in passes of pass_samples samples (rounded up to whole sample
+ * chunks; 0 selects ZRT_DEFAULT_PASS_CHUNKS chunks) on one GPU
+ * (params->device).  After each pass on_pass (may be NULL) receives the
+ * assembled frame so far (width*height*3 f32, row 0 = bottom; it is out_rgb)
+ * and the pass's info; a nonzero return stops the run.  out_rgb and stats then
+ * hold the frame and the counters at info.samples_done samples per pixel: for a
+ * run that was not stopped, zrt_render's. */
+typedef int (*zrt_pass_fn)(void* user, const float* rgb, const zrt_pass_info* info);
+/* Every pass is a launch with an end of its own, so passes cost time: the bunny
+ * at 2048 x 2048, 1024 spp in passes of 1 / 2 / 4 / 8 chunks takes 81 / 34 / 15 /
+ * 5.7 % longer than the single launch; no pass shorter than
+ * the frame stays inside the single launch's run-to-run spread (0.2 %). */
+enum { ZRT_DEFAULT_PASS_CHUNKS = 8u };
+int zrt_render_progressive(const zrt_scene* scene, const zrt_camera* camera,
+                           const zrt_params* params, uint32_t pass_samples,
+                           zrt_pass_fn on_pass, void* user, float* out_rgb, zrt_stats* stats);
+
+/* How zrt_ctx_accum_pass turns (params->samples_per_pixel = the cap,
+ * params->sample_chunk, done, n_samples) into a launch, with no device (the
+ * launch path calls the same function; it returns the refusals above). */
+typedef struct zrt_pass_plan {
+  uint32_t first_sample;   /* = done: the frame's sample index of the pass's sample 0 */
+  uint32_t pass_samples;
+  uint32_t samples_after;  /* done + n_samples */
+  uint32_t chunk;          /* the sample chunk in use (sample_chunk, or 32 for 0) */
+  uint32_t pass_chunks;    /* chunk sums per pixel the pass writes */
+  uint32_t last_chunk;     /* samples in the last of them (< chunk: a ragged pass) */
+  uint64_t partial_bytes;  /* the pass's chunk sums: this rank's tiles x 64 x pass_chunks x 16 B */
+  uint64_t key_offset;     /* added to the launch's seed term: sample s of the pass draws the
+                              stream of the frame's sample s + done */
+} zrt_pass_plan;
+int zrt_debug_pass_plan(const zrt_params* params, uint32_t done, uint32_t n_samples, zrt_pass_plan* out);
+
 /* ---- host-side scene ingestion (the caller side of the seam) ------------- *
  * Restatement of scenes.zig / obj_reader.zig / png_image.zig texture loading
  * so tests and bench can build the reference's scenes without Zig.  Assets are

@@ -157,6 +157,37 @@ def render(scene, camera: _ffi.Camera, params: RenderParams):
     return out, st.as_dict()
 
 
+def render_progressive(scene, camera: _ffi.Camera, params: RenderParams, pass_samples: int = 0, on_pass=None):
+    """render() in passes of pass_samples samples (zrt_render_progressive; rounded up to
+    whole sample chunks, 0: the library's default): returns (image, stats, [info dict
+    per pass]).  on_pass(image[H, W, 3] so far, info dict) is called after every pass; a
+    true return stops the run, and image / stats are then those of info["samples_done"]
+    samples per pixel."""
+    view = scene.view if isinstance(scene, LoadedScene) else scene
+    out = np.zeros((params.height, params.width, 3), dtype=np.float32)
+    st = _ffi.Stats()
+    p = params.abi()
+    infos = []
+
+    def cb(_user, _rgb, info):
+        infos.append(info.contents.as_dict())
+        return 1 if on_pass is not None and on_pass(out, infos[-1]) else 0
+
+    check(lib().zrt_render_progressive(view, C.byref(camera), C.byref(p), pass_samples, _ffi.PASS_FN(cb), None,
+                                       out.ctypes.data_as(C.POINTER(C.c_float)), C.byref(st)))
+    return out, st.as_dict(), infos
+
+
+def debug_pass_plan(params: RenderParams, done: int, n_samples: int) -> dict:
+    """How an accumulation run with these params (samples_per_pixel = its cap) renders
+    samples [done, done + n_samples) (zrt_debug_pass_plan; no device): the zrt_pass_plan
+    fields as a dict.  Raises ZrtError for a pass the run would refuse."""
+    out = _ffi.PassPlan()
+    p = params.abi()
+    check(lib().zrt_debug_pass_plan(C.byref(p), done, n_samples, C.byref(out)))
+    return out.as_dict()
+
+
 def _scanlines_np(rows) -> np.ndarray:
     """zrt_scanline[height] -> uint64 array [height, 6] (columns: _ffi.SCANLINE_FIELDS)."""
     return np.ctypeslib.as_array(rows).view(np.uint64).reshape(len(rows), 6).copy()
@@ -286,6 +317,22 @@ class RenderContext:
         p = params.abi()
         check(lib().zrt_ctx_assemble(self._h, C.byref(p), C.c_void_p(dev_gathered),
                                      C.c_void_p(dev_frame), C.c_void_p(stream or None)))
+
+    def accum_begin(self, camera, params: RenderParams):
+        """Start an accumulation run (zrt_ctx_accum_begin): params.samples_per_pixel is its cap."""
+        p = params.abi()
+        check(lib().zrt_ctx_accum_begin(self._h, C.byref(camera), C.byref(p)))
+
+    def accum_pass(self, n_samples: int, dev_tiles: int, stream: int = 0):
+        """Render the run's next n_samples samples per pixel, accumulate them and write the
+        resolved tiles (zrt_ctx_accum_pass; asynchronous)."""
+        check(lib().zrt_ctx_accum_pass(self._h, n_samples, C.c_void_p(dev_tiles), C.c_void_p(stream or None)))
+
+    def accum_info(self) -> dict:
+        """The last pass's metrics and times (zrt_ctx_accum_info; waits for it)."""
+        out = _ffi.PassInfo()
+        check(lib().zrt_ctx_accum_info(self._h, C.byref(out)))
+        return out.as_dict()
 
     def sync(self):
         """Wait for the last launch; raises ZrtError on a device error (zrt_ctx_sync)."""

@@ -123,6 +123,28 @@ class LaunchPlan(C.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_}
 
 
+class PassInfo(C.Structure):
+    _fields_ = [("samples_done", C.c_uint32), ("pass_samples", C.c_uint32), ("changed_pixels", C.c_uint64),
+                ("max_abs_change", C.c_float), ("render_ms", C.c_float), ("schedule_ms", C.c_float),
+                ("reserved", C.c_uint32)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_ if name != "reserved"}
+
+
+class PassPlan(C.Structure):
+    _fields_ = [("first_sample", C.c_uint32), ("pass_samples", C.c_uint32), ("samples_after", C.c_uint32),
+                ("chunk", C.c_uint32), ("pass_chunks", C.c_uint32), ("last_chunk", C.c_uint32),
+                ("partial_bytes", C.c_uint64), ("key_offset", C.c_uint64)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
+# zrt_pass_fn: int (*)(void* user, const float* rgb, const zrt_pass_info* info)
+PASS_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_float), C.POINTER(PassInfo))
+
+
 class BvhNode(C.Structure):
     _fields_ = [("min", Vec3), ("left", C.c_int32), ("max", Vec3), ("right", C.c_int32)]
 
@@ -167,6 +189,12 @@ SIGNATURES = [
     ("zrt_ctx_debug_wave_times", C.c_int, [_P, C.POINTER(C.c_uint64), C.c_uint32, C.POINTER(C.c_uint32)]),
     ("zrt_ctx_debug_schedule", C.c_int, [_P, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_uint32,
                                          C.POINTER(C.c_uint32)]),
+    ("zrt_ctx_accum_begin", C.c_int, [_P, C.POINTER(Camera), C.POINTER(Params)]),
+    ("zrt_ctx_accum_pass", C.c_int, [_P, C.c_uint32, _P, _P]),
+    ("zrt_ctx_accum_info", C.c_int, [_P, C.POINTER(PassInfo)]),
+    ("zrt_render_progressive", C.c_int, [C.POINTER(Scene), C.POINTER(Camera), C.POINTER(Params), C.c_uint32,
+                                         PASS_FN, _P, C.POINTER(C.c_float), C.POINTER(Stats)]),
+    ("zrt_debug_pass_plan", C.c_int, [C.POINTER(Params), C.c_uint32, C.c_uint32, C.POINTER(PassPlan)]),
     ("zrt_scene_load", C.c_int, [C.c_uint32, C.c_char_p, C.POINTER(_P), C.POINTER(Camera)]),
     ("zrt_scene_view", C.POINTER(Scene), [_P]),
     ("zrt_scene_free", None, [_P]),

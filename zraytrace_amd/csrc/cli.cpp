@@ -12,7 +12,11 @@
 // printed when the frame is done (it is one launch), and their Pixels/s is the
 // frame's rate, since rows are not rendered one after another.  Assets come from $ZRT_ASSETS, else <exe dir>/../assets;
 // $ZRT_DEVICE picks the GPU, $ZRT_DEVICES="0,1,..." renders over several
-// (zrt_render_multi: tiles round-robin, one RCCL gather).
+// (zrt_render_multi: tiles round-robin, one RCCL gather).  $ZRT_PASS_SAMPLES=N renders
+// progressively (zrt_render_progressive, passes of N samples rounded up to whole
+// sample chunks; 0: the library's default): one line per pass on stderr in place
+// of the scanline lines, and the PNG rewritten after every pass - the final PNG
+// and the summary's counters are those of a run without the variable.
 #include <unistd.h>
 
 #include <chrono>
@@ -81,6 +85,23 @@ double seconds_since(std::chrono::steady_clock::time_point t0) {
   return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
 }
 
+// $ZRT_PASS_SAMPLES: the preview after every pass of zrt_render_progressive
+struct Preview {
+  const char* filename;
+  uint32_t width, height;
+  uint64_t pixels;  // rendered: x < height (raytrace.zig:168)
+};
+int on_pass(void* user, const float* rgb, const zrt_pass_info* info) {
+  const Preview* pv = static_cast<const Preview*>(user);
+  // (the pass's rays are not counted per pass: camera rays / s is the rate a pass can report)
+  std::fprintf(stderr, "Pass: %u samples done (+%u) Changed pixels: %llu Max change: %.6g Msamples/s: %.2f\n",
+               info->samples_done, info->pass_samples, (unsigned long long)info->changed_pixels,
+               double(info->max_abs_change),
+               double(pv->pixels) * info->pass_samples / (double(info->render_ms) / 1000.0) / 1e6);
+  // (an unwritable preview stops the run; the final write below reports the error)
+  return zrt_image_write_png(pv->filename, rgb, pv->width, pv->height) != ZRT_OK;
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -136,6 +157,13 @@ int main(int argc, char** argv) {
     }
   }
 
+  const char* pass_env = std::getenv("ZRT_PASS_SAMPLES");
+  if (pass_env && !devices.empty()) {
+    std::fprintf(stderr, "error: ZRT_PASS_SAMPLES renders on one GPU: unset ZRT_DEVICES (or ZRT_PASS_SAMPLES)\n");
+    zrt_scene_free(data);
+    return 1;
+  }
+
   std::fprintf(stderr, "Raytrace start\n");
   std::fprintf(stderr, " - Surfaces:                 %u\n", scene->n_prims);
   std::fprintf(stderr, " - Pixels:                   %ux%u\n", unsigned(width), unsigned(height));
@@ -148,7 +176,11 @@ int main(int argc, char** argv) {
   std::vector<zrt_scanline> rows(height);
   zrt_stats stats;
   const auto t_render = std::chrono::steady_clock::now();
-  if (devices.empty()) {
+  if (pass_env) {
+    const Preview pv{filename, width, height, uint64_t(height) * height};
+    rc = zrt_render_progressive(scene, &camera, &params, uint32_t(std::strtoul(pass_env, nullptr, 10)), on_pass,
+                                const_cast<Preview*>(&pv), image.data(), &stats);
+  } else if (devices.empty()) {
     rc = zrt_render_progress(scene, &camera, &params, image.data(), &stats, rows.data());
   } else {
     params.flags |= ZRT_FLAG_SCANLINES;
@@ -172,7 +204,7 @@ int main(int argc, char** argv) {
   // printProgress after every scanline (raytrace.zig:37-50, 184)
   const double pixels_per_second = double(stats.pixels_processed) / render_runtime;
   unsigned long long pixels = 0, samples_sum = 0, rays = 0;
-  for (uint32_t y = 0; y < height; ++y) {
+  for (uint32_t y = 0; y < height && !pass_env; ++y) {
     pixels += rows[y].pixels;
     samples_sum += rows[y].samples;
     rays += rows[y].rays;

@@ -3913,6 +3913,90 @@ __global__ void finalize_kernel(const float4* __restrict__ partial, float* __res
   out[3ull * i + 2] = b;
 }
 
+// png_image.zig:136-138 on the device (image_io.cpp png_channel): std.math.min / max
+// are `x < y ? x : y` / `x > y ? x : y`, clamp = max(lower, min(val, upper))
+__device__ __forceinline__ uint32_t png_channel_dev(float c) {
+  const float v = 255.999f * c;
+  const float m = v < 255.0f ? v : 255.0f;
+  return uint32_t(0.0f > m ? 0.0f : m);
+}
+
+// finalize_kernel's progressive counterpart (zrt_ctx_accum_pass): a pass's chunk
+// sums added, in chunk order, onto the run's resident per-slot sums, which are
+// stored back; the frame written is the sum times new_scale = 1 / (samples in
+// the accumulator after the pass) - the bits finalize_kernel gives for a whole
+// frame of that many samples (raytrace.zig:157, 177, 182).  Out-of-frame slots
+// stay 0.  A nonzero device error flag leaves NaN in every pixel and in every
+// slot of accum, so no later pass resolves a clean frame from it.
+// metrics: kMetricShards pairs, kMetricStride words apart (a block adds into pair
+// blockIdx.x % kMetricShards: one word takes some 90 atomics per microsecond, and a
+// 2048 x 2048 frame has 65 536 waves; the host adds the pairs up).  Word 0: in-frame
+// pixels whose 8-bit PNG value (any channel) differs between this frame and the one
+// shown before the pass (accum before x prev_scale; prev_scale is 0 before the first
+// pass); word 1: the bits of the largest |new - previous| over the in-frame channels
+// (non-negative floats order as their bit patterns; a NaN difference is skipped).
+// At most one atomic of each per wave (none for a maximum already reached: the word
+// only grows, so a stale read can only cost an atomic, never skip one).
+constexpr uint32_t kMetricShards = 64, kMetricStride = 16, kMetricWords = kMetricShards * kMetricStride;
+__global__ void accumulate_kernel(const float4* __restrict__ partial, float4* __restrict__ accum,
+                                  float* __restrict__ out, uint32_t n_slots, uint32_t pass_chunks, uint32_t world,
+                                  uint32_t rank, uint32_t tiles_x, uint32_t xbound, uint32_t height, float prev_scale,
+                                  float new_scale, const unsigned long long* __restrict__ error_flag,
+                                  unsigned long long* __restrict__ metrics) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  const bool live = i < n_slots;
+  const uint32_t lt = i >> 6, p = i & 63u;
+  const uint32_t t = lt * world + rank;
+  const uint32_t px = (t % tiles_x) * 8u + (p & 7u);
+  const uint32_t py = (t / tiles_x) * 8u + (p >> 3);
+  float r = 0.0f, g = 0.0f, b = 0.0f;
+  float change = 0.0f;
+  bool changed = false;
+  if (live && *error_flag != 0ull) {
+    r = g = b = __builtin_nanf("");
+    accum[i] = make_float4(r, g, b, 0.0f);
+  } else if (live && px < xbound && py < height) {
+    const float4 before = accum[i];
+    r = before.x;
+    g = before.y;
+    b = before.z;
+    for (uint32_t j = 0; j < pass_chunks; ++j) {  // [chunk][slot], as finalize_kernel reads them
+      const float4 v = partial[(size_t)j * n_slots + i];
+      r += v.x;
+      g += v.y;
+      b += v.z;
+    }
+    accum[i] = make_float4(r, g, b, 0.0f);
+    r *= new_scale;
+    g *= new_scale;
+    b *= new_scale;
+    const float pr = before.x * prev_scale, pg = before.y * prev_scale, pb = before.z * prev_scale;
+    const float dr = fabsf(r - pr), dg = fabsf(g - pg), db = fabsf(b - pb);
+    change = dr > change ? dr : change;  // (a NaN compares false: skipped)
+    change = dg > change ? dg : change;
+    change = db > change ? db : change;
+    changed = png_channel_dev(r) != png_channel_dev(pr) || png_channel_dev(g) != png_channel_dev(pg) ||
+              png_channel_dev(b) != png_channel_dev(pb);
+  }
+  if (live) {
+    out[3ull * i + 0] = r;
+    out[3ull * i + 1] = g;
+    out[3ull * i + 2] = b;
+  }
+  for (int off = 32; off > 0; off >>= 1) {
+    const float o = __shfl_xor(change, off, 64);
+    change = o > change ? o : change;
+  }
+  const unsigned long long ballot = __ballot(changed);
+  if ((threadIdx.x & 63u) == 0u) {
+    unsigned long long* m = metrics + (blockIdx.x % kMetricShards) * kMetricStride;
+    if (ballot) atomicAdd(&m[0], (unsigned long long)__popcll(ballot));
+    unsigned int* mx = reinterpret_cast<unsigned int*>(&m[1]);
+    const unsigned int bits = __float_as_uint(change);
+    if (bits > __hip_atomic_load(mx, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(mx, bits);
+  }
+}
+
 // Scatter gathered rank tiles into the framebuffer (raytrace.zig:182 layout).
 // Packed (stride_px == 0): rank r's tiles start at rank_base[r].  Padded: rank r
 // starts at r * stride_px, as a gather of equal per-rank counts leaves them.
@@ -4238,7 +4322,34 @@ struct zrt_ctx {
   int last_loop = 0;  // zrt_stats::sampling_loop
   float last_guard = 0.0f;  // zrt_stats::guard
   int cu_count = 0;
+  // ---- the accumulation run (zrt_ctx_accum_*): at most one per context ----
+  struct EvSet {
+    hipEvent_t pre = nullptr, e0 = nullptr, e1 = nullptr;
+    bool probed = false;  // the pass ran the scheduling probe (pre .. e0 is its schedule_ms)
+  };
+  bool run_live = false;       // between zrt_ctx_accum_begin and the next plain render
+  bool run_stats = false;      // the last launch was a pass: zrt_ctx_stats reports the run's sums
+  zrt_camera run_cam{};
+  zrt_params run_p{};
+  uint32_t run_done = 0;       // samples per pixel in accum
+  uint32_t run_passes = 0;     // passes enqueued
+  bool run_ordered = false;    // the first pass's probe left tile_order and probe_scratch for the later ones
+  bool pass_probed = false;    // the last pass ran the probe
+  uint32_t pass_samples = 0;   // the last pass's
+  zrt::DevBuf<float4> accum;   // [slot] running chunk sums (rank's tile-major layout)
+  zrt::DevBuf<unsigned long long> metrics;  // accumulate_kernel's {changed pixels, max change bits} shards
+  unsigned long long* metrics_host = nullptr;  // ... of the last pass, pinned, copied behind ev_done
+  // earlier passes' events not yet added into run_render_ms / run_sched_ms, and spare sets
+  std::vector<EvSet> run_pending, ev_spare;
+  double run_render_ms = 0, run_sched_ms = 0;
   ~zrt_ctx() {
+    for (const std::vector<EvSet>* v : {&run_pending, &ev_spare})
+      for (const EvSet& e : *v) {
+        (void)hipEventDestroy(e.pre);
+        (void)hipEventDestroy(e.e0);
+        (void)hipEventDestroy(e.e1);
+      }
+    if (metrics_host) (void)hipHostFree(metrics_host);
     if (ev_pre) (void)hipEventDestroy(ev_pre);
     if (ev0) (void)hipEventDestroy(ev0);
     if (ev1) (void)hipEventDestroy(ev1);
@@ -5243,6 +5354,62 @@ int launch_status(zrt_ctx* c, bool wait) {
   return fail(ZRT_E_UNSUPPORTED, device_error_msg(*c->err_host));
 }
 
+// A run's earlier passes whose events have completed (wait: all of them) added into
+// its render and schedule times; their event sets become spare.  Passes complete in
+// the order they were enqueued.
+void fold_pass_times(zrt_ctx* c, bool wait) {
+  while (!c->run_pending.empty()) {
+    const zrt_ctx::EvSet e = c->run_pending.front();
+    if (wait) {
+      HIPCHK(hipEventSynchronize(e.e1));
+    } else if (hipEventQuery(e.e1) != hipSuccess) {
+      (void)hipGetLastError();  // (not ready is no error of this launch)
+      break;
+    }
+    float ms = 0.0f, sched = 0.0f;
+    HIPCHK(hipEventElapsedTime(&ms, e.pre, e.e1));
+    HIPCHK(hipEventElapsedTime(&sched, e.pre, e.e0));
+    c->run_render_ms += ms;
+    if (e.probed) c->run_sched_ms += sched;
+    c->ev_spare.push_back(e);
+    c->run_pending.erase(c->run_pending.begin());
+  }
+}
+
+// One pass of an accumulation run (zrt_ctx_accum_pass; zrt_debug_pass_plan reports
+// the same): samples [done, done + n_samples) of a run capped at
+// p->samples_per_pixel, as a launch of n_samples samples in pass_chunks chunks whose
+// sample keys are shifted by `done`.  A sample's stream is keyed by
+// ((pixel << 16) | sample) + seed * 0x9E37...; for sample + done < 65536,
+// ((o << 16) | s) + done == (o << 16) | (s + done), so key_offset = done added to
+// the seed term gives the pass the keys of the frame's samples done .. done + n - 1.
+// The pass must start on a chunk boundary: its chunk sums are then the frame's
+// chunks done / chunk .., and a ragged last chunk is the frame's last one.
+int plan_pass(const zrt_params* p, uint32_t done, uint32_t n_samples, zrt_pass_plan* out) {
+  const int rc = validate_params(p);
+  if (rc) return rc;
+  const uint32_t chunk = p->sample_chunk ? p->sample_chunk : ZRT_DEFAULT_SAMPLE_CHUNK;
+  if (n_samples == 0) return fail(ZRT_E_INVALID, "a pass of 0 samples");
+  if (uint64_t(done) + n_samples > p->samples_per_pixel)
+    return fail(ZRT_E_INVALID, "the pass ends past the run's samples_per_pixel");
+  if (done % chunk != 0)
+    return fail(ZRT_E_INVALID, "the pass does not start on a sample chunk boundary (a ragged pass ends the run)");
+  const uint32_t my_tiles = rank_tiles(geometry(p), p->rank, p->world_size);
+  zrt_pass_plan P{};
+  P.first_sample = done;
+  P.pass_samples = n_samples;
+  P.samples_after = done + n_samples;
+  P.chunk = chunk;
+  P.pass_chunks = (n_samples + chunk - 1) / chunk;
+  P.last_chunk = n_samples - (P.pass_chunks - 1) * chunk;
+  if (uint64_t(my_tiles) * 64u * P.pass_chunks >= (1ull << 32) - (1ull << 26))  // (+ one refill per lane of slack)
+    return fail(ZRT_E_UNSUPPORTED, "more than 2^32 (pixel, chunk) work items");
+  P.partial_bytes = uint64_t(my_tiles) * 64u * P.pass_chunks * sizeof(float4);
+  P.key_offset = done;
+  *out = P;
+  return ZRT_OK;
+}
+
 // RCCL for zrt_render_multi, opened on first use so that single-GPU callers do
 // not load it: the copy already in the process when torch brought one (same
 // soname, librccl.so.1), else ROCm's.
@@ -5435,17 +5602,30 @@ int zrt_ctx_tile_count(const zrt_ctx* ctx, const zrt_params* params, uint32_t* n
   return ZRT_OK;
 }
 
-int zrt_ctx_render_tiles(zrt_ctx* c, const zrt_camera* cam, const zrt_params* p, float* dev_tiles,
-                         void* hip_stream) {
-  if (!c || !cam || !dev_tiles) return fail(ZRT_E_INVALID, "null argument");
-  int rc = zrt::validate_params(p);
-  if (rc) return rc;
+// Valid params (zrt::validate_params) are also the context's: its device, its BVH decision.
+static int params_fit_ctx(const zrt_ctx* c, const zrt_params* p) {
   if (int(p->device) != c->device)
     return fail(ZRT_E_INVALID, "params->device differs from the device the context was created on");
   if ((p->bounded_volume_hierarchy != 0 && c->n_prims > 10) != c->use_bvh)
     return fail(ZRT_E_INVALID,
                 "params->bounded_volume_hierarchy implies another preprocessSufraces decision (raytrace.zig:124-133) "
                 "than the one the context was built with");
+  return ZRT_OK;
+}
+
+// The launch behind zrt_ctx_render_tiles (run_pass false: the whole frame, resolved by
+// finalize_kernel) and zrt_ctx_accum_pass (run_pass true: samples [c->run_done,
+// c->run_done + n_samples) of the context's run, p = its params, resolved by
+// accumulate_kernel): one launch path and one kernel choice for both.
+static int launch_frame(zrt_ctx* c, const zrt_camera* cam, const zrt_params* p, float* dev_tiles, void* hip_stream,
+                        bool run_pass, uint32_t n_samples) {
+  if (!c || !cam || !dev_tiles) return fail(ZRT_E_INVALID, "null argument");
+  zrt_pass_plan pass{};
+  int rc = zrt::plan_pass(p, run_pass ? c->run_done : 0u, run_pass ? n_samples : (p ? p->samples_per_pixel : 0u), &pass);
+  if (rc) return rc;
+  const bool first = !run_pass || c->run_passes == 0;  // the launch zeroes the counters it adds into
+  rc = params_fit_ctx(c, p);
+  if (rc) return rc;
   try {
     HIPCHK(hipSetDevice(c->device));
     // a device error of the previous launch that finished meanwhile is reported
@@ -5471,11 +5651,9 @@ int zrt_ctx_render_tiles(zrt_ctx* c, const zrt_camera* cam, const zrt_params* p,
     HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kfn, zrt::kBlock, lds));
     per_cu = std::max(1, std::min(per_cu, 8));
     uint32_t grid = uint32_t(c->cu_count) * uint32_t(per_cu);
-    const uint32_t chunk = p->sample_chunk ? p->sample_chunk : ZRT_DEFAULT_SAMPLE_CHUNK;
-    const uint32_t n_chunks = (p->samples_per_pixel + chunk - 1) / chunk;
-    const uint64_t work64 = uint64_t(my_tiles) * n_chunks;  // units: (tile, chunk)
-    if (uint64_t(my_tiles) * 64u * n_chunks >= (1ull << 32) - (1ull << 26))  // (+ one refill per lane of slack)
-      return fail(ZRT_E_UNSUPPORTED, "more than 2^32 (pixel, chunk) work items");
+    const uint32_t chunk = pass.chunk;
+    const uint32_t n_chunks = pass.pass_chunks;
+    const uint64_t work64 = uint64_t(my_tiles) * n_chunks;  // units: (tile, chunk); < 2^32 (plan_pass)
     const uint32_t work = uint32_t(work64);
     // one wave per unit at the start; more waves than units would only idle
     grid = std::max(1u, std::min(grid, (work + (zrt::kBlock / 64) - 1) / (zrt::kBlock / 64)));
@@ -5489,7 +5667,30 @@ int zrt_ctx_render_tiles(zrt_ctx* c, const zrt_camera* cam, const zrt_params* p,
     if (need.att_elems * sizeof(uint32_t) > (16ull << 30))
       return fail(ZRT_E_UNSUPPORTED, "max_depth too large for the per-lane attenuation stack");
     if (c->att.n < need.att_elems) c->att.alloc(need.att_elems);
-    HIPCHK(hipMemsetAsync(c->scratch.p, 0, zrt::kScratchSlots * sizeof(unsigned long long), st));
+    if (first)
+      HIPCHK(hipMemsetAsync(c->scratch.p, 0, zrt::kScratchSlots * sizeof(unsigned long long), st));
+    else  // a run's later passes add into its counters and keep its error flag: a new work counter only
+      HIPCHK(hipMemsetAsync(c->scratch.p + zrt::kWorkSlot, 0, sizeof(unsigned long long), st));
+    if (run_pass) {
+      // the previous pass's events wait to be added into the run's times (no host wait here)
+      if (!first) {
+        zrt::fold_pass_times(c, false);  // (frees the sets of passes that have finished)
+        if (c->ev_spare.empty()) {
+          zrt_ctx::EvSet e;
+          HIPCHK(hipEventCreate(&e.pre));
+          HIPCHK(hipEventCreate(&e.e0));
+          HIPCHK(hipEventCreate(&e.e1));
+          c->ev_spare.push_back(e);
+        }
+        const zrt_ctx::EvSet e = c->ev_spare.back();
+        c->ev_spare.pop_back();
+        c->run_pending.push_back({c->ev_pre, c->ev0, c->ev1, c->pass_probed});
+        c->ev_pre = e.pre;
+        c->ev0 = e.e0;
+        c->ev1 = e.e1;
+      }
+      if (first) HIPCHK(hipMemsetAsync(c->accum.p, 0, c->accum.n * sizeof(float4), st));
+    }
 
     zrt::KArgs a{};
     a.nodes = c->nodes.p;
@@ -5514,11 +5715,11 @@ int zrt_ctx_render_tiles(zrt_ctx* c, const zrt_camera* cam, const zrt_params* p,
     a.f_height = float(p->height);
     a.inv_width = 1.0f / a.f_width;  // IEEE RN(1/width): dev::div_core's y
     a.inv_height = 1.0f / a.f_height;
-    a.color_scale = 1.0f / float(p->samples_per_pixel);  // raytrace.zig:157
+    a.color_scale = 1.0f / float(pass.samples_after);  // raytrace.zig:157
     a.width = p->width;
     a.height = p->height;
     a.xbound = g.xbound;
-    a.spp = p->samples_per_pixel;
+    a.spp = pass.pass_samples;
     a.max_depth = p->max_depth;
     a.tiles_x = g.tiles_x;
     a.rank = p->rank;
@@ -5567,7 +5768,7 @@ int zrt_ctx_render_tiles(zrt_ctx* c, const zrt_camera* cam, const zrt_params* p,
     // at max_depth 0, which shades nothing - copies none: its plan holds no region for it)
     a.n_mats = ZRT_MATS_LDS_ONLY && kmode == 3 && !lp.mats_in_lds ? 0u : c->n_mats;
     a.mats_in_lds = lp.mats_in_lds;
-    a.seed_mix = p->seed * 0x9E3779B97F4A7C15ULL;
+    a.seed_mix = p->seed * 0x9E3779B97F4A7C15ULL + pass.key_offset;
     if (std::getenv("ZRT_DEBUG_LAUNCH"))
       std::fprintf(stderr, "zrt launch: mode %d stk16 %d grid %u (%d blocks/CU x %d CUs) lds %zu B "
                    "(stack rows %u, top nodes %u @%u, att rows %u @%u, mats %u @%u)\n", mode, int(stk16), grid,
@@ -5589,7 +5790,16 @@ int zrt_ctx_render_tiles(zrt_ctx* c, const zrt_camera* cam, const zrt_params* p,
     HIPCHK(hipEventRecord(c->ev_pre, st));
     bool schedule =
         mode == 3 && !(p->flags & ZRT_FLAG_NO_SCHEDULE) && p->samples_per_pixel >= 128 && my_tiles >= 2;
-    if (schedule) schedule = zrt::schedule_tiles(c, a, p->prng, stk16, my_tiles, grid, lds, st);
+    // (a run decides once, by its cap: its first pass probes, the later ones reuse the
+    // order and the probe's counters)
+    if (schedule && !first) {
+      schedule = c->run_ordered;
+      if (schedule) a.tile_order = c->tile_order.p;
+    } else if (schedule) {
+      schedule = zrt::schedule_tiles(c, a, p->prng, stk16, my_tiles, grid, lds, st);
+    }
+    if (run_pass && first) c->run_ordered = schedule;
+    c->pass_probed = schedule && first;
     c->scheduled = schedule;
     // the lockstep loop takes its interval from the probe's lane efficiency (auto_sync;
     // ZRT_SYNC or ZRT_AUTO_SYNC=0: the fixed interval, A/B)
@@ -5601,7 +5811,7 @@ int zrt_ctx_render_tiles(zrt_ctx* c, const zrt_camera* cam, const zrt_params* p,
     c->scanline_rows = 0;
     if (p->flags & ZRT_FLAG_SCANLINES) {  // (not the probe's: set after it)
       if (c->scanlines.n < size_t(p->height) * 3) c->scanlines.alloc(size_t(p->height) * 3);
-      HIPCHK(hipMemsetAsync(c->scanlines.p, 0, size_t(p->height) * 3 * sizeof(unsigned long long), st));
+      if (first) HIPCHK(hipMemsetAsync(c->scanlines.p, 0, size_t(p->height) * 3 * sizeof(unsigned long long), st));
       a.scanlines = c->scanlines.p;
       c->scanline_rows = p->height;
     }
@@ -5630,7 +5840,19 @@ int zrt_ctx_render_tiles(zrt_ctx* c, const zrt_camera* cam, const zrt_params* p,
       HIPCHK(hipLaunchKernel(kfn, dim3(grid), dim3(zrt::kBlock), args, lds, st));
     }
     HIPCHK(hipEventRecord(c->ev1, st));
-    if (my_tiles > 0) {
+    if (run_pass) {
+      HIPCHK(hipMemsetAsync(c->metrics.p, 0, zrt::kMetricWords * sizeof(unsigned long long), st));
+      if (my_tiles > 0) {
+        const uint32_t n_slots = my_tiles * 64u;
+        const float prev_scale = c->run_done ? 1.0f / float(c->run_done) : 0.0f;
+        hipLaunchKernelGGL(zrt::accumulate_kernel, dim3((n_slots + 255) / 256), dim3(256), 0, st, c->partial.p,
+                           c->accum.p, dev_tiles, n_slots, n_chunks, p->world_size, p->rank, g.tiles_x, g.xbound,
+                           p->height, prev_scale, a.color_scale, c->scratch.p + zrt::kErrorSlot, c->metrics.p);
+        HIPCHK(hipGetLastError());
+      }
+      HIPCHK(hipMemcpyAsync(c->metrics_host, c->metrics.p, zrt::kMetricWords * sizeof(unsigned long long),
+                            hipMemcpyDeviceToHost, st));
+    } else if (my_tiles > 0) {
       const uint32_t n_slots = my_tiles * 64u;
       hipLaunchKernelGGL(zrt::finalize_kernel, dim3((n_slots + 255) / 256), dim3(256), 0, st, c->partial.p,
                          dev_tiles, n_slots, n_chunks, p->world_size, p->rank, g.tiles_x, g.xbound, p->height,
@@ -5650,7 +5872,7 @@ int zrt_ctx_render_tiles(zrt_ctx* c, const zrt_camera* cam, const zrt_params* p,
       pixels += uint64_t(w) * h;
     }
     c->last_pixels = uint32_t(pixels);
-    c->last_spp = p->samples_per_pixel;
+    c->last_spp = pass.samples_after;
     c->last_tiles = my_tiles;
     c->last_rank = p->rank;
     c->last_world = p->world_size;
@@ -5662,9 +5884,99 @@ int zrt_ctx_render_tiles(zrt_ctx* c, const zrt_camera* cam, const zrt_params* p,
     c->last_qn = qn;
     c->last_guard = a.guard;
     c->launched = 1;
+    c->run_stats = run_pass;
+    if (run_pass) {
+      c->run_done = pass.samples_after;
+      c->run_passes += 1;
+      c->pass_samples = pass.pass_samples;
+    } else {
+      c->run_live = false;  // a plain render overwrites the probe's buffers: it ends the run
+    }
     return ZRT_OK;
   }
   ZRT_CATCH_ALL
+}
+
+int zrt_ctx_render_tiles(zrt_ctx* c, const zrt_camera* cam, const zrt_params* p, float* dev_tiles,
+                         void* hip_stream) {
+  return launch_frame(c, cam, p, dev_tiles, hip_stream, false, 0);
+}
+
+int zrt_ctx_accum_begin(zrt_ctx* c, const zrt_camera* cam, const zrt_params* p) {
+  if (!c || !cam) return fail(ZRT_E_INVALID, "null argument");
+  int rc = zrt::validate_params(p);
+  if (rc) return rc;
+  rc = params_fit_ctx(c, p);
+  if (rc) return rc;
+  try {
+    HIPCHK(hipSetDevice(c->device));
+    c->run_live = false;
+    const uint64_t n_slots = uint64_t(zrt::rank_tiles(zrt::geometry(p), p->rank, p->world_size)) * 64u;
+    if (c->accum.n < n_slots) c->accum.alloc(n_slots);
+    if (c->metrics.n < zrt::kMetricWords) c->metrics.alloc(zrt::kMetricWords);
+    if (!c->metrics_host) {
+      HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&c->metrics_host),
+                           zrt::kMetricWords * sizeof(unsigned long long), hipHostMallocDefault));
+      std::memset(c->metrics_host, 0, zrt::kMetricWords * sizeof(unsigned long long));
+    }
+    // (a restarted run's unread pass times are dropped; the accumulator, the counters
+    // and the error flag are zeroed by the first pass, on its stream)
+    for (const zrt_ctx::EvSet& e : c->run_pending) c->ev_spare.push_back(e);
+    c->run_pending.clear();
+    c->run_render_ms = c->run_sched_ms = 0.0;
+    c->run_cam = *cam;
+    c->run_p = *p;
+    c->run_done = 0;
+    c->run_passes = 0;
+    c->run_ordered = false;
+    c->run_live = true;
+    return ZRT_OK;
+  }
+  ZRT_CATCH_ALL
+}
+
+int zrt_ctx_accum_pass(zrt_ctx* c, uint32_t n_samples, float* dev_tiles, void* hip_stream) {
+  if (!c || !dev_tiles) return fail(ZRT_E_INVALID, "null argument");
+  if (!c->run_live)
+    return fail(ZRT_E_INVALID, "no accumulation run is live on this context (zrt_ctx_accum_begin; a "
+                               "zrt_ctx_render_tiles ends the run)");
+  // a device error of an earlier pass is sticky for the run: its accumulator is poisoned
+  if (c->run_passes > 0 && hipEventQuery(c->ev_done) == hipSuccess && *c->err_host != 0) {
+    c->err_reported = true;
+    return fail(ZRT_E_UNSUPPORTED, zrt::device_error_msg(*c->err_host));
+  }
+  (void)hipGetLastError();
+  return launch_frame(c, &c->run_cam, &c->run_p, dev_tiles, hip_stream, true, n_samples);
+}
+
+int zrt_ctx_accum_info(zrt_ctx* c, zrt_pass_info* out) {
+  if (!c || !out) return fail(ZRT_E_INVALID, "null argument");
+  if (!c->launched || !c->run_stats) return fail(ZRT_E_INVALID, "the context's last launch was not a zrt_ctx_accum_pass");
+  try {
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipEventSynchronize(c->ev_done));
+    std::memset(out, 0, sizeof(*out));
+    out->samples_done = c->run_done;
+    out->pass_samples = c->pass_samples;
+    uint32_t bits = 0;  // the shards' sum and maximum
+    for (uint32_t k = 0; k < zrt::kMetricShards; ++k) {
+      out->changed_pixels += c->metrics_host[k * zrt::kMetricStride];
+      bits = std::max(bits, uint32_t(c->metrics_host[k * zrt::kMetricStride + 1]));
+    }
+    std::memcpy(&out->max_abs_change, &bits, 4);
+    float ms = 0.0f, sched = 0.0f;
+    HIPCHK(hipEventElapsedTime(&ms, c->ev_pre, c->ev1));
+    HIPCHK(hipEventElapsedTime(&sched, c->ev_pre, c->ev0));
+    out->render_ms = ms;
+    out->schedule_ms = c->pass_probed ? sched : 0.0f;
+    return zrt::launch_status(c, true);
+  }
+  ZRT_CATCH_ALL
+}
+
+int zrt_debug_pass_plan(const zrt_params* params, uint32_t done, uint32_t n_samples, zrt_pass_plan* out) {
+  if (!out) return fail(ZRT_E_INVALID, "null argument");
+  return zrt::plan_pass(params, done, n_samples, out);
 }
 
 int zrt_ctx_stats(zrt_ctx* c, zrt_stats* out) {
@@ -5718,6 +6030,11 @@ int zrt_ctx_stats(zrt_ctx* c, zrt_stats* out) {
     HIPCHK(hipEventElapsedTime(&sched, c->ev_pre, c->ev0));
     out->render_ms = ms;
     out->schedule_ms = c->scheduled ? sched : 0.0f;
+    if (c->run_stats) {  // a run: the sums over its passes (the counters above were never re-zeroed)
+      zrt::fold_pass_times(c, true);
+      out->render_ms = c->run_render_ms + ms;
+      out->schedule_ms = float(c->run_sched_ms + (c->pass_probed ? sched : 0.0f));
+    }
     out->used_bvh = c->use_bvh ? 1 : 0;
     out->bvh_nodes = c->n_nodes;
     out->bvh_max_depth = c->bvh_depth;
@@ -5901,6 +6218,59 @@ int zrt_render_progress(const zrt_scene* scene, const zrt_camera* camera, const 
                         float* out_rgb, zrt_stats* stats, zrt_scanline* scanlines) {
   if (!scanlines) return fail(ZRT_E_INVALID, "null argument");
   return zrt::render_one(scene, camera, params, out_rgb, stats, scanlines);
+}
+
+int zrt_render_progressive(const zrt_scene* scene, const zrt_camera* camera, const zrt_params* params,
+                           uint32_t pass_samples, zrt_pass_fn on_pass, void* user, float* out_rgb,
+                           zrt_stats* stats) {
+  if (!camera || !out_rgb) return fail(ZRT_E_INVALID, "null argument");
+  int rc = zrt::validate_params(params);
+  if (rc) return rc;
+  zrt_params p = *params;
+  p.rank = 0;
+  p.world_size = 1;
+  const uint32_t chunk = p.sample_chunk ? p.sample_chunk : ZRT_DEFAULT_SAMPLE_CHUNK;
+  // whole chunks per pass (a pass must start on a chunk boundary); 0: the default
+  const uint64_t per_pass = pass_samples ? (uint64_t(pass_samples) + chunk - 1) / chunk * chunk
+                                         : uint64_t(ZRT_DEFAULT_PASS_CHUNKS) * chunk;
+  zrt_ctx* c = nullptr;
+  rc = zrt_ctx_create(scene, &p, &c);
+  if (rc) return rc;
+  std::unique_ptr<zrt_ctx, int (*)(zrt_ctx*)> guard(c, zrt_ctx_destroy);
+  try {
+    uint32_t n_tiles = 0;
+    rc = zrt_ctx_tile_count(c, &p, &n_tiles);
+    if (rc) return rc;
+    zrt::DevBuf<float> tiles, frame;
+    tiles.alloc(size_t(n_tiles) * 64 * 3);
+    frame.alloc(size_t(p.width) * p.height * 3);
+    rc = zrt_ctx_accum_begin(c, camera, &p);
+    if (rc) return rc;
+    const size_t frame_bytes = sizeof(float) * 3 * size_t(p.width) * p.height;
+    for (uint32_t done = 0; done < p.samples_per_pixel;) {
+      const uint32_t n = uint32_t(std::min<uint64_t>(per_pass, p.samples_per_pixel - done));
+      rc = zrt_ctx_accum_pass(c, n, tiles.p, nullptr);
+      if (rc) return rc;
+      rc = zrt_ctx_assemble(c, &p, tiles.p, frame.p, nullptr);
+      if (rc) return rc;
+      done += n;
+      if (!on_pass && done < p.samples_per_pixel) continue;  // nobody looks: the passes queue up
+      HIPCHK(hipStreamSynchronize(c->stream));
+      HIPCHK(hipMemcpy(out_rgb, frame.p, frame_bytes, hipMemcpyDeviceToHost));
+      if (on_pass) {
+        zrt_pass_info info;
+        rc = zrt_ctx_accum_info(c, &info);
+        if (rc) return rc;
+        if (on_pass(user, out_rgb, &info) != 0) break;
+      }
+    }
+    zrt_stats s;
+    rc = zrt_ctx_stats(c, &s);
+    if (rc) return rc;
+    if (stats) *stats = s;
+    return ZRT_OK;
+  }
+  ZRT_CATCH_ALL
 }
 
 // ---- several GPUs from one host thread (zrt_multi_*, zrt_render_multi) -------
