@@ -487,6 +487,99 @@ typedef struct zrt_pass_plan {
 } zrt_pass_plan;
 int zrt_debug_pass_plan(const zrt_params* params, uint32_t done, uint32_t n_samples, zrt_pass_plan* out);
 
+/* ---- adaptive sampling: stop refining 8x8 tiles that have converged --------- *
+ * An accumulation run whose passes ("levels") cover only the tiles still active.
+ *
+ * Levels.  chunk is the sample chunk in use (zrt_pass_plan.chunk).  L_0 is
+ * first_level rounded up to whole chunks, at least one chunk; L_k = 2 L_(k-1)
+ * while that is below the cap, params->samples_per_pixel; the last level is the
+ * cap itself (it may be ragged, as a run's last pass).  Level k renders samples
+ * [L_(k-1), L_k) (L_(-1) = 0) of every pixel of the active tiles, as a pass does.
+ * L_0 >= cap: one level, no decision, zrt_render's frame.
+ *
+ * Decision, after every level k >= 1 but the last, per in-frame pixel of an
+ * active tile: A = the preview at L_k (the pixel's sum x 1.0f / float(L_k), as
+ * every pass resolves it), H = the preview at L_(k-1); in f32, in this order,
+ * nothing fused:
+ *     d = (|A.r - H.r| + |A.g - H.g|) + |A.b - H.b|
+ *     s = (A.r + A.g) + A.b
+ *     pass = d <= tolerance * sqrtf(s)      (IEEE sqrtf; a NaN compares false)
+ * With P(2n) = (P(n) + Q) / 2, Q the mean of the second half, P(2n) - P(n) =
+ * (Q - P(n)) / 2 has the variance of P(2n) itself: |A - H| is a one-sample
+ * estimate of the preview's standard error (the half-buffer estimate), taken
+ * relative to sqrt(brightness).  A tile has converged when every in-frame pixel
+ * of it passes (lanes outside the frame pass; a tile with a NaN pixel runs to
+ * the cap).  A converged tile is frozen: its samples stay at L_k and its sums
+ * and its pixels in dev_tiles are not touched again.  Both previews are, bit for
+ * bit, full renders at L_k and L_(k-1) samples per pixel, so the decisions are a
+ * function of two such frames.  The surviving tiles keep their order (the
+ * scheduling probe's costliest-first order, or tile order).
+ *
+ * tolerance must be finite and >= 0 (ZRT_E_INVALID otherwise). */
+typedef struct zrt_adaptive {
+  float tolerance;
+  uint32_t first_level;  /* samples per pixel of level 0 (0: one chunk) */
+  uint32_t reserved[2];
+} zrt_adaptive;
+
+typedef struct zrt_level_info {
+  uint32_t level_samples;       /* L_k: samples per pixel of the tiles rendered in this level */
+  uint32_t tiles_rendered;      /* this rank's tiles active in the level */
+  uint32_t tiles_active_after;  /* of them, still active (0 after the last level) */
+  uint32_t reserved;
+  uint64_t samples_rendered;    /* in-frame pixels of the rendered tiles x the level's samples */
+  uint64_t changed_pixels;      /* as zrt_pass_info, over the rendered tiles */
+  float    max_abs_change;
+  float    render_ms;           /* probe (level 0, if scheduled) + render kernel */
+  float    schedule_ms;         /* the probe + sort; 0 on every level but a scheduled run's first */
+  uint32_t reserved2;
+} zrt_level_info;
+
+/* zrt_ctx_adapt_begin starts an adaptive run as zrt_ctx_accum_begin starts a
+ * plain one (same validation; one run of either kind is live per context, a
+ * begin of either kind restarts, a zrt_ctx_render_tiles ends it).
+ *
+ * zrt_ctx_adapt_level renders and resolves the next level and returns once the
+ * number of surviving tiles is known: one stream wait per level, at most
+ * log2(cap / L_0) + 2 levels.  out may be NULL.  dev_tiles must be the same
+ * buffer for the whole run: frozen tiles keep what was last written there.
+ * ZRT_E_INVALID: no live adaptive run, after the last level, or nothing active.
+ * A device error is sticky as in a plain run: NaN in every tile of the rank,
+ * ZRT_E_UNSUPPORTED from this and every later level.
+ *
+ * zrt_ctx_adapt_samples: samples per pixel of each local tile so far (per_tile:
+ * cap_tiles >= zrt_ctx_tile_count entries).  zrt_ctx_stats / zrt_ctx_scanlines
+ * report the run so far: samples_processed = sum over tiles of in-frame pixels x
+ * samples(tile), rays_processed = samples + reflections - recursion_depth_hits
+ * (counted by the kernel under ZRT_FLAG_STATS). */
+int zrt_ctx_adapt_begin(zrt_ctx* ctx, const zrt_camera* camera, const zrt_params* params,
+                        const zrt_adaptive* adaptive);
+int zrt_ctx_adapt_level(zrt_ctx* ctx, float* dev_tiles, void* hip_stream, zrt_level_info* out);
+int zrt_ctx_adapt_samples(zrt_ctx* ctx, uint32_t* per_tile, uint32_t cap_tiles);
+
+/* zrt_render with adaptive sampling on one GPU (params->device).  After each
+ * level on_level (may be NULL) receives the assembled frame so far (it is
+ * out_rgb) and the level's info; a nonzero return stops the run.  out_samples
+ * (may be NULL): width*height samples per pixel in the frame's layout (0 for
+ * pixels outside the rendered square, x >= height). */
+typedef int (*zrt_level_fn)(void* user, const float* rgb, const zrt_level_info* info);
+int zrt_render_adaptive(const zrt_scene* scene, const zrt_camera* camera, const zrt_params* params,
+                        const zrt_adaptive* adaptive, zrt_level_fn on_level, void* user, float* out_rgb,
+                        uint32_t* out_samples, zrt_stats* stats);
+/* zrt_render_adaptive that also returns the run's per-scanline counters, as
+ * zrt_render_progress does (scanlines: params->height entries; a row's samples
+ * are its tiles' own). */
+int zrt_render_adaptive_progress(const zrt_scene* scene, const zrt_camera* camera, const zrt_params* params,
+                                 const zrt_adaptive* adaptive, zrt_level_fn on_level, void* user, float* out_rgb,
+                                 uint32_t* out_samples, zrt_stats* stats, zrt_scanline* scanlines);
+
+/* The level list L_0 .. of a run with these params, with no device (the launch
+ * path calls the same function; it returns the refusals above and those of
+ * zrt_debug_pass_plan for the cap).  *n_levels: the number of levels; the first
+ * min(cap, *n_levels) are written to levels. */
+int zrt_debug_adapt_plan(const zrt_params* params, const zrt_adaptive* adaptive, uint32_t* levels,
+                         uint32_t cap, uint32_t* n_levels);
+
 /* ---- host-side scene ingestion (the caller side of the seam) ------------- *
  * Restatement of scenes.zig / obj_reader.zig / png_image.zig texture loading
  * so tests and bench can build the reference's scenes without Zig.  Assets are

@@ -178,6 +178,45 @@ def render_progressive(scene, camera: _ffi.Camera, params: RenderParams, pass_sa
     return out, st.as_dict(), infos
 
 
+def _adaptive(tolerance: float, first_level: int) -> _ffi.Adaptive:
+    return _ffi.Adaptive(tolerance=tolerance, first_level=first_level)
+
+
+def render_adaptive(scene, camera: _ffi.Camera, params: RenderParams, tolerance: float, first_level: int = 0,
+                    on_level=None):
+    """render() with adaptive sampling (zrt_render_adaptive; the rule: zrt.h): 8x8 tiles whose
+    pixels all changed by no more than tolerance * sqrt(brightness) between two sample levels
+    stop there.  Returns (image, samples uint32[H, W] per pixel, stats, [info dict per level]).
+    on_level(image so far, info dict) is called after every level; a true return stops the run."""
+    view = scene.view if isinstance(scene, LoadedScene) else scene
+    out = np.zeros((params.height, params.width, 3), dtype=np.float32)
+    samples = np.zeros((params.height, params.width), dtype=np.uint32)
+    st = _ffi.Stats()
+    p = params.abi()
+    ad = _adaptive(tolerance, first_level)
+    infos = []
+
+    def cb(_user, _rgb, info):
+        infos.append(info.contents.as_dict())
+        return 1 if on_level is not None and on_level(out, infos[-1]) else 0
+
+    check(lib().zrt_render_adaptive(view, C.byref(camera), C.byref(p), C.byref(ad), _ffi.LEVEL_FN(cb), None,
+                                    out.ctypes.data_as(C.POINTER(C.c_float)),
+                                    samples.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(st)))
+    return out, samples, st.as_dict(), infos
+
+
+def adapt_plan(params: RenderParams, tolerance: float, first_level: int = 0) -> list:
+    """The sample levels of an adaptive run with these params (zrt_debug_adapt_plan; no
+    device).  Raises ZrtError for what the run would refuse."""
+    p = params.abi()
+    ad = _adaptive(tolerance, first_level)
+    levels = (C.c_uint32 * 32)()
+    n = C.c_uint32()
+    check(lib().zrt_debug_adapt_plan(C.byref(p), C.byref(ad), levels, 32, C.byref(n)))
+    return list(levels[:n.value])
+
+
 def debug_pass_plan(params: RenderParams, done: int, n_samples: int) -> dict:
     """How an accumulation run with these params (samples_per_pixel = its cap) renders
     samples [done, done + n_samples) (zrt_debug_pass_plan; no device): the zrt_pass_plan
@@ -333,6 +372,28 @@ class RenderContext:
         out = _ffi.PassInfo()
         check(lib().zrt_ctx_accum_info(self._h, C.byref(out)))
         return out.as_dict()
+
+    def adapt_begin(self, camera, params: RenderParams, tolerance: float, first_level: int = 0):
+        """Start an adaptive run (zrt_ctx_adapt_begin): params.samples_per_pixel is its cap."""
+        p = params.abi()
+        ad = _adaptive(tolerance, first_level)
+        check(lib().zrt_ctx_adapt_begin(self._h, C.byref(camera), C.byref(p), C.byref(ad)))
+        self._adapt_tiles = self.tile_count(params)
+
+    def adapt_level(self, dev_tiles: int, stream: int = 0) -> dict:
+        """Render and resolve the run's next level over the tiles still active
+        (zrt_ctx_adapt_level; returns once the surviving count is known): the level's info.
+        dev_tiles must be the same buffer for the whole run."""
+        out = _ffi.LevelInfo()
+        check(lib().zrt_ctx_adapt_level(self._h, C.c_void_p(dev_tiles), C.c_void_p(stream or None), C.byref(out)))
+        return out.as_dict()
+
+    def adapt_samples(self) -> np.ndarray:
+        """Samples per pixel of each local tile so far (zrt_ctx_adapt_samples)."""
+        n = getattr(self, "_adapt_tiles", 0)
+        out = np.zeros(max(1, n), dtype=np.uint32)
+        check(lib().zrt_ctx_adapt_samples(self._h, out.ctypes.data_as(C.POINTER(C.c_uint32)), n))
+        return out[:n]
 
     def sync(self):
         """Wait for the last launch; raises ZrtError on a device error (zrt_ctx_sync)."""

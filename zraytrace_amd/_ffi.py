@@ -145,6 +145,24 @@ class PassPlan(C.Structure):
 PASS_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_float), C.POINTER(PassInfo))
 
 
+class Adaptive(C.Structure):
+    _fields_ = [("tolerance", C.c_float), ("first_level", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
+class LevelInfo(C.Structure):
+    _fields_ = [("level_samples", C.c_uint32), ("tiles_rendered", C.c_uint32), ("tiles_active_after", C.c_uint32),
+                ("reserved", C.c_uint32), ("samples_rendered", C.c_uint64), ("changed_pixels", C.c_uint64),
+                ("max_abs_change", C.c_float), ("render_ms", C.c_float), ("schedule_ms", C.c_float),
+                ("reserved2", C.c_uint32)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_ if not name.startswith("reserved")}
+
+
+# zrt_level_fn: int (*)(void* user, const float* rgb, const zrt_level_info* info)
+LEVEL_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_float), C.POINTER(LevelInfo))
+
+
 class BvhNode(C.Structure):
     _fields_ = [("min", Vec3), ("left", C.c_int32), ("max", Vec3), ("right", C.c_int32)]
 
@@ -195,6 +213,16 @@ SIGNATURES = [
     ("zrt_render_progressive", C.c_int, [C.POINTER(Scene), C.POINTER(Camera), C.POINTER(Params), C.c_uint32,
                                          PASS_FN, _P, C.POINTER(C.c_float), C.POINTER(Stats)]),
     ("zrt_debug_pass_plan", C.c_int, [C.POINTER(Params), C.c_uint32, C.c_uint32, C.POINTER(PassPlan)]),
+    ("zrt_ctx_adapt_begin", C.c_int, [_P, C.POINTER(Camera), C.POINTER(Params), C.POINTER(Adaptive)]),
+    ("zrt_ctx_adapt_level", C.c_int, [_P, _P, _P, C.POINTER(LevelInfo)]),
+    ("zrt_ctx_adapt_samples", C.c_int, [_P, C.POINTER(C.c_uint32), C.c_uint32]),
+    ("zrt_render_adaptive", C.c_int, [C.POINTER(Scene), C.POINTER(Camera), C.POINTER(Params), C.POINTER(Adaptive),
+                                      LEVEL_FN, _P, C.POINTER(C.c_float), C.POINTER(C.c_uint32), C.POINTER(Stats)]),
+    ("zrt_render_adaptive_progress", C.c_int, [C.POINTER(Scene), C.POINTER(Camera), C.POINTER(Params),
+                                               C.POINTER(Adaptive), LEVEL_FN, _P, C.POINTER(C.c_float),
+                                               C.POINTER(C.c_uint32), C.POINTER(Stats), C.POINTER(Scanline)]),
+    ("zrt_debug_adapt_plan", C.c_int, [C.POINTER(Params), C.POINTER(Adaptive), C.POINTER(C.c_uint32), C.c_uint32,
+                                       C.POINTER(C.c_uint32)]),
     ("zrt_scene_load", C.c_int, [C.c_uint32, C.c_char_p, C.POINTER(_P), C.POINTER(Camera)]),
     ("zrt_scene_view", C.POINTER(Scene), [_P]),
     ("zrt_scene_free", None, [_P]),

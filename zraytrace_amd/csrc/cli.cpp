@@ -17,6 +17,11 @@
 // sample chunks; 0: the library's default): one line per pass on stderr in place
 // of the scanline lines, and the PNG rewritten after every pass - the final PNG
 // and the summary's counters are those of a run without the variable.
+// $ZRT_ADAPTIVE_TOL=<t> renders with adaptive sampling (zrt_render_adaptive: 8x8 tiles
+// that have converged within t stop early; $ZRT_ADAPTIVE_FIRST = the first level's
+// samples, default one chunk): one line per level, then the scanline lines once, from the
+// rows accumulated over the levels (a row's samples are its tiles' own), and
+// $ZRT_ADAPTIVE_MAP=<file.png> receives the sample-count map as a grey PNG (samples / cap).
 #include <unistd.h>
 
 #include <chrono>
@@ -102,6 +107,15 @@ int on_pass(void* user, const float* rgb, const zrt_pass_info* info) {
   return zrt_image_write_png(pv->filename, rgb, pv->width, pv->height) != ZRT_OK;
 }
 
+int on_level(void*, const float*, const zrt_level_info* info) {
+  std::fprintf(stderr, "Level: %u samples Tiles: %u Still active: %u Samples: %llu Changed pixels: %llu "
+                       "Max change: %.6g Msamples/s: %.2f\n",
+               info->level_samples, info->tiles_rendered, info->tiles_active_after,
+               (unsigned long long)info->samples_rendered, (unsigned long long)info->changed_pixels,
+               double(info->max_abs_change), double(info->samples_rendered) / (double(info->render_ms) / 1000.0) / 1e6);
+  return 0;
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -164,6 +178,14 @@ int main(int argc, char** argv) {
     return 1;
   }
 
+  const char* tol_env = std::getenv("ZRT_ADAPTIVE_TOL");
+  if (tol_env && (pass_env || !devices.empty())) {
+    std::fprintf(stderr, "error: ZRT_ADAPTIVE_TOL renders on one GPU, not in plain passes: unset ZRT_DEVICES and "
+                         "ZRT_PASS_SAMPLES (or ZRT_ADAPTIVE_TOL)\n");
+    zrt_scene_free(data);
+    return 1;
+  }
+
   std::fprintf(stderr, "Raytrace start\n");
   std::fprintf(stderr, " - Surfaces:                 %u\n", scene->n_prims);
   std::fprintf(stderr, " - Pixels:                   %ux%u\n", unsigned(width), unsigned(height));
@@ -176,7 +198,16 @@ int main(int argc, char** argv) {
   std::vector<zrt_scanline> rows(height);
   zrt_stats stats;
   const auto t_render = std::chrono::steady_clock::now();
-  if (pass_env) {
+  std::vector<uint32_t> sample_map;
+  if (tol_env) {
+    zrt_adaptive ad;
+    std::memset(&ad, 0, sizeof(ad));
+    ad.tolerance = std::strtof(tol_env, nullptr);
+    if (const char* first = std::getenv("ZRT_ADAPTIVE_FIRST")) ad.first_level = uint32_t(std::strtoul(first, nullptr, 10));
+    sample_map.assign(size_t(width) * height, 0u);
+    rc = zrt_render_adaptive_progress(scene, &camera, &params, &ad, on_level, nullptr, image.data(),
+                                      sample_map.data(), &stats, rows.data());
+  } else if (pass_env) {
     const Preview pv{filename, width, height, uint64_t(height) * height};
     rc = zrt_render_progressive(scene, &camera, &params, uint32_t(std::strtoul(pass_env, nullptr, 10)), on_pass,
                                 const_cast<Preview*>(&pv), image.data(), &stats);
@@ -230,6 +261,12 @@ int main(int argc, char** argv) {
                double(stats.rays_processed) / render_runtime / 1e6, call, stats.n_gpus);
 
   rc = zrt_image_write_png(filename, image.data(), width, height);
+  if (const char* map = std::getenv("ZRT_ADAPTIVE_MAP"); map && tol_env && rc == ZRT_OK) {
+    std::vector<float> grey(size_t(width) * height * 3);
+    for (size_t i = 0; i < sample_map.size(); ++i)
+      grey[3 * i] = grey[3 * i + 1] = grey[3 * i + 2] = float(sample_map[i]) / float(samples);
+    rc = zrt_image_write_png(map, grey.data(), width, height);
+  }
   zrt_scene_free(data);
   if (rc != ZRT_OK) {
     std::fprintf(stderr, "error: %s\n", zrt_last_error());

@@ -3997,6 +3997,132 @@ __global__ void accumulate_kernel(const float4* __restrict__ partial, float4* __
   }
 }
 
+// accumulate_kernel for a level of an adaptive run (zrt_ctx_adapt_level; the rule:
+// zrt.h "adaptive sampling"): one wave per ACTIVE tile (wave w takes tile active[w]),
+// lane = pixel.  The level's chunk sums are added onto accum in chunk order and the
+// tile's preview (sum x new_scale) is written to out, as accumulate_kernel does; the
+// sums read before the add are the previous level's, so H = before x prev_scale is the
+// preview at L_(k-1) with no second buffer: accum is the snapshot.  decide: lanes
+// failing d <= tolerance * sqrtf(s) are balloted and a tile without one is frozen.
+// tile_done[lt] = the tile's samples per pixel (level_samples), bit 31 set once frozen.
+// metrics as accumulate_kernel's, over the tiles touched, plus word 2 of each pair's
+// shard: in-frame pixels resolved.  A nonzero error flag: the waves stride over ALL
+// the rank's tiles, leave NaN in accum and out and freeze them (nothing survives).
+constexpr uint32_t kTileFrozen = 0x80000000u;
+__global__ void resolve_kernel(const float4* __restrict__ partial, float4* __restrict__ accum,
+                               float* __restrict__ out, const uint32_t* __restrict__ active, uint32_t n_active,
+                               uint32_t my_tiles, uint32_t pass_chunks, uint32_t world, uint32_t rank,
+                               uint32_t tiles_x, uint32_t xbound, uint32_t height, float prev_scale, float new_scale,
+                               float tolerance, uint32_t decide, uint32_t level_samples,
+                               uint32_t* __restrict__ tile_done, const unsigned long long* __restrict__ error_flag,
+                               unsigned long long* __restrict__ metrics) {
+  const uint32_t w = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, p = threadIdx.x & 63u;
+  if (w >= n_active) return;  // (whole waves)
+  const size_t n_slots = size_t(my_tiles) * 64u;
+  if (*error_flag != 0ull) {
+    const float nan = __builtin_nanf("");
+    for (uint32_t lt = w; lt < my_tiles; lt += n_active) {
+      const size_t i = size_t(lt) * 64u + p;
+      accum[i] = make_float4(nan, nan, nan, 0.0f);
+      out[3ull * i + 0] = nan;
+      out[3ull * i + 1] = nan;
+      out[3ull * i + 2] = nan;
+      if (p == 0u) tile_done[lt] |= kTileFrozen;
+    }
+    return;
+  }
+  const uint32_t lt = active[w];
+  const size_t i = size_t(lt) * 64u + p;
+  const uint32_t t = lt * world + rank;
+  const uint32_t px = (t % tiles_x) * 8u + (p & 7u);
+  const uint32_t py = (t / tiles_x) * 8u + (p >> 3);
+  const bool in_frame = px < xbound && py < height;
+  float r = 0.0f, g = 0.0f, b = 0.0f;
+  float change = 0.0f;
+  bool changed = false, failing = false;
+  if (in_frame) {
+    const float4 before = accum[i];
+    r = before.x;
+    g = before.y;
+    b = before.z;
+    for (uint32_t j = 0; j < pass_chunks; ++j) {  // [chunk][slot] over all the rank's slots
+      const float4 v = partial[(size_t)j * n_slots + i];
+      r += v.x;
+      g += v.y;
+      b += v.z;
+    }
+    accum[i] = make_float4(r, g, b, 0.0f);
+    r *= new_scale;
+    g *= new_scale;
+    b *= new_scale;
+    const float pr = before.x * prev_scale, pg = before.y * prev_scale, pb = before.z * prev_scale;
+    const float dr = fabsf(r - pr), dg = fabsf(g - pg), db = fabsf(b - pb);
+    change = dr > change ? dr : change;  // (a NaN compares false: skipped)
+    change = dg > change ? dg : change;
+    change = db > change ? db : change;
+    changed = png_channel_dev(r) != png_channel_dev(pr) || png_channel_dev(g) != png_channel_dev(pg) ||
+              png_channel_dev(b) != png_channel_dev(pb);
+    const float d = (dr + dg) + db;
+    const float s = (r + g) + b;
+    failing = !(d <= tolerance * __builtin_sqrtf(s));  // (HIP's IEEE sqrtf; a NaN anywhere: the lane fails)
+  }
+  out[3ull * i + 0] = r;
+  out[3ull * i + 1] = g;
+  out[3ull * i + 2] = b;
+  for (int off = 32; off > 0; off >>= 1) {
+    const float o = __shfl_xor(change, off, 64);
+    change = o > change ? o : change;
+  }
+  const unsigned long long ballot = __ballot(changed), fails = __ballot(failing), inside = __ballot(in_frame);
+  if (p == 0u) {
+    tile_done[lt] = level_samples | (decide && fails == 0ull ? kTileFrozen : 0u);
+    unsigned long long* m = metrics + (blockIdx.x % kMetricShards) * kMetricStride;
+    if (ballot) atomicAdd(&m[0], (unsigned long long)__popcll(ballot));
+    if (inside) atomicAdd(&m[2], (unsigned long long)__popcll(inside));
+    unsigned int* mx = reinterpret_cast<unsigned int*>(&m[1]);
+    const unsigned int bits = __float_as_uint(change);
+    if (bits > __hip_atomic_load(mx, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(mx, bits);
+  }
+}
+
+// The tiles of `in` that resolve_kernel left unfrozen, packed into `out` in their
+// order (so the probe's costliest-first order survives a level), and their number.
+// One block: per round of blockDim.x list entries a ballot and the lanes' mbcnt ranks
+// within each wave, the waves' counts scanned through LDS, a running base across rounds.
+// out[base + ...] stays below the number of entries read, so within n.
+constexpr uint32_t kCompactBlock = 1024;
+__global__ void __launch_bounds__(kCompactBlock) compact_kernel(const uint32_t* __restrict__ in, uint32_t n,
+                                                                const uint32_t* __restrict__ tile_done,
+                                                                uint32_t* __restrict__ out,
+                                                                uint32_t* __restrict__ count) {
+  __shared__ uint32_t wave_count[kCompactBlock / 64];
+  const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
+  uint32_t base = 0;
+  for (uint32_t start = 0; start < n; start += kCompactBlock) {
+    const uint32_t pos = start + threadIdx.x;
+    uint32_t lt = 0;
+    bool keep = false;
+    if (pos < n) {
+      lt = in[pos];
+      keep = (tile_done[lt] & kTileFrozen) == 0u;
+    }
+    const unsigned long long b = __ballot(keep);
+    const uint32_t below = __builtin_amdgcn_mbcnt_hi(uint32_t(b >> 32), __builtin_amdgcn_mbcnt_lo(uint32_t(b), 0u));
+    if (lane == 0u) wave_count[wv] = uint32_t(__popcll(b));
+    __syncthreads();
+    uint32_t off = 0, total = 0;
+    for (uint32_t k = 0; k < kCompactBlock / 64; ++k) {
+      const uint32_t v = wave_count[k];
+      off += k < wv ? v : 0u;
+      total += v;
+    }
+    if (keep) out[base + off + below] = lt;
+    base += total;
+    __syncthreads();
+  }
+  if (threadIdx.x == 0u) *count = base;
+}
+
 // Scatter gathered rank tiles into the framebuffer (raytrace.zig:182 layout).
 // Packed (stride_px == 0): rank r's tiles start at rank_base[r].  Padded: rank r
 // starts at r * stride_px, as a gather of equal per-rank counts leaves them.
@@ -4342,7 +4468,20 @@ struct zrt_ctx {
   // earlier passes' events not yet added into run_render_ms / run_sched_ms, and spare sets
   std::vector<EvSet> run_pending, ev_spare;
   double run_render_ms = 0, run_sched_ms = 0;
+  // ---- an adaptive run (zrt_ctx_adapt_*): an accumulation run over the active tiles ----
+  bool adapt = false;          // the live run is adaptive
+  bool last_adapt = false;     // the last launch was a level: stats / scanlines count per-tile samples
+  zrt_adaptive adapt_a{};
+  std::vector<uint32_t> adapt_levels;  // L_0 .. (zrt::plan_adapt)
+  uint32_t adapt_k = 0;        // the next level
+  uint32_t adapt_active = 0;   // tiles in active[adapt_cur]
+  uint32_t adapt_cur = 0;      // the list the next level's launch reads (the other one is written)
+  uint64_t adapt_samples = 0;  // sum over tiles of in-frame pixels x samples so far
+  float* adapt_tiles = nullptr;  // the run's dev_tiles
+  zrt::DevBuf<uint32_t> active[2], tile_done, active_count;
+  uint32_t* count_host = nullptr;  // the surviving count of the last level, pinned
   ~zrt_ctx() {
+    if (count_host) (void)hipHostFree(count_host);
     for (const std::vector<EvSet>* v : {&run_pending, &ev_spare})
       for (const EvSet& e : *v) {
         (void)hipEventDestroy(e.pre);
@@ -5410,6 +5549,25 @@ int plan_pass(const zrt_params* p, uint32_t done, uint32_t n_samples, zrt_pass_p
   return ZRT_OK;
 }
 
+// The levels of an adaptive run (zrt.h "adaptive sampling"; zrt_debug_adapt_plan
+// reports the same): L_0 = first_level in whole chunks (at least one), doubled while
+// below the cap, then the cap.  Every level but the last ends on a chunk boundary, so
+// every level is a pass plan_pass accepts.
+int plan_adapt(const zrt_params* p, const zrt_adaptive* ad, std::vector<uint32_t>* levels) {
+  if (!ad) return fail(ZRT_E_INVALID, "null argument");
+  zrt_pass_plan whole{};
+  const int rc = plan_pass(p, 0u, p ? p->samples_per_pixel : 0u, &whole);  // (validates the params and the cap)
+  if (rc) return rc;
+  if (!(ad->tolerance >= 0.0f) || !std::isfinite(ad->tolerance))
+    return fail(ZRT_E_INVALID, "zrt_adaptive.tolerance must be finite and >= 0");
+  const uint64_t cap = p->samples_per_pixel, chunk = whole.chunk;
+  uint64_t L = std::max<uint64_t>(1u, (uint64_t(ad->first_level) + chunk - 1) / chunk) * chunk;
+  levels->clear();
+  for (; L < cap; L *= 2) levels->push_back(uint32_t(L));
+  levels->push_back(uint32_t(cap));
+  return ZRT_OK;
+}
+
 // RCCL for zrt_render_multi, opened on first use so that single-GPU callers do
 // not load it: the copy already in the process when torch brought one (same
 // soname, librccl.so.1), else ROCm's.
@@ -5624,6 +5782,7 @@ static int launch_frame(zrt_ctx* c, const zrt_camera* cam, const zrt_params* p, 
   int rc = zrt::plan_pass(p, run_pass ? c->run_done : 0u, run_pass ? n_samples : (p ? p->samples_per_pixel : 0u), &pass);
   if (rc) return rc;
   const bool first = !run_pass || c->run_passes == 0;  // the launch zeroes the counters it adds into
+  const bool adapt = run_pass && c->adapt;  // a level of an adaptive run: the active tiles only
   rc = params_fit_ctx(c, p);
   if (rc) return rc;
   try {
@@ -5653,7 +5812,8 @@ static int launch_frame(zrt_ctx* c, const zrt_camera* cam, const zrt_params* p, 
     uint32_t grid = uint32_t(c->cu_count) * uint32_t(per_cu);
     const uint32_t chunk = pass.chunk;
     const uint32_t n_chunks = pass.pass_chunks;
-    const uint64_t work64 = uint64_t(my_tiles) * n_chunks;  // units: (tile, chunk); < 2^32 (plan_pass)
+    const uint32_t n_act = adapt ? c->adapt_active : my_tiles;  // tiles the launch hands out
+    const uint64_t work64 = uint64_t(n_act) * n_chunks;  // units: (tile, chunk); < 2^32 (plan_pass)
     const uint32_t work = uint32_t(work64);
     // one wave per unit at the start; more waves than units would only idle
     grid = std::max(1u, std::min(grid, (work + (zrt::kBlock / 64) - 1) / (zrt::kBlock / 64)));
@@ -5690,6 +5850,7 @@ static int launch_frame(zrt_ctx* c, const zrt_camera* cam, const zrt_params* p, 
         c->ev1 = e.e1;
       }
       if (first) HIPCHK(hipMemsetAsync(c->accum.p, 0, c->accum.n * sizeof(float4), st));
+      if (first && adapt) HIPCHK(hipMemsetAsync(c->tile_done.p, 0, c->tile_done.n * sizeof(uint32_t), st));
     }
 
     zrt::KArgs a{};
@@ -5799,6 +5960,15 @@ static int launch_frame(zrt_ctx* c, const zrt_camera* cam, const zrt_params* p, 
       schedule = zrt::schedule_tiles(c, a, p->prng, stk16, my_tiles, grid, lds, st);
     }
     if (run_pass && first) c->run_ordered = schedule;
+    if (adapt) {
+      // the launch hands out the active list: level 0's is the probe's order where the run
+      // is scheduled (else the identity zrt_ctx_adapt_begin uploaded), a later level's is
+      // what the previous level's compaction wrote
+      uint32_t* list = c->active[c->adapt_cur].p;
+      if (first && schedule)
+        HIPCHK(hipMemcpyAsync(list, c->tile_order.p, size_t(my_tiles) * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
+      a.tile_order = list;
+    }
     c->pass_probed = schedule && first;
     c->scheduled = schedule;
     // the lockstep loop takes its interval from the probe's lane efficiency (auto_sync;
@@ -5842,7 +6012,25 @@ static int launch_frame(zrt_ctx* c, const zrt_camera* cam, const zrt_params* p, 
     HIPCHK(hipEventRecord(c->ev1, st));
     if (run_pass) {
       HIPCHK(hipMemsetAsync(c->metrics.p, 0, zrt::kMetricWords * sizeof(unsigned long long), st));
-      if (my_tiles > 0) {
+      if (adapt) {
+        // resolve the active tiles, decide (levels 1 .. last - 1), pack the survivors in
+        // order into the other list; the host reads their number (zrt_ctx_adapt_level)
+        const uint32_t decide = c->adapt_k >= 1 && c->adapt_k + 1 < c->adapt_levels.size() ? 1u : 0u;
+        const float prev_scale = c->run_done ? 1.0f / float(c->run_done) : 0.0f;
+        HIPCHK(hipMemsetAsync(c->active_count.p, 0, sizeof(uint32_t), st));
+        if (n_act > 0) {
+          hipLaunchKernelGGL(zrt::resolve_kernel, dim3((n_act + 3) / 4), dim3(256), 0, st, c->partial.p, c->accum.p,
+                             dev_tiles, c->active[c->adapt_cur].p, n_act, my_tiles, n_chunks, p->world_size, p->rank,
+                             g.tiles_x, g.xbound, p->height, prev_scale, a.color_scale, c->adapt_a.tolerance, decide,
+                             pass.samples_after, c->tile_done.p, c->scratch.p + zrt::kErrorSlot, c->metrics.p);
+          HIPCHK(hipGetLastError());
+          hipLaunchKernelGGL(zrt::compact_kernel, dim3(1), dim3(zrt::kCompactBlock), 0, st,
+                             c->active[c->adapt_cur].p, n_act, c->tile_done.p, c->active[c->adapt_cur ^ 1u].p,
+                             c->active_count.p);
+          HIPCHK(hipGetLastError());
+        }
+        HIPCHK(hipMemcpyAsync(c->count_host, c->active_count.p, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+      } else if (my_tiles > 0) {
         const uint32_t n_slots = my_tiles * 64u;
         const float prev_scale = c->run_done ? 1.0f / float(c->run_done) : 0.0f;
         hipLaunchKernelGGL(zrt::accumulate_kernel, dim3((n_slots + 255) / 256), dim3(256), 0, st, c->partial.p,
@@ -5885,6 +6073,7 @@ static int launch_frame(zrt_ctx* c, const zrt_camera* cam, const zrt_params* p, 
     c->last_guard = a.guard;
     c->launched = 1;
     c->run_stats = run_pass;
+    c->last_adapt = adapt;
     if (run_pass) {
       c->run_done = pass.samples_after;
       c->run_passes += 1;
@@ -5929,6 +6118,7 @@ int zrt_ctx_accum_begin(zrt_ctx* c, const zrt_camera* cam, const zrt_params* p) 
     c->run_done = 0;
     c->run_passes = 0;
     c->run_ordered = false;
+    c->adapt = false;
     c->run_live = true;
     return ZRT_OK;
   }
@@ -5937,7 +6127,7 @@ int zrt_ctx_accum_begin(zrt_ctx* c, const zrt_camera* cam, const zrt_params* p) 
 
 int zrt_ctx_accum_pass(zrt_ctx* c, uint32_t n_samples, float* dev_tiles, void* hip_stream) {
   if (!c || !dev_tiles) return fail(ZRT_E_INVALID, "null argument");
-  if (!c->run_live)
+  if (!c->run_live || c->adapt)
     return fail(ZRT_E_INVALID, "no accumulation run is live on this context (zrt_ctx_accum_begin; a "
                                "zrt_ctx_render_tiles ends the run)");
   // a device error of an earlier pass is sticky for the run: its accumulator is poisoned
@@ -5979,6 +6169,126 @@ int zrt_debug_pass_plan(const zrt_params* params, uint32_t done, uint32_t n_samp
   return zrt::plan_pass(params, done, n_samples, out);
 }
 
+int zrt_debug_adapt_plan(const zrt_params* params, const zrt_adaptive* adaptive, uint32_t* levels, uint32_t cap,
+                         uint32_t* n_levels) {
+  if (!n_levels || (cap && !levels)) return fail(ZRT_E_INVALID, "null argument");
+  std::vector<uint32_t> L;
+  const int rc = zrt::plan_adapt(params, adaptive, &L);
+  if (rc) return rc;
+  *n_levels = uint32_t(L.size());
+  for (uint32_t k = 0; k < cap && k < L.size(); ++k) levels[k] = L[k];
+  return ZRT_OK;
+}
+
+int zrt_ctx_adapt_begin(zrt_ctx* c, const zrt_camera* cam, const zrt_params* p, const zrt_adaptive* ad) {
+  if (!c || !cam || !ad) return fail(ZRT_E_INVALID, "null argument");
+  std::vector<uint32_t> levels;
+  int rc = zrt::plan_adapt(p, ad, &levels);
+  if (rc) return rc;
+  rc = zrt_ctx_accum_begin(c, cam, p);  // the accumulator, the metrics, the run's state
+  if (rc) return rc;
+  try {
+    c->run_live = false;
+    const uint32_t my_tiles = zrt::rank_tiles(zrt::geometry(p), p->rank, p->world_size);
+    // (no level of an earlier run is in flight: zrt_ctx_adapt_level waits for its own)
+    std::vector<uint32_t> ids(my_tiles);
+    for (uint32_t i = 0; i < my_tiles; ++i) ids[i] = i;
+    if (c->active[0].n < my_tiles || c->active[1].n < my_tiles || c->tile_done.n < my_tiles) {
+      c->active[0].alloc(my_tiles);
+      c->active[1].alloc(my_tiles);
+      c->tile_done.alloc(my_tiles);
+    }
+    if (my_tiles)
+      HIPCHK(hipMemcpy(c->active[0].p, ids.data(), size_t(my_tiles) * sizeof(uint32_t), hipMemcpyHostToDevice));
+    if (c->active_count.n < 1) c->active_count.alloc(1);
+    if (!c->count_host)
+      HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&c->count_host), sizeof(uint32_t), hipHostMallocDefault));
+    *c->count_host = 0;
+    c->adapt_a = *ad;
+    c->adapt_levels = levels;
+    c->adapt_k = 0;
+    c->adapt_cur = 0;
+    c->adapt_active = my_tiles;
+    c->adapt_samples = 0;
+    c->adapt_tiles = nullptr;
+    c->adapt = true;
+    c->run_live = true;
+    return ZRT_OK;
+  }
+  ZRT_CATCH_ALL
+}
+
+int zrt_ctx_adapt_level(zrt_ctx* c, float* dev_tiles, void* hip_stream, zrt_level_info* out) {
+  if (!c || !dev_tiles) return fail(ZRT_E_INVALID, "null argument");
+  if (!c->run_live || !c->adapt)
+    return fail(ZRT_E_INVALID, "no adaptive run is live on this context (zrt_ctx_adapt_begin; a "
+                               "zrt_ctx_render_tiles ends the run)");
+  // a device error of an earlier level is sticky for the run (every level is waited for)
+  if (c->run_passes > 0 && *c->err_host != 0) {
+    c->err_reported = true;
+    return fail(ZRT_E_UNSUPPORTED, zrt::device_error_msg(*c->err_host));
+  }
+  if (c->adapt_k >= c->adapt_levels.size()) return fail(ZRT_E_INVALID, "the adaptive run has rendered its last level");
+  if (c->adapt_active == 0 && c->run_passes > 0) return fail(ZRT_E_INVALID, "no tile of the adaptive run is active");
+  if (c->adapt_tiles && c->adapt_tiles != dev_tiles)
+    return fail(ZRT_E_INVALID, "dev_tiles differs from the run's earlier levels' (frozen tiles live there)");
+  const uint32_t level = c->adapt_levels[c->adapt_k], rendered = c->adapt_active;
+  const uint32_t level_samples = level - c->run_done;
+  const int rc = launch_frame(c, &c->run_cam, &c->run_p, dev_tiles, hip_stream, true, level_samples);
+  if (rc) return rc;
+  try {
+    HIPCHK(hipEventSynchronize(c->ev_done));  // the one wait of the level: the surviving count is here
+    c->adapt_tiles = dev_tiles;
+    c->adapt_k += 1;
+    c->adapt_cur ^= 1u;
+    c->adapt_active = c->adapt_k < c->adapt_levels.size() ? *c->count_host : 0u;
+    uint64_t pixels = 0, changed = 0;
+    uint32_t bits = 0;
+    for (uint32_t k = 0; k < zrt::kMetricShards; ++k) {
+      changed += c->metrics_host[k * zrt::kMetricStride];
+      bits = std::max(bits, uint32_t(c->metrics_host[k * zrt::kMetricStride + 1]));
+      pixels += c->metrics_host[k * zrt::kMetricStride + 2];
+    }
+    if (*c->err_host == 0) c->adapt_samples += pixels * level_samples;
+    if (out) {
+      std::memset(out, 0, sizeof(*out));
+      out->level_samples = level;
+      out->tiles_rendered = rendered;
+      out->tiles_active_after = c->adapt_active;
+      out->samples_rendered = pixels * level_samples;
+      out->changed_pixels = changed;
+      std::memcpy(&out->max_abs_change, &bits, 4);
+      float ms = 0.0f, sched = 0.0f;
+      HIPCHK(hipEventElapsedTime(&ms, c->ev_pre, c->ev1));
+      HIPCHK(hipEventElapsedTime(&sched, c->ev_pre, c->ev0));
+      out->render_ms = ms;
+      out->schedule_ms = c->pass_probed ? sched : 0.0f;
+    }
+    return zrt::launch_status(c, true);
+  }
+  ZRT_CATCH_ALL
+}
+
+int zrt_ctx_adapt_samples(zrt_ctx* c, uint32_t* per_tile, uint32_t cap_tiles) {
+  if (!c || !per_tile) return fail(ZRT_E_INVALID, "null argument");
+  if (!c->run_live || !c->adapt) return fail(ZRT_E_INVALID, "no adaptive run is live on this context");
+  const uint32_t my_tiles = zrt::rank_tiles(zrt::geometry(&c->run_p), c->run_p.rank, c->run_p.world_size);
+  if (cap_tiles < my_tiles) return fail(ZRT_E_INVALID, "per_tile holds fewer entries than the rank has tiles");
+  try {
+    HIPCHK(hipSetDevice(c->device));
+    if (c->run_passes == 0) {
+      std::fill(per_tile, per_tile + my_tiles, 0u);
+      return ZRT_OK;
+    }
+    HIPCHK(hipEventSynchronize(c->ev_done));
+    if (my_tiles)
+      HIPCHK(hipMemcpy(per_tile, c->tile_done.p, size_t(my_tiles) * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    for (uint32_t i = 0; i < my_tiles; ++i) per_tile[i] &= ~zrt::kTileFrozen;
+    return ZRT_OK;
+  }
+  ZRT_CATCH_ALL
+}
+
 int zrt_ctx_stats(zrt_ctx* c, zrt_stats* out) {
   if (!c || !out) return fail(ZRT_E_INVALID, "null argument");
   if (!c->launched) return fail(ZRT_E_INVALID, "zrt_ctx_stats before any zrt_ctx_render_tiles");
@@ -6001,9 +6311,9 @@ int zrt_ctx_stats(zrt_ctx* c, zrt_stats* out) {
     out->reflections = h[zrt::kReflections];
     out->background_hits = h[zrt::kBackground];
     // rayColor calls = samples + reflections = rays + depth-limit hits
-    out->rays_processed = c->last_stats ? h[zrt::kRays]
-                                        : uint64_t(c->last_pixels) * c->last_spp + h[zrt::kReflections] -
-                                              h[zrt::kDepthHits];
+    // (an adaptive run: per-tile sample counts, summed level by level)
+    const uint64_t samples = c->last_adapt ? c->adapt_samples : uint64_t(c->last_pixels) * c->last_spp;
+    out->rays_processed = c->last_stats ? h[zrt::kRays] : samples + h[zrt::kReflections] - h[zrt::kDepthHits];
     out->node_visits = h[zrt::kNodes];
     out->prim_tests = h[zrt::kTriTests] + h[zrt::kSphereTests];
     out->sphere_tests = h[zrt::kSphereTests];
@@ -6022,7 +6332,7 @@ int zrt_ctx_stats(zrt_ctx* c, zrt_stats* out) {
     out->guard = c->last_guard;
     out->texel_bytes = c->texel_bytes;
     out->pixels_processed = c->last_pixels;
-    out->samples_processed = uint64_t(c->last_pixels) * c->last_spp;
+    out->samples_processed = samples;
     out->preprocess_ms = c->preprocess_ms;
     out->upload_ms = c->upload_ms;
     float ms = 0.0f, sched = 0.0f;
@@ -6066,11 +6376,21 @@ int add_scanlines(zrt_ctx* c, zrt_scanline* out, uint32_t height) {
   HIPCHK(hipEventSynchronize(c->ev_done));
   std::vector<unsigned long long> rows(size_t(height) * 3);
   HIPCHK(hipMemcpy(rows.data(), c->scanlines.p, rows.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+  std::vector<uint32_t> done;  // an adaptive run: samples per pixel of each tile
+  if (c->last_adapt) {
+    done.resize(std::max(1u, c->last_tiles));
+    HIPCHK(hipMemcpy(done.data(), c->tile_done.p, size_t(c->last_tiles) * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  }
+  std::vector<uint64_t> row_samples(height, 0);
   for (uint32_t lt = 0; lt < c->last_tiles; ++lt) {  // pixels of this rank's tiles, per row
     const uint32_t t = lt * c->last_world + c->last_rank;
     const uint32_t tx = t % c->last_tiles_x, ty = t / c->last_tiles_x;
     const uint32_t w = std::min(8u, c->last_xbound - tx * 8u);
-    for (uint32_t y = ty * 8u; y < std::min(height, ty * 8u + 8u); ++y) out[y].pixels += w;
+    const uint32_t spp = c->last_adapt ? done[lt] & ~kTileFrozen : c->last_spp;
+    for (uint32_t y = ty * 8u; y < std::min(height, ty * 8u + 8u); ++y) {
+      out[y].pixels += w;
+      row_samples[y] += uint64_t(w) * spp;
+    }
   }
   for (uint32_t y = 0; y < height; ++y) {
     out[y].recursion_depth_hits += rows[3 * y];
@@ -6079,7 +6399,7 @@ int add_scanlines(zrt_ctx* c, zrt_scanline* out, uint32_t height) {
   }
   // samples and rays from the pixels (rays = rayColor calls - depth-limit hits)
   for (uint32_t y = 0; y < height; ++y) {
-    out[y].samples = out[y].pixels * uint64_t(c->last_spp);
+    out[y].samples += row_samples[y];
     out[y].rays = out[y].samples + out[y].reflections - out[y].recursion_depth_hits;
   }
   return ZRT_OK;
@@ -6271,6 +6591,89 @@ int zrt_render_progressive(const zrt_scene* scene, const zrt_camera* camera, con
     return ZRT_OK;
   }
   ZRT_CATCH_ALL
+}
+
+namespace zrt {
+namespace {
+int render_adaptive(const zrt_scene* scene, const zrt_camera* camera, const zrt_params* params,
+                    const zrt_adaptive* adaptive, zrt_level_fn on_level, void* user, float* out_rgb,
+                    uint32_t* out_samples, zrt_stats* stats, zrt_scanline* rows) {
+  if (!camera || !out_rgb || !adaptive) return fail(ZRT_E_INVALID, "null argument");
+  std::vector<uint32_t> levels;
+  int rc = zrt::plan_adapt(params, adaptive, &levels);
+  if (rc) return rc;
+  zrt_params p = *params;
+  p.rank = 0;
+  p.world_size = 1;
+  if (rows) p.flags |= ZRT_FLAG_SCANLINES;
+  zrt_ctx* c = nullptr;
+  rc = zrt_ctx_create(scene, &p, &c);
+  if (rc) return rc;
+  std::unique_ptr<zrt_ctx, int (*)(zrt_ctx*)> guard(c, zrt_ctx_destroy);
+  try {
+    uint32_t n_tiles = 0;
+    rc = zrt_ctx_tile_count(c, &p, &n_tiles);
+    if (rc) return rc;
+    zrt::DevBuf<float> tiles, frame;
+    tiles.alloc(size_t(n_tiles) * 64 * 3);
+    frame.alloc(size_t(p.width) * p.height * 3);
+    HIPCHK(hipMemset(tiles.p, 0, sizeof(float) * tiles.n));
+    rc = zrt_ctx_adapt_begin(c, camera, &p, adaptive);
+    if (rc) return rc;
+    const size_t frame_bytes = sizeof(float) * 3 * size_t(p.width) * p.height;
+    for (size_t k = 0; k < levels.size(); ++k) {
+      zrt_level_info info;
+      rc = zrt_ctx_adapt_level(c, tiles.p, nullptr, &info);
+      if (rc) return rc;
+      const bool over = info.tiles_active_after == 0;
+      if (on_level || over) {
+        rc = zrt_ctx_assemble(c, &p, tiles.p, frame.p, nullptr);
+        if (rc) return rc;
+        HIPCHK(hipStreamSynchronize(c->stream));
+        HIPCHK(hipMemcpy(out_rgb, frame.p, frame_bytes, hipMemcpyDeviceToHost));
+      }
+      if (on_level && on_level(user, out_rgb, &info) != 0 && !over) {
+        break;
+      }
+      if (over) break;
+    }
+    if (out_samples) {
+      std::vector<uint32_t> per_tile(std::max(1u, n_tiles));
+      rc = zrt_ctx_adapt_samples(c, per_tile.data(), n_tiles);
+      if (rc) return rc;
+      const zrt::Geometry g = zrt::geometry(&p);
+      std::fill(out_samples, out_samples + size_t(p.width) * p.height, 0u);
+      for (uint32_t y = 0; y < p.height; ++y)
+        for (uint32_t x = 0; x < g.xbound; ++x)
+          out_samples[size_t(y) * p.width + x] = per_tile[(y / 8u) * g.tiles_x + x / 8u];
+    }
+    zrt_stats s;
+    rc = zrt_ctx_stats(c, &s);
+    if (rc) return rc;
+    if (rows) {
+      std::memset(rows, 0, sizeof(zrt_scanline) * p.height);
+      rc = add_scanlines(c, rows, p.height);
+      if (rc) return rc;
+    }
+    if (stats) *stats = s;
+    return ZRT_OK;
+  }
+  ZRT_CATCH_ALL
+}
+}  // namespace
+}  // namespace zrt
+
+int zrt_render_adaptive(const zrt_scene* scene, const zrt_camera* camera, const zrt_params* params,
+                        const zrt_adaptive* adaptive, zrt_level_fn on_level, void* user, float* out_rgb,
+                        uint32_t* out_samples, zrt_stats* stats) {
+  return zrt::render_adaptive(scene, camera, params, adaptive, on_level, user, out_rgb, out_samples, stats, nullptr);
+}
+
+int zrt_render_adaptive_progress(const zrt_scene* scene, const zrt_camera* camera, const zrt_params* params,
+                                 const zrt_adaptive* adaptive, zrt_level_fn on_level, void* user, float* out_rgb,
+                                 uint32_t* out_samples, zrt_stats* stats, zrt_scanline* scanlines) {
+  if (!scanlines) return fail(ZRT_E_INVALID, "null argument");
+  return zrt::render_adaptive(scene, camera, params, adaptive, on_level, user, out_rgb, out_samples, stats, scanlines);
 }
 
 // ---- several GPUs from one host thread (zrt_multi_*, zrt_render_multi) -------
