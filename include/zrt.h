@@ -580,6 +580,100 @@ int zrt_render_adaptive_progress(const zrt_scene* scene, const zrt_camera* camer
 int zrt_debug_adapt_plan(const zrt_params* params, const zrt_adaptive* adaptive, uint32_t* levels,
                          uint32_t cap, uint32_t* n_levels);
 
+/* ---- denoising: first-hit feature buffers and an a-trous filter ------------- *
+ * A frame of few samples is noisy; an edge-avoiding a-trous wavelet filter
+ * (Dammertz et al. 2010) smooths it where the surface under a pixel's
+ * neighbours is the same surface.  What it knows of the surface is a feature
+ * buffer: two float4 per pixel in the frame's layout (row-major, row 0 = bottom),
+ *     {N.x, N.y, N.z, t}   the first hit's normal (HitRecord.normal) and t
+ *     {A.r, A.g, A.b, id}  its albedo; id = the bits of uint32(prim + 1), 0: a miss
+ * The filter is a pure function of (frame, features, params, zrt_denoise): the
+ * features may come from anywhere.
+ *
+ * Definition.  All f32, nothing fused, in this order.  D = the pixels with
+ * x < height and y < height (raytrace.zig:168's square); pixels outside D are
+ * copied.  h = {1/16, 1/4, 3/8, 1/4, 1/16} for offsets -2 .. 2.  On the host,
+ * in f32: inv_c = 1.0f / sigma_color, likewise inv_n, inv_a, inv_z.  C_0 = the
+ * input.  Iteration i = 0 .. iterations - 1 has step s = 2^i and colour scale
+ * kc = inv_c * float(1 << i) (sigma_color halves every iteration).  Per pixel p
+ * of D: rz = 1.0f / t(p) (IEEE) if id(p) != 0, else 0; kz = inv_z * rz;
+ * acc = (0, 0, 0), wsum = 0.  Then dy = -2 .. 2 (outer), dx = -2 .. 2 (inner),
+ * q = p + s (dx, dy):
+ *     q outside D: skip.
+ *     dx = dy = 0: w = h(0) * h(0), no tests.
+ *     otherwise:  (id(p) == 0) != (id(q) == 0): skip.  w = h(dx) * h(dy); for each
+ *       term that is on, in the order colour, normal, albedo, depth: compute t_x,
+ *       skip the tap unless t_x > 0, then w = w * t_x:
+ *         t_c = 1.0f - ((|dR| + |dG|) + |dB|) * kc         d = C_i(p) - C_i(q)
+ *         t_n = 1.0f - ((dNx*dNx + dNy*dNy) + dNz*dNz) * inv_n
+ *         t_a = 1.0f - ((|dAr| + |dAg|) + |dAb|) * inv_a
+ *         t_z = 1.0f - |t(p) - t(q)| * kz
+ *       skip the tap unless w > 0.
+ *     acc.c = acc.c + C_i(q).c * w per channel, then wsum = wsum + w.
+ * C_(i+1)(p).c = acc.c / wsum (IEEE).  The output is C_iterations.
+ * The weights are tents (1 - x, cut at 0), not exp(-x): every step is an f32
+ * operation a caller can restate exactly, and the tap loop holds no
+ * transcendental.  A NaN compares false: a NaN neighbour is skipped, a pixel
+ * whose own colour is NaN stays NaN through the untested centre tap, so the NaN
+ * frame of a device error stays recognisable. */
+typedef struct zrt_denoise {
+  uint32_t iterations;      /* 1..8; 0 selects ZRT_DEFAULT_DENOISE_ITERATIONS */
+  float sigma_color;        /* each: finite > 0 = on, 0 = that term off (factor 1) */
+  float sigma_normal;
+  float sigma_albedo;
+  float sigma_depth;        /* relative: a fraction of the centre pixel's depth */
+  uint32_t reserved[3];
+} zrt_denoise;
+enum { ZRT_DEFAULT_DENOISE_ITERATIONS = 5u };
+
+/* The default filter (host only).  The sigmas are the winner of the grid search
+ * of tools/denoise_probe.py (profiles/r10/denoise/defaults.json). */
+int zrt_denoise_defaults(zrt_denoise* out);
+
+/* The feature buffer of a frame (see above) written to dev_features (a device
+ * pointer, width*height*8 f32, 16-byte aligned) on hip_stream (NULL: the
+ * context's own).  Asynchronous, as zrt_ctx_render_tiles; params validated the
+ * same way; the whole frame whatever rank / world_size say; one ray per pixel.
+ * The ray goes through the pixel centre: u = float(x) / float(width), v =
+ * float(y) / float(height) - raytrace.zig:173-174's ((float)x + r - 0.5f) /
+ * f_width at r = 0.5 - then Camera.getRay (camera.zig:46-51) and Ray.init.
+ * The hit is rayColor's closest hit (t_min = 0.001, t_max = inf) through
+ * params->traversal with the grazing-triangle guard on, as zrt_trace.  On a
+ * hit: N = HitRecord.normal (the outward normal flipped against the ray), t
+ * the hit's t, A the material's texture albedo at the hit's (u, v) for
+ * Lambertian and metal, (1, 1, 1) for a dielectric, id = uint32(prim + 1), prim
+ * the index in scene->prims.  On a miss: N = 0, t = 0, A = backgroundColor(d),
+ * id = 0.  Pixels with x >= height (outside the rendered square,
+ * raytrace.zig:168): all eight floats 0.  A traversal stack overflow sets the
+ * context's error flag, as in a render launch (zrt_ctx_sync reports it), and
+ * the buffer then holds NaN. */
+int zrt_ctx_features(zrt_ctx* ctx, const zrt_camera* camera, const zrt_params* params,
+                     float* dev_features, void* hip_stream);
+
+/* Filters dev_frame into dev_out (device pointers, width*height*3 f32 each;
+ * dev_out != dev_frame) guided by dev_features (width*height*8 f32, 16-byte
+ * aligned) on hip_stream (NULL: the context's own).  Asynchronous; one launch
+ * per iteration.  The ping-pong planes belong to the context, so one denoise
+ * is in flight per context.  params gives width and height and is validated as
+ * zrt_ctx_render_tiles validates it.  ZRT_E_INVALID: a negative, NaN or infinite
+ * sigma, iterations > 8, height > width, dev_out == dev_frame, a null or
+ * misaligned pointer. */
+int zrt_ctx_denoise(zrt_ctx* ctx, const zrt_params* params, const zrt_denoise* dn,
+                    const float* dev_frame, const float* dev_features,
+                    float* dev_out, void* hip_stream);
+/* Device time of the last zrt_ctx_denoise in ms (HIP events; waits for it). */
+int zrt_ctx_denoise_ms(zrt_ctx* ctx, double* ms);
+
+/* One-shot on one GPU (params->device): zrt_render (adaptive NULL) or
+ * zrt_render_adaptive, then assemble, zrt_ctx_features and zrt_ctx_denoise on
+ * the device, then the copy out.  dn NULL: zrt_denoise_defaults.  out_rgb: the
+ * denoised frame; out_noisy (may be NULL): the unfiltered frame, bit for bit
+ * zrt_render's / zrt_render_adaptive's; out_features (may be NULL): width*
+ * height*8 f32; denoise_ms (may be NULL): the filter's device time. */
+int zrt_render_denoised(const zrt_scene* scene, const zrt_camera* camera, const zrt_params* params,
+                        const zrt_adaptive* adaptive, const zrt_denoise* dn, float* out_rgb, float* out_noisy,
+                        float* out_features, zrt_stats* stats, double* denoise_ms);
+
 /* ---- host-side scene ingestion (the caller side of the seam) ------------- *
  * Restatement of scenes.zig / obj_reader.zig / png_image.zig texture loading
  * so tests and bench can build the reference's scenes without Zig.  Assets are

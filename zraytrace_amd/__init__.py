@@ -34,7 +34,7 @@ def lib():
 
 
 # csrc/Makefile ID_SRC, in its order, then include/zrt.h
-_ID_SRC = ("render.hip", "bvh_gpu.hip", "accel_build.cpp", "accel_build.hpp", "bvh_build.cpp", "bvh_build.hpp",
+_ID_SRC = ("render.hip", "bvh_gpu.hip", "denoise.hip", "denoise.hpp", "accel_build.cpp", "accel_build.hpp", "bvh_build.cpp", "bvh_build.hpp",
            "device_math.hpp", "zrt.hpp", "scene_io.cpp", "image_io.cpp", "cli.cpp")
 
 
@@ -227,6 +227,37 @@ def debug_pass_plan(params: RenderParams, done: int, n_samples: int) -> dict:
     return out.as_dict()
 
 
+def denoise_defaults() -> _ffi.Denoise:
+    """The default a-trous filter (zrt_denoise_defaults; no device): iterations and the
+    sigmas tools/denoise_probe.py's grid search chose."""
+    out = _ffi.Denoise()
+    check(lib().zrt_denoise_defaults(C.byref(out)))
+    return out
+
+
+def render_denoised(scene, camera: _ffi.Camera, params: RenderParams, tolerance: float = None, first_level: int = 0,
+                    denoise: _ffi.Denoise = None):
+    """render() (tolerance None) or render_adaptive(), then the first-hit feature buffers and
+    the a-trous filter on the device (zrt_render_denoised; denoise None: the defaults).
+    Returns (rgb: the denoised frame, noisy: the unfiltered one, features float32[H, W, 8]:
+    {N.xyz, t, A.rgb, id bits}, stats); stats["denoise_ms"] is the filter's device time."""
+    view = scene.view if isinstance(scene, LoadedScene) else scene
+    f = C.POINTER(C.c_float)
+    rgb = np.zeros((params.height, params.width, 3), dtype=np.float32)
+    noisy = np.zeros((params.height, params.width, 3), dtype=np.float32)
+    features = np.zeros((params.height, params.width, 8), dtype=np.float32)
+    st = _ffi.Stats()
+    ms = C.c_double()
+    p = params.abi()
+    ad = C.byref(_adaptive(tolerance, first_level)) if tolerance is not None else None
+    dn = C.byref(denoise) if denoise is not None else None
+    check(lib().zrt_render_denoised(view, C.byref(camera), C.byref(p), ad, dn, rgb.ctypes.data_as(f),
+                                    noisy.ctypes.data_as(f), features.ctypes.data_as(f), C.byref(st), C.byref(ms)))
+    stats = st.as_dict()
+    stats["denoise_ms"] = ms.value
+    return rgb, noisy, features, stats
+
+
 def _scanlines_np(rows) -> np.ndarray:
     """zrt_scanline[height] -> uint64 array [height, 6] (columns: _ffi.SCANLINE_FIELDS)."""
     return np.ctypeslib.as_array(rows).view(np.uint64).reshape(len(rows), 6).copy()
@@ -394,6 +425,27 @@ class RenderContext:
         out = np.zeros(max(1, n), dtype=np.uint32)
         check(lib().zrt_ctx_adapt_samples(self._h, out.ctypes.data_as(C.POINTER(C.c_uint32)), n))
         return out[:n]
+
+    def features(self, camera, params: RenderParams, dev_ptr: int, stream: int = 0):
+        """The frame's first-hit feature buffer (zrt_ctx_features; asynchronous): width *
+        height * 8 f32 at the device pointer dev_ptr - {N.xyz, t} and {A.rgb, id bits} per pixel."""
+        p = params.abi()
+        check(lib().zrt_ctx_features(self._h, C.byref(camera), C.byref(p), C.c_void_p(dev_ptr),
+                                     C.c_void_p(stream or None)))
+
+    def denoise(self, params: RenderParams, dn: _ffi.Denoise, dev_frame: int, dev_features: int, dev_out: int,
+                stream: int = 0):
+        """Filter the frame at dev_frame into dev_out, guided by the feature buffer at
+        dev_features (zrt_ctx_denoise; device pointers, asynchronous; the definition: zrt.h)."""
+        p = params.abi()
+        check(lib().zrt_ctx_denoise(self._h, C.byref(p), C.byref(dn), C.c_void_p(dev_frame),
+                                    C.c_void_p(dev_features), C.c_void_p(dev_out), C.c_void_p(stream or None)))
+
+    def denoise_ms(self) -> float:
+        """Device time of the last denoise() in ms (zrt_ctx_denoise_ms; waits for it)."""
+        ms = C.c_double()
+        check(lib().zrt_ctx_denoise_ms(self._h, C.byref(ms)))
+        return ms.value
 
     def sync(self):
         """Wait for the last launch; raises ZrtError on a device error (zrt_ctx_sync)."""

@@ -163,6 +163,14 @@ class LevelInfo(C.Structure):
 LEVEL_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_float), C.POINTER(LevelInfo))
 
 
+class Denoise(C.Structure):
+    _fields_ = [("iterations", C.c_uint32), ("sigma_color", C.c_float), ("sigma_normal", C.c_float),
+                ("sigma_albedo", C.c_float), ("sigma_depth", C.c_float), ("reserved", C.c_uint32 * 3)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_ if name != "reserved"}
+
+
 class BvhNode(C.Structure):
     _fields_ = [("min", Vec3), ("left", C.c_int32), ("max", Vec3), ("right", C.c_int32)]
 
@@ -223,6 +231,13 @@ SIGNATURES = [
                                                C.POINTER(C.c_uint32), C.POINTER(Stats), C.POINTER(Scanline)]),
     ("zrt_debug_adapt_plan", C.c_int, [C.POINTER(Params), C.POINTER(Adaptive), C.POINTER(C.c_uint32), C.c_uint32,
                                        C.POINTER(C.c_uint32)]),
+    ("zrt_ctx_features", C.c_int, [_P, C.POINTER(Camera), C.POINTER(Params), _P, _P]),
+    ("zrt_render_denoised", C.c_int, [C.POINTER(Scene), C.POINTER(Camera), C.POINTER(Params), C.POINTER(Adaptive),
+                                      C.POINTER(Denoise), C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                      C.POINTER(C.c_float), C.POINTER(Stats), C.POINTER(C.c_double)]),
+    ("zrt_denoise_defaults", C.c_int, [C.POINTER(Denoise)]),
+    ("zrt_ctx_denoise", C.c_int, [_P, C.POINTER(Params), C.POINTER(Denoise), _P, _P, _P, _P]),
+    ("zrt_ctx_denoise_ms", C.c_int, [_P, C.POINTER(C.c_double)]),
     ("zrt_scene_load", C.c_int, [C.c_uint32, C.c_char_p, C.POINTER(_P), C.POINTER(Camera)]),
     ("zrt_scene_view", C.POINTER(Scene), [_P]),
     ("zrt_scene_free", None, [_P]),

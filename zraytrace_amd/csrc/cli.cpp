@@ -22,6 +22,11 @@
 // samples, default one chunk): one line per level, then the scanline lines once, from the
 // rows accumulated over the levels (a row's samples are its tiles' own), and
 // $ZRT_ADAPTIVE_MAP=<file.png> receives the sample-count map as a grey PNG (samples / cap).
+// $ZRT_DENOISE=1 filters the frame with the default a-trous filter (zrt_render_denoised;
+// $ZRT_DENOISE=iters,sigma_color,sigma_normal,sigma_albedo,sigma_depth sets it explicitly):
+// the PNG is the denoised frame, $ZRT_DENOISE_NOISY=<file.png> also receives the
+// unfiltered one.  It composes with $ZRT_ADAPTIVE_TOL (no level or scanline lines then,
+// and no sample map) and is refused with $ZRT_DEVICES or $ZRT_PASS_SAMPLES.
 #include <unistd.h>
 
 #include <chrono>
@@ -186,6 +191,31 @@ int main(int argc, char** argv) {
     return 1;
   }
 
+  // $ZRT_DENOISE=1 (the defaults) or iters,sigma_color,sigma_normal,sigma_albedo,sigma_depth: the
+  // output file is the a-trous-filtered frame (zrt_render_denoised); $ZRT_DENOISE_NOISY=path
+  // also writes the unfiltered one
+  const char* dn_env = std::getenv("ZRT_DENOISE");
+  zrt_denoise dn;
+  if (dn_env) {
+    if (pass_env || !devices.empty()) {
+      std::fprintf(stderr, "error: ZRT_DENOISE filters a frame rendered on one GPU, not in plain passes: unset "
+                           "ZRT_DEVICES and ZRT_PASS_SAMPLES (or ZRT_DENOISE)\n");
+      zrt_scene_free(data);
+      return 1;
+    }
+    zrt_denoise_defaults(&dn);
+    if (std::strchr(dn_env, ',')) {
+      unsigned iters = 0;
+      if (std::sscanf(dn_env, "%u,%f,%f,%f,%f", &iters, &dn.sigma_color, &dn.sigma_normal, &dn.sigma_albedo,
+                      &dn.sigma_depth) != 5) {
+        std::fprintf(stderr, "error: ZRT_DENOISE is 1 or iterations,sigma_color,sigma_normal,sigma_albedo,sigma_depth\n");
+        zrt_scene_free(data);
+        return 1;
+      }
+      dn.iterations = iters;
+    }
+  }
+
   std::fprintf(stderr, "Raytrace start\n");
   std::fprintf(stderr, " - Surfaces:                 %u\n", scene->n_prims);
   std::fprintf(stderr, " - Pixels:                   %ux%u\n", unsigned(width), unsigned(height));
@@ -199,7 +229,17 @@ int main(int argc, char** argv) {
   zrt_stats stats;
   const auto t_render = std::chrono::steady_clock::now();
   std::vector<uint32_t> sample_map;
-  if (tol_env) {
+  std::vector<float> noisy;
+  double denoise_ms = 0.0;
+  if (dn_env) {
+    zrt_adaptive ad;
+    std::memset(&ad, 0, sizeof(ad));
+    if (tol_env) ad.tolerance = std::strtof(tol_env, nullptr);
+    if (const char* first = std::getenv("ZRT_ADAPTIVE_FIRST")) ad.first_level = uint32_t(std::strtoul(first, nullptr, 10));
+    noisy.assign(image.size(), 0.0f);
+    rc = zrt_render_denoised(scene, &camera, &params, tol_env ? &ad : nullptr, &dn, image.data(), noisy.data(), nullptr,
+                             &stats, &denoise_ms);
+  } else if (tol_env) {
     zrt_adaptive ad;
     std::memset(&ad, 0, sizeof(ad));
     ad.tolerance = std::strtof(tol_env, nullptr);
@@ -235,7 +275,7 @@ int main(int argc, char** argv) {
   // printProgress after every scanline (raytrace.zig:37-50, 184)
   const double pixels_per_second = double(stats.pixels_processed) / render_runtime;
   unsigned long long pixels = 0, samples_sum = 0, rays = 0;
-  for (uint32_t y = 0; y < height && !pass_env; ++y) {
+  for (uint32_t y = 0; y < height && !pass_env && !dn_env; ++y) {
     pixels += rows[y].pixels;
     samples_sum += rows[y].samples;
     rays += rows[y].rays;
@@ -260,8 +300,14 @@ int main(int argc, char** argv) {
   std::fprintf(stderr, "  Mrays/s (render):      %.2f  (zrt_render call %.2f s, %u GPU)\n",
                double(stats.rays_processed) / render_runtime / 1e6, call, stats.n_gpus);
 
+  if (dn_env)
+    std::fprintf(stderr, "  Denoise:               %u iterations, %.3f ms\n",
+                 dn.iterations ? dn.iterations : unsigned(ZRT_DEFAULT_DENOISE_ITERATIONS), denoise_ms);
+
   rc = zrt_image_write_png(filename, image.data(), width, height);
-  if (const char* map = std::getenv("ZRT_ADAPTIVE_MAP"); map && tol_env && rc == ZRT_OK) {
+  if (const char* path = std::getenv("ZRT_DENOISE_NOISY"); path && dn_env && rc == ZRT_OK)
+    rc = zrt_image_write_png(path, noisy.data(), width, height);
+  if (const char* map = std::getenv("ZRT_ADAPTIVE_MAP"); map && tol_env && !dn_env && rc == ZRT_OK) {
     std::vector<float> grey(size_t(width) * height * 3);
     for (size_t i = 0; i < sample_map.size(); ++i)
       grey[3 * i] = grey[3 * i + 1] = grey[3 * i + 2] = float(sample_map[i]) / float(samples);

@@ -1,0 +1,213 @@
+// denoise.hip — edge-avoiding a-trous wavelet filter (Dammertz et al. 2010) on
+// the assembled frame, guided by the first-hit feature buffers.
+//
+// The definition (include/zrt.h) is f32 operation by
+// operation; this file is compiled with -ffp-contract=off like the render
+// kernels, so every product, sum and `/` below is one IEEE rounding and
+// tests/denoise_ref.py restates the result bit for bit.
+//
+// Plan: a packing pass turns the frame's RGB triples inside D into float4 (and
+// copies the pixels outside D to the output); then one launch per iteration,
+// ping-ponging between two float4 planes, the last one writing RGB triples to
+// the output.  A tap is three 16-byte loads: the colour and the two feature
+// float4.  Steps 1 and 2 stage the block's pixels plus halo in LDS (every pixel
+// of the region is read by up to 25 lanes of the block); from step 4 on the
+// taps of one block no longer share pixels with each other's, and are read
+// straight from memory.
+#include "denoise.hpp"
+
+namespace zrt {
+namespace {
+
+constexpr int kDnBX = 32, kDnBY = 8;  // a wave is two 32-pixel rows: 512 contiguous bytes per row and load
+
+// h = {1/16, 1/4, 3/8, 1/4, 1/16}; every h(dx) * h(dy) is exact in f32
+__device__ __forceinline__ float dn_h(int d) { return d == 0 ? 0.375f : (d == 1 || d == -1) ? 0.25f : 0.0625f; }
+
+struct DnCentre {
+  float4 c, f0, f1;
+  bool hit;
+  float kz;
+};
+
+// One tap q of pixel p (not the centre): the weight's tests in the definition's
+// order; adds into acc / wsum when the tap survives.
+__device__ __forceinline__ void dn_tap(const DnCentre& p, const float4 cq, const float4 f0q, const float4 f1q,
+                                       float w, uint32_t terms, float kc, float inv_n, float inv_a, float& ar,
+                                       float& ag, float& ab, float& wsum) {
+  const bool hit_q = __float_as_uint(f1q.w) != 0u;
+  if (p.hit != hit_q) return;
+  if (terms & kDnColor) {
+    const float t = 1.0f - ((fabsf(p.c.x - cq.x) + fabsf(p.c.y - cq.y)) + fabsf(p.c.z - cq.z)) * kc;
+    if (!(t > 0.0f)) return;
+    w = w * t;
+  }
+  if (terms & kDnNormal) {
+    const float dx = p.f0.x - f0q.x, dy = p.f0.y - f0q.y, dz = p.f0.z - f0q.z;
+    const float t = 1.0f - ((dx * dx + dy * dy) + dz * dz) * inv_n;
+    if (!(t > 0.0f)) return;
+    w = w * t;
+  }
+  if (terms & kDnAlbedo) {
+    const float t = 1.0f - ((fabsf(p.f1.x - f1q.x) + fabsf(p.f1.y - f1q.y)) + fabsf(p.f1.z - f1q.z)) * inv_a;
+    if (!(t > 0.0f)) return;
+    w = w * t;
+  }
+  if (terms & kDnDepth) {
+    const float t = 1.0f - fabsf(p.f0.w - f0q.w) * p.kz;
+    if (!(t > 0.0f)) return;
+    w = w * t;
+  }
+  if (!(w > 0.0f)) return;
+  ar = ar + cq.x * w;
+  ag = ag + cq.y * w;
+  ab = ab + cq.z * w;
+  wsum = wsum + w;
+}
+
+// S = 1, 2: the step, staged through LDS; S = 0: any step, taps from memory.
+// LAST: the iteration writes RGB triples into the output frame.
+template <int S, bool LAST>
+__global__ void __launch_bounds__(kDnBX* kDnBY)
+    atrous_kernel(const float4* __restrict__ cin, const float4* __restrict__ feat, float4* __restrict__ cout,
+                  float* __restrict__ out, uint32_t n, uint32_t width, int step, uint32_t terms, float kc,
+                  float inv_n, float inv_a, float inv_z) {
+  constexpr int RW = kDnBX + 4 * S, RH = kDnBY + 4 * S;
+  __shared__ float4 s_c[S ? RW * RH : 1], s_f0[S ? RW * RH : 1], s_f1[S ? RW * RH : 1];
+  const int x0 = int(blockIdx.x) * kDnBX, y0 = int(blockIdx.y) * kDnBY;
+  const int px = x0 + int(threadIdx.x), py = y0 + int(threadIdx.y);
+  const int ni = int(n);
+  if (S) {
+    const int tid = int(threadIdx.y) * kDnBX + int(threadIdx.x);
+    for (int i = tid; i < RW * RH; i += kDnBX * kDnBY) {
+      const int gx = x0 - 2 * S + i % RW, gy = y0 - 2 * S + i / RW;
+      float4 c = make_float4(0.0f, 0.0f, 0.0f, 0.0f), f0 = c, f1 = c;
+      if (gx >= 0 && gx < ni && gy >= 0 && gy < ni) {
+        c = cin[size_t(gy) * n + size_t(gx)];
+        const size_t f = (size_t(gy) * width + size_t(gx)) * 2;
+        f0 = feat[f];
+        f1 = feat[f + 1];
+      }
+      s_c[i] = c;
+      s_f0[i] = f0;
+      s_f1[i] = f1;
+    }
+    __syncthreads();
+  }
+  if (px >= ni || py >= ni) return;
+  const int s = S ? S : step;
+  DnCentre p;
+  if (S) {
+    const int l = (int(threadIdx.y) + 2 * S) * RW + int(threadIdx.x) + 2 * S;
+    p.c = s_c[l];
+    p.f0 = s_f0[l];
+    p.f1 = s_f1[l];
+  } else {
+    p.c = cin[size_t(py) * n + size_t(px)];
+    const size_t f = (size_t(py) * width + size_t(px)) * 2;
+    p.f0 = feat[f];
+    p.f1 = feat[f + 1];
+  }
+  p.hit = __float_as_uint(p.f1.w) != 0u;
+  const float rz = p.hit ? 1.0f / p.f0.w : 0.0f;
+  p.kz = inv_z * rz;
+  float ar = 0.0f, ag = 0.0f, ab = 0.0f, wsum = 0.0f;
+#pragma unroll
+  for (int dy = -2; dy <= 2; ++dy) {
+#pragma unroll
+    for (int dx = -2; dx <= 2; ++dx) {
+      if (dx == 0 && dy == 0) {  // the centre tap: no tests
+        const float w = 0.375f * 0.375f;
+        ar = ar + p.c.x * w;
+        ag = ag + p.c.y * w;
+        ab = ab + p.c.z * w;
+        wsum = wsum + w;
+        continue;
+      }
+      // (step <= 128 and n <= 65535: no overflow)
+      const int qx = px + s * dx, qy = py + s * dy;
+      if (qx < 0 || qx >= ni || qy < 0 || qy >= ni) continue;
+      float4 cq, f0q, f1q;
+      if (S) {
+        const int l = (int(threadIdx.y) + 2 * S + S * dy) * RW + int(threadIdx.x) + 2 * S + S * dx;
+        cq = s_c[l];
+        f0q = s_f0[l];
+        f1q = s_f1[l];
+      } else {
+        cq = cin[size_t(qy) * n + size_t(qx)];
+        const size_t f = (size_t(qy) * width + size_t(qx)) * 2;
+        f0q = feat[f];
+        f1q = feat[f + 1];
+      }
+      dn_tap(p, cq, f0q, f1q, dn_h(dx) * dn_h(dy), terms, kc, inv_n, inv_a, ar, ag, ab, wsum);
+    }
+  }
+  const float r = ar / wsum, g = ag / wsum, b = ab / wsum;
+  if (LAST) {
+    float* o = out + (size_t(py) * width + size_t(px)) * 3;
+    o[0] = r;
+    o[1] = g;
+    o[2] = b;
+  } else {
+    cout[size_t(py) * n + size_t(px)] = make_float4(r, g, b, 0.0f);
+  }
+}
+
+// C_0: the frame's pixels inside D as float4; the pixels outside D go to the output as they are.
+__global__ void dn_pack_kernel(const float* __restrict__ frame, float4* __restrict__ c0, float* __restrict__ out,
+                               uint32_t n, uint32_t width) {
+  const size_t i = size_t(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (i >= size_t(width) * n) return;
+  const uint32_t x = uint32_t(i % width), y = uint32_t(i / width);
+  const float r = frame[3 * i], g = frame[3 * i + 1], b = frame[3 * i + 2];
+  if (x < n) {
+    c0[size_t(y) * n + x] = make_float4(r, g, b, 0.0f);
+  } else {
+    out[3 * i] = r;
+    out[3 * i + 1] = g;
+    out[3 * i + 2] = b;
+  }
+}
+
+template <int S>
+hipError_t launch_iter(bool last, dim3 grid, hipStream_t st, const float4* cin, const float4* feat, float4* cout,
+                       float* out, const DenoiseLaunch& l, int step, float kc) {
+  const dim3 block(kDnBX, kDnBY);
+  if (last)
+    hipLaunchKernelGGL((atrous_kernel<S, true>), grid, block, 0, st, cin, feat, cout, out, l.n, l.width, step, l.terms,
+                       kc, l.inv_n, l.inv_a, l.inv_z);
+  else
+    hipLaunchKernelGGL((atrous_kernel<S, false>), grid, block, 0, st, cin, feat, cout, out, l.n, l.width, step,
+                       l.terms, kc, l.inv_n, l.inv_a, l.inv_z);
+  return hipGetLastError();
+}
+
+}  // namespace
+
+hipError_t denoise_enqueue(const DenoiseLaunch& l, const float* frame, const float4* feat, float* out, float4* buf0,
+                           float4* buf1, hipStream_t st) {
+  if (l.n == 0 || l.width < l.n || l.iterations == 0 || l.iterations > 8) return hipErrorInvalidValue;
+  const size_t pixels = size_t(l.width) * l.n;
+  hipLaunchKernelGGL(dn_pack_kernel, dim3(uint32_t((pixels + 255) / 256)), dim3(256), 0, st, frame, buf0, out, l.n,
+                     l.width);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  const dim3 grid((l.n + kDnBX - 1) / kDnBX, (l.n + kDnBY - 1) / kDnBY);
+  float4* cur = buf0;
+  float4* nxt = buf1;
+  for (uint32_t i = 0; i < l.iterations; ++i) {
+    const int step = 1 << i;
+    const float kc = l.inv_c * float(1 << i);  // sigma_color halves every iteration
+    const bool last = i + 1 == l.iterations;
+    e = step == 1   ? launch_iter<1>(last, grid, st, cur, feat, nxt, out, l, step, kc)
+        : step == 2 ? launch_iter<2>(last, grid, st, cur, feat, nxt, out, l, step, kc)
+                    : launch_iter<0>(last, grid, st, cur, feat, nxt, out, l, step, kc);
+    if (e != hipSuccess) return e;
+    float4* t = cur;
+    cur = nxt;
+    nxt = t;
+  }
+  return hipSuccess;
+}
+
+}  // namespace zrt

@@ -32,6 +32,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <memory>
 #include <mutex>
 #include <string>
@@ -40,6 +41,7 @@
 
 #include "accel_build.hpp"
 #include "bvh_build.hpp"
+#include "denoise.hpp"
 #include "device_math.hpp"
 #include "zrt.hpp"
 
@@ -2284,6 +2286,87 @@ __device__ __forceinline__ V3 att_product(const KArgs& a, const DevMaterial* __r
   return col;
 }
 
+// HitRecord.init (hit_record.zig:28-41) of a closest hit: the material, the hit
+// location, the normal flipped against the ray, and the texture coordinates
+// (u, v) where the material reads an image.  shade_step's first half, and what
+// features_kernel records of a first hit.
+struct HitRec {
+  MatReg mat;
+  uint32_t tag, mkind;
+  V3 loc, normal;
+  float tu, tv;
+  bool front;
+};
+template <bool STATS, bool LEAN>
+__device__ __forceinline__ void hit_record(const KArgs& a, const DevMaterial* __restrict__ mats, int best,
+                                           float best_t, const V3& o, const V3& d, uint32_t& c_shade,
+                                           uint32_t& c_tex, Coh& coh, HitRec& h) {
+  float4 sh;
+  const int fb = __builtin_amdgcn_readfirstlane(best);
+  if (ZRT_SCALAR_PRIMS && __ballot(best != fb) == 0ull) {  // one hit surface in every lane here
+#if defined(__HIP_DEVICE_COMPILE__)
+    typedef const __attribute__((address_space(4))) float4 cfloat4;
+    sh = ((cfloat4*)a.shade)[fb];
+#else
+    sh = a.shade[fb];
+#endif
+  } else {
+    if (STATS) coh.vsh_trips += wave_once();
+    sh = a.shade[best];
+  }
+  const uint32_t tag = __float_as_uint(sh.w);
+  const MatReg mat = load_material(mats, tag & 0x7fffffffu);
+  const uint32_t mkind = mat.kind();
+  const bool need_uv = !Lean<LEAN>::tex && mkind != ZRT_MAT_DIELECTRIC && mat.tex_kind() == ZRT_TEX_IMAGE;
+  if (STATS) {
+    ++c_shade;
+    c_tex += need_uv ? 1u : 0u;
+  }
+  const V3 loc = add(o, scale(d, best_t));
+  V3 outward;
+  float tu = 0.0f, tv = 0.0f;
+  if (tag >> 31) {
+    outward = mk(sh.x, sh.y, sh.z);  // face_unit_normal
+    if (need_uv) {  // barycentric (u, v), same arithmetic as the hit test
+      const float4 p0 = a.prims[3 * best + 0];
+      const float4 p1 = a.prims[3 * best + 1];
+      const float4 p2 = a.prims[3 * best + 2];
+      const V3 n = mk(p2.y, p2.z, p2.w);
+      const float det = -dot(d, n);
+      const float inv_det = inv_det_rn(det, a.tri_rcp_fast);
+      const V3 ao = mk(o.x - p0.x, o.y - p0.y, o.z - p0.z);
+      const V3 dao = cross(ao, d);
+      tu = dot(mk(p1.z, p1.w, p2.x), dao) * inv_det;
+      tv = -dot(mk(p0.w, p1.x, p1.y), dao) * inv_det;
+    }
+  } else {
+    const float4 c = a.prims[3 * best];
+    outward = scale(sub(loc, mk(c.x, c.y, c.z)), sh.x);  // (p - c) * (1/r)
+    if (need_uv) {  // sphere.zig:47-51
+      const float theta = dev::acos_z(-outward.y);
+      const float phi = dev::atan2_z(-outward.z, -outward.x) + kPi;
+      // phi in {+0} u [2^-23, 2pi], theta in {+0} u [2^-12, pi]: dev::div_core's
+      // range, and +0 stays +0 (q = +0, r = +0, q + r*y = +0)
+      tu = dev::div_known(phi, kTwoPi, kInvTwoPi);
+      tv = dev::div_known(theta, kPi, kInvPi);
+    }
+  }
+  bool front = true;
+  V3 normal = outward;
+  if (dot(d, outward) > 0.0f) {
+    normal = neg(outward);
+    front = false;
+  }
+  h.mat = mat;
+  h.tag = tag;
+  h.mkind = mkind;
+  h.loc = loc;
+  h.normal = normal;
+  h.tu = tu;
+  h.tv = tv;
+  h.front = front;
+}
+
 template <bool STATS, class R, bool LEAN = false>
 __device__ __forceinline__ void shade_step(const KArgs& a, const DevMaterial* __restrict__ mats,
                                            const AttRows& ar, R& rng, int best, float best_t,
@@ -2297,62 +2380,15 @@ __device__ __forceinline__ void shade_step(const KArgs& a, const DevMaterial* __
     sky = true;
   } else {
     // ---- HitRecord.init (hit_record.zig:28-41)
-    float4 sh;
-    const int fb = __builtin_amdgcn_readfirstlane(best);
-    if (ZRT_SCALAR_PRIMS && __ballot(best != fb) == 0ull) {  // one hit surface in every lane here
-#if defined(__HIP_DEVICE_COMPILE__)
-      typedef const __attribute__((address_space(4))) float4 cfloat4;
-      sh = ((cfloat4*)a.shade)[fb];
-#else
-      sh = a.shade[fb];
-#endif
-    } else {
-      if (STATS) coh.vsh_trips += wave_once();
-      sh = a.shade[best];
-    }
-    const uint32_t tag = __float_as_uint(sh.w);
-    const MatReg mat = load_material(mats, tag & 0x7fffffffu);
-    const uint32_t mkind = mat.kind();
-    const bool need_uv = !Lean<LEAN>::tex && mkind != ZRT_MAT_DIELECTRIC && mat.tex_kind() == ZRT_TEX_IMAGE;
-    if (STATS) {
-      ++c_shade;
-      c_tex += need_uv ? 1u : 0u;
-    }
-    const V3 loc = add(o, scale(d, best_t));
-    V3 outward;
-    float tu = 0.0f, tv = 0.0f;
-    if (tag >> 31) {
-      outward = mk(sh.x, sh.y, sh.z);  // face_unit_normal
-      if (need_uv) {  // barycentric (u, v), same arithmetic as the hit test
-        const float4 p0 = a.prims[3 * best + 0];
-        const float4 p1 = a.prims[3 * best + 1];
-        const float4 p2 = a.prims[3 * best + 2];
-        const V3 n = mk(p2.y, p2.z, p2.w);
-        const float det = -dot(d, n);
-        const float inv_det = inv_det_rn(det, a.tri_rcp_fast);
-        const V3 ao = mk(o.x - p0.x, o.y - p0.y, o.z - p0.z);
-        const V3 dao = cross(ao, d);
-        tu = dot(mk(p1.z, p1.w, p2.x), dao) * inv_det;
-        tv = -dot(mk(p0.w, p1.x, p1.y), dao) * inv_det;
-      }
-    } else {
-      const float4 c = a.prims[3 * best];
-      outward = scale(sub(loc, mk(c.x, c.y, c.z)), sh.x);  // (p - c) * (1/r)
-      if (need_uv) {  // sphere.zig:47-51
-        const float theta = dev::acos_z(-outward.y);
-        const float phi = dev::atan2_z(-outward.z, -outward.x) + kPi;
-        // phi in {+0} u [2^-23, 2pi], theta in {+0} u [2^-12, pi]: dev::div_core's
-        // range, and +0 stays +0 (q = +0, r = +0, q + r*y = +0)
-        tu = dev::div_known(phi, kTwoPi, kInvTwoPi);
-        tv = dev::div_known(theta, kPi, kInvPi);
-      }
-    }
-    bool front = true;
-    V3 normal = outward;
-    if (dot(d, outward) > 0.0f) {
-      normal = neg(outward);
-      front = false;
-    }
+    HitRec hr;
+    hit_record<STATS, LEAN>(a, mats, best, best_t, o, d, c_shade, c_tex, coh, hr);
+    const uint32_t tag = hr.tag;
+    const MatReg mat = hr.mat;
+    const uint32_t mkind = hr.mkind;
+    const V3 loc = hr.loc;
+    const V3 normal = hr.normal;
+    const float tu = hr.tu, tv = hr.tv;
+    const bool front = hr.front;
     // ---- Material.scatter (material.zig:43-129)
     bool absorbed = false;
     uint32_t att = kAttOne;  // the attenuation as an att code (dielectric: (1, 1, 1))
@@ -3830,32 +3866,22 @@ __global__ void __launch_bounds__(kBlock, ZRT_WAVES_WIDE) schedule_probe_kernel(
   render_loop<3, PRNG, false, StackT, true>(a);
 }
 
-// Closest hit of a batch of rays (zrt_trace): the top-level query of rayColor
-// (raytrace.zig:71-81, t_min 0.001, t_max shrinking) through the same
-// traversal code as the render loop, one lane per ray.  Ray.init normalises the
-// direction (ray.zig:11-13).  Result: t (+inf on a miss) and the device slot.
+// The closest hit of one ray whose direction Ray.init has normalised: the
+// top-level query of rayColor (raytrace.zig:71-81, t_min 0.001, t_max shrinking)
+// through the same traversal code as the render loop.  best < 0: a miss.
 template <int MODE, class StackT>
-__global__ void __launch_bounds__(kBlock) trace_kernel(const KArgs a, const float* __restrict__ rays, uint32_t n,
-                                                       float* __restrict__ out_t, int32_t* __restrict__ out_slot) {
-  extern __shared__ __attribute__((aligned(16))) char lds_raw[];
-  StackT* stk = reinterpret_cast<StackT*>(lds_raw) + threadIdx.x;
-  float4* lds_top = reinterpret_cast<float4*>(lds_raw + a.lds_top_off);
-  if ((MODE == 3 || MODE == 8) && !layout_ok(a)) return;
-  if ((MODE == 3 || MODE == 8) && ZRT_LDS_TOP) fill_lds_top(a, lds_top);
-  const uint32_t gl = blockIdx.x * kBlock + threadIdx.x;
-  if (gl >= n) return;
-  const float* q = rays + 6ull * gl;
-  const V3 d = unit(mk(q[3], q[4], q[5]));
+__device__ __forceinline__ void closest_hit(const KArgs& a, const V3 o, const V3 d, StackT* stk, float4* lds_top,
+                                            uint32_t gl, float& best_t, int& best) {
   RayT r;
-  r.ox = q[0]; r.oy = q[1]; r.oz = q[2];
+  r.ox = o.x; r.oy = o.y; r.oz = o.z;
   r.dx = d.x; r.dy = d.y; r.dz = d.z;
   r.rcp_det = a.tri_rcp_fast;
   r.gm = a.graze_m;
   r.gl = a.graze_leaf;
   r.gk = a.guard;
   inv_dir(d.x, d.y, d.z, r.ix, r.iy, r.iz);
-    float best_t = __builtin_inff();
-  int best = -1;
+  best_t = __builtin_inff();
+  best = -1;
   uint32_t c_nodes = 0, c_leaves = 0, c_tri = 0, c_sph = 0;
   if (MODE == 0) {
     for (uint32_t i = 0; i < a.n_list; ++i) {  // surfaces in list order
@@ -3875,8 +3901,89 @@ __global__ void __launch_bounds__(kBlock) trace_kernel(const KArgs a, const floa
   } else {
     traverse_bvh<MODE == 1, false>(a, r, stk, best_t, best, c_nodes, c_tri, c_sph);
   }
+}
+
+// Closest hit of a batch of rays (zrt_trace), one lane per ray.  Ray.init
+// normalises the direction (ray.zig:11-13).  Result: t (+inf on a miss) and the
+// device slot.
+template <int MODE, class StackT>
+__global__ void __launch_bounds__(kBlock) trace_kernel(const KArgs a, const float* __restrict__ rays, uint32_t n,
+                                                       float* __restrict__ out_t, int32_t* __restrict__ out_slot) {
+  extern __shared__ __attribute__((aligned(16))) char lds_raw[];
+  StackT* stk = reinterpret_cast<StackT*>(lds_raw) + threadIdx.x;
+  float4* lds_top = reinterpret_cast<float4*>(lds_raw + a.lds_top_off);
+  if ((MODE == 3 || MODE == 8) && !layout_ok(a)) return;
+  if ((MODE == 3 || MODE == 8) && ZRT_LDS_TOP) fill_lds_top(a, lds_top);
+  const uint32_t gl = blockIdx.x * kBlock + threadIdx.x;
+  if (gl >= n) return;
+  const float* q = rays + 6ull * gl;
+  const V3 d = unit(mk(q[3], q[4], q[5]));
+  float best_t;
+  int best;
+  closest_hit<MODE, StackT>(a, mk(q[0], q[1], q[2]), d, stk, lds_top, gl, best_t, best);
   out_t[gl] = best < 0 ? __builtin_inff() : best_t;
   out_slot[gl] = best;
+}
+
+// First-hit feature buffers (zrt_ctx_features): one lane per pixel of the whole
+// frame, lanes in 8x8 tiles as the render loops take them.  The pixel-centre
+// primary ray (raytrace.zig:173-175 at r = 0.5: u = x / width, v = y / height;
+// camera.zig:46-51), trace_kernel's closest hit, shade_step's hit record and
+// albedo.  out: two float4 per pixel in the frame's layout, {N, t} and {A, id};
+// id = the bits of uint32(prim + 1), prim the index in the reference's list.
+template <int MODE, class StackT>
+__global__ void __launch_bounds__(kBlock) features_kernel(const KArgs a, const uint32_t* __restrict__ slot_prim,
+                                                          float4* __restrict__ out) {
+  extern __shared__ __attribute__((aligned(16))) char lds_raw[];
+  StackT* stk = reinterpret_cast<StackT*>(lds_raw) + threadIdx.x;
+  float4* lds_top = reinterpret_cast<float4*>(lds_raw + a.lds_top_off);
+  if ((MODE == 3 || MODE == 8) && !layout_ok(a)) return;
+  if ((MODE == 3 || MODE == 8) && ZRT_LDS_TOP) fill_lds_top(a, lds_top);
+  const uint32_t gl = blockIdx.x * kBlock + threadIdx.x;
+  const uint32_t tiles_w = (a.width + 7u) / 8u;  // (tiles over the whole width here, not tiles_x)
+  const uint32_t tile = gl >> 6, p = gl & 63u;
+  const uint32_t px = (tile % tiles_w) * 8u + (p & 7u), py = (tile / tiles_w) * 8u + (p >> 3);
+  if (px >= a.width || py >= a.height) return;
+  float4* dst = out + 2ull * ((uint64_t)py * a.width + px);
+  if (px >= a.xbound) {  // outside the rendered square (raytrace.zig:168)
+    dst[0] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    dst[1] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    return;
+  }
+  const float u = (float)px / a.f_width;  // IEEE `/`
+  const float v = (float)py / a.f_height;
+  const V3 llc = mk(a.llc[0], a.llc[1], a.llc[2]);
+  const V3 hor = mk(a.hor[0], a.hor[1], a.hor[2]);
+  const V3 ver = mk(a.ver[0], a.ver[1], a.ver[2]);
+  const V3 o = mk(a.org[0], a.org[1], a.org[2]);
+  const V3 d = unit(sub(add(add(llc, scale(hor, u)), scale(ver, v)), o));
+  float best_t;
+  int best;
+  closest_hit<MODE, StackT>(a, o, d, stk, lds_top, gl, best_t, best);
+  if (best < 0) {
+    const V3 bg = background(d);
+    dst[0] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    dst[1] = make_float4(bg.x, bg.y, bg.z, 0.0f);
+    return;
+  }
+  uint32_t c_shade = 0, c_tex = 0;
+  Coh coh;
+  HitRec h;
+  hit_record<false, false>(a, a.mats, best, best_t, o, d, c_shade, c_tex, coh, h);
+  const uint32_t code = h.mkind == ZRT_MAT_DIELECTRIC ? kAttOne : albedo_code<false>(h.mat, h.tag & 0x7fffffffu, h.tu, h.tv);
+  const V3 alb = att_value<false>(a, a.mats, code);
+  dst[0] = make_float4(h.normal.x, h.normal.y, h.normal.z, best_t);
+  dst[1] = make_float4(alb.x, alb.y, alb.z, __uint_as_float(slot_prim[best] + 1u));
+}
+
+// A feature launch that set the device error flag (a traversal stack overflow)
+// leaves NaN in the whole buffer, as a render launch does in its tiles.
+__global__ void features_error_kernel(float4* __restrict__ out, uint64_t n_f4,
+                                      const unsigned long long* __restrict__ error_flag) {
+  if (*error_flag == 0ull) return;
+  const float q = __builtin_nanf("");
+  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_f4; i += (uint64_t)gridDim.x * blockDim.x)
+    out[i] = make_float4(q, q, q, q);
 }
 
 // Per-pixel sum of the chunk sums in chunk order, times 1/spp
@@ -4480,7 +4587,22 @@ struct zrt_ctx {
   float* adapt_tiles = nullptr;  // the run's dev_tiles
   zrt::DevBuf<uint32_t> active[2], tile_done, active_count;
   uint32_t* count_host = nullptr;  // the surviving count of the last level, pinned
+  // ---- the a-trous filter (zrt_ctx_denoise): its ping-pong colour planes and its events ----
+  zrt::DevBuf<float4> dn_buf[2];
+  hipEvent_t dn_ev0 = nullptr, dn_ev1 = nullptr;
+  bool dn_launched = false;
+  // ---- first-hit feature buffers (zrt_ctx_features): the launch's own deep stack rows,
+  // the slot -> primitive table, and its device error status behind feat_done ----
+  zrt::DevBuf<uint8_t> feat_ovf;
+  zrt::DevBuf<uint32_t> feat_slot_prim;
+  unsigned long long* feat_err_host = nullptr;
+  hipEvent_t feat_done = nullptr;
+  bool feat_launched = false, feat_err_reported = false;
   ~zrt_ctx() {
+    if (feat_done) (void)hipEventDestroy(feat_done);
+    if (feat_err_host) (void)hipHostFree(feat_err_host);
+    if (dn_ev0) (void)hipEventDestroy(dn_ev0);
+    if (dn_ev1) (void)hipEventDestroy(dn_ev1);
     if (count_host) (void)hipHostFree(count_host);
     for (const std::vector<EvSet>* v : {&run_pending, &ev_spare})
       for (const EvSet& e : *v) {
@@ -5482,6 +5604,19 @@ const char* device_error_msg(unsigned long long flag) {
 // error (every such call does); else (render_tiles' sticky check) report it only
 // if the launch has finished and no call has reported it yet.
 int launch_status(zrt_ctx* c, bool wait) {
+  if (c->feat_launched && !c->feat_err_reported) {  // a feature launch's error, reported once
+    bool done = true;
+    if (wait) {
+      HIPCHK(hipEventSynchronize(c->feat_done));
+    } else if (hipEventQuery(c->feat_done) != hipSuccess) {
+      (void)hipGetLastError();  // (not ready is no error of this launch)
+      done = false;
+    }
+    if (done && *c->feat_err_host != 0) {
+      c->feat_err_reported = true;
+      return fail(ZRT_E_UNSUPPORTED, device_error_msg(*c->feat_err_host));
+    }
+  }
   if (!c->launched) return ZRT_OK;
   if (wait) {
     HIPCHK(hipEventSynchronize(c->ev_done));
@@ -6485,11 +6620,237 @@ int zrt_ctx_assemble_padded(zrt_ctx* c, const zrt_params* p, const float* dev_ga
   return zrt::assemble(c, p, dev_gathered, stride_tiles, dev_frame, hip_stream);
 }
 
+// ---- first-hit feature buffers (zrt.h "denoising") ---------------------------
+int zrt_ctx_features(zrt_ctx* c, const zrt_camera* cam, const zrt_params* p, float* dev_features, void* hip_stream) {
+  if (!c || !cam || !dev_features) return fail(ZRT_E_INVALID, "null argument");
+  int rc = zrt::validate_params(p);
+  if (rc) return rc;
+  rc = params_fit_ctx(c, p);
+  if (rc) return rc;
+  if (reinterpret_cast<uintptr_t>(dev_features) & 15u)
+    return fail(ZRT_E_INVALID, "dev_features must be 16-byte aligned");
+  try {
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t st = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
+    // the traversal of zrt_trace: the loop's own, with the grazing-triangle guard
+    const int mode = !c->use_bvh ? 0
+                     : p->traversal == ZRT_TRAVERSAL_REFERENCE ? 2
+                     : p->traversal == ZRT_TRAVERSAL_BINARY ? 1 : 3;
+    const uint32_t stack_depth = mode == 3 ? std::max(c->wide_stack, c->stack_depth) : c->stack_depth;
+    const bool stk16 = mode == 3 ? zrt::fast_stk16(c->n_wide, c->n_nodes) : c->n_nodes < 65536;
+    const bool qn = mode == 3 && c->q_ok;
+    const uint32_t node_f4 = qn ? zrt::kQuantNodeF4 : 8u;
+    const zrt::LdsPlan lp = zrt::plan_lds(c, mode, stk16, stack_depth, 0, false, false, ZRT_PRNG_XOROSHIRO128, node_f4);
+    const uint32_t tiles = ((p->width + 7u) / 8u) * ((p->height + 7u) / 8u);
+    const uint32_t grid = (tiles + zrt::kBlock / 64 - 1) / (zrt::kBlock / 64);
+    const uint64_t n_lanes = uint64_t(grid) * zrt::kBlock;
+    if (c->feat_slot_prim.n < c->slot_to_prim.size() || c->feat_slot_prim.p == nullptr)
+      c->feat_slot_prim.upload(c->slot_to_prim);
+    if (!c->feat_done) {
+      HIPCHK(hipEventCreateWithFlags(&c->feat_done, hipEventDisableTiming));
+      HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&c->feat_err_host), sizeof(unsigned long long),
+                           hipHostMallocDefault));
+      *c->feat_err_host = 0;
+    }
+    // the context's error flag: what a render launch left there stays (a run's flag is
+    // sticky); before the first launch the slots hold nothing yet
+    if (!c->launched && !c->feat_launched)
+      HIPCHK(hipMemsetAsync(c->scratch.p, 0, zrt::kScratchSlots * sizeof(unsigned long long), st));
+    zrt::KArgs a{};
+    a.nodes = c->nodes.p;
+    a.prims = c->prims.p;
+    a.shade = c->shade.p;
+    a.mats = c->mats.p;
+    a.texels = c->texels.p;
+    a.texels8 = c->texels8.p;
+    a.n_mats = c->n_mats;
+    a.wnodes = qn ? c->qnodes.p : c->wnodes.p;
+    a.wide_stride = qn ? c->q_stride : c->wide_stride;
+    a.node_f4 = node_f4;
+    a.qleaves = qn ? c->qleaves.p : nullptr;
+    a.n_qnodes = qn ? c->q_stride / zrt::kQuantNodeF4 : 0u;
+    a.n_qleaves = qn ? c->n_qleaves : 0u;
+    a.error_flag = reinterpret_cast<uint32_t*>(c->scratch.p + zrt::kErrorSlot);
+    const zrt_vec3* v[4] = {&cam->origin, &cam->lower_left_corner, &cam->horizontal, &cam->vertical};
+    float* dst[4] = {a.org, a.llc, a.hor, a.ver};
+    for (int k = 0; k < 4; ++k) {
+      dst[k][0] = v[k]->x;
+      dst[k][1] = v[k]->y;
+      dst[k][2] = v[k]->z;
+    }
+    a.f_width = float(p->width);
+    a.f_height = float(p->height);
+    a.width = p->width;
+    a.height = p->height;
+    a.xbound = zrt::geometry(p).xbound;
+    a.n_list = c->use_bvh ? 0 : c->n_prims;
+    a.tri_rcp_fast = c->tri_rcp_fast;
+    a.scene_extent = c->scene_extent;
+    a.paxis_m = zrt::paxis_threshold();
+    for (int k = 0; k < 3; ++k) {
+      a.tri_c[k] = c->tri_c[k];
+      a.tri_h[k] = c->tri_h[k];
+    }
+    a.stack_depth = stack_depth;
+    a.ref_stack = c->stack_depth;
+    a.leaf_of_slot = c->leaf_of_slot.p;
+    a.ref_sph = c->ref_sph.p;
+    for (int k = 0; k < 3; ++k) a.root_c[k] = c->root_c[k];
+    a.origin_bound = c->origin_bound;
+    a.check_origins = 1;  // any camera
+    a.layout = c->layout;
+    a.graze_m = c->graze_m;
+    a.graze_leaf = c->graze_leaf;
+    a.guard = c->guard;  // as zrt_trace
+    a.lds_rows = lp.stack_rows;
+    a.n_lanes = uint32_t(n_lanes);
+    a.n_top = qn ? c->q_top : c->n_top;
+    a.lds_top_off = lp.top_off;
+    a.lds_att_off = lp.att_off;
+    const zrt::BufNeed need = zrt::buffer_need(lp, 0, stack_depth, n_lanes, n_lanes, stk16);
+    if (need.ovf_bytes) {
+      if (c->feat_ovf.n < need.ovf_bytes) {
+        HIPCHK(hipStreamSynchronize(st));  // (an earlier feature launch may still use the old rows)
+        c->feat_ovf.alloc(need.ovf_bytes);
+      }
+      a.stack_ovf = c->feat_ovf.p;
+    }
+    zrt::check_buffers("feature launch", zrt::BufNeed{0, need.ovf_bytes}, c->att.n, c->feat_ovf.n);
+    a.att_cap = c->att.n;
+    a.ovf_cap = zrt::ovf_cap_elems(c->feat_ovf.n, stk16);
+    void* fn = nullptr;
+#define ZRT_FK(M) (stk16 ? reinterpret_cast<void*>(&zrt::features_kernel<M, uint16_t>) \
+                         : reinterpret_cast<void*>(&zrt::features_kernel<M, uint32_t>))
+#ifndef ZRT_ISA_KERNEL
+    fn = mode == 0 ? ZRT_FK(0) : mode == 1 ? ZRT_FK(1) : mode == 2 ? ZRT_FK(2) : qn ? ZRT_FK(8) : ZRT_FK(3);
+#endif
+#undef ZRT_FK
+    const uint32_t* sp = c->feat_slot_prim.p;
+    float4* out = reinterpret_cast<float4*>(dev_features);
+    void* args[] = {&a, &sp, &out};
+    HIPCHK(hipLaunchKernel(fn, dim3(grid), dim3(zrt::kBlock), args, lp.bytes, st));
+    const uint64_t n_f4 = 2ull * p->width * p->height;
+    hipLaunchKernelGGL(zrt::features_error_kernel, dim3(uint32_t(std::min<uint64_t>((n_f4 + 255) / 256, 4096))),
+                       dim3(256), 0, st, out, n_f4, c->scratch.p + zrt::kErrorSlot);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(c->feat_err_host, c->scratch.p + zrt::kErrorSlot, sizeof(unsigned long long),
+                          hipMemcpyDeviceToHost, st));
+    HIPCHK(hipEventRecord(c->feat_done, st));
+    c->feat_launched = true;
+    c->feat_err_reported = false;
+    return ZRT_OK;
+  }
+  ZRT_CATCH_ALL
+}
+
+// ---- denoising (zrt.h "denoising"; the kernels: denoise.hip) ----------------
+// the default sigmas: the winner of tools/denoise_probe.py's grid of powers of two
+// (profiles/r10/denoise/defaults.json)
+#define ZRT_DN_SIGMA_COLOR 2.0f
+#define ZRT_DN_SIGMA_NORMAL 0.125f
+#define ZRT_DN_SIGMA_ALBEDO 0x1p-12f
+#define ZRT_DN_SIGMA_DEPTH 0.015625f
+int zrt_denoise_defaults(zrt_denoise* out) {
+  if (!out) return fail(ZRT_E_INVALID, "null argument");
+  *out = zrt_denoise{};
+  out->iterations = ZRT_DEFAULT_DENOISE_ITERATIONS;
+  // the winner of tools/denoise_probe.py's grid (profiles/r10/denoise/defaults.json)
+  out->sigma_color = ZRT_DN_SIGMA_COLOR;
+  out->sigma_normal = ZRT_DN_SIGMA_NORMAL;
+  out->sigma_albedo = ZRT_DN_SIGMA_ALBEDO;
+  out->sigma_depth = ZRT_DN_SIGMA_DEPTH;
+  return ZRT_OK;
+}
+
 namespace zrt {
 namespace {
+// What zrt_ctx_denoise refuses of a zrt_denoise, and the launch it asks for otherwise.
+int plan_denoise(const zrt_params* p, const zrt_denoise* dn, DenoiseLaunch* out) {
+  if (!dn) return fail(ZRT_E_INVALID, "denoise is null");
+  int rc = validate_params(p);
+  if (rc) return rc;
+  if (dn->iterations > 8) return fail(ZRT_E_INVALID, "denoise iterations must be <= 8");
+  const float sg[4] = {dn->sigma_color, dn->sigma_normal, dn->sigma_albedo, dn->sigma_depth};
+  const char* names[4] = {"sigma_color", "sigma_normal", "sigma_albedo", "sigma_depth"};
+  float inv[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+  uint32_t terms = 0;
+  for (int k = 0; k < 4; ++k) {
+    if (!std::isfinite(sg[k]) || sg[k] < 0.0f)
+      return fail(ZRT_E_INVALID, std::string("denoise ") + names[k] + " must be finite and >= 0");
+    if (sg[k] > 0.0f) {
+      terms |= 1u << k;
+      inv[k] = 1.0f / sg[k];
+    }
+  }
+  out->width = p->width;
+  out->n = p->height;
+  out->iterations = dn->iterations ? dn->iterations : ZRT_DEFAULT_DENOISE_ITERATIONS;
+  out->terms = terms;
+  out->inv_c = inv[0];
+  out->inv_n = inv[1];
+  out->inv_a = inv[2];
+  out->inv_z = inv[3];
+  return ZRT_OK;
+}
+}  // namespace
+}  // namespace zrt
+
+int zrt_ctx_denoise(zrt_ctx* c, const zrt_params* p, const zrt_denoise* dn, const float* dev_frame,
+                    const float* dev_features, float* dev_out, void* hip_stream) {
+  zrt::DenoiseLaunch l{};
+  int rc = zrt::plan_denoise(p, dn, &l);  // (the refusals that need no context come first)
+  if (rc) return rc;
+  if (dev_out && static_cast<const float*>(dev_out) == dev_frame)
+    return fail(ZRT_E_INVALID, "denoise: dev_out must not be dev_frame");
+  if (reinterpret_cast<uintptr_t>(dev_features) & 15u)
+    return fail(ZRT_E_INVALID, "denoise: dev_features must be 16-byte aligned");
+  if (!c || !dev_frame || !dev_features || !dev_out) return fail(ZRT_E_INVALID, "null argument");
+  if (int(p->device) != c->device)
+    return fail(ZRT_E_INVALID, "params->device differs from the device the context was created on");
+  try {
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t st = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
+    const size_t plane = size_t(l.n) * l.n;
+    for (zrt::DevBuf<float4>& b : c->dn_buf)
+      if (b.n < plane) b.alloc(plane);
+    if (!c->dn_ev0) {
+      HIPCHK(hipEventCreate(&c->dn_ev0));
+      HIPCHK(hipEventCreate(&c->dn_ev1));
+    }
+    HIPCHK(hipEventRecord(c->dn_ev0, st));
+    HIPCHK(zrt::denoise_enqueue(l, dev_frame, reinterpret_cast<const float4*>(dev_features), dev_out, c->dn_buf[0].p,
+                                c->dn_buf[1].p, st));
+    HIPCHK(hipEventRecord(c->dn_ev1, st));
+    c->dn_launched = true;
+    return ZRT_OK;
+  }
+  ZRT_CATCH_ALL
+}
+
+int zrt_ctx_denoise_ms(zrt_ctx* c, double* ms) {
+  if (!c || !ms) return fail(ZRT_E_INVALID, "null argument");
+  if (!c->dn_launched) return fail(ZRT_E_INVALID, "no denoise launched on this context yet");
+  try {
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipEventSynchronize(c->dn_ev1));
+    float f = 0.0f;
+    HIPCHK(hipEventElapsedTime(&f, c->dn_ev0, c->dn_ev1));
+    *ms = f;
+    return ZRT_OK;
+  }
+  ZRT_CATCH_ALL
+}
+
+namespace zrt {
+namespace {
+// What a one-shot render does with its assembled frame while it still lies on the
+// device (zrt_render_denoised): called last, with the context, the params rendered
+// with and the frame.
+using FramePost = std::function<int(zrt_ctx*, const zrt_params&, const float*)>;
+
 int render_one(const zrt_scene* scene, const zrt_camera* camera, const zrt_params* params, float* out_rgb,
-               zrt_stats* stats, zrt_scanline* rows) {
-  if (!camera || !out_rgb) return fail(ZRT_E_INVALID, "null argument");
+               zrt_stats* stats, zrt_scanline* rows, const FramePost* post = nullptr) {
+  if (!camera || (!out_rgb && !post)) return fail(ZRT_E_INVALID, "null argument");
   int rc = zrt::validate_params(params);
   if (rc) return rc;
   zrt_params p = *params;
@@ -6512,7 +6873,8 @@ int render_one(const zrt_scene* scene, const zrt_camera* camera, const zrt_param
     rc = zrt_ctx_assemble(c, &p, tiles.p, frame.p, nullptr);
     if (rc) return rc;
     HIPCHK(hipStreamSynchronize(c->stream));
-    HIPCHK(hipMemcpy(out_rgb, frame.p, sizeof(float) * 3 * size_t(p.width) * p.height, hipMemcpyDeviceToHost));
+    if (out_rgb)
+      HIPCHK(hipMemcpy(out_rgb, frame.p, sizeof(float) * 3 * size_t(p.width) * p.height, hipMemcpyDeviceToHost));
     zrt_stats s;
     rc = zrt_ctx_stats(c, &s);
     if (rc) return rc;
@@ -6522,6 +6884,7 @@ int render_one(const zrt_scene* scene, const zrt_camera* camera, const zrt_param
       if (rc) return rc;
     }
     if (stats) *stats = s;
+    if (post) return (*post)(c, p, frame.p);
     return ZRT_OK;
   }
   ZRT_CATCH_ALL
@@ -6597,8 +6960,9 @@ namespace zrt {
 namespace {
 int render_adaptive(const zrt_scene* scene, const zrt_camera* camera, const zrt_params* params,
                     const zrt_adaptive* adaptive, zrt_level_fn on_level, void* user, float* out_rgb,
-                    uint32_t* out_samples, zrt_stats* stats, zrt_scanline* rows) {
-  if (!camera || !out_rgb || !adaptive) return fail(ZRT_E_INVALID, "null argument");
+                    uint32_t* out_samples, zrt_stats* stats, zrt_scanline* rows, const FramePost* post = nullptr) {
+  if (!camera || (!out_rgb && !post) || !adaptive) return fail(ZRT_E_INVALID, "null argument");
+  if (!out_rgb && on_level) return fail(ZRT_E_INVALID, "on_level needs out_rgb");
   std::vector<uint32_t> levels;
   int rc = zrt::plan_adapt(params, adaptive, &levels);
   if (rc) return rc;
@@ -6630,7 +6994,7 @@ int render_adaptive(const zrt_scene* scene, const zrt_camera* camera, const zrt_
         rc = zrt_ctx_assemble(c, &p, tiles.p, frame.p, nullptr);
         if (rc) return rc;
         HIPCHK(hipStreamSynchronize(c->stream));
-        HIPCHK(hipMemcpy(out_rgb, frame.p, frame_bytes, hipMemcpyDeviceToHost));
+        if (out_rgb) HIPCHK(hipMemcpy(out_rgb, frame.p, frame_bytes, hipMemcpyDeviceToHost));
       }
       if (on_level && on_level(user, out_rgb, &info) != 0 && !over) {
         break;
@@ -6656,6 +7020,7 @@ int render_adaptive(const zrt_scene* scene, const zrt_camera* camera, const zrt_
       if (rc) return rc;
     }
     if (stats) *stats = s;
+    if (post) return (*post)(c, p, frame.p);
     return ZRT_OK;
   }
   ZRT_CATCH_ALL
@@ -6674,6 +7039,45 @@ int zrt_render_adaptive_progress(const zrt_scene* scene, const zrt_camera* camer
                                  uint32_t* out_samples, zrt_stats* stats, zrt_scanline* scanlines) {
   if (!scanlines) return fail(ZRT_E_INVALID, "null argument");
   return zrt::render_adaptive(scene, camera, params, adaptive, on_level, user, out_rgb, out_samples, stats, scanlines);
+}
+
+int zrt_render_denoised(const zrt_scene* scene, const zrt_camera* camera, const zrt_params* params,
+                        const zrt_adaptive* adaptive, const zrt_denoise* dn, float* out_rgb, float* out_noisy,
+                        float* out_features, zrt_stats* stats, double* denoise_ms) {
+  if (!camera || !out_rgb) return fail(ZRT_E_INVALID, "null argument");
+  zrt_denoise d;
+  if (dn) d = *dn;
+  else zrt_denoise_defaults(&d);
+  zrt::DenoiseLaunch l{};
+  int rc = zrt::plan_denoise(params, &d, &l);  // (refused before any device work)
+  if (rc) return rc;
+  const zrt::FramePost post = [&](zrt_ctx* c, const zrt_params& p, const float* dev_frame) -> int {
+    try {
+      const size_t px = size_t(p.width) * p.height;
+      zrt::DevBuf<float> feat, outb;
+      feat.alloc(px * 8);
+      outb.alloc(px * 3);
+      int r = zrt_ctx_features(c, camera, &p, feat.p, nullptr);
+      if (r) return r;
+      r = zrt_ctx_denoise(c, &p, &d, dev_frame, feat.p, outb.p, nullptr);
+      if (r) return r;
+      HIPCHK(hipStreamSynchronize(c->stream));
+      r = zrt_ctx_sync(c);  // (a feature launch's device error)
+      if (r) return r;
+      HIPCHK(hipMemcpy(out_rgb, outb.p, sizeof(float) * 3 * px, hipMemcpyDeviceToHost));
+      if (out_features) HIPCHK(hipMemcpy(out_features, feat.p, sizeof(float) * 8 * px, hipMemcpyDeviceToHost));
+      if (denoise_ms) {
+        r = zrt_ctx_denoise_ms(c, denoise_ms);
+        if (r) return r;
+      }
+      return ZRT_OK;
+    }
+    ZRT_CATCH_ALL
+  };
+  if (adaptive)
+    return zrt::render_adaptive(scene, camera, params, adaptive, nullptr, nullptr, out_noisy, nullptr, stats, nullptr,
+                                &post);
+  return zrt::render_one(scene, camera, params, out_noisy, stats, nullptr, &post);
 }
 
 // ---- several GPUs from one host thread (zrt_multi_*, zrt_render_multi) -------
