@@ -2,7 +2,7 @@
 
 zrt_ctx_accum_pass renders samples [done, done + n) of a run capped at
 samples_per_pixel as one launch of n samples whose sample keys are shifted by
-`done` (render.hip plan_pass, the function the launch path itself calls).  Here
+`done` (planner.cpp plan_pass, the function the launch path itself calls).  Here
 its plan is compared with a restatement in Python integers: the chunk
 bookkeeping, the refusals, the bytes of chunk sums a pass parks, and the key
 identity the shift rests on.

@@ -1,6 +1,6 @@
 """The level list of an adaptive run (zrt_debug_adapt_plan; CPU only).
 
-zrt_ctx_adapt_begin takes its sample levels from render.hip plan_adapt, the
+zrt_ctx_adapt_begin takes its sample levels from planner.cpp plan_adapt, the
 function zrt_debug_adapt_plan reports: L_0 = first_level in whole sample chunks
 (at least one), doubled while below the cap, then the cap itself (zrt.h,
 "adaptive sampling").  Here the list is compared with a restatement in Python

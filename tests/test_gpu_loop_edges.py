@@ -1,7 +1,7 @@
 """Launch-configuration edges of the sampling loops against the oracle.
 
 The parity suite (test_gpu_parity.py) is wide on geometry; this file is about
-what the launch decision (render.hip plan_launch, reported with no device by
+what the launch decision (planner.cpp plan_launch, reported with no device by
 zrt_debug_launch_plan) and the loops' row bookkeeping do at their edges:
 
 * max_depth 0 .. 3 in every loop (no loop shades at 0; no attenuation row is

@@ -322,7 +322,7 @@ def test_lds_plans_disjoint(scenes, index):
     32-bit stacks, both PRNGs, max depths 0..50 - keeps its regions (stack rows,
     top wide nodes, pool queues, the lockstep loop's parked lane state, attenuation
     rows, materials) disjoint, inside the plan and float4-aligned, and the lockstep
-    plan inside its 6-block share (render.hip check_plan).  No device needed."""
+    plan inside its 6-block share (planner.cpp check_plan).  No device needed."""
     n = z.debug_lds_plans(scenes(index))
     # modes 0-2 one loop each, mode 3 lockstep / wavefront / pool (full nodes, and compressed
     # ones where the scene has a tree: their real top levels); x stk16 x prng x depth
@@ -338,7 +338,7 @@ def test_shared_buffer_sizing_covers_every_launch(scenes, index):
     attenuation rows past the LDS ones and the stack rows past the LDS ones - are
     sized (zrt_render, schedule_tiles) to cover the render launch AND its scheduling
     probe, for every loop x stack width x PRNG x node format x depth x grid
-    (render.hip buffer_need / check_buffers, the same check that guards each launch).
+    (planner.cpp buffer_need / check_buffers, the same check that guards each launch).
     The sizing before commit 4072f5f (the probe reused the render's attenuation rows
     without growing them) must fail where the render keeps more LDS rows than the
     probe's 4: the wavefront loop's 12 - the round-5 GPU fault of ZRT_WF=1 on C3."""
@@ -387,7 +387,7 @@ def _check_plan(d, depth, where):
 
 @pytest.mark.parametrize("which", [0, 1, 2, 3, 4, "many-materials"])
 def test_launch_plan_invariants(scenes, which, monkeypatch):
-    """The launch decision of zrt_ctx_render_tiles (render.hip plan_launch, reported
+    """The launch decision of zrt_ctx_render_tiles (planner.cpp plan_launch, reported
     with no device by zrt_debug_launch_plan) over traversal x max_depth x PRNG x the
     loop knobs (ZRT_WF, ZRT_POOL, ZRT_LIST_LANES: unset, 0, 1) x ZRT_FLAG_GUARD x the
     16-bit stack-row cap (ZRT_STACK_LDS_ROWS16): the invariants of _check_plan.
@@ -570,7 +570,7 @@ def _scene_calls(s):
 
 @pytest.mark.parametrize("name,mutate,message", REFUSALS, ids=[r[0] for r in REFUSALS])
 def test_validate_scene_refusals(name, mutate, message):
-    """render.hip validate_scene: each refusal, reached by changing one field of a valid
+    """planner.cpp validate_scene: each refusal, reached by changing one field of a valid
     scene, comes back as ZRT_E_INVALID with its own message from zrt_ctx_create,
     zrt_render and zrt_debug_launch_plan - before the device check, so with no GPU too."""
     s, keep = _valid_scene()

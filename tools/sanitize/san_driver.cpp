@@ -8,12 +8,16 @@
 //   image_io.cpp   zrt_image_read_png / write_png / write_ppm (png_image.zig)
 //   bvh_build.cpp  zrt_bvh_build (bvh.zig:62-185)
 //   accel_build.cpp  the wide tree over the reference leaves (render.hip's FAST layout)
+//   planner.cpp, flatten.cpp, debug_plans.cpp  the LDS / buffer / launch / pass /
+//                  adaptive planners and the scene flattener, through the zrt_debug_*
+//                  entry points that need no device
 //   oracle/        oracle_render (both RNG modes), oracle_render_scanlines,
 //                  oracle_trace, oracle_bvh_build
 //
 // Device code is not built here (GPU sanitizers are not available on the pool);
 // build_bvh_device is stubbed to "not available", which is what the host build
-// path does without a GPU.  Any sanitizer report aborts with a non-zero status
+// path does without a GPU, and kernel_config() (render.hip's) returns the values the
+// shipped kernels are built with.  Any sanitizer report aborts with a non-zero status
 // (-fno-sanitize-recover=all); tests/test_sanitizers.py builds and runs this.
 #include <cmath>
 #include <cstdio>
@@ -26,9 +30,27 @@
 #include "../../oracle/oracle.h"
 #include "../../zraytrace_amd/csrc/accel_build.hpp"
 #include "../../zraytrace_amd/csrc/bvh_build.hpp"
+#include "../../zraytrace_amd/csrc/kernels.hpp"
 
 namespace zrt {
 bool build_bvh_device(const zrt_prim*, uint32_t, int, BuiltBvh*) { return false; }
+// render.hip's defaults: its #ifndef values, and the sizes that follow from them
+const KernelConfig& kernel_config() {
+  static const KernelConfig k = [] {
+    KernelConfig c{};
+    c.waves_wide = 6, c.waves_wf = 4, c.waves_pool = 4, c.waves_list = 6, c.waves_per_simd = 8;
+    c.att_rows_lock = 4, c.att_rows_wf = 12, c.att_rows_pool = 3, c.att_rows_list = 24;
+    c.stack_rows_lock = 16, c.sync_samples = 1, c.probe_spp = 1;
+    c.oct_copies = 8;
+    c.lane_words[0] = 4 + 5, c.lane_words[1] = 8 + 5;  // Rng<PRNG>'s words + 5 (LaneState)
+    c.block_paths = 128 * 4;                           // kPoolPaths per wave x 4 waves
+    c.layout = kLayoutVersion | kLayoutSphereSlots | kLayoutSphereFirst;
+    c.paxis_m = 1024.0f;
+    c.lds_top = c.lane_lds = c.mats_lds_only = c.lean_default = c.grow = c.sphere_slots = true;
+    return c;
+  }();
+  return k;
+}
 }  // namespace zrt
 // the C++ scene API's render() (zrt.hpp) forwards here; nothing in this harness calls it
 extern "C" int zrt_render(const zrt_scene*, const zrt_camera*, const zrt_params*, float*, zrt_stats*) {
@@ -61,7 +83,7 @@ static zrt_params params(uint32_t w, uint32_t h, uint32_t spp, uint32_t depth, u
   return p;
 }
 
-// the reference BVH's leaves in DFS order, as render.hip's flatten_scene hands
+// the reference BVH's leaves in DFS order, as flatten.cpp's flatten_scene hands
 // them to build_wide_bvh (refs are placeholders: the builder only carries them)
 static uint32_t wide_tree(const zrt::BuiltBvh& bvh) {
   std::vector<zrt::RefLeaf> leaves;
@@ -133,6 +155,37 @@ static void one_scene(uint32_t index, const std::string& assets, const std::stri
     CHECK(rc == 0, "scene %u: oracle_trace(bvh=%d) rc %d", index, bvh, rc);
   }
 
+  // the planners and the flattener (planner.cpp, flatten.cpp) through the no-device
+  // debug entry points: every LDS plan, both buffer sizings, the launch decision
+  uint32_t n_plans = 0;
+  rc = zrt_debug_lds_plans(s, &n_plans);
+  CHECK(rc == ZRT_OK && n_plans > 0, "scene %u lds plans: %s", index, zrt_last_error());
+  for (uint32_t legacy : {0u, 1u}) {
+    rc = zrt_debug_buffer_plans(s, legacy, &n_plans);
+    // (legacy = 1 is the sizing the check exists to refuse: either answer, no report)
+    CHECK(legacy ? (rc == ZRT_OK || rc == ZRT_E_UNSUPPORTED) : rc == ZRT_OK, "scene %u buffer plans (legacy %u): %s",
+          index, legacy, zrt_last_error());
+  }
+  for (uint32_t trav : {uint32_t(ZRT_TRAVERSAL_FAST), uint32_t(ZRT_TRAVERSAL_BINARY), uint32_t(ZRT_TRAVERSAL_REFERENCE)})
+    for (uint32_t depth : {0u, 1u, 30u})
+      for (uint32_t prng : {uint32_t(ZRT_PRNG_XOROSHIRO128), uint32_t(ZRT_PRNG_XOSHIRO256)}) {
+        zrt_params p = params(64, 48, 256, depth, ZRT_RNG_COUNTER);
+        p.traversal = trav;
+        p.prng = prng;
+        zrt_launch_plan lp;
+        rc = zrt_debug_launch_plan(s, &p, &lp);
+        CHECK(rc == ZRT_OK && lp.lds_bytes <= (160u << 10), "scene %u launch plan (traversal %u depth %u prng %u): %s",
+              index, trav, depth, prng, zrt_last_error());
+        uint32_t lean = 0;
+        rc = zrt_debug_lean_kernel(s, &cam, &p, &lean);
+        CHECK(rc == ZRT_OK, "scene %u lean kernel: %s", index, zrt_last_error());
+      }
+  if (s->n_prims > 10) {
+    uint64_t n_slots = 0;
+    rc = zrt_debug_qnodes(s, &n_slots);
+    CHECK(rc == ZRT_OK && n_slots > 0, "scene %u qnodes: %s", index, zrt_last_error());
+  }
+
   // binary scene file round trip
   const std::string path = tmp + "/scene" + std::to_string(index) + ".zrts";
   rc = zrt_scene_write(s, &cam, path.c_str());
@@ -151,6 +204,58 @@ static void one_scene(uint32_t index, const std::string& assets, const std::stri
   zrt_scene_free(data);
 }
 
+// plan_pass / plan_adapt at the edge values of tests/test_accum_plan.py and
+// tests/test_adapt_plan.py: whole and ragged passes, every refusal, chunk 0, the
+// last sample of a u16 cap; the level lists, their refusals and a short array
+static void pass_and_adapt_plans() {
+  struct Case { uint32_t cap, chunk, w, h, done, n; bool ok; };
+  const Case cases[] = {{12, 3, 24, 24, 0, 3, true},    {12, 3, 24, 24, 3, 6, true},   {12, 3, 24, 24, 9, 3, true},
+                        {12, 3, 24, 24, 12, 1, false},  {10, 3, 24, 24, 6, 4, true},   {10, 3, 24, 24, 10, 1, false},
+                        {12, 3, 24, 24, 10, 2, false},  {12, 3, 24, 24, 0, 0, false},  {12, 3, 24, 24, 9, 4, false},
+                        {12, 3, 24, 24, 0, 13, false},  {12, 3, 24, 24, 4, 3, false},  {65536, 3, 24, 24, 0, 3, false},
+                        {256, 0, 24, 24, 64, 100, true}, {256, 0, 24, 24, 16, 32, false}, {12, 3, 20, 13, 6, 4, true},
+                        {12, 3, 13, 20, 0, 6, false},   {65535, 4096, 2, 2, 0, 61440, true},
+                        {65535, 4096, 2, 2, 61440, 4095, true}, {65535, 4096, 2, 2, 65535, 1, false}};
+  for (const Case& c : cases) {
+    zrt_params p = params(c.w, c.h, c.cap, 4, ZRT_RNG_COUNTER);
+    p.sample_chunk = c.chunk;
+    zrt_pass_plan plan;
+    const int rc = zrt_debug_pass_plan(&p, c.done, c.n, &plan);
+    CHECK(c.ok ? rc == ZRT_OK && plan.samples_after == c.done + c.n : rc == ZRT_E_INVALID,
+          "pass plan cap %u chunk %u done %u n %u: rc %d", c.cap, c.chunk, c.done, c.n, rc);
+  }
+  zrt_params p3 = params(24, 24, 12, 4, ZRT_RNG_COUNTER);
+  p3.world_size = 3;
+  p3.rank = 1;
+  zrt_pass_plan plan;
+  CHECK(zrt_debug_pass_plan(&p3, 0, 12, &plan) == ZRT_OK && plan.pass_chunks == 4, "pass plan of rank 1 of 3");
+  CHECK(zrt_debug_pass_plan(nullptr, 0, 1, &plan) == ZRT_E_INVALID && zrt_debug_pass_plan(&p3, 0, 1, nullptr) == ZRT_E_INVALID,
+        "pass plan: null arguments accepted");
+
+  struct Adapt { uint32_t cap, chunk, first; float tol; uint32_t n_levels; };  // n_levels 0: refused
+  const Adapt adapts[] = {{12, 3, 3, 0.5f, 3},  {48, 3, 3, 0.5f, 5},    {1024, 0, 32, 0.0f, 6}, {20, 3, 3, 0.5f, 4},
+                          {48, 3, 4, 0.5f, 4},  {48, 3, 0, 0.5f, 5},    {64, 0, 1, 0.5f, 2},    {12, 3, 12, 0.5f, 1},
+                          {12, 3, 4000000000u, 0.5f, 1}, {2, 3, 0, 0.5f, 1}, {12, 3, 3, 1e30f, 3},
+                          {12, 3, 3, -1.0f, 0}, {12, 3, 3, NAN, 0},     {12, 3, 3, INFINITY, 0}, {65536, 3, 3, 0.5f, 0}};
+  for (const Adapt& a : adapts) {
+    zrt_params p = params(24, 24, a.cap, 4, ZRT_RNG_COUNTER);
+    p.sample_chunk = a.chunk;
+    const zrt_adaptive ad = {a.tol, a.first};
+    uint32_t levels[2], n = 0;  // (a short array: the count is still the plan's)
+    const int rc = zrt_debug_adapt_plan(&p, &ad, levels, 2, &n);
+    CHECK(a.n_levels ? rc == ZRT_OK && n == a.n_levels : rc == ZRT_E_INVALID,
+          "adapt plan cap %u chunk %u first %u: rc %d, %u levels", a.cap, a.chunk, a.first, rc, n);
+  }
+  const zrt_adaptive ad = {0.5f, 3};
+  uint32_t n = 0;
+  CHECK(zrt_debug_adapt_plan(&p3, &ad, nullptr, 0, &n) == ZRT_OK && n == 3, "adapt plan: count alone");
+  CHECK(zrt_debug_adapt_plan(nullptr, &ad, nullptr, 0, &n) == ZRT_E_INVALID &&
+            zrt_debug_adapt_plan(&p3, nullptr, nullptr, 0, &n) == ZRT_E_INVALID &&
+            zrt_debug_adapt_plan(&p3, &ad, nullptr, 8, &n) == ZRT_E_INVALID &&
+            zrt_debug_adapt_plan(&p3, &ad, nullptr, 0, nullptr) == ZRT_E_INVALID,
+        "adapt plan: null arguments accepted");
+}
+
 int main(int argc, char** argv) {
   if (argc < 3) {
     std::fprintf(stderr, "usage: %s ASSETS_DIR TMP_DIR\n", argv[0]);
@@ -158,6 +263,7 @@ int main(int argc, char** argv) {
   }
   const std::string assets = argv[1], tmp = argv[2];
   for (uint32_t i : {0u, 1u, 2u, 3u, 4u}) one_scene(i, assets, tmp);
+  pass_and_adapt_plans();
 
   // error paths: unknown scene index, missing files, a truncated binary scene
   zrt_scene_data* d = nullptr;

@@ -33,11 +33,6 @@ def lib():
     return _ffi.load()
 
 
-# csrc/Makefile ID_SRC, in its order, then include/zrt.h
-_ID_SRC = ("render.hip", "bvh_gpu.hip", "denoise.hip", "denoise.hpp", "accel_build.cpp", "accel_build.hpp", "bvh_build.cpp", "bvh_build.hpp",
-           "device_math.hpp", "zrt.hpp", "scene_io.cpp", "image_io.cpp", "cli.cpp")
-
-
 def build_id() -> str:
     """zrt_build_id() of the loaded library: sha1 of the kernel sources (16 hex)
     - sha1 of the device compile flags (8)."""
@@ -53,7 +48,8 @@ def build_id_of_sources() -> str:
     import hashlib
     h = hashlib.sha1()
     csrc = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
-    for f in _ID_SRC:
+    # csrc/Makefile ID_SRC: every source of the directory in sorted order, then include/zrt.h
+    for f in sorted(f for f in os.listdir(csrc) if f.endswith((".hip", ".hpp", ".cpp"))):
         with open(os.path.join(csrc, f), "rb") as fh:
             h.update(fh.read())
     with open(os.path.join(REPO, "include", "zrt.h"), "rb") as fh:

@@ -29,7 +29,7 @@
 //                  render.hip (< 0; b == a for a one-primitive leaf);
 //     empty slot:  an empty box (min = +inf, max = -inf), never entered.
 //   An inner child's box is stored grown by `inflate` x its own largest
-//   |coordinate| (render.hip passes 2^-19): a computed primitive hit lies outside
+//   |coordinate| (flatten.cpp passes 2^-19): a computed primitive hit lies outside
 //   its box by a few ulps of the coordinates, and growing the box in space grows
 //   each axis's t interval by that distance x |1/d_k| - the right slack for a
 //   ray (nearly) parallel to a box face, at no cost per node (DESIGN.md §3

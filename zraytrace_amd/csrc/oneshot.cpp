@@ -1,0 +1,250 @@
+// oneshot.cpp - the one-shot renders (zrt_render*): a context, the frame, the
+// copy back.  They call the C ABI of context.cpp and hold device buffers; nothing
+// else.
+#include <algorithm>
+#include <cstring>
+#include <functional>
+#include <memory>
+
+#include "context.hpp"
+
+using zrt::fail;
+
+namespace zrt {
+namespace {
+// What a one-shot render does with its assembled frame while it still lies on the
+// device (zrt_render_denoised): called last, with the context, the params rendered
+// with and the frame.
+using FramePost = std::function<int(zrt_ctx*, const zrt_params&, const float*)>;
+
+int render_one(const zrt_scene* scene, const zrt_camera* camera, const zrt_params* params, float* out_rgb,
+               zrt_stats* stats, zrt_scanline* rows, const FramePost* post = nullptr) {
+  if (!camera || (!out_rgb && !post)) return fail(ZRT_E_INVALID, "null argument");
+  int rc = zrt::validate_params(params);
+  if (rc) return rc;
+  zrt_params p = *params;
+  p.rank = 0;
+  p.world_size = 1;
+  if (rows) p.flags |= ZRT_FLAG_SCANLINES;
+  zrt_ctx* c = nullptr;
+  rc = zrt_ctx_create(scene, &p, &c);
+  if (rc) return rc;
+  std::unique_ptr<zrt_ctx, int (*)(zrt_ctx*)> guard(c, zrt_ctx_destroy);
+  try {
+    uint32_t n_tiles = 0;
+    rc = zrt_ctx_tile_count(c, &p, &n_tiles);
+    if (rc) return rc;
+    zrt::DevBuf<float> tiles, frame;
+    tiles.alloc(size_t(n_tiles) * 64 * 3);
+    frame.alloc(size_t(p.width) * p.height * 3);
+    rc = zrt_ctx_render_tiles(c, camera, &p, tiles.p, nullptr);
+    if (rc) return rc;
+    rc = zrt_ctx_assemble(c, &p, tiles.p, frame.p, nullptr);
+    if (rc) return rc;
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (out_rgb)
+      HIPCHK(hipMemcpy(out_rgb, frame.p, sizeof(float) * 3 * size_t(p.width) * p.height, hipMemcpyDeviceToHost));
+    zrt_stats s;
+    rc = zrt_ctx_stats(c, &s);
+    if (rc) return rc;
+    if (rows) {
+      std::memset(rows, 0, sizeof(zrt_scanline) * p.height);
+      rc = add_scanlines(c, rows, p.height);
+      if (rc) return rc;
+    }
+    if (stats) *stats = s;
+    if (post) return (*post)(c, p, frame.p);
+    return ZRT_OK;
+  }
+  ZRT_CATCH_ALL
+}
+}  // namespace
+}  // namespace zrt
+
+int zrt_render(const zrt_scene* scene, const zrt_camera* camera, const zrt_params* params,
+               float* out_rgb, zrt_stats* stats) {
+  return zrt::render_one(scene, camera, params, out_rgb, stats, nullptr);
+}
+
+int zrt_render_progress(const zrt_scene* scene, const zrt_camera* camera, const zrt_params* params,
+                        float* out_rgb, zrt_stats* stats, zrt_scanline* scanlines) {
+  if (!scanlines) return fail(ZRT_E_INVALID, "null argument");
+  return zrt::render_one(scene, camera, params, out_rgb, stats, scanlines);
+}
+
+int zrt_render_progressive(const zrt_scene* scene, const zrt_camera* camera, const zrt_params* params,
+                           uint32_t pass_samples, zrt_pass_fn on_pass, void* user, float* out_rgb,
+                           zrt_stats* stats) {
+  if (!camera || !out_rgb) return fail(ZRT_E_INVALID, "null argument");
+  int rc = zrt::validate_params(params);
+  if (rc) return rc;
+  zrt_params p = *params;
+  p.rank = 0;
+  p.world_size = 1;
+  const uint32_t chunk = p.sample_chunk ? p.sample_chunk : ZRT_DEFAULT_SAMPLE_CHUNK;
+  // whole chunks per pass (a pass must start on a chunk boundary); 0: the default
+  const uint64_t per_pass = pass_samples ? (uint64_t(pass_samples) + chunk - 1) / chunk * chunk
+                                         : uint64_t(ZRT_DEFAULT_PASS_CHUNKS) * chunk;
+  zrt_ctx* c = nullptr;
+  rc = zrt_ctx_create(scene, &p, &c);
+  if (rc) return rc;
+  std::unique_ptr<zrt_ctx, int (*)(zrt_ctx*)> guard(c, zrt_ctx_destroy);
+  try {
+    uint32_t n_tiles = 0;
+    rc = zrt_ctx_tile_count(c, &p, &n_tiles);
+    if (rc) return rc;
+    zrt::DevBuf<float> tiles, frame;
+    tiles.alloc(size_t(n_tiles) * 64 * 3);
+    frame.alloc(size_t(p.width) * p.height * 3);
+    rc = zrt_ctx_accum_begin(c, camera, &p);
+    if (rc) return rc;
+    const size_t frame_bytes = sizeof(float) * 3 * size_t(p.width) * p.height;
+    for (uint32_t done = 0; done < p.samples_per_pixel;) {
+      const uint32_t n = uint32_t(std::min<uint64_t>(per_pass, p.samples_per_pixel - done));
+      rc = zrt_ctx_accum_pass(c, n, tiles.p, nullptr);
+      if (rc) return rc;
+      rc = zrt_ctx_assemble(c, &p, tiles.p, frame.p, nullptr);
+      if (rc) return rc;
+      done += n;
+      if (!on_pass && done < p.samples_per_pixel) continue;  // nobody looks: the passes queue up
+      HIPCHK(hipStreamSynchronize(c->stream));
+      HIPCHK(hipMemcpy(out_rgb, frame.p, frame_bytes, hipMemcpyDeviceToHost));
+      if (on_pass) {
+        zrt_pass_info info;
+        rc = zrt_ctx_accum_info(c, &info);
+        if (rc) return rc;
+        if (on_pass(user, out_rgb, &info) != 0) break;
+      }
+    }
+    zrt_stats s;
+    rc = zrt_ctx_stats(c, &s);
+    if (rc) return rc;
+    if (stats) *stats = s;
+    return ZRT_OK;
+  }
+  ZRT_CATCH_ALL
+}
+
+namespace zrt {
+namespace {
+int render_adaptive(const zrt_scene* scene, const zrt_camera* camera, const zrt_params* params,
+                    const zrt_adaptive* adaptive, zrt_level_fn on_level, void* user, float* out_rgb,
+                    uint32_t* out_samples, zrt_stats* stats, zrt_scanline* rows, const FramePost* post = nullptr) {
+  if (!camera || (!out_rgb && !post) || !adaptive) return fail(ZRT_E_INVALID, "null argument");
+  if (!out_rgb && on_level) return fail(ZRT_E_INVALID, "on_level needs out_rgb");
+  std::vector<uint32_t> levels;
+  int rc = zrt::plan_adapt(params, adaptive, &levels);
+  if (rc) return rc;
+  zrt_params p = *params;
+  p.rank = 0;
+  p.world_size = 1;
+  if (rows) p.flags |= ZRT_FLAG_SCANLINES;
+  zrt_ctx* c = nullptr;
+  rc = zrt_ctx_create(scene, &p, &c);
+  if (rc) return rc;
+  std::unique_ptr<zrt_ctx, int (*)(zrt_ctx*)> guard(c, zrt_ctx_destroy);
+  try {
+    uint32_t n_tiles = 0;
+    rc = zrt_ctx_tile_count(c, &p, &n_tiles);
+    if (rc) return rc;
+    zrt::DevBuf<float> tiles, frame;
+    tiles.alloc(size_t(n_tiles) * 64 * 3);
+    frame.alloc(size_t(p.width) * p.height * 3);
+    HIPCHK(hipMemset(tiles.p, 0, sizeof(float) * tiles.n));
+    rc = zrt_ctx_adapt_begin(c, camera, &p, adaptive);
+    if (rc) return rc;
+    const size_t frame_bytes = sizeof(float) * 3 * size_t(p.width) * p.height;
+    for (size_t k = 0; k < levels.size(); ++k) {
+      zrt_level_info info;
+      rc = zrt_ctx_adapt_level(c, tiles.p, nullptr, &info);
+      if (rc) return rc;
+      const bool over = info.tiles_active_after == 0;
+      if (on_level || over) {
+        rc = zrt_ctx_assemble(c, &p, tiles.p, frame.p, nullptr);
+        if (rc) return rc;
+        HIPCHK(hipStreamSynchronize(c->stream));
+        if (out_rgb) HIPCHK(hipMemcpy(out_rgb, frame.p, frame_bytes, hipMemcpyDeviceToHost));
+      }
+      if (on_level && on_level(user, out_rgb, &info) != 0 && !over) {
+        break;
+      }
+      if (over) break;
+    }
+    if (out_samples) {
+      std::vector<uint32_t> per_tile(std::max(1u, n_tiles));
+      rc = zrt_ctx_adapt_samples(c, per_tile.data(), n_tiles);
+      if (rc) return rc;
+      const zrt::Geometry g = zrt::geometry(&p);
+      std::fill(out_samples, out_samples + size_t(p.width) * p.height, 0u);
+      for (uint32_t y = 0; y < p.height; ++y)
+        for (uint32_t x = 0; x < g.xbound; ++x)
+          out_samples[size_t(y) * p.width + x] = per_tile[(y / 8u) * g.tiles_x + x / 8u];
+    }
+    zrt_stats s;
+    rc = zrt_ctx_stats(c, &s);
+    if (rc) return rc;
+    if (rows) {
+      std::memset(rows, 0, sizeof(zrt_scanline) * p.height);
+      rc = add_scanlines(c, rows, p.height);
+      if (rc) return rc;
+    }
+    if (stats) *stats = s;
+    if (post) return (*post)(c, p, frame.p);
+    return ZRT_OK;
+  }
+  ZRT_CATCH_ALL
+}
+}  // namespace
+}  // namespace zrt
+
+int zrt_render_adaptive(const zrt_scene* scene, const zrt_camera* camera, const zrt_params* params,
+                        const zrt_adaptive* adaptive, zrt_level_fn on_level, void* user, float* out_rgb,
+                        uint32_t* out_samples, zrt_stats* stats) {
+  return zrt::render_adaptive(scene, camera, params, adaptive, on_level, user, out_rgb, out_samples, stats, nullptr);
+}
+
+int zrt_render_adaptive_progress(const zrt_scene* scene, const zrt_camera* camera, const zrt_params* params,
+                                 const zrt_adaptive* adaptive, zrt_level_fn on_level, void* user, float* out_rgb,
+                                 uint32_t* out_samples, zrt_stats* stats, zrt_scanline* scanlines) {
+  if (!scanlines) return fail(ZRT_E_INVALID, "null argument");
+  return zrt::render_adaptive(scene, camera, params, adaptive, on_level, user, out_rgb, out_samples, stats, scanlines);
+}
+
+int zrt_render_denoised(const zrt_scene* scene, const zrt_camera* camera, const zrt_params* params,
+                        const zrt_adaptive* adaptive, const zrt_denoise* dn, float* out_rgb, float* out_noisy,
+                        float* out_features, zrt_stats* stats, double* denoise_ms) {
+  if (!camera || !out_rgb) return fail(ZRT_E_INVALID, "null argument");
+  zrt_denoise d;
+  if (dn) d = *dn;
+  else zrt_denoise_defaults(&d);
+  zrt::DenoiseLaunch l{};
+  int rc = zrt::plan_denoise(params, &d, &l);  // (refused before any device work)
+  if (rc) return rc;
+  const zrt::FramePost post = [&](zrt_ctx* c, const zrt_params& p, const float* dev_frame) -> int {
+    try {
+      const size_t px = size_t(p.width) * p.height;
+      zrt::DevBuf<float> feat, outb;
+      feat.alloc(px * 8);
+      outb.alloc(px * 3);
+      int r = zrt_ctx_features(c, camera, &p, feat.p, nullptr);
+      if (r) return r;
+      r = zrt_ctx_denoise(c, &p, &d, dev_frame, feat.p, outb.p, nullptr);
+      if (r) return r;
+      HIPCHK(hipStreamSynchronize(c->stream));
+      r = zrt_ctx_sync(c);  // (a feature launch's device error)
+      if (r) return r;
+      HIPCHK(hipMemcpy(out_rgb, outb.p, sizeof(float) * 3 * px, hipMemcpyDeviceToHost));
+      if (out_features) HIPCHK(hipMemcpy(out_features, feat.p, sizeof(float) * 8 * px, hipMemcpyDeviceToHost));
+      if (denoise_ms) {
+        r = zrt_ctx_denoise_ms(c, denoise_ms);
+        if (r) return r;
+      }
+      return ZRT_OK;
+    }
+    ZRT_CATCH_ALL
+  };
+  if (adaptive)
+    return zrt::render_adaptive(scene, camera, params, adaptive, nullptr, nullptr, out_noisy, nullptr, stats, nullptr,
+                                &post);
+  return zrt::render_one(scene, camera, params, out_noisy, stats, nullptr, &post);
+}

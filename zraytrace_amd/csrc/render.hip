@@ -21,127 +21,18 @@
 //     (conflict-free: every lane of a wave hits a distinct bank);
 //   * RNG: one Xoroshiro128+ (or Xoshiro256++) stream per (pixel, sample),
 //     seeded through SplitMix64 exactly as DefaultPrng.init seeds.
-#include <dlfcn.h>
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
-#include <rccl/rccl.h>
 
-#include <algorithm>
-#include <chrono>
-#include <cmath>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <functional>
-#include <memory>
-#include <mutex>
-#include <string>
+#include <cstdint>
 #include <type_traits>
-#include <vector>
 
 #include "accel_build.hpp"
-#include "bvh_build.hpp"
-#include "denoise.hpp"
 #include "device_math.hpp"
+#include "kernels.hpp"
 #include "zrt.hpp"
 
 namespace zrt {
-
-// ---------------------------------------------------------------------------
-// device data layout
-// ---------------------------------------------------------------------------
-// nodes: 2 x float4 per node {min.xyz, left}, {max.xyz, right}; child >= 0 is
-//   a node index, child < 0 a primitive slot ref -(2*slot + kind) - 1.
-// prims: 3 x float4 per slot (slots in DFS leaf order, or list order):
-//   triangle {a.xyz, e1.x} {e1.yz, e2.xy} {e2.z, n.xyz}  (n = e1 x e2)
-//   sphere   {center.xyz, radius^2} {0} {0}   (radius * radius rounded once, on the host)
-// shade: 1 x float4 per slot: triangle {unit normal.xyz, tag},
-//   sphere {1/radius, 0, 0, tag}; tag = material | kind << 31 (as u32 bits)
-struct alignas(16) DevMaterial {
-  float r, g, b, ior;          // texture color / index of refraction
-  float u_off, v_off;          // image texture offsets
-  uint32_t kind, tex_kind;     // ZRT_MAT_*, ZRT_TEX_*
-  uint32_t img_w, img_h, img_off;  // image texture (img_off in texels of its store)
-  uint32_t img_u8;                 // 1: the image is stored as 8-bit RGBX (exact k/255), 0: f32 RGB
-};
-
-struct KArgs {
-  const float4* __restrict__ nodes;
-  const float4* __restrict__ prims;
-  const float4* __restrict__ shade;
-  const float4* __restrict__ wnodes;   // FAST: 4-wide nodes (node_f4 float4 each: 8 full, 4 compressed)
-  const float4* __restrict__ qleaves;  // compressed nodes' leaf records (kLeafRecF4 float4 each), else null
-  uint32_t n_qnodes, n_qleaves;        // compressed nodes per octant copy and leaf records (bounds checks)
-  const DevMaterial* __restrict__ mats;
-  const float* __restrict__ texels;    // f32 RGB images
-  const uint32_t* __restrict__ texels8;  // 8-bit RGBX images (every value exactly k/255)
-  uint32_t* __restrict__ att;          // [row - att_lds_rows][lane or path]: attenuation codes (att_code)
-  float4* __restrict__ partial;        // [chunk][tile slot] chunk sums
-  uint32_t* __restrict__ work_counter;
-  uint32_t* __restrict__ unit_cost;         // probe: loop iterations a wave spent on each tile, else null
-  // lockstep render after a scheduling probe: the probe's counters, from which every
-  // wave derives the same lockstep interval (render_loop, auto_sync); null: a.sync
-  const unsigned long long* __restrict__ sync_probe;
-  const uint32_t* __restrict__ tile_order;  // local tiles in the order units are handed out, or null
-  unsigned long long* __restrict__ wave_times;  // ZRT_PROFILE builds: {start, end} realtime per wave
-  unsigned long long* __restrict__ counters;  // kNumCounters x u64
-  // ZRT_FLAG_SCANLINES: [row][3] recursion-limit hits, reflections, background
-  // hits per frame row (raytrace.zig:184's printProgress deltas), else null
-  unsigned long long* __restrict__ scanlines;
-  uint32_t* __restrict__ error_flag;
-  float org[3], llc[3], hor[3], ver[3];
-  // jitter (raytrace.zig:173-174) divides by width / height: (x + r - 0.5) lies
-  // in {+0} u [2^-23, 65536], so dev::div_core with inv_* = RN(1 / width) (IEEE on
-  // the host) is the IEEE quotient with no range check
-  float f_width, f_height, color_scale, inv_width, inv_height;
-  uint32_t width, height, xbound, spp, max_depth;
-  uint32_t tiles_x, rank, world, total_work;
-  uint32_t n_list, stack_depth, n_lanes;
-  uint32_t chunk, n_chunks, sync;  // a work unit = one chunk of one tile
-  uint32_t n_slots;  // this launch's pixel slots (tiles x 64): the stride of a chunk in partial
-  uint32_t wide_stride;  // float4s per octant copy of the wide tree
-  uint32_t node_f4;      // float4s per wide node: 8 (full, wide_iter) or 4 (compressed, wide_iter_q)
-  uint32_t lds_rows;     // FAST: stack rows in LDS; rows lds_rows.. stack_depth-1 in stack_ovf
-  uint32_t ref_stack;    // rows the reference traversal needs (FAST's order-hazard replay)
-  const uint32_t* __restrict__ leaf_of_slot;  // primitive slot -> its reference BVH leaf node
-  void* stack_ovf;       // [row - lds_rows][lane] overflow rows of the FAST stack (StackT)
-  unsigned long long seed_mix;
-  // LDS beyond the stack rows (byte offsets into the block's dynamic LDS):
-  uint32_t n_top;         // FAST: wide nodes 0 .. n_top-1 (the top levels) served from LDS
-  uint32_t lds_top_off;   //   [copy][node][8] float4, copied in at kernel start
-  uint32_t lds_att_off;   // attenuation rows 0 .. att_lds_rows-1: [row][lane] u32 codes (att_code)
-  uint32_t att_lds_rows;  //   (rows att_lds_rows.. in `att`, [row - att_lds_rows][lane])
-  uint32_t lds_mat_off;   // the material table (n_mats DevMaterial), when mats_in_lds
-  uint32_t n_mats, mats_in_lds;
-  uint32_t wf_thresh;  // wavefront loop: shade when ready lanes >= this / 64 of the unit's active lanes
-                       // (path-pool loop: once the queue is empty and fewer than 64 - this lanes traverse)
-  uint32_t lds_pool_off;  // path-pool loop: rays, hits and queues (kBlockPaths paths per block)
-  uint32_t lds_state_off;  // lockstep FAST loop: lane state across the traversal, [word][lane] u32 (LaneState)
-  uint32_t n_paths;       //   paths of the launch (grid x kBlockPaths): the stride of its global attenuation rows
-  uint32_t tri_rcp_fast;  // every triangle |n| < 2^125: 1/det by dev::rcp_core (RayT::rcp_det)
-  float scene_extent;     // the triangles' largest |coordinate| (ray_slack)
-  float tri_c[3], tri_h[3];  // the triangles' bounding box: centre, half extents (paxis_grow)
-  float paxis_m;             // per-axis margins in waves with a lane of max_k |1/d_k| above this (kPaxisM)
-  // Spheres (DESIGN.md §3 "Spheres"): the reference BVH nodes whose subtree holds
-  // a sphere (1 byte each), and the origins the wide tree's sphere growth was
-  // sized for: max_k |o_k - root_c[k]| <= origin_bound (other rays are traced the
-  // reference's way, ray_origin_ok)
-  const uint8_t* __restrict__ ref_sph;
-  float root_c[3], origin_bound;
-  uint32_t check_origins;  // 0: every ray of the launch starts inside the bound (the camera does, checked
-                           // on the host, and scattered rays start at hits), so ray_origin_ok is skipped
-  uint32_t layout;         // the wide tree's encoding (accel_build.hpp kLayout*): must equal kKernelLayout
-  float graze_m;           // the grazing margins' coefficient (RayT::gm; DESIGN.md §3 "Grazing rays")
-  float graze_leaf;        // ... of leaf slots' relative margin (RayT::gl, >= graze_m)
-  float guard;             // the grazing-triangle guard (RayT::gk, wide_iter; 0: off)
-  uint64_t att_cap, ovf_cap;  // elements of `att` and of `stack_ovf` (StackT): row_ok's bounds
-};
-
-
-// error_flag bits (zrt_ctx_sync / zrt_ctx_stats / zrt_render report them as ZRT_E_UNSUPPORTED)
-constexpr uint32_t kErrOverflow = 1u;  // a traversal stack deeper than it was sized for
-constexpr uint32_t kErrLayout = 2u;    // the wide tree's encoding is not the one this kernel decodes
-constexpr uint32_t kErrBounds = 4u;    // STATS flavour: a global row index past its buffer (row_ok)
 
 // The STATS flavour's bounds check of a global row index (attenuation rows,
 // stack overflow rows) against its buffer (KArgs::att_cap / ovf_cap, set from the
@@ -158,47 +49,6 @@ __device__ __forceinline__ bool row_ok(const KArgs& a, uint64_t idx, uint64_t ca
   return false;
 }
 
-// counters[]: progress counters of raytrace.zig:20-34 + traffic diagnostics
-enum { kDepthHits, kReflections, kBackground, kRays, kNodes, kTriTests, kSphereTests, kShades, kTexels,
-       kLeaves, kReplays, kExcessTri, kExcessSph, kExcessHits, kNumCounters };
-constexpr int kWorkSlot = 14, kErrorSlot = 15, kProfSlot = 16, kScratchSlots = 48;
-// STATS flavour, SIMD efficiency (zrt_ctx_debug_counters): traversal loop trips
-// of the waves (per traced step, the most node visits of any lane: kNodes /
-// (64 kTravTrips) is the lane efficiency of traversal), loop iterations in which
-// some lane ran a rayColor step, and the lane-steps run in them
-constexpr int kTravTrips = 21, kLoopTrips = 22, kLaneSteps = 23;
-// STATS flavour, coherence of the FAST loop's vector-memory fetches (lane
-// counts): wide nodes read from global memory, and those read while every
-// active lane of the wave read the same node; primitive tests, and those in
-// which every active lane tested the same primitive (a wave-uniform address
-// could come through the scalar cache instead of the vector data return)
-constexpr int kGlobalNodes = 24, kUniformNodes = 25, kPrimLaneTests = 26, kUniformPrims = 27;
-// STATS: attenuation-stack rows written to / read from global memory (rows past
-// the LDS ones): with the chunk sums, the loop's HBM writes
-constexpr int kAttWrites = 28, kAttReads = 29;
-// STATS: FAST traversal stack entries written to the global rows (deep trees:
-// rows past the LDS ones, 32-bit entries)
-constexpr int kStackOvfWrites = 30;
-// scheduling probe: the loop iterations in which some lane of the wave ran a
-// rayColor step, summed over the waves (with kReflections, kBackground and
-// kDepthHits, the steps run: the probe's lane efficiency, auto_sync)
-constexpr int kProbeTrips = 31;
-// STATS: the FAST loops' vector-memory wave-instructions by shape (wave-level
-// event counts, not lane counts): the inputs of bench.py's data-return model
-// (DESIGN.md §4 "The data-return model"), priced per shape by
-// tools/ubench_shapes.hip.  Wave trips that read a global wide node through the
-// vector path (8 dwordx4 loads but for the last: 7) and the distinct nodes they
-// read; trips that read one through the scalar cache; leaf trips that read a
-// node's second refs (one flat dwordx4); wave trips of vector primitive tests and
-// their distinct primitives; scalar primitive tests; shade records read through
-// the vector path; attenuation rows written to / read from global memory.
-// kVNodeCost / kVPrimCost: the same trips' sum of max(16, distinct records) - the
-// data-return cycles of one of their dwordx4 loads (ubench_shapes: 16 per
-// wave-instruction up to 16 distinct 64-B lines, one per line beyond)
-constexpr int kVNodeTrips = 32, kVNodeLines = 33, kSNodeTrips = 34, kRbTrips = 35, kVPrimTrips = 36,
-              kVPrimLines = 37, kSPrimTrips = 38, kVShadeTrips = 39, kAttWTrips = 40, kAttRTrips = 41,
-              kVNodeCost = 42, kVPrimCost = 43;
-
 // ZRT_PROFILE builds (diagnostic only, never the shipped library) add s_memtime
 // cycle sums per loop section into counters[kProfSlot + section].
 #ifndef ZRT_PROFILE
@@ -214,7 +64,6 @@ __device__ __forceinline__ uint64_t prof_stamp() {
   return t;
 }
 
-constexpr int kBlock = 256;
 #ifndef ZRT_PROBE_SPP
 #define ZRT_PROBE_SPP 1  // samples per pixel of the scheduling probe; A/B at N=8: 1, 2, 4, 8 give the same render launch
 #endif
@@ -1701,17 +1550,6 @@ __device__ __forceinline__ bool wide_iter(const KArgs& a, const RayT& r, const W
         if (wave_once()) { ++coh.vn_trips; coh.vn_lines += dn; coh.vn_cost += max(16u, dn); }
       }
       wide_load(g, sx, sy, sz, w);
-#if ZRT_AB_DOUBLE_NODE  // A/B probe only (never shipped): the same node read again from another octant copy
-      {
-        WideNode w2;
-        const uint32_t o2 = (v.base + a.wide_stride * (ZRT_AB_DOUBLE_NODE)) % (a.wide_stride * 8u);
-        wide_load(a.wnodes + o2 + 8u * (uint32_t)next, sx, sy, sz, w2);
-        const uint32_t x = __float_as_uint(w2.nx.x) ^ __float_as_uint(w2.ny.y) ^ __float_as_uint(w2.nz.z) ^
-                           __float_as_uint(w2.fx.w) ^ __float_as_uint(w2.fy.x) ^ __float_as_uint(w2.fz.y) ^
-                           __float_as_uint(w2.ra.z);
-        if (x == 0x7fc01234u) w.ra.x = w.ra.y;  // never true for the scenes measured
-      }
-#endif
     }
   }
   return true;
@@ -1729,10 +1567,6 @@ __device__ __forceinline__ void wide_finish(const KArgs& a, const RayT& r, Stack
   const bool far = __builtin_expect((!Lean<LEAN>::origin && !ray_origin_ok(a, r)) || ray_degenerate(r), 0);
   if (__builtin_expect((ZRT_ORDER_EXACT && order_hazard<false>(a, r, best_t, best)) || far, 0)) {
     if (STATS) ++c_replays;
-#if ZRT_REPLAY_OFF
-    if (!far) best_t = -best_t;  // A/B only: the replay's cost without its code (results not exact)
-    else
-#endif
     reference_replay<StackT>(a, r, stk, gl, best_t, best, !far);
   }
 }
@@ -2256,11 +2090,6 @@ __device__ __forceinline__ uint32_t att_row(const KArgs& a, const AttRows& ar, u
   const uint64_t k = (uint64_t)(i - a.att_lds_rows) * ar.g_stride + ar.g_index;
   return row_ok<STATS>(a, k, a.att_cap) ? a.att[k] : kAttOne;
 }
-#ifndef ZRT_SHADE_CONVERGE
-#define ZRT_SHADE_CONVERGE 0  // BVH loops' shade_step: the operations materials share in Material.scatter issued
-                              // once (1, 2: exact at 5 waves per SIMD, a wrong frame from the 6-wave lockstep
-                              // kernel's timed flavour - DESIGN.md §3 "The lockstep kernel's spills"; A/B only)
-#endif
 #ifndef ZRT_ATT_PAIRS
 #define ZRT_ATT_PAIRS 1  // att_product decodes two rows at a time (their texel loads in flight together)
 #endif
@@ -2393,124 +2222,6 @@ __device__ __forceinline__ void shade_step(const KArgs& a, const DevMaterial* __
     bool absorbed = false;
     uint32_t att = kAttOne;  // the attenuation as an att code (dielectric: (1, 1, 1))
     V3 nd;
-#if ZRT_SHADE_CONVERGE == 2
-    // as below, every shared piece under a wave-uniform branch (taken when some lane
-    // of the wave needs it) that all the wave's lanes run, each lane keeping its own
-    // result by a select: no divergent branch around the scatter (the divergent form
-    // miscompiled in the 80-VGPR lockstep kernel's timed flavour)
-    {
-      const bool lamb = mkind == ZRT_MAT_LAMBERTIAN, metal = mkind == ZRT_MAT_METAL;
-      const bool diel = !lamb && !metal;
-      V3 ud = d;
-      if (__ballot(!lamb) != 0ull) {
-        const V3 u = unit(d);
-        if (!lamb) ud = u;
-      }
-      float r1 = 0.0f;
-      if (__ballot(lamb) != 0ull) {
-        R t = rng;
-        const float v = rand_float(t);
-        rng_keep(rng, t, lamb);
-        r1 = lamb ? v : 0.0f;
-      }
-      float ratio = 1.0f, cos_theta = 0.0f;
-      if (__ballot(diel) != 0ull) {
-        const float rt = front ? dev::rcp_rn(mat.ior()) : mat.ior();
-        const float ct = dev::fmin_z(dot(neg(ud), normal), 1.0f);
-        ratio = diel ? rt : 1.0f;
-        cos_theta = diel ? ct : 0.0f;
-      }
-      const float qv = lamb ? r1 : cos_theta;
-      const float root = dev::sqrt_rn(1.0f - qv * qv);  // Lambertian rr, dielectric sin_theta
-      bool refl = diel && ratio * root > 1.0f;
-      const bool schlick = diel && !refl;
-      float reflectance = 0.0f;
-      if (__ballot(schlick) != 0ull) {
-        const float r0 = dev::div_rn(1.0f - ratio, 1.0f + ratio);
-        reflectance = r0 + (1.0f - r0) * dev::pow5_z(1.0f - cos_theta);
-      }
-      const bool draw2 = lamb || schlick;
-      float r2 = 0.0f;
-      if (__ballot(draw2) != 0ull) {
-        R t = rng;
-        const float v = rand_float(t);
-        rng_keep(rng, t, draw2);
-        r2 = draw2 ? v : 0.0f;
-      }
-      refl = schlick ? reflectance > r2 : refl;
-      V3 x = mk(0.0f, 0.0f, 0.0f);
-      if (__ballot(lamb) != 0ull) {
-        float sn, cs;
-        dev::sincos_z(kTwoPi * r2, &sn, &cs);
-        V3 hv = mk(cs * root, sn * root, r1);
-        R t = rng;
-        const bool b = rand_bool(t);
-        rng_keep(rng, t, lamb);
-        if (!b) hv.z = hv.z * -1.0f;
-        const V3 xl = add(normal, hv);
-        if (lamb) x = xl;
-      }
-      const bool rfl = metal || refl, rfr = diel && !refl;
-      if (__ballot(rfl) != 0ull) {
-        const V3 xr = reflect(ud, normal);
-        if (rfl) x = xr;
-      }
-      if (__ballot(rfr) != 0ull) {
-        const V3 xf = refract(ud, normal, ratio);
-        if (rfr) x = xf;
-      }
-      nd = unit(x);
-      if (!diel) att = albedo_code(mat, tag & 0x7fffffffu, tu, tv);
-      if (metal && !(dot(nd, normal) > 0.0f)) absorbed = true;
-    }
-#elif ZRT_SHADE_CONVERGE
-    // the operations the materials share issued once for the lanes of all of them
-    // (shade_hit_a's ZRT_LIST_CONVERGE for the BVH loops): unit(d) of metal and
-    // dielectric, sqrt(1 - q^2) and the second draw of Lambertian and dielectric, the
-    // reflection of metal and reflected dielectric rays, the final unit() of every
-    // scatter and the albedo of Lambertian and metal.  Per lane the same operations on
-    // the same values in the same order: bit-identical.
-    {
-      const bool lamb = mkind == ZRT_MAT_LAMBERTIAN, metal = mkind == ZRT_MAT_METAL;
-      const bool diel = !lamb && !metal;
-      V3 ud = d;
-      if (!lamb) ud = unit(d);
-      float r1 = 0.0f;
-      if (lamb) r1 = rand_float(rng);
-      float ratio = 1.0f, cos_theta = 0.0f;
-      if (diel) {
-        ratio = front ? dev::rcp_rn(mat.ior()) : mat.ior();
-        cos_theta = dev::fmin_z(dot(neg(ud), normal), 1.0f);
-      }
-      const float qv = lamb ? r1 : cos_theta;
-      const float root = dev::sqrt_rn(1.0f - qv * qv);  // Lambertian rr, dielectric sin_theta
-      bool refl = diel && ratio * root > 1.0f;
-      float reflectance = 0.0f;
-      const bool schlick = diel && !refl;
-      if (schlick) {
-        const float r0 = dev::div_rn(1.0f - ratio, 1.0f + ratio);
-        reflectance = r0 + (1.0f - r0) * dev::pow5_z(1.0f - cos_theta);
-      }
-      float r2 = 0.0f;
-      if (lamb || schlick) r2 = rand_float(rng);
-      if (schlick) refl = reflectance > r2;
-      V3 x;
-      if (lamb) {
-        float sn, cs;
-        dev::sincos_z(kTwoPi * r2, &sn, &cs);
-        V3 hv = mk(cs * root, sn * root, r1);
-        if (!rand_bool(rng)) hv.z = hv.z * -1.0f;
-        x = add(normal, hv);
-      } else if (metal || refl) {
-        x = reflect(ud, normal);
-      } else {
-        x = refract(ud, normal, ratio);
-      }
-      nd = unit(x);
-      if (!diel) att = albedo_code(mat, tag & 0x7fffffffu, tu, tv);
-      if (metal && !(dot(nd, normal) > 0.0f)) absorbed = true;
-    }
-#else
     if (mkind == ZRT_MAT_LAMBERTIAN) {
       const float r1 = rand_float(rng);
       const float r2 = rand_float(rng);
@@ -2538,7 +2249,6 @@ __device__ __forceinline__ void shade_step(const KArgs& a, const DevMaterial* __
       }
       nd = unit(refl ? reflect(ud, normal) : refract(ud, normal, ratio));
     }
-#endif
     if (absorbed) {
       path_end = true;  // black
     } else {
@@ -4044,7 +3754,6 @@ __device__ __forceinline__ uint32_t png_channel_dev(float c) {
 // (non-negative floats order as their bit patterns; a NaN difference is skipped).
 // At most one atomic of each per wave (none for a maximum already reached: the word
 // only grows, so a stale read can only cost an atomic, never skip one).
-constexpr uint32_t kMetricShards = 64, kMetricStride = 16, kMetricWords = kMetricShards * kMetricStride;
 __global__ void accumulate_kernel(const float4* __restrict__ partial, float4* __restrict__ accum,
                                   float* __restrict__ out, uint32_t n_slots, uint32_t pass_chunks, uint32_t world,
                                   uint32_t rank, uint32_t tiles_x, uint32_t xbound, uint32_t height, float prev_scale,
@@ -4115,7 +3824,6 @@ __global__ void accumulate_kernel(const float4* __restrict__ partial, float4* __
 // metrics as accumulate_kernel's, over the tiles touched, plus word 2 of each pair's
 // shard: in-frame pixels resolved.  A nonzero error flag: the waves stride over ALL
 // the rank's tiles, leave NaN in accum and out and freeze them (nothing survives).
-constexpr uint32_t kTileFrozen = 0x80000000u;
 __global__ void resolve_kernel(const float4* __restrict__ partial, float4* __restrict__ accum,
                                float* __restrict__ out, const uint32_t* __restrict__ active, uint32_t n_active,
                                uint32_t my_tiles, uint32_t pass_chunks, uint32_t world, uint32_t rank,
@@ -4373,752 +4081,9 @@ __global__ void debug_rng_kernel(uint64_t key, unsigned long long* out, uint32_t
 }
 
 // ---------------------------------------------------------------------------
-// host side
+// host side (kernels.hpp): what must see a kernel symbol or a device template
 // ---------------------------------------------------------------------------
 namespace {
-
-struct HipError {
-  hipError_t err;
-  std::string where;
-};
-
-#define HIPCHK(expr)                                                       \
-  do {                                                                     \
-    const hipError_t e_ = (expr);                                          \
-    if (e_ != hipSuccess) throw ::zrt::HipError{e_, std::string(#expr)};          \
-  } while (0)
-
-template <class T>
-struct DevBuf {
-  T* p = nullptr;
-  size_t n = 0;
-  DevBuf() = default;
-  DevBuf(const DevBuf&) = delete;
-  DevBuf& operator=(const DevBuf&) = delete;
-  DevBuf(DevBuf&& o) noexcept : p(o.p), n(o.n) {
-    o.p = nullptr;
-    o.n = 0;
-  }
-  ~DevBuf() { release(); }
-  void release() {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    n = 0;
-  }
-  void alloc(size_t count) {
-    release();
-    if (count == 0) count = 1;
-    HIPCHK(hipMalloc(&p, count * sizeof(T)));
-    n = count;
-  }
-  void upload(const std::vector<T>& v) {
-    alloc(v.size());
-    if (!v.empty()) HIPCHK(hipMemcpy(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
-  }
-};
-
-double now_ms() {
-  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
-
-int check_device(int dev) {
-  int count = 0;
-  if (hipGetDeviceCount(&count) != hipSuccess || count == 0)
-    return fail(ZRT_E_NODEVICE, "no HIP device visible (the HIP path needs an MI355X / gfx950)");
-  if (dev < 0 || dev >= count) return fail(ZRT_E_NODEVICE, "device ordinal out of range");
-  hipDeviceProp_t prop;
-  if (hipGetDeviceProperties(&prop, dev) != hipSuccess) return fail(ZRT_E_NODEVICE, "hipGetDeviceProperties failed");
-  if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
-    return fail(ZRT_E_NODEVICE, std::string("device is ") + prop.gcnArchName + ", libzrt is built for gfx950 only");
-  return ZRT_OK;
-}
-
-int validate_scene(const zrt_scene* s) {
-  if (!s) return fail(ZRT_E_INVALID, "scene is null");
-  if (s->n_prims && !s->prims) return fail(ZRT_E_INVALID, "prims is null");
-  if (s->n_materials && !s->materials) return fail(ZRT_E_INVALID, "materials is null");
-  if (s->n_textures && !s->textures) return fail(ZRT_E_INVALID, "textures is null");
-  if (s->n_images && !s->images) return fail(ZRT_E_INVALID, "images is null");
-  if (s->n_prims >= (1u << 29)) return fail(ZRT_E_UNSUPPORTED, "more than 2^29 primitives");
-  for (uint32_t i = 0; i < s->n_prims; ++i) {
-    const zrt_prim& p = s->prims[i];
-    if (p.kind != ZRT_PRIM_SPHERE && p.kind != ZRT_PRIM_TRIANGLE) return fail(ZRT_E_INVALID, "unknown primitive kind");
-    if (p.material >= s->n_materials) return fail(ZRT_E_INVALID, "material index out of range");
-  }
-  for (uint32_t i = 0; i < s->n_materials; ++i) {
-    const zrt_material& m = s->materials[i];
-    if (m.kind > ZRT_MAT_DIELECTRIC) return fail(ZRT_E_INVALID, "unknown material kind");
-    if (m.kind != ZRT_MAT_DIELECTRIC) {
-      if (m.texture >= s->n_textures) return fail(ZRT_E_INVALID, "texture index out of range");
-      const zrt_texture& t = s->textures[m.texture];
-      if (t.kind > ZRT_TEX_IMAGE) return fail(ZRT_E_INVALID, "unknown texture kind");
-      if (t.kind == ZRT_TEX_IMAGE) {
-        if (t.image >= s->n_images) return fail(ZRT_E_INVALID, "image index out of range");
-        const zrt_image& im = s->images[t.image];
-        if (!im.pixels || im.width == 0 || im.height == 0) return fail(ZRT_E_INVALID, "empty image");
-      }
-    }
-  }
-  return ZRT_OK;
-}
-
-int validate_params(const zrt_params* p) {
-  if (!p) return fail(ZRT_E_INVALID, "params is null");
-  if (p->width == 0 || p->height == 0 || p->samples_per_pixel == 0)
-    return fail(ZRT_E_INVALID, "width, height and samples_per_pixel must be > 0");
-  if (p->width > 65535 || p->height > 65535 || p->samples_per_pixel > 65535 || p->max_depth > 65535)
-    return fail(ZRT_E_INVALID, "RenderParams fields are u16 (raytrace.zig:102-108)");
-  if (p->height > p->width)
-    return fail(ZRT_E_INVALID,
-                "height > width: raytrace.zig:168 iterates x over image.height and would write past the image");
-  if (p->rng_mode != ZRT_RNG_COUNTER)
-    return fail(ZRT_E_UNSUPPORTED,
-                "the single sequential reference stream cannot be split across GPU lanes; use ZRT_RNG_COUNTER");
-  if (p->prng > ZRT_PRNG_XOSHIRO256) return fail(ZRT_E_INVALID, "unknown prng");
-  if (p->traversal > ZRT_TRAVERSAL_BINARY) return fail(ZRT_E_INVALID, "unknown traversal");
-  if (p->world_size == 0 || p->rank >= p->world_size) return fail(ZRT_E_INVALID, "rank must be < world_size");
-  if (p->sample_chunk > 65535) return fail(ZRT_E_INVALID, "sample_chunk must be <= 65535");
-  return ZRT_OK;
-}
-
-struct Geometry {
-  uint32_t xbound, tiles_x, tiles_y, n_tiles;
-};
-Geometry geometry(const zrt_params* p) {
-  Geometry g;
-  g.xbound = p->height;  // raytrace.zig:168: `while (x < image.height)`
-  g.tiles_x = (g.xbound + 7) / 8;
-  g.tiles_y = (p->height + 7) / 8;
-  g.n_tiles = g.tiles_x * g.tiles_y;
-  return g;
-}
-uint32_t rank_tiles(const Geometry& g, uint32_t rank, uint32_t world) {
-  return g.n_tiles > rank ? (g.n_tiles - rank + world - 1) / world : 0;
-}
-
-}  // namespace
-}  // namespace zrt
-
-struct zrt_ctx {
-  int device = 0;
-  hipStream_t stream = nullptr;
-  bool use_bvh = false;
-  uint32_t n_prims = 0, n_nodes = 0, bvh_depth = 0, stack_depth = 0;
-  uint32_t n_wide = 0, n_leaves = 0, wide_stack = 0, wide_stride = 0, n_top = 0, n_mats = 0;
-  std::vector<uint32_t> slot_to_prim;  // device primitive slot -> reference list index
-  zrt::DevBuf<float4> wnodes;
-  zrt::DevBuf<float4> qnodes, qleaves;  // compressed wide nodes + leaf records (q_ok)
-  bool q_ok = false;
-  uint32_t q_stride = 0, q_top = 0, n_qleaves = 0;
-  zrt::DevBuf<float4> nodes, prims, shade;
-  zrt::DevBuf<zrt::DevMaterial> mats;
-  zrt::DevBuf<float> texels;
-  zrt::DevBuf<uint32_t> texels8;
-  zrt::DevBuf<uint32_t> leaf_of_slot;
-  zrt::DevBuf<uint8_t> ref_sph;
-  float root_c[3] = {0.0f, 0.0f, 0.0f}, origin_bound = 0.0f;
-  uint32_t layout = 0;  // the wide tree's encoding (KArgs::layout)
-  float graze_m = 0x1p-18f, graze_leaf = 0x1p-18f;  // KArgs::graze_m / graze_leaf
-  float guard = 0.0f;                                // KArgs::guard
-  uint32_t texel_bytes = 0;
-  uint32_t tri_rcp_fast = 1;
-  uint32_t has_dielectric = 0, has_image_texture = 0;  // HostScene's
-  float scene_extent = 1.0f;
-  float tri_c[3] = {0.0f, 0.0f, 0.0f}, tri_h[3] = {0.0f, 0.0f, 0.0f};  // KArgs::tri_c / tri_h
-  zrt::DevBuf<uint32_t> att;  // attenuation rows past the LDS ones (att codes)
-  zrt::DevBuf<uint8_t> stack_ovf;  // FAST stack rows beyond the LDS part (deep trees)
-  zrt::DevBuf<unsigned long long> scratch;  // counters, work counter, error flag (kScratchSlots)
-  zrt::DevBuf<float4> partial;
-  zrt::DevBuf<uint32_t> rank_base;
-  // scheduling probe: its own partial sums + counters, per-tile costs, the sort
-  zrt::DevBuf<float4> probe_partial;
-  zrt::DevBuf<unsigned long long> probe_scratch;
-  zrt::DevBuf<uint32_t> tile_cost, tile_ids, cost_sorted, tile_order;
-  zrt::DevBuf<uint8_t> sort_temp;
-  uint32_t tile_ids_n = 0;
-  zrt::DevBuf<unsigned long long> wave_times;  // ZRT_PROFILE builds
-  uint32_t n_waves = 0;
-  zrt::DevBuf<unsigned long long> scanlines;  // ZRT_FLAG_SCANLINES: [row][3] of the last launch
-  uint32_t scanline_rows = 0;                 // rows counted by the last launch (0: not flagged)
-  bool scheduled = false;
-  hipEvent_t ev_pre = nullptr, ev0 = nullptr, ev1 = nullptr, ev_done = nullptr;
-  double preprocess_ms = 0, upload_ms = 0;
-  // last launch: its device error flag, copied into pinned host memory behind
-  // ev_done on the stream it was enqueued on (the caller's, or `stream`)
-  unsigned long long* err_host = nullptr;
-  bool err_reported = false;  // the last launch's device error was returned to the caller
-  uint32_t last_pixels = 0, last_spp = 0, launched = 0;
-  uint32_t last_tiles = 0, last_rank = 0, last_world = 1, last_tiles_x = 0, last_xbound = 0;
-  bool last_stats = false;
-  int last_mode = 0;
-  bool last_qn = false;  // the last launch read compressed nodes
-  int last_loop = 0;  // zrt_stats::sampling_loop
-  float last_guard = 0.0f;  // zrt_stats::guard
-  int cu_count = 0;
-  // ---- the accumulation run (zrt_ctx_accum_*): at most one per context ----
-  struct EvSet {
-    hipEvent_t pre = nullptr, e0 = nullptr, e1 = nullptr;
-    bool probed = false;  // the pass ran the scheduling probe (pre .. e0 is its schedule_ms)
-  };
-  bool run_live = false;       // between zrt_ctx_accum_begin and the next plain render
-  bool run_stats = false;      // the last launch was a pass: zrt_ctx_stats reports the run's sums
-  zrt_camera run_cam{};
-  zrt_params run_p{};
-  uint32_t run_done = 0;       // samples per pixel in accum
-  uint32_t run_passes = 0;     // passes enqueued
-  bool run_ordered = false;    // the first pass's probe left tile_order and probe_scratch for the later ones
-  bool pass_probed = false;    // the last pass ran the probe
-  uint32_t pass_samples = 0;   // the last pass's
-  zrt::DevBuf<float4> accum;   // [slot] running chunk sums (rank's tile-major layout)
-  zrt::DevBuf<unsigned long long> metrics;  // accumulate_kernel's {changed pixels, max change bits} shards
-  unsigned long long* metrics_host = nullptr;  // ... of the last pass, pinned, copied behind ev_done
-  // earlier passes' events not yet added into run_render_ms / run_sched_ms, and spare sets
-  std::vector<EvSet> run_pending, ev_spare;
-  double run_render_ms = 0, run_sched_ms = 0;
-  // ---- an adaptive run (zrt_ctx_adapt_*): an accumulation run over the active tiles ----
-  bool adapt = false;          // the live run is adaptive
-  bool last_adapt = false;     // the last launch was a level: stats / scanlines count per-tile samples
-  zrt_adaptive adapt_a{};
-  std::vector<uint32_t> adapt_levels;  // L_0 .. (zrt::plan_adapt)
-  uint32_t adapt_k = 0;        // the next level
-  uint32_t adapt_active = 0;   // tiles in active[adapt_cur]
-  uint32_t adapt_cur = 0;      // the list the next level's launch reads (the other one is written)
-  uint64_t adapt_samples = 0;  // sum over tiles of in-frame pixels x samples so far
-  float* adapt_tiles = nullptr;  // the run's dev_tiles
-  zrt::DevBuf<uint32_t> active[2], tile_done, active_count;
-  uint32_t* count_host = nullptr;  // the surviving count of the last level, pinned
-  // ---- the a-trous filter (zrt_ctx_denoise): its ping-pong colour planes and its events ----
-  zrt::DevBuf<float4> dn_buf[2];
-  hipEvent_t dn_ev0 = nullptr, dn_ev1 = nullptr;
-  bool dn_launched = false;
-  // ---- first-hit feature buffers (zrt_ctx_features): the launch's own deep stack rows,
-  // the slot -> primitive table, and its device error status behind feat_done ----
-  zrt::DevBuf<uint8_t> feat_ovf;
-  zrt::DevBuf<uint32_t> feat_slot_prim;
-  unsigned long long* feat_err_host = nullptr;
-  hipEvent_t feat_done = nullptr;
-  bool feat_launched = false, feat_err_reported = false;
-  ~zrt_ctx() {
-    if (feat_done) (void)hipEventDestroy(feat_done);
-    if (feat_err_host) (void)hipHostFree(feat_err_host);
-    if (dn_ev0) (void)hipEventDestroy(dn_ev0);
-    if (dn_ev1) (void)hipEventDestroy(dn_ev1);
-    if (count_host) (void)hipHostFree(count_host);
-    for (const std::vector<EvSet>* v : {&run_pending, &ev_spare})
-      for (const EvSet& e : *v) {
-        (void)hipEventDestroy(e.pre);
-        (void)hipEventDestroy(e.e0);
-        (void)hipEventDestroy(e.e1);
-      }
-    if (metrics_host) (void)hipHostFree(metrics_host);
-    if (ev_pre) (void)hipEventDestroy(ev_pre);
-    if (ev0) (void)hipEventDestroy(ev0);
-    if (ev1) (void)hipEventDestroy(ev1);
-    if (ev_done) (void)hipEventDestroy(ev_done);
-    if (err_host) (void)hipHostFree(err_host);
-    if (stream) (void)hipStreamDestroy(stream);
-  }
-};
-
-namespace zrt {
-namespace {
-
-// The scene flattened for the device (host arrays, built once, uploaded to
-// every GPU that renders it).
-struct HostScene {
-  bool use_bvh = false;
-  uint32_t n_prims = 0, n_nodes = 0, bvh_depth = 0;
-  uint32_t n_wide = 0, n_leaves = 0, wide_stack = 0, wide_stride = 0, n_top = 0, n_mats = 0;
-  uint32_t texel_bytes = 0;
-  uint32_t tri_rcp_fast = 1;  // KArgs::tri_rcp_fast
-  // a dielectric / an image-textured material in the table (used or not): no lean kernel (plan_launch)
-  uint32_t has_dielectric = 0, has_image_texture = 0;
-  float scene_extent = 0.0f;  // KArgs::scene_extent
-  float tri_c[3] = {0.0f, 0.0f, 0.0f}, tri_h[3] = {0.0f, 0.0f, 0.0f};  // KArgs::tri_c / tri_h
-  float root_c[3] = {0.0f, 0.0f, 0.0f}, origin_bound = 0.0f;  // KArgs::root_c / origin_bound
-  uint32_t layout = 0;           // KArgs::layout: the wide tree's encoding
-  float graze_m = 0x1p-18f;      // KArgs::graze_m (the inner boxes are grown by half of it)
-  float graze_leaf = 0x1p-18f;   // KArgs::graze_leaf
-  float guard = 0.0f;            // KArgs::guard
-  std::vector<uint8_t> ref_sph;  // KArgs::ref_sph
-  std::vector<float4> nodes, wn, prims, shade;
-  std::vector<float4> qn, ql;  // compressed wide nodes (8 octant copies) and leaf records, when q_ok
-  bool q_ok = false;
-  uint32_t q_stride = 0;       // float4s per octant copy of qn
-  uint32_t q_top = 0;          // compressed nodes served from LDS (their top levels)
-  std::vector<DevMaterial> mats;
-  std::vector<float> tex;
-  std::vector<uint32_t> tex8;
-  std::vector<uint32_t> slot_to_prim;  // device primitive slot -> reference list index
-  std::vector<uint32_t> leaf_of_slot;  // device primitive slot -> its reference BVH leaf node
-  double preprocess_ms = 0;
-};
-
-// Meshes from this many primitives have their reference BVH built on the GPU
-// (bvh_gpu.hip: same tree; 1.6 M triangles in a fraction of a second instead of
-// 5.6 s on the host).  ZRT_BVH_DEVICE=0/1 forces the host / device build.
-constexpr uint32_t kDeviceBvhMin = 1u << 16;
-bool device_bvh(uint32_t n) {
-  if (const char* e = std::getenv("ZRT_BVH_DEVICE")) return std::atoi(e) != 0;
-  return n >= kDeviceBvhMin;
-}
-
-// The grazing margins' coefficient (DESIGN.md §3 "Grazing rays"): 2^-18;
-// ZRT_GRAZE_M overrides it (A/B of larger margins)
-float graze_margin() {
-  if (const char* e = std::getenv("ZRT_GRAZE_M")) return std::max(0x1p-18f, float(std::atof(e)));
-  return 0x1p-18f;
-}
-
-// The grazing-triangle guard's coefficient for a scene (DESIGN.md §3
-// "Triangles"): an accepted hit of the rounded test (triangle.zig:48-70) lies
-// outside its triangle by at most K u |ao| |e1||e2| / det, K = 2.6 the largest
-// measured (tools/tri_reach.py; 1.3 on the reference scenes' own triangles,
-// tools/tri_reach_bound.py gives the first-order worst case), and det >= 1e-6:
-// K u max |e1||e2| / 1e-6 per unit of |ao| <= T + extent (guard_grow).  Capped at
-// 2^-10 (above it the guard opens much of the tree; the teapot's model asks 0.024):
-// the grazing-triangle rays of every reference scene are exact from 2^-12
-// (profiles/r04/r04f).  ZRT_GUARD_K overrides it (A/B).
-float guard_model(double max_p12) {
-  if (const char* e = std::getenv("ZRT_GUARD_K")) return std::max(0.0f, float(std::atof(e)));
-  const double k = 2.6 * 0x1p-24 * max_p12 / 1e-6;
-  return float(std::min(k, double(0x1p-10)));
-}
-float graze_leaf_margin() {  // ZRT_GRAZE_LEAF: leaf slots' coefficient (A/B of a leaf-only guard)
-  if (const char* e = std::getenv("ZRT_GRAZE_LEAF")) return std::max(0x1p-18f, float(std::atof(e)));
-  return 0x1p-18f;
-}
-
-// Flatten the scene for the device: BVH (pre-order), slots in DFS leaf order.
-// `device` >= 0: the GPU that may build the BVH (device_bvh).  `qnodes`: build
-// the compressed nodes too (1), not (0), or as want_qnodes decides (-1, ZRT_QNODES).
-bool want_qnodes(uint32_t n_wide);
-uint32_t qtop_levels();
-void flatten_scene(HostScene* c, const zrt_scene* s, bool use_bvh, int device, int qnodes = -1) {
-  const double t0 = now_ms();
-  const uint32_t n = s->n_prims;
-  std::vector<uint32_t> slot_to_prim, leaf_of_slot;
-  std::vector<float4> nodes;
-  uint32_t depth = 0;
-  if (use_bvh) {
-    BuiltBvh bvh;
-    bool built = false;
-    if (device >= 0 && device_bvh(n)) {
-      // the same tree on the GPU; any HIP failure there (hipMalloc on a busy GPU,
-      // a hipcub error) falls back to the host build, which gives the same tree
-      try {
-        built = build_bvh_device(s->prims, n, device, &bvh);
-      } catch (const Error& e) {
-        if (std::getenv("ZRT_DEBUG_LAUNCH"))
-          std::fprintf(stderr, "zrt preprocess: device BVH build failed (%s); host build\n", e.what());
-        (void)hipGetLastError();  // clear a sticky runtime error of the failed build
-      }
-    }
-    if (!built) bvh = build_bvh(s->prims, n);
-    if (std::getenv("ZRT_DEBUG_LAUNCH"))
-      std::fprintf(stderr, "zrt preprocess: reference BVH %zu nodes in %.1f ms\n", bvh.nodes.size(), now_ms() - t0);
-    depth = bvh.max_depth;
-    nodes.resize(2 * bvh.nodes.size());
-    std::vector<int32_t> prim_slot(n, -1);
-    auto ref_of = [&](int32_t child) -> int32_t {
-      if (child >= 0) return child;
-      const uint32_t prim = uint32_t(-child - 1);
-      if (prim_slot[prim] < 0) {
-        prim_slot[prim] = int32_t(slot_to_prim.size());
-        slot_to_prim.push_back(prim);
-      }
-      const int32_t kind = s->prims[prim].kind == ZRT_PRIM_TRIANGLE ? 1 : 0;
-      return -(2 * prim_slot[prim] + kind) - 1;
-    };
-    std::vector<RefLeaf> leaves;
-    for (size_t i = 0; i < bvh.nodes.size(); ++i) {  // pre-order == reference DFS order
-      const BuildNode& b = bvh.nodes[i];
-      const int32_t l = ref_of(b.left);
-      const int32_t r = ref_of(b.right);
-      if (b.left < 0) {  // a reference leaf: its box and its primitive refs
-        for (const int32_t ref : {l, r}) {
-          const uint32_t slot = uint32_t(-ref - 1) >> 1;
-          if (leaf_of_slot.size() <= slot) leaf_of_slot.resize(slot + 1);
-          leaf_of_slot[slot] = uint32_t(i);
-        }
-        RefLeaf L;
-        for (int k = 0; k < 3; ++k) {
-          L.mn[k] = b.mn[k];
-          L.mx[k] = b.mx[k];
-        }
-        L.prim_a = l;
-        L.prim_b = r;
-        leaves.push_back(L);
-      }
-      float4 lo, hi;
-      lo.x = b.mn[0]; lo.y = b.mn[1]; lo.z = b.mn[2];
-      hi.x = b.mx[0]; hi.y = b.mx[1]; hi.z = b.mx[2];
-      std::memcpy(&lo.w, &l, 4);
-      std::memcpy(&hi.w, &r, 4);
-      nodes[2 * i] = lo;
-      nodes[2 * i + 1] = hi;
-    }
-    c->n_nodes = uint32_t(bvh.nodes.size());
-    // Spheres (DESIGN.md §3 "Spheres").  The rounded disc of sphere.zig:31-41 errs by
-    // E <= 32 u (|oc|^2 + r^2) (u = 2^-24, three rounded dot products and two
-    // subtractions), so an accepted ray passes within sqrt(r^2 + E) - r <= sqrt(E) of
-    // the sphere and its hit errs by <= 1.5 sqrt(E) in t: subtrees holding a sphere
-    // are grown by 2 sqrt(E) = 2^-8.5 R, R >= |oc| + r for every ray whose origin
-    // lies within 2 H of the root box's center on every axis (H: its largest half
-    // extent; |oc| <= 2 sqrt(3) H + sqrt(3) H, r <= H).  Rays from farther out are
-    // traced the reference's way (render.hip ray_origin_ok).
-    c->ref_sph.assign(bvh.nodes.size(), 0);
-    bool any_sphere = false;
-    for (size_t i = bvh.nodes.size(); i-- > 0;) {  // pre-order: children after their parent
-      const BuildNode& b = bvh.nodes[i];
-      uint8_t f = 0;
-      for (const int32_t ch : {b.left, b.right}) {
-        if (ch >= 0) f |= c->ref_sph[size_t(ch)];
-        else f |= s->prims[uint32_t(-ch - 1)].kind == ZRT_PRIM_SPHERE ? 1 : 0;
-      }
-      c->ref_sph[i] = f;
-      any_sphere = any_sphere || f;
-    }
-    // The region the bound is sized over: the root box united with every sphere's
-    // centre -+ |radius|.  A negative radius (the reference scenes use them) makes
-    // sphere.zig:25's box inverted, so the root box alone need not cover that
-    // sphere's surface.
-    float lo[3], hi[3];
-    for (int k = 0; k < 3; ++k) {
-      lo[k] = bvh.nodes[0].mn[k];
-      hi[k] = bvh.nodes[0].mx[k];
-    }
-    for (uint32_t i = 0; i < n; ++i) {
-      const zrt_prim& p = s->prims[i];
-      if (p.kind != ZRT_PRIM_SPHERE) continue;
-      const float r = std::fabs(p.radius), cc[3] = {p.center.x, p.center.y, p.center.z};
-      for (int k = 0; k < 3; ++k) {  // (rounded outward: the f32 box contains the exact one)
-        lo[k] = std::min(lo[k], std::nextafter(cc[k] - r, -HUGE_VALF));
-        hi[k] = std::max(hi[k], std::nextafter(cc[k] + r, HUGE_VALF));
-      }
-    }
-    float H = 0.0f;
-    for (int k = 0; k < 3; ++k) {
-      c->root_c[k] = 0.5f * lo[k] + 0.5f * hi[k];
-      H = std::max(H, std::max(hi[k] - c->root_c[k], c->root_c[k] - lo[k]));
-    }
-    if (!(H < 0x1p100f)) H = 0x1p100f;  // NaN / huge extents: every origin fails ray_origin_ok's bound
-    // Only sphere slots depend on where a ray starts (their growth is sized for
-    // origins within 2 H); the triangle margins do not, so a scene without spheres
-    // accepts every origin (a distant camera no longer replays every ray)
-    c->origin_bound = any_sphere ? 2.0f * H : HUGE_VALF;
-    const float sphere_grow = any_sphere ? float(std::ldexp(std::sqrt(2.0), -9) * (3.0 * std::sqrt(3.0) + 1.0) * double(H)) : 0.0f;
-    const double tw = now_ms();
-    c->graze_m = graze_margin();
-    c->graze_leaf = std::max(c->graze_m, graze_leaf_margin());
-    c->guard = 0.0f;  // (set below, once the triangles are known)
-    // the top levels stored first (LDS): two for the full 128-B nodes; a tree that
-    // also gets compressed nodes stores qtop_levels() (their 64-B nodes leave room
-    // for a third level in the path pool's LDS), the full kernels reading the first two
-    const uint32_t n_leaf_est = uint32_t(leaves.size());
-    const bool want_q = qnodes >= 0 ? qnodes != 0 : want_qnodes((n_leaf_est + 2) / 3);  // (about leaves / 3 nodes)
-    const uint32_t top_levels = want_q ? qtop_levels() : 2u;
-    const WideBvh wide = build_wide_bvh(leaves, top_levels, ZRT_GROW ? 0.5f * c->graze_m : 0.0f,
-                                        ZRT_SPHERE_SLOTS ? sphere_grow : 0.0f, ZRT_SPHERE_SLOTS != 0);
-    if (std::getenv("ZRT_DEBUG_LAUNCH"))
-      std::fprintf(stderr, "zrt preprocess: wide tree %u nodes in %.1f ms\n", wide.n_nodes, now_ms() - tw);
-    const size_t nw = wide.nodes.size();
-#if ZRT_OCT_COPIES
-    // one copy per ray octant o (bit k set: direction k negative) with axis k's
-    // min / max planes swapped, so float4 0-2 are the near planes, 3-5 the far
-    std::vector<float4> wn(8 * nw);
-    for (uint32_t o = 0; o < 8; ++o) {
-      float4* dst = wn.data() + o * nw;
-      std::memcpy(dst, wide.nodes.data(), nw * sizeof(float4));
-      for (size_t i = 0; i < nw; i += 8)
-        for (int k = 0; k < 3; ++k)
-          if (o >> k & 1u) std::swap(dst[i + k], dst[i + 3 + k]);
-    }
-#else
-    std::vector<float4> wn(nw);
-    std::memcpy(wn.data(), wide.nodes.data(), nw * sizeof(float4));
-#endif
-    c->wide_stack = wide.max_stack + 3;  // + the dead entries of a branch-free push
-    // compressed nodes for trees past the caches (want_qnodes): the same tree, 64-B nodes
-    // (quantize_wide stores octant copies with pre-swapped planes, which wide_iter_q
-    // reads as such: never built for a one-copy A/B build, ZRT_OCT_COPIES = 0)
-    if (want_q && ZRT_OCT_COPIES) {
-      const double tq = now_ms();
-      QuantWide qw = quantize_wide(wide);
-      if (qw.ok) {
-        c->qn.resize(qw.nodes.size());
-        std::memcpy(c->qn.data(), qw.nodes.data(), qw.nodes.size() * sizeof(float4));
-        c->ql.resize(std::max<size_t>(1, qw.leaves.size()));
-        std::memcpy(c->ql.data(), qw.leaves.data(), qw.leaves.size() * sizeof(float4));
-        c->q_ok = true;
-        c->q_stride = qw.n_nodes * kQuantNodeF4;
-        c->q_top = wide.n_top;
-      }
-      if (std::getenv("ZRT_DEBUG_LAUNCH"))
-        std::fprintf(stderr, "zrt preprocess: compressed nodes %s, %u leaf records, %.1f ms\n", qw.ok ? "built" : "refused",
-                     qw.n_leaves, now_ms() - tq);
-    }
-    c->wn = std::move(wn);
-    c->wide_stride = uint32_t(nw);
-    c->n_wide = wide.n_nodes;
-    c->n_leaves = wide.n_leaves;
-    c->n_top = wide.level_end.empty() ? 0u : wide.level_end[std::min<size_t>(2, wide.level_end.size()) - 1];
-    c->layout = wide.layout;
-    if (const char* e = std::getenv("ZRT_DEBUG_TREE_LAYOUT"))  // tests: a tree another kernel would have to decode
-      c->layout ^= uint32_t(std::strtoul(e, nullptr, 0));
-    if (c->layout != kKernelLayout)
-      throw Error(ZRT_E_UNSUPPORTED, "the wide tree's layout (" + std::to_string(c->layout) +
-                                         ") is not the one this library's kernels decode (" +
-                                         std::to_string(kKernelLayout) + "): accel_build and render.hip disagree");
-  } else {
-    for (uint32_t i = 0; i < n; ++i) slot_to_prim.push_back(i);
-  }
-  std::vector<float4> prims(3 * size_t(slot_to_prim.size()));
-  std::vector<float4> shade(slot_to_prim.size());
-  double tlo[3] = {HUGE_VAL, HUGE_VAL, HUGE_VAL}, thi[3] = {-HUGE_VAL, -HUGE_VAL, -HUGE_VAL};
-  double tri_p12 = 0.0;  // the largest |e1| |e2| (guard_model)
-  for (size_t sl = 0; sl < slot_to_prim.size(); ++sl) {
-    const zrt_prim& p = s->prims[slot_to_prim[sl]];
-    if (p.kind == ZRT_PRIM_TRIANGLE)  // ray_slack: the triangles' largest |coordinate|
-      for (const auto& v : {p.a, p.b, p.c}) {
-        c->scene_extent = std::max({c->scene_extent, std::fabs(v.x), std::fabs(v.y), std::fabs(v.z)});
-        const double vk[3] = {v.x, v.y, v.z};
-        for (int k = 0; k < 3; ++k) {  // (NaN coordinates: the box becomes NaN, paxis_grow infinite)
-          tlo[k] = vk[k] < tlo[k] || vk[k] != vk[k] ? vk[k] : tlo[k];
-          thi[k] = vk[k] > thi[k] || vk[k] != vk[k] ? vk[k] : thi[k];
-        }
-      }
-    float4* q = &prims[3 * sl];
-    float4& sh = shade[sl];
-    uint32_t tag = p.material;
-    if (p.kind == ZRT_PRIM_TRIANGLE) {
-      // triangle.zig:35-38: e1 = b-a, e2 = c-a, n = e1 x e2, unit n = n / |n|
-      const float e1x = p.b.x - p.a.x, e1y = p.b.y - p.a.y, e1z = p.b.z - p.a.z;
-      const float e2x = p.c.x - p.a.x, e2y = p.c.y - p.a.y, e2z = p.c.z - p.a.z;
-      const float nx = e1y * e2z - e1z * e2y;
-      const float ny = e1z * e2x - e1x * e2z;
-      const float nz = e1x * e2y - e1y * e2x;
-      const float len = std::sqrt(nx * nx + ny * ny + nz * nz);
-      q[0] = make_float4(p.a.x, p.a.y, p.a.z, e1x);
-      q[1] = make_float4(e1y, e1z, e2x, e2y);
-      q[2] = make_float4(e2z, nx, ny, nz);
-      tag |= 0x80000000u;
-      sh = make_float4(nx / len, ny / len, nz / len, 0.0f);
-      // |det| = |d . n| <= |d| |n| < (1 + 2^-22) sqrt(3) 2^124 < 2^126 (NaN fails too)
-      const float mn = std::max(std::fabs(nx), std::max(std::fabs(ny), std::fabs(nz)));
-      if (!(mn < 0x1p124f)) c->tri_rcp_fast = 0;
-      // the grazing guard's model (guard_model): the largest |e1| |e2| of the scene
-      const double p12 = std::sqrt((double(e1x) * e1x + double(e1y) * e1y + double(e1z) * e1z) *
-                                   (double(e2x) * e2x + double(e2y) * e2y + double(e2z) * e2z));
-      if (p12 == p12) tri_p12 = std::max(tri_p12, p12);
-    } else {
-      q[0] = make_float4(p.center.x, p.center.y, p.center.z, p.radius * p.radius);  // sphere.zig:35 r*r, once
-      q[1] = make_float4(0, 0, 0, 0);
-      q[2] = make_float4(0, 0, 0, 0);
-      sh = make_float4(1.0f / p.radius, 0.0f, 0.0f, 0.0f);  // sphere.zig:46 scale(1.0/radius)
-    }
-    std::memcpy(&sh.w, &tag, 4);
-  }
-  if (use_bvh) c->guard = guard_model(tri_p12);
-  // the triangles' bounding box as centre and half extents, rounded so that the
-  // f32 box contains the exact one (paxis_grow); no triangle: an empty box at 0
-  for (int k = 0; k < 3; ++k) {
-    if (!(tlo[k] <= thi[k])) {
-      if (tlo[k] == HUGE_VAL) tlo[k] = thi[k] = 0.0;  // no triangles
-      else { c->tri_c[k] = 0.0f; c->tri_h[k] = HUGE_VALF; continue; }  // NaN
-    }
-    const double ctr = 0.5 * tlo[k] + 0.5 * thi[k];
-    c->tri_c[k] = float(ctr);
-    const double h = std::max(thi[k] - double(c->tri_c[k]), double(c->tri_c[k]) - tlo[k]);
-    c->tri_h[k] = std::nextafter(float(h), HUGE_VALF);
-  }
-  // materials + textures.  An image whose every value is exactly k/255 (what
-  // png_image.zig:76-89 produces) is stored as 8-bit RGBX and expanded through
-  // a table of the same f32 values; any other image stays f32 RGB.
-  float lut[256];
-  for (int k = 0; k < 256; ++k) lut[k] = float(k) / 255.0f;
-  std::vector<DevMaterial> mats(s->n_materials);
-  std::vector<uint64_t> img_off(s->n_images);
-  std::vector<uint32_t> img_u8(s->n_images, 0);
-  uint64_t texel_count = 0, texel8_count = 0;
-  for (uint32_t i = 0; i < s->n_images; ++i) {
-    const zrt_image& im = s->images[i];
-    const size_t nv = 3 * size_t(im.width) * im.height;
-    bool exact = true;
-    for (size_t j = 0; j < nv && exact; ++j) {
-      const float v = im.pixels[j];
-      const long k = std::lrint(double(v) * 255.0);
-      exact = k >= 0 && k <= 255 && std::memcmp(&lut[k], &v, 4) == 0;
-    }
-    img_u8[i] = exact ? 1u : 0u;
-    uint64_t& count = exact ? texel8_count : texel_count;
-    img_off[i] = count;
-    count += uint64_t(im.width) * im.height;
-  }
-  if (texel_count >= (1ull << 30) || texel8_count >= (1ull << 30))  // (att codes carry a 30-bit texel index)
-    throw Error(ZRT_E_UNSUPPORTED, "more than 2^30 texels in one store");
-  for (uint32_t i = 0; i < s->n_materials; ++i) {
-    const zrt_material& m = s->materials[i];
-    DevMaterial dm{};
-    dm.kind = m.kind;
-    dm.ior = m.index_of_refraction;
-    dm.tex_kind = ZRT_TEX_COLOR;
-    // (the kernels take every kind that is neither Lambertian nor metal as a dielectric)
-    if (m.kind != ZRT_MAT_LAMBERTIAN && m.kind != ZRT_MAT_METAL) c->has_dielectric = 1;
-    if (m.kind != ZRT_MAT_DIELECTRIC) {
-      const zrt_texture& t = s->textures[m.texture];
-      dm.tex_kind = t.kind;
-      if (t.kind != ZRT_TEX_COLOR) c->has_image_texture = 1;
-      dm.r = t.color.x;
-      dm.g = t.color.y;
-      dm.b = t.color.z;
-      dm.u_off = t.u_offset;
-      dm.v_off = t.v_offset;
-      if (t.kind == ZRT_TEX_IMAGE) {
-        dm.img_w = s->images[t.image].width;
-        dm.img_h = s->images[t.image].height;
-        dm.img_off = uint32_t(img_off[t.image]);
-        dm.img_u8 = img_u8[t.image];
-      }
-    }
-    mats[i] = dm;
-  }
-  std::vector<float> tex(3 * texel_count);
-  std::vector<uint32_t> tex8(texel8_count);
-  for (uint32_t i = 0; i < s->n_images; ++i) {
-    const zrt_image& im = s->images[i];
-    const size_t np = size_t(im.width) * im.height;
-    if (img_u8[i]) {
-      for (size_t j = 0; j < np; ++j) {
-        uint32_t px = 0;
-        for (int ch = 0; ch < 3; ++ch)
-          px |= uint32_t(std::lrint(double(im.pixels[3 * j + ch]) * 255.0)) << (8 * ch);
-        tex8[img_off[i] + j] = px;
-      }
-    } else {
-      std::memcpy(&tex[3 * img_off[i]], im.pixels, sizeof(float) * 3 * np);
-    }
-  }
-  c->texel_bytes = s->n_images == 0 ? 0u : texel_count == 0 ? 4u : 12u;
-  c->nodes = std::move(nodes);
-  c->prims = std::move(prims);
-  c->shade = std::move(shade);
-  c->mats = std::move(mats);
-  c->tex = std::move(tex);
-  c->tex8 = std::move(tex8);
-  c->slot_to_prim = std::move(slot_to_prim);
-  c->leaf_of_slot = std::move(leaf_of_slot);
-  c->preprocess_ms = now_ms() - t0;
-  c->use_bvh = use_bvh;
-  c->n_prims = n;
-  c->bvh_depth = depth;
-}
-
-// Upload a flattened scene to the context's device.
-void upload_scene(zrt_ctx* c, const HostScene& h) {
-  const double t1 = now_ms();
-  c->nodes.upload(h.nodes);
-  c->wnodes.upload(h.wn);
-  if (h.q_ok) {
-    c->qnodes.upload(h.qn);
-    c->qleaves.upload(h.ql);
-  }
-  c->q_ok = h.q_ok;
-  c->q_stride = h.q_stride;
-  c->q_top = h.q_top;
-  c->n_qleaves = uint32_t(h.ql.size() / kLeafRecF4);
-  c->prims.upload(h.prims);
-  c->shade.upload(h.shade);
-  c->mats.upload(h.mats);
-  c->texels.upload(h.tex);
-  c->texels8.upload(h.tex8);
-  c->leaf_of_slot.upload(h.leaf_of_slot);
-  c->ref_sph.upload(h.ref_sph);
-  for (int k = 0; k < 3; ++k) c->root_c[k] = h.root_c[k];
-  c->origin_bound = h.origin_bound;
-  c->layout = h.layout;
-  c->graze_m = h.graze_m;
-  c->graze_leaf = h.graze_leaf;
-  c->guard = h.guard;
-  c->upload_ms = now_ms() - t1;
-  c->preprocess_ms = h.preprocess_ms;
-  c->use_bvh = h.use_bvh;
-  c->n_prims = h.n_prims;
-  c->n_nodes = h.n_nodes;
-  c->bvh_depth = h.bvh_depth;
-  c->stack_depth = h.use_bvh ? h.bvh_depth + 2 : 0;
-  c->n_wide = h.n_wide;
-  c->n_leaves = h.n_leaves;
-  c->n_top = h.n_top;
-  c->n_mats = uint32_t(h.mats.size());
-  c->wide_stack = h.wide_stack;
-  c->wide_stride = h.wide_stride;
-  c->texel_bytes = h.texel_bytes;
-  c->tri_rcp_fast = h.tri_rcp_fast;
-  c->has_dielectric = h.has_dielectric;
-  c->has_image_texture = h.has_image_texture;
-  c->scene_extent = h.scene_extent;
-  for (int k = 0; k < 3; ++k) {
-    c->tri_c[k] = h.tri_c[k];
-    c->tri_h[k] = h.tri_h[k];
-  }
-  c->slot_to_prim = h.slot_to_prim;
-}
-
-// The wavefront loop (render_loop_wf) for this scene?  ZRT_WF=0/1 forces it.
-// It doubles the traversal lane efficiency where traversal lengths diverge
-// (C3 0.29 -> 0.59, C5 0.22 -> 0.41), but the FAST loop is bound by its
-// per-lane node fetches (vector memory), not by VALU lane slots, so that buys
-// little time: C5 +2.6 %, C3 -3 .. +1 %, and on the bunny, whose lockstep
-// camera rays share cache lines, it costs a third.  Default:
-// trees too large for the 16-bit stack (million-triangle meshes, C5).
-bool use_wavefront(bool stk16) {
-  if (const char* e = std::getenv("ZRT_WF")) return std::atoi(e) != 0;
-  return !stk16;
-}
-// Per-axis margins (wide_iter) in waves with a lane whose max_k |1/d_k| exceeds
-// this; ZRT_PAXIS_M overrides (the tests set 0: every wave takes them)
-float paxis_threshold() {
-  if (const char* e = std::getenv("ZRT_PAXIS_M")) return float(std::atof(e));
-  return kPaxisM;
-}
-// The path-pool loop (render_loop_pool, MODE 5) instead of the wavefront loop?
-// ZRT_POOL=0/1 forces it.  Default: the wavefront loop's cases (trees past the
-// 16-bit stack), where it is 4 % faster at C5's full size (8.30 -> 8.65 Gray/s,
-// profiles/r03/ab5); on the teapot (C3) and the bunny (C4) the lockstep loop
-// stays ahead (14.7 vs 14.3, 50.5 vs 29.4 Gray/s).
-bool use_pool(bool stk16) {
-  if (const char* e = std::getenv("ZRT_POOL")) return std::atoi(e) != 0;
-  return !stk16;
-}
-// Compressed wide nodes (wide_iter_q, MODE 8 / 9) for this tree?  ZRT_QNODES=1
-// builds them (for trees of the path-pool loop's size, >= 65536 wide nodes, past the
-// 16-bit stack, or any tree when forced); off by default: on the C5 mesh the pool
-// over compressed nodes ran 7.17 Gray/s against 8.57 over the full nodes - each
-// opened leaf's record is one more dependent fetch (DESIGN.md §3 "Compressed nodes")
-bool want_qnodes(uint32_t n_wide) {
-  if (const char* e = std::getenv("ZRT_QNODES")) return std::atoi(e) != 0;
-  (void)n_wide;
-  return ZRT_LOCK_QN != 0;  // (the A/B build's lockstep loop reads nothing else)
-}
-// Top levels of a compressed tree served from LDS (ZRT_QTOP overrides): every ray
-// reads the root and a level-1 node, most a level-2 node - with 64-B nodes the
-// third level (<= 21 nodes, 10.5 KiB of octant copies) fits beside the pool's queues
-uint32_t qtop_levels() {
-  if (const char* e = std::getenv("ZRT_QTOP")) return uint32_t(std::max(1, std::min(4, std::atoi(e))));
-  return 3;
-}
-// The list loop with per-lane work items (render_loop_list, MODE 6) for scenes
-// without a BVH; ZRT_LIST_LANES=0 forces the wave-unit loop (render_loop MODE 0).
-// C2: 34.1 (MODE 0, lanes in per-sample lockstep) -> 45.4 (MODE 0, free lanes
-// within a unit) -> MODE 6.
-bool use_list_lanes() {
-  if (const char* e = std::getenv("ZRT_LIST_LANES")) return std::atoi(e) != 0;
-  return true;
-}
-// LDS of the path-pool loop's rays, hits and queues per block (render_loop_pool)
-constexpr size_t kPoolLdsBytes = ((8 * sizeof(float) + 1) * kBlockPaths + 15) & ~size_t(15);
-
 template <int MODE, int PRNG, bool STATS, class StackT, bool LEAN = false>
 void* kernel_ptr() {
   return reinterpret_cast<void*>(&render_kernel<MODE, PRNG, STATS, StackT, LEAN>);
@@ -5137,6 +4102,7 @@ void* select_kernel_ps(int mode, bool stk16) {
   if (mode == 9) return stk16 ? kernel_ptr<9, PRNG, STATS, uint16_t>() : kernel_ptr<9, PRNG, STATS, uint32_t>();
   return stk16 ? kernel_ptr<2, PRNG, STATS, uint16_t>() : kernel_ptr<2, PRNG, STATS, uint32_t>();
 }
+}  // namespace
 #ifdef ZRT_ISA_KERNEL
 // tools/isa.sh: device assembly of ONE render kernel (register / spill probes in
 // seconds instead of minutes); ZRT_ISA_KERNEL = MODE, PRNG, STATS, StackT[, true: the lean kernel]
@@ -5160,2544 +4126,102 @@ void* select_kernel(int mode, uint32_t prng, bool stats, bool stk16, bool lean) 
 }
 #endif
 
-template <int PRNG>
-void* probe_ptr(bool stk16) {
+// every other kernel-pointer table is empty under ZRT_ISA_KERNEL (tools/isa.sh: one render kernel alone).
+// The templates are instantiated, and their kernels laid out in the code object, in the order
+// of the functions from here on (probe, sort, features, trace, debug_rng): moving one reorders the
+// device assembly, which is otherwise compared byte for byte across host-only changes.
 #ifdef ZRT_ISA_KERNEL
-  (void)stk16;
-  return nullptr;
+#define ZRT_STK(K, ...) ((void)stk16, static_cast<void*>(nullptr))
 #else
-  return stk16 ? reinterpret_cast<void*>(&schedule_probe_kernel<PRNG, uint16_t>)
-               : reinterpret_cast<void*>(&schedule_probe_kernel<PRNG, uint32_t>);
+#define ZRT_STK(K, ...) (stk16 ? reinterpret_cast<void*>(&K<__VA_ARGS__, uint16_t>) \
+                               : reinterpret_cast<void*>(&K<__VA_ARGS__, uint32_t>))
 #endif
+void* probe_kernel(uint32_t prng, bool stk16) {
+  return prng == ZRT_PRNG_XOSHIRO256 ? ZRT_STK(schedule_probe_kernel, ZRT_PRNG_XOSHIRO256)
+                                     : ZRT_STK(schedule_probe_kernel, ZRT_PRNG_XOROSHIRO128);
 }
+hipError_t sort_tiles(void* temp, size_t* temp_bytes, const uint32_t* cost, uint32_t* cost_sorted, const uint32_t* ids,
+                      uint32_t* order, uint32_t n, hipStream_t st) {
+  return hipcub::DeviceRadixSort::SortPairsDescending(temp, *temp_bytes, cost, cost_sorted, ids, order, int(n), 0, 32, st);
+}
+void* features_kernel_ptr(int mode, bool stk16) {
+  return mode == 0 ? ZRT_STK(features_kernel, 0) : mode == 1 ? ZRT_STK(features_kernel, 1)
+       : mode == 2 ? ZRT_STK(features_kernel, 2) : mode == 8 ? ZRT_STK(features_kernel, 8) : ZRT_STK(features_kernel, 3);
+}
+void* trace_kernel_ptr(int mode, bool stk16) {
+  return mode == 0 ? ZRT_STK(trace_kernel, 0) : mode == 1 ? ZRT_STK(trace_kernel, 1)
+       : mode == 2 ? ZRT_STK(trace_kernel, 2) : mode == 8 ? ZRT_STK(trace_kernel, 8) : ZRT_STK(trace_kernel, 3);
+}
+#undef ZRT_STK
 
-// The block's dynamic LDS: [stack rows][lane] (StackT), then (FAST) the top
-// wide nodes of every octant copy, then the first attenuation rows
-// [row][rgb][lane] f32.  Sized so the waves per SIMD the kernel is built for
-// (its __launch_bounds__) still fit: 160 KiB / that many blocks per CU.
-struct LdsPlan {
-  uint32_t stack_rows = 0, top_off = 0, att_off = 0, att_rows = 0, mat_off = 0, mats_in_lds = 0, pool_off = 0;
-  uint32_t state_off = 0;
-  size_t bytes = 0, budget = 0;
-  size_t stack_b = 0, top_b = 0, pool_b = 0, state_b = 0, att_b = 0, mats_b = 0;  // region sizes (check_plan)
-};
-constexpr size_t kLdsPerBlockMax = 160u << 10;  // gfx950: a work-group may use the CU's whole LDS
-// Every region of a plan inside the block's share and disjoint from the others,
-// float4 regions 16-B aligned (the kernels index them from lds_raw by these
-// offsets, nothing else keeps them apart); a violation is a bug in plan_lds.
-void check_plan(const LdsPlan& L) {
-  struct Reg { size_t off, n; const char* name; bool f4; };
-  const Reg regs[] = {{0, L.stack_b, "stack", false}, {L.top_off, L.top_b, "top nodes", true},
-                      {L.pool_off, L.pool_b, "pool", true}, {L.state_off, L.state_b, "lane state", false},
-                      {L.att_off, L.att_b, "attenuation rows", false}, {L.mat_off, L.mats_b, "materials", true}};
-  if (L.bytes > kLdsPerBlockMax)
-    throw Error(ZRT_E_UNSUPPORTED, "LDS plan: " + std::to_string(L.bytes) + " B, past a block's " +
-                                       std::to_string(kLdsPerBlockMax) + " B");
-  for (const Reg& x : regs) {
-    if (!x.n) continue;
-    if (x.off + x.n > L.bytes)
-      throw Error(ZRT_E_UNSUPPORTED, std::string("LDS plan: ") + x.name + " past the plan's end");
-    if (x.f4 && x.off % 16)
-      throw Error(ZRT_E_UNSUPPORTED, std::string("LDS plan: ") + x.name + " not 16-B aligned");
-    for (const Reg& y : regs)
-      if (&x != &y && y.n && x.off < y.off + y.n && y.off < x.off + x.n)
-        throw Error(ZRT_E_UNSUPPORTED, std::string("LDS plan: ") + x.name + " overlaps " + y.name);
-  }
-}
-// 32-bit words of the lockstep loop's lane state (LaneState)
-uint32_t lane_state_words(uint32_t prng) {
-  return (prng == ZRT_PRNG_XOSHIRO256 ? LaneState<ZRT_PRNG_XOSHIRO256>::kWords
-                                      : LaneState<ZRT_PRNG_XOROSHIRO128>::kWords);
-}
-// tests: a cap on the FAST stack's LDS rows, so that the global overflow rows come
-// into use.  ZRT_STACK_LDS_ROWS=<n> also forces the 32-bit stack (fast_stk16);
-// ZRT_STACK_LDS_ROWS16=<n> caps the rows the same way and leaves the stack's width
-// alone, so a 16-bit stack reads its overflow rows too.
-constexpr uint32_t kNoRowsCap = 0xffffffffu;
-uint32_t stack_rows_cap() {
-  const char* f = std::getenv("ZRT_STACK_LDS_ROWS");
-  if (!f) f = std::getenv("ZRT_STACK_LDS_ROWS16");
-  return f ? uint32_t(std::atoi(f)) : kNoRowsCap;
-}
-// FAST: a 16-bit stack when node indices fit (either width keeps its first rows in
-// LDS and deeper ones in global memory, plan_lds)
-bool fast_stk16(uint32_t n_wide, uint32_t n_nodes) {
-  return n_wide < 65536 && n_nodes < 65536 && !std::getenv("ZRT_STACK_LDS_ROWS");
-}
-// pool: the path-pool loop (MODE 5): its attenuation rows are per path
-// (kBlockPaths per block), and its rays / hits / queues follow them.
-// The lockstep FAST loop (mode 3, neither wf nor pool) also holds its lane state
-// (ZRT_LANE_LDS) and keeps at most ZRT_STACK_ROWS_LOCK stack rows in LDS.
-LdsPlan plan_lds(uint32_t n_top, uint32_t n_mats, int mode, bool stk16, uint32_t stack_depth, uint32_t max_depth,
-                 bool wf, bool pool, uint32_t prng, uint32_t node_f4 = 8, uint32_t rows_cap = stack_rows_cap()) {
-  const uint32_t waves = mode == 3 ? (pool ? ZRT_WAVES_POOL : wf ? ZRT_WAVES_WF : ZRT_WAVES_WIDE)
-                         : mode == 0 ? ZRT_WAVES_LIST : ZRT_WAVES_PER_SIMD;
-  // 256-thread blocks: `waves` blocks per CU; 1 KiB below the even share (a
-  // block of exactly 32 KiB ran 8 % slower at 5 blocks per CU)
-  const size_t budget = (160u << 10) / waves - (1u << 10);
-  const size_t entry = stk16 ? sizeof(uint16_t) : sizeof(uint32_t);
-  const size_t row_att = sizeof(uint32_t) * (pool ? kBlockPaths : kBlock);  // one att code per lane / path
-  const size_t top = mode == 3 && ZRT_LDS_TOP ? size_t(n_top) * node_f4 * sizeof(float4) * kOctCopies : 0;
-  const size_t pool_b = pool ? kPoolLdsBytes : 0;
-  const bool lock = mode == 3 && !wf && !pool;
-  const size_t state = lock && ZRT_LANE_LDS ? size_t(lane_state_words(prng)) * sizeof(uint32_t) * kBlock : 0;
-  // attenuation rows wanted: rows 0 .. max_depth-2 are ever pushed (raytrace.zig:99 at depth > 1).
-  // A row is one 4-B att code per lane (att_code; round 3: three floats, 12 B), so
-  // the same LDS holds three times the rows: the lockstep loop 6 (round 3, 2 rows
-  // of floats - C4 A/B: none 50.35, 1 row 50.57, 2 rows 50.70 Gray/s; a 32 KiB
-  // block 46.5), the wavefront loop 12 (its 4 blocks per CU have a larger share;
-  // the textured C5 mesh scatters often), the path pool 3 per path, the list loops
-  // 24 (no stack, no tree in LDS; C2 at depth 30 with glass: round 3 2 -> 4 -> 8
-  // rows of floats 32.7 -> 33.3 -> 34.0 Gray/s, profiles/r03/ab12)
-  const uint32_t att_cap = pool ? ZRT_ATT_ROWS_POOL : wf ? ZRT_ATT_ROWS_WF : mode == 0 ? ZRT_ATT_ROWS_LIST : ZRT_ATT_ROWS_LOCK;
-  uint32_t want = att_cap;
-  if (const char* e = std::getenv("ZRT_ATT_LDS_ROWS")) want = uint32_t(std::atoi(e));
-  want = std::min<uint32_t>(want, max_depth > 1 ? max_depth - 1 : 0);
-  LdsPlan L;
-  L.budget = budget;
-  if (mode == 3) {
-    // the stack takes what the top nodes, the lane state and the wanted attenuation
-    // rows leave (the lockstep loop: at most ZRT_STACK_ROWS_LOCK rows; it wants
-    // ZRT_ATT_ROWS_LOCK att rows); deeper rows live in global memory (wide_iter and
-    // wide_iter_q read them at either stack width, so no FAST plan holds a stack
-    // the block's LDS cannot)
-    want = std::min<uint32_t>(want, att_cap);
-    const size_t fixed = top + pool_b + state + want * row_att;
-    const size_t room = budget > fixed ? budget - fixed : 0;
-    L.stack_rows = std::max<uint32_t>(1, std::min<uint32_t>(stack_depth, uint32_t(room / (kBlock * entry))));
-    if (lock) L.stack_rows = std::min<uint32_t>(L.stack_rows, ZRT_STACK_ROWS_LOCK);
-  } else {
-    L.stack_rows = stack_depth;  // BINARY / REFERENCE: the whole stack in LDS (check_plan: within a block's LDS)
-  }
-  if (rows_cap != kNoRowsCap && mode == 3)  // tests: force the overflow rows into use
-    L.stack_rows = std::max<uint32_t>(1, std::min<uint32_t>(L.stack_rows, rows_cap));
-  const size_t stack = (size_t(L.stack_rows) * kBlock * entry + 15) & ~size_t(15);
-  const size_t used = stack + top + pool_b + state;
-  // loops that read the material table from LDS only (ZRT_MATS_LDS_ONLY): the table
-  // before the attenuation rows, which live in global memory when LDS runs out
-  const size_t mats = size_t(n_mats) * sizeof(DevMaterial);
-  const bool mats_first = ZRT_MATS_LDS_ONLY && (lock || mode == 0);
-  const size_t mats_res = mats_first && used + mats <= budget ? mats : 0;
-  L.att_rows = std::min<uint32_t>(want, used + mats_res < budget ? uint32_t((budget - used - mats_res) / row_att) : 0u);
-  L.top_off = uint32_t(stack);
-  L.pool_off = uint32_t(stack + top);
-  L.state_off = uint32_t(stack + top + pool_b);
-  L.att_off = uint32_t(used);
-  L.bytes = used + L.att_rows * row_att;
-  L.stack_b = size_t(L.stack_rows) * kBlock * entry;
-  L.top_b = top;
-  L.pool_b = pool_b;
-  L.state_b = state;
-  L.att_b = L.att_rows * row_att;
-  // the material table, if it fits what is left (ZRT_MATS_LDS=0: A/B, always global,
-  // for the loops that can read it there)
-  const char* me = std::getenv("ZRT_MATS_LDS");
-  if (mats > 0 && L.bytes + mats <= budget && (mats_first || !(me && std::atoi(me) == 0))) {
-    L.mat_off = uint32_t(L.bytes);
-    L.mats_in_lds = 1;
-    L.bytes += mats;
-    L.mats_b = mats;
-  }
-  // the lockstep FAST kernel's waves per SIMD hold only within the share (the
-  // other loops' plans may exceed it: their launch then fits fewer blocks per CU)
-  if (lock && L.bytes > budget) throw Error(ZRT_E_UNSUPPORTED, "LDS plan: the lockstep loop's regions exceed its share");
-  check_plan(L);
-  return L;
-}
-LdsPlan plan_lds(const zrt_ctx* c, int mode, bool stk16, uint32_t stack_depth, uint32_t max_depth, bool wf, bool pool,
-                 uint32_t prng, uint32_t node_f4 = 8) {
-  return plan_lds(node_f4 == kQuantNodeF4 ? c->q_top : c->n_top, c->n_mats, mode, stk16, stack_depth, max_depth, wf,
-                  pool, prng, node_f4);
-}
-
-// The context's global buffers that the launches of a frame share (the render
-// launch and its scheduling probe) and that later frames reuse: attenuation rows
-// past the plan's LDS rows ([row][lane], the path pool [row][path]: elements of
-// c->att) and FAST stack rows past the plan's LDS rows ([row][lane]: bytes of
-// c->stack_ovf).  A launch's need follows from its own plan; every launch is
-// checked against the allocation before it is enqueued (check_buffers), so a
-// sizing mistake - round 5's scheduling probe kept 4 LDS attenuation rows where
-// the wavefront render it shared the buffer with kept 12 - is refused as
-// ZRT_E_UNSUPPORTED on the host instead of faulting on the GPU.
-struct BufNeed {
-  uint64_t att_elems = 0;  // u32 attenuation codes
-  uint64_t ovf_bytes = 0;  // stack entries (StackT) past the LDS rows
-};
-// global attenuation rows a path (a lane; the path pool: a path) is given
-uint32_t att_rows_per_path(const LdsPlan& lp, uint32_t max_depth) {
-  return std::max<uint32_t>(1, max_depth - std::min(max_depth, lp.att_rows));
-}
-BufNeed buffer_need(const LdsPlan& lp, uint32_t max_depth, uint32_t stack_depth, uint64_t n_paths, uint64_t n_lanes,
-                    bool stk16) {
-  BufNeed n;
-  n.att_elems = uint64_t(att_rows_per_path(lp, max_depth)) * n_paths;
-  if (stack_depth > lp.stack_rows)
-    n.ovf_bytes = uint64_t(stack_depth - lp.stack_rows) * n_lanes * (stk16 ? sizeof(uint16_t) : sizeof(uint32_t));
-  return n;
-}
-void check_buffers(const char* launch, const BufNeed& need, uint64_t att_elems, uint64_t ovf_bytes) {
-  if (need.att_elems > att_elems)
-    throw Error(ZRT_E_UNSUPPORTED, std::string(launch) + ": needs " + std::to_string(need.att_elems) +
-                                       " global attenuation-row entries, the context holds " + std::to_string(att_elems));
-  if (need.ovf_bytes > ovf_bytes)
-    throw Error(ZRT_E_UNSUPPORTED, std::string(launch) + ": needs " + std::to_string(need.ovf_bytes) +
-                                       " B of global stack rows, the context holds " + std::to_string(ovf_bytes));
-}
-// The device side of the same check (KArgs::att_cap / ovf_cap: the allocations'
-// elements), in the STATS flavour: a row index past its buffer sets kErrBounds and
-// the access is skipped (tests/test_gpu_runtime.py shrinks the capacity it is told)
-uint64_t ovf_cap_elems(uint64_t ovf_bytes, bool stk16) { return ovf_bytes / (stk16 ? 2u : 4u); }
-
-// What the launch decision reads of a scene: a context's copy of it, or (no
-// device: zrt_debug_launch_plan) the flattened scene itself.
-struct SceneShape {
-  bool use_bvh = false, q_ok = false;
-  uint32_t n_nodes = 0, n_wide = 0, wide_stack = 0, stack_depth = 0, n_top = 0, q_top = 0, n_mats = 0;
-  float guard = 0.0f;
-  bool tri_rcp_fast = false, has_dielectric = true, has_image_texture = true;  // (the lean kernel's conditions)
-};
-SceneShape shape_of(const zrt_ctx* c) {
-  SceneShape s;
-  s.tri_rcp_fast = c->tri_rcp_fast != 0;
-  s.has_dielectric = c->has_dielectric != 0;
-  s.has_image_texture = c->has_image_texture != 0;
-  s.use_bvh = c->use_bvh;
-  s.q_ok = c->q_ok;
-  s.n_nodes = c->n_nodes;
-  s.n_wide = c->n_wide;
-  s.wide_stack = c->wide_stack;
-  s.stack_depth = c->stack_depth;
-  s.n_top = c->n_top;
-  s.q_top = c->q_top;
-  s.n_mats = c->n_mats;
-  s.guard = c->guard;
-  return s;
-}
-SceneShape shape_of(const HostScene& h) {  // (as upload_scene fills the context)
-  SceneShape s;
-  s.tri_rcp_fast = h.tri_rcp_fast != 0;
-  s.has_dielectric = h.has_dielectric != 0;
-  s.has_image_texture = h.has_image_texture != 0;
-  s.use_bvh = h.use_bvh;
-  s.q_ok = h.q_ok;
-  s.n_nodes = h.n_nodes;
-  s.n_wide = h.n_wide;
-  s.wide_stack = h.wide_stack;
-  s.stack_depth = h.use_bvh ? h.bvh_depth + 2 : 0;
-  s.n_top = h.n_top;
-  s.q_top = h.q_top;
-  s.n_mats = uint32_t(h.mats.size());
-  s.guard = h.guard;
-  return s;
-}
-
-// The launch decision of a render (zrt_ctx_render_tiles; zrt_debug_launch_plan
-// reports it with no device): traversal mode, stack width and depth, sampling
-// loop (kmode: the kernel's MODE), node format and the block's LDS plan.  Pure:
-// it reads the scene's shape, the params and the environment knobs only.
-struct LaunchPlan {
-  int mode = 0;   // 0 list, 1 binary, 2 reference, 3 FAST
-  int kmode = 0;  // the kernel: mode, or 4 wavefront, 5 / 7 / 8 / 9 path pool, 6 list with per-lane items
-  bool stk16 = false, wf = false, pool = false, qn = false, guard_on = false;
-  // the timed launch may take the lean kernel (ZRT_LEAN_*): the scene and the params
-  // allow it; the launch itself adds that its camera lies inside the origin bound
-  // and that it is not the STATS flavour (lean_launch)
-  bool lean = false;
-  uint32_t node_f4 = 8, stack_depth = 0;
-  LdsPlan lp;
-};
-// ZRT_LEAN=0 forces the general kernel; an ineligible launch never takes the lean one
-bool lean_wanted() {
-  if (const char* e = std::getenv("ZRT_LEAN")) return std::atoi(e) != 0;
-  return ZRT_LEAN_DEFAULT != 0;
-}
-// KArgs::check_origins of a render launch is 0: its camera lies inside the scene's origin bound
-bool camera_inside(const zrt_camera* cam, const float root_c[3], float origin_bound) {
-  const float m = std::max({std::fabs(cam->origin.x - root_c[0]), std::fabs(cam->origin.y - root_c[1]),
-                            std::fabs(cam->origin.z - root_c[2])});
-  return m <= origin_bound;
-}
-// The kernel of one launch: the lean one where the plan allows it, for the timed
-// flavour (the STATS flavour stays general) of a launch that checks no origin
-bool lean_launch(const LaunchPlan& P, bool stats, bool cam_inside) { return P.lean && !stats && cam_inside; }
-// zrt_stats::sampling_loop of a kernel: the path pool's flavours report as the pool
-uint32_t reported_loop(int kmode) { return kmode == 7 || kmode == 8 || kmode == 9 ? 5u : uint32_t(kmode); }
-LaunchPlan plan_launch(const SceneShape& s, const zrt_params* p) {
-  LaunchPlan P;
-  P.mode = !s.use_bvh ? 0 : p->traversal == ZRT_TRAVERSAL_REFERENCE ? 2 : p->traversal == ZRT_TRAVERSAL_BINARY ? 1 : 3;
-  const int mode = P.mode;
-  // (FAST also holds the reference traversal's rows for its order-hazard replay)
-  P.stack_depth = mode == 3 ? std::max(s.wide_stack, s.stack_depth) : s.stack_depth;
-  if (const char* cap = std::getenv("ZRT_DEBUG_STACK_CAP"))  // tests: a stack too small for the tree
-    P.stack_depth = std::max<uint32_t>(4, std::min<uint32_t>(P.stack_depth, uint32_t(std::atoi(cap))));
-  P.stk16 = mode == 3 ? fast_stk16(s.n_wide, s.n_nodes) : s.n_nodes < 65536;
-  // no loop shades at max_depth 0 (every sample ends at the depth limit before it
-  // traces): the lockstep / list loops return black there; the wavefront and
-  // path-pool loops assume max_depth >= 1 and are never chosen
-  const bool shades = p->max_depth >= 1;
-  // FAST: the wavefront loop (MODE 4) where lanes' traversal lengths diverge
-  P.wf = mode == 3 && shades && use_wavefront(P.stk16);
-  // the grazing-triangle guard (ZRT_FLAG_GUARD): carried by the path-pool loop's traversal
-  P.guard_on = mode == 3 && (p->flags & ZRT_FLAG_GUARD) != 0 && s.guard > 0.0f;
-  // the path-pool loop (MODE 5) for the same cases, when asked for; a 16-bit stack
-  // must fit beside its rays and queues in the block's LDS share, else the 32-bit
-  // stack with overflow rows
-  P.pool = mode == 3 && shades && (use_pool(P.stk16) || P.guard_on);
-  // the path pool over compressed nodes (MODE 8 / 9) where the context built them (and
-  // the lockstep loop in the ZRT_LOCK_QN A/B build, which has no other traversal)
-  const bool lock_qn = ZRT_LOCK_QN && mode == 3 && !P.pool && !P.wf;
-  if (lock_qn && !s.q_ok) throw Error(ZRT_E_UNSUPPORTED, "ZRT_LOCK_QN build: no compressed nodes for this tree");
-  P.qn = (P.pool || lock_qn) && s.q_ok;
-  P.node_f4 = P.qn ? kQuantNodeF4 : 8u;
-  const uint32_t n_top = P.qn ? s.q_top : s.n_top;
-  if (P.pool && P.stk16) {
-    const size_t budget = (160u << 10) / ZRT_WAVES_POOL - (1u << 10);
-    const size_t top = ZRT_LDS_TOP ? size_t(n_top) * P.node_f4 * sizeof(float4) * kOctCopies : 0;
-    // (rows the tests' cap keeps out of LDS need not fit it)
-    const uint32_t rows = std::min(P.stack_depth, stack_rows_cap());
-    if (size_t(rows) * kBlock * sizeof(uint16_t) + top + kPoolLdsBytes > budget) P.stk16 = false;
-  }
-  const bool list_lanes = mode == 0 && use_list_lanes();
-  // (the guard's branch costs the path pool 0.7 % on C5, so a guarded render has a
-  // kernel of its own, MODE 7; profiles/r04/r04n)
-  P.kmode = P.pool ? (P.qn ? (P.guard_on ? 9 : 8) : (P.guard_on ? 7 : 5)) : P.wf ? 4 : list_lanes ? 6 : mode;
-  // FAST: deep trees keep their last stack rows in global memory (rarely
-  // touched) so the LDS never caps the occupancy the registers allow; the
-  // other traversals keep the whole stack in LDS (plan_lds)
-  P.lp = plan_lds(n_top, s.n_mats, mode, P.stk16, P.stack_depth, p->max_depth, P.wf, P.pool, p->prng, P.node_f4);
-  if (ZRT_MATS_LDS_ONLY && (P.kmode == 3 || P.kmode == 6) && !P.lp.mats_in_lds) {
-    // a material table past the loop's LDS share: the loop that reads it from global
-    // memory (the wavefront loop for FAST, the wave-unit list loop; same images).
-    // At max_depth 0 the lockstep loop stays (the wavefront loop would trace, and its
-    // first scatter would write attenuation row 1 of a one-row buffer): it reads no
-    // material there, and the launch copies no table into LDS (KArgs::n_mats = 0)
-    if (P.kmode == 6) {
-      P.kmode = 0;
-    } else if (shades) {
-      P.wf = true;
-      P.kmode = 4;
-    }
-    P.lp = plan_lds(n_top, s.n_mats, mode, P.stk16, P.stack_depth, p->max_depth, P.wf, P.pool, p->prng, P.node_f4);
-  }
-  // the lean kernel: the lockstep FAST loop over full nodes, shading (it reads the
-  // material table from LDS only), in a scene that has none of what it leaves out
-  P.lean = P.kmode == 3 && !ZRT_LOCK_QN && shades && P.lp.mats_in_lds != 0 && s.tri_rcp_fast && !s.has_dielectric &&
-           !s.has_image_texture && (p->flags & ZRT_FLAG_SCANLINES) == 0 && lean_wanted();
-  return P;
-}
-
-// Longest-processing-time-first order of this rank's tiles (zrt.h,
-// ZRT_FLAG_NO_SCHEDULE): the probe renders kProbeSpp samples of every tile as
-// one unit each and records the loop iterations its wave spent (lockstep makes
-// that the unit's time); a stable device radix sort orders the tiles by
-// descending cost, ties in tile order.  Sets a.tile_order for the render launch.
-bool schedule_tiles(zrt_ctx* c, KArgs& a, uint32_t prng, bool stk16, uint32_t my_tiles, uint32_t grid,
-                    size_t lds, hipStream_t st) {
-  constexpr uint32_t kProbeSpp = ZRT_PROBE_SPP;
-  KArgs pa = a;
-  pa.spp = kProbeSpp;
-  pa.chunk = kProbeSpp;
-  pa.n_chunks = 1;
-  pa.total_work = my_tiles;
-  if (c->probe_partial.n < uint64_t(my_tiles) * 64u) c->probe_partial.alloc(uint64_t(my_tiles) * 64u);
-  if (c->probe_scratch.n < uint64_t(kScratchSlots)) c->probe_scratch.alloc(kScratchSlots);
-  if (c->tile_cost.n < my_tiles) {
-    c->tile_cost.alloc(my_tiles);
-    c->cost_sorted.alloc(my_tiles);
-    c->tile_order.alloc(my_tiles);
-  }
-  if (c->tile_ids_n != my_tiles) {
-    std::vector<uint32_t> ids(my_tiles);
-    for (uint32_t i = 0; i < my_tiles; ++i) ids[i] = i;
-    c->tile_ids.upload(ids);
-    c->tile_ids_n = my_tiles;
-  }
-  pa.partial = c->probe_partial.p;
-  pa.counters = c->probe_scratch.p;
-  pa.work_counter = reinterpret_cast<uint32_t*>(c->probe_scratch.p + kWorkSlot);
-  // pa.error_flag stays the render launch's: a probe overflow fails the frame too
-  pa.unit_cost = c->tile_cost.p;
-  pa.tile_order = nullptr;
-  const uint32_t pgrid = std::max(1u, std::min(grid, (my_tiles + kBlock / 64 - 1) / (kBlock / 64)));
-  pa.n_lanes = pgrid * kBlock;
-  // the probe is the lockstep loop over the full nodes, whatever loop and node
-  // format the render launch uses: its own LDS plan (the render's may be the path
-  // pool's, whose regions the lockstep loop would read as its lane state and rows)
-  const LdsPlan pp = plan_lds(c, 3, stk16, a.stack_depth, a.max_depth, false, false, prng, 8);
-  pa.wnodes = c->wnodes.p;
-  pa.wide_stride = c->wide_stride;
-  pa.node_f4 = 8;
-  pa.n_top = c->n_top;  // (the full nodes' top levels: a compressed tree keeps more in LDS)
-  pa.qleaves = nullptr;
-  pa.n_qnodes = pa.n_qleaves = 0;
-  pa.lds_rows = pp.stack_rows;
-  pa.lds_top_off = pp.top_off;
-  pa.lds_att_off = pp.att_off;
-  pa.att_lds_rows = pp.att_rows;
-  pa.lds_mat_off = pp.mat_off;
-  pa.mats_in_lds = pp.mats_in_lds;
-  // (the probe is the lockstep loop, which reads the table from LDS only: no schedule
-  // for a table past its LDS share - the render then takes the tiles in order)
-  if (ZRT_MATS_LDS_ONLY && !pp.mats_in_lds) return false;
-  pa.lds_pool_off = pp.pool_off;
-  pa.lds_state_off = pp.state_off;
-  lds = pp.bytes;
-  // its deep stack rows and global attenuation rows ([row][lane] past its LDS rows):
-  // the render launch's buffers, grown if the probe's plan needs more (the wavefront
-  // loop keeps 12 attenuation rows in LDS, the lockstep probe 4)
-  const BufNeed need = buffer_need(pp, a.max_depth, a.stack_depth, pa.n_lanes, pa.n_lanes, stk16);
-  if (need.ovf_bytes) {
-    if (c->stack_ovf.n < need.ovf_bytes) {
-      HIPCHK(hipStreamSynchronize(st));  // (the previous launch may still read the old buffer)
-      c->stack_ovf.alloc(need.ovf_bytes);
-    }
-    a.stack_ovf = pa.stack_ovf = c->stack_ovf.p;
-  }
-  if (c->att.n < need.att_elems) {
-    HIPCHK(hipStreamSynchronize(st));  // (the previous launch may still read the old buffer)
-    c->att.alloc(need.att_elems);
-  }
-  a.att = pa.att = c->att.p;
-  a.att_cap = pa.att_cap = c->att.n;
-  a.ovf_cap = pa.ovf_cap = ovf_cap_elems(c->stack_ovf.n, stk16);
-  check_buffers("scheduling probe", need, c->att.n, c->stack_ovf.n);
-  HIPCHK(hipMemsetAsync(c->probe_scratch.p, 0, kScratchSlots * sizeof(unsigned long long), st));
-  void* fn = prng == ZRT_PRNG_XOSHIRO256 ? probe_ptr<ZRT_PRNG_XOSHIRO256>(stk16)
-                                         : probe_ptr<ZRT_PRNG_XOROSHIRO128>(stk16);
-  void* args[] = {&pa};
-  HIPCHK(hipLaunchKernel(fn, dim3(pgrid), dim3(kBlock), args, lds, st));
-  size_t bytes = 0;
-  HIPCHK(hipcub::DeviceRadixSort::SortPairsDescending(nullptr, bytes, c->tile_cost.p, c->cost_sorted.p,
-                                                      c->tile_ids.p, c->tile_order.p, int(my_tiles), 0, 32, st));
-  if (c->sort_temp.n < bytes) c->sort_temp.alloc(bytes);
-  HIPCHK(hipcub::DeviceRadixSort::SortPairsDescending(c->sort_temp.p, bytes, c->tile_cost.p, c->cost_sorted.p,
-                                                      c->tile_ids.p, c->tile_order.p, int(my_tiles), 0, 32, st));
-  a.tile_order = c->tile_order.p;
-  return true;
-}
-
-int hip_fail(const HipError& e) {
-  return fail(ZRT_E_HIP, e.where + ": " + hipGetErrorString(e.err));
-}
-
-// The catch clauses of every C entry point: no exception crosses the ABI.
-#define ZRT_CATCH_ALL                                  \
-  catch (const ::zrt::HipError& e) {                   \
-    return ::zrt::hip_fail(e);                         \
-  }                                                    \
-  catch (const ::zrt::Error& e) {                      \
-    return ::zrt::fail(e.code, e.what());              \
-  }                                                    \
-  catch (const std::bad_alloc&) {                      \
-    return ::zrt::fail(ZRT_E_NOMEM, "OutOfMemory");    \
-  }
-
-constexpr const char* kOverflowMsg = "BVH traversal stack overflow (tree deeper than the stack was sized for)";
-constexpr const char* kLayoutMsg = "the kernel refused the wide tree: its layout is not the one the kernel decodes";
-constexpr const char* kBoundsMsg = "a global attenuation or stack row index past its buffer (STATS bounds check)";
-const char* device_error_msg(unsigned long long flag) {
-  return (flag & kErrLayout) ? kLayoutMsg : (flag & kErrBounds) ? kBoundsMsg : kOverflowMsg;
-}
-
-// The device error flag of the context's last launch, copied to pinned host
-// memory behind ev_done.  wait: block until the launch is done and report its
-// error (every such call does); else (render_tiles' sticky check) report it only
-// if the launch has finished and no call has reported it yet.
-int launch_status(zrt_ctx* c, bool wait) {
-  if (c->feat_launched && !c->feat_err_reported) {  // a feature launch's error, reported once
-    bool done = true;
-    if (wait) {
-      HIPCHK(hipEventSynchronize(c->feat_done));
-    } else if (hipEventQuery(c->feat_done) != hipSuccess) {
-      (void)hipGetLastError();  // (not ready is no error of this launch)
-      done = false;
-    }
-    if (done && *c->feat_err_host != 0) {
-      c->feat_err_reported = true;
-      return fail(ZRT_E_UNSUPPORTED, device_error_msg(*c->feat_err_host));
-    }
-  }
-  if (!c->launched) return ZRT_OK;
-  if (wait) {
-    HIPCHK(hipEventSynchronize(c->ev_done));
-  } else if (hipEventQuery(c->ev_done) != hipSuccess || c->err_reported) {
-    return ZRT_OK;
-  }
-  if (*c->err_host == 0) return ZRT_OK;
-  c->err_reported = true;
-  return fail(ZRT_E_UNSUPPORTED, device_error_msg(*c->err_host));
-}
-
-// A run's earlier passes whose events have completed (wait: all of them) added into
-// its render and schedule times; their event sets become spare.  Passes complete in
-// the order they were enqueued.
-void fold_pass_times(zrt_ctx* c, bool wait) {
-  while (!c->run_pending.empty()) {
-    const zrt_ctx::EvSet e = c->run_pending.front();
-    if (wait) {
-      HIPCHK(hipEventSynchronize(e.e1));
-    } else if (hipEventQuery(e.e1) != hipSuccess) {
-      (void)hipGetLastError();  // (not ready is no error of this launch)
-      break;
-    }
-    float ms = 0.0f, sched = 0.0f;
-    HIPCHK(hipEventElapsedTime(&ms, e.pre, e.e1));
-    HIPCHK(hipEventElapsedTime(&sched, e.pre, e.e0));
-    c->run_render_ms += ms;
-    if (e.probed) c->run_sched_ms += sched;
-    c->ev_spare.push_back(e);
-    c->run_pending.erase(c->run_pending.begin());
-  }
-}
-
-// One pass of an accumulation run (zrt_ctx_accum_pass; zrt_debug_pass_plan reports
-// the same): samples [done, done + n_samples) of a run capped at
-// p->samples_per_pixel, as a launch of n_samples samples in pass_chunks chunks whose
-// sample keys are shifted by `done`.  A sample's stream is keyed by
-// ((pixel << 16) | sample) + seed * 0x9E37...; for sample + done < 65536,
-// ((o << 16) | s) + done == (o << 16) | (s + done), so key_offset = done added to
-// the seed term gives the pass the keys of the frame's samples done .. done + n - 1.
-// The pass must start on a chunk boundary: its chunk sums are then the frame's
-// chunks done / chunk .., and a ragged last chunk is the frame's last one.
-int plan_pass(const zrt_params* p, uint32_t done, uint32_t n_samples, zrt_pass_plan* out) {
-  const int rc = validate_params(p);
-  if (rc) return rc;
-  const uint32_t chunk = p->sample_chunk ? p->sample_chunk : ZRT_DEFAULT_SAMPLE_CHUNK;
-  if (n_samples == 0) return fail(ZRT_E_INVALID, "a pass of 0 samples");
-  if (uint64_t(done) + n_samples > p->samples_per_pixel)
-    return fail(ZRT_E_INVALID, "the pass ends past the run's samples_per_pixel");
-  if (done % chunk != 0)
-    return fail(ZRT_E_INVALID, "the pass does not start on a sample chunk boundary (a ragged pass ends the run)");
-  const uint32_t my_tiles = rank_tiles(geometry(p), p->rank, p->world_size);
-  zrt_pass_plan P{};
-  P.first_sample = done;
-  P.pass_samples = n_samples;
-  P.samples_after = done + n_samples;
-  P.chunk = chunk;
-  P.pass_chunks = (n_samples + chunk - 1) / chunk;
-  P.last_chunk = n_samples - (P.pass_chunks - 1) * chunk;
-  if (uint64_t(my_tiles) * 64u * P.pass_chunks >= (1ull << 32) - (1ull << 26))  // (+ one refill per lane of slack)
-    return fail(ZRT_E_UNSUPPORTED, "more than 2^32 (pixel, chunk) work items");
-  P.partial_bytes = uint64_t(my_tiles) * 64u * P.pass_chunks * sizeof(float4);
-  P.key_offset = done;
-  *out = P;
-  return ZRT_OK;
-}
-
-// The levels of an adaptive run (zrt.h "adaptive sampling"; zrt_debug_adapt_plan
-// reports the same): L_0 = first_level in whole chunks (at least one), doubled while
-// below the cap, then the cap.  Every level but the last ends on a chunk boundary, so
-// every level is a pass plan_pass accepts.
-int plan_adapt(const zrt_params* p, const zrt_adaptive* ad, std::vector<uint32_t>* levels) {
-  if (!ad) return fail(ZRT_E_INVALID, "null argument");
-  zrt_pass_plan whole{};
-  const int rc = plan_pass(p, 0u, p ? p->samples_per_pixel : 0u, &whole);  // (validates the params and the cap)
-  if (rc) return rc;
-  if (!(ad->tolerance >= 0.0f) || !std::isfinite(ad->tolerance))
-    return fail(ZRT_E_INVALID, "zrt_adaptive.tolerance must be finite and >= 0");
-  const uint64_t cap = p->samples_per_pixel, chunk = whole.chunk;
-  uint64_t L = std::max<uint64_t>(1u, (uint64_t(ad->first_level) + chunk - 1) / chunk) * chunk;
-  levels->clear();
-  for (; L < cap; L *= 2) levels->push_back(uint32_t(L));
-  levels->push_back(uint32_t(cap));
-  return ZRT_OK;
-}
-
-// RCCL for zrt_render_multi, opened on first use so that single-GPU callers do
-// not load it: the copy already in the process when torch brought one (same
-// soname, librccl.so.1), else ROCm's.
-struct Rccl {
-  decltype(&ncclCommInitAll) comm_init_all = nullptr;
-  decltype(&ncclCommDestroy) comm_destroy = nullptr;
-  decltype(&ncclGather) gather = nullptr;
-  decltype(&ncclGroupStart) group_start = nullptr;
-  decltype(&ncclGroupEnd) group_end = nullptr;
-  decltype(&ncclGetErrorString) error_string = nullptr;
-};
-const Rccl& rccl() {
-  static Rccl r;
-  static std::once_flag once;
-  std::call_once(once, [] {
-    void* h = dlopen("librccl.so.1", RTLD_NOW | RTLD_LOCAL);
-    if (!h) h = dlopen("/opt/rocm/lib/librccl.so.1", RTLD_NOW | RTLD_LOCAL);
-    if (!h) return;
-    r.comm_init_all = reinterpret_cast<decltype(r.comm_init_all)>(dlsym(h, "ncclCommInitAll"));
-    r.comm_destroy = reinterpret_cast<decltype(r.comm_destroy)>(dlsym(h, "ncclCommDestroy"));
-    r.gather = reinterpret_cast<decltype(r.gather)>(dlsym(h, "ncclGather"));
-    r.group_start = reinterpret_cast<decltype(r.group_start)>(dlsym(h, "ncclGroupStart"));
-    r.group_end = reinterpret_cast<decltype(r.group_end)>(dlsym(h, "ncclGroupEnd"));
-    r.error_string = reinterpret_cast<decltype(r.error_string)>(dlsym(h, "ncclGetErrorString"));
-  });
-  if (!r.comm_init_all || !r.comm_destroy || !r.gather || !r.group_start || !r.group_end || !r.error_string)
-    throw Error(ZRT_E_UNSUPPORTED, "RCCL (librccl.so.1 with ncclGather) is not available");
-  return r;
-}
-
-#define NCCLCHK(R, expr)                                                                     \
-  do {                                                                                       \
-    const ncclResult_t r_ = (expr);                                                          \
-    if (r_ != ncclSuccess) throw ::zrt::Error(ZRT_E_HIP, std::string("RCCL ") + #expr + ": " + (R).error_string(r_)); \
-  } while (0)
-
-// A context on `device` holding an uploaded copy of a flattened scene.
-std::unique_ptr<zrt_ctx> ctx_on_device(const HostScene& h, int device) {
-  std::unique_ptr<zrt_ctx> c(new zrt_ctx);
-  c->device = device;
-  HIPCHK(hipSetDevice(c->device));
-  // a blocking stream: work a caller enqueues on the legacy default stream (NULL,
-  // e.g. torch's default stream) after a render on this one waits for it
-  HIPCHK(hipStreamCreateWithFlags(&c->stream, hipStreamDefault));
-  HIPCHK(hipEventCreate(&c->ev_pre));
-  HIPCHK(hipEventCreate(&c->ev0));
-  HIPCHK(hipEventCreate(&c->ev1));
-  HIPCHK(hipEventCreateWithFlags(&c->ev_done, hipEventDisableTiming));
-  HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&c->err_host), sizeof(unsigned long long), hipHostMallocDefault));
-  *c->err_host = 0;
-  hipDeviceProp_t prop;
-  HIPCHK(hipGetDeviceProperties(&prop, c->device));
-  c->cu_count = prop.multiProcessorCount;
-  upload_scene(c.get(), h);
-  c->scratch.alloc(kScratchSlots);
-  return c;
-}
-
-// ncclCommInitAll communicators, one per device, destroyed with the call.
-struct Comms {
-  const Rccl* R = nullptr;
-  std::vector<ncclComm_t> c;
-  ~Comms() {
-    for (ncclComm_t x : c)
-      if (x) (void)R->comm_destroy(x);
-  }
-};
-
-struct CtxDeleter {
-  void operator()(zrt_ctx* c) const { zrt_ctx_destroy(c); }
-};
-
-}  // namespace
-}  // namespace zrt
-
-// One rank per entry of `devices`: its context (scene copy in that GPU's HBM),
-// its padded tile buffer, and - one rank per distinct device - the RCCL
-// communicators, all kept across frames.  Members are destroyed in reverse
-// order: the communicators go before the contexts.
-struct zrt_multi {
-  std::vector<uint32_t> devices;
-  uint32_t n_distinct = 0;
-  bool use_rccl = false;
-  std::vector<std::unique_ptr<zrt_ctx, zrt::CtxDeleter>> ctx;
-  std::vector<zrt::DevBuf<float>> send;
-  zrt::DevBuf<float> gathered, frame;  // on devices[0]
-  size_t frame_n = 0;                  // floats of the last frame in `frame` (0: none rendered yet)
-  std::vector<double> rank_ms;         // the last frame: each rank's render-kernel time (HIP events)
-  zrt::Comms comms;
-};
-
-namespace zrt {
+// One launch function per small kernel (kernels.hpp)
 namespace {
-int assemble(zrt_ctx* c, const zrt_params* p, const float* dev_gathered, uint32_t stride_tiles, float* dev_frame,
-             void* hip_stream) {
-  if (!c || !dev_gathered || !dev_frame) return fail(ZRT_E_INVALID, "null argument");
-  const int rc = validate_params(p);
-  if (rc) return rc;
-  try {
-    HIPCHK(hipSetDevice(c->device));
-    hipStream_t st = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
-    const Geometry g = geometry(p);
-    uint32_t total = 0;
-    if (stride_tiles) {
-      for (uint32_t r = 0; r < p->world_size; ++r)
-        if (rank_tiles(g, r, p->world_size) > stride_tiles)
-          return fail(ZRT_E_INVALID, "stride_tiles is smaller than a rank's tile count");
-      if (uint64_t(stride_tiles) * 64u * p->world_size >= (1ull << 32)) return fail(ZRT_E_UNSUPPORTED, "frame too large");
-      total = stride_tiles * 64u * p->world_size;
-    } else {
-      std::vector<uint32_t> base(p->world_size + 1, 0);
-      for (uint32_t r = 0; r < p->world_size; ++r) base[r + 1] = base[r] + rank_tiles(g, r, p->world_size) * 64u;
-      c->rank_base.upload(base);
-      total = base[p->world_size];
-    }
-    HIPCHK(hipMemsetAsync(dev_frame, 0, sizeof(float) * 3 * size_t(p->width) * p->height, st));
-    if (total) {
-      hipLaunchKernelGGL(assemble_kernel, dim3((total + 255) / 256), dim3(256), 0, st, dev_gathered, dev_frame,
-                         stride_tiles ? nullptr : c->rank_base.p, p->world_size, g.tiles_x, g.xbound, p->height,
-                         p->width, total, stride_tiles * 64u, g.n_tiles);
-      HIPCHK(hipGetLastError());
-    }
-    return ZRT_OK;
-  }
-  ZRT_CATCH_ALL
+template <class... P, class... A>
+hipError_t launch(void (*kernel)(P...), uint32_t grid, uint32_t block, hipStream_t st, A... args) {
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), 0, st, args...);
+  return hipGetLastError();
 }
 }  // namespace
-}  // namespace zrt
-
-using zrt::fail;
-
-extern "C" {
-
-int zrt_abi_version(void) { return ZRT_ABI_VERSION; }
-
-const char* zrt_build_info(void) {
-  return "libzrt: HIP path for gfx950 (MI355X); persistent wave64 path-tracing kernel; -ffp-contract=off";
+hipError_t launch_finalize(hipStream_t st, const float4* partial, float* out, uint32_t n_slots, uint32_t n_chunks,
+                           uint32_t world, uint32_t rank, uint32_t tiles_x, uint32_t xbound, uint32_t height,
+                           float color_scale, const unsigned long long* error_flag) {
+  return launch(finalize_kernel, (n_slots + 255) / 256, 256, st, partial, out, n_slots, n_chunks, world, rank,
+                    tiles_x, xbound, height, color_scale, error_flag);
+}
+hipError_t launch_accumulate(hipStream_t st, const float4* partial, float4* accum, float* out, uint32_t n_slots,
+                             uint32_t pass_chunks, uint32_t world, uint32_t rank, uint32_t tiles_x, uint32_t xbound,
+                             uint32_t height, float prev_scale, float new_scale, const unsigned long long* error_flag,
+                             unsigned long long* metrics) {
+  return launch(accumulate_kernel, (n_slots + 255) / 256, 256, st, partial, accum, out, n_slots, pass_chunks, world,
+                    rank, tiles_x, xbound, height, prev_scale, new_scale, error_flag, metrics);
+}
+hipError_t launch_resolve(hipStream_t st, const float4* partial, float4* accum, float* out, const uint32_t* active,
+                          uint32_t n_active, uint32_t my_tiles, uint32_t pass_chunks, uint32_t world, uint32_t rank,
+                          uint32_t tiles_x, uint32_t xbound, uint32_t height, float prev_scale, float new_scale,
+                          float tolerance, uint32_t decide, uint32_t level_samples, uint32_t* tile_done,
+                          const unsigned long long* error_flag, unsigned long long* metrics) {
+  return launch(resolve_kernel, (n_active + 3) / 4, 256, st, partial, accum, out, active, n_active, my_tiles,
+                    pass_chunks, world, rank, tiles_x, xbound, height, prev_scale, new_scale, tolerance, decide,
+                    level_samples, tile_done, error_flag, metrics);
+}
+hipError_t launch_compact(hipStream_t st, const uint32_t* in, uint32_t n, const uint32_t* tile_done, uint32_t* out,
+                          uint32_t* count) {
+  return launch(compact_kernel, 1, kCompactBlock, st, in, n, tile_done, out, count);
+}
+hipError_t launch_assemble(hipStream_t st, const float* gathered, float* frame, const uint32_t* rank_base,
+                           uint32_t world, uint32_t tiles_x, uint32_t xbound, uint32_t height, uint32_t width,
+                           uint32_t total, uint32_t stride_px, uint32_t n_tiles) {
+  return launch(assemble_kernel, (total + 255) / 256, 256, st, gathered, frame, rank_base, world, tiles_x, xbound,
+                    height, width, total, stride_px, n_tiles);
+}
+hipError_t launch_features_error(hipStream_t st, float4* out, uint64_t n_f4, const unsigned long long* error_flag) {
+  const uint32_t grid = uint32_t(n_f4 + 255 < 4096ull * 256 ? (n_f4 + 255) / 256 : 4096);
+  return launch(features_error_kernel, grid, 256, st, out, n_f4, error_flag);
+}
+hipError_t launch_debug_math(int fn, const float* x, const float* y, float* out, uint32_t n) {
+  return launch(debug_math_kernel, (n + 255) / 256, 256, 0, fn, x, y, out, n);
+}
+hipError_t launch_debug_division(uint64_t n, unsigned long long* counts) {
+  return launch(debug_division_kernel, 8192, 256, 0, n, counts);
+}
+hipError_t launch_debug_rng(uint32_t prng, uint64_t key, unsigned long long* out, uint32_t n) {
+  if (prng == ZRT_PRNG_XOSHIRO256) return launch(debug_rng_kernel<ZRT_PRNG_XOSHIRO256>, 1, 64, 0, key, out, n);
+  return launch(debug_rng_kernel<ZRT_PRNG_XOROSHIRO128>, 1, 64, 0, key, out, n);
 }
 
-int zrt_ctx_create(const zrt_scene* scene, const zrt_params* params, zrt_ctx** out) {
-  if (!out) return fail(ZRT_E_INVALID, "out is null");
-  *out = nullptr;
-  int rc = zrt::validate_scene(scene);
-  if (rc) return rc;
-  if (!params) return fail(ZRT_E_INVALID, "params is null");
-  try {
-    // raytrace.zig:124-133: BVH iff requested and more than 10 surfaces.  The
-    // scene is flattened before the device is checked, so a tree whose layout
-    // the kernels do not decode is refused on any machine (flatten_scene); the
-    // GPU builds the reference BVH only when one is visible
-    const bool use_bvh = params->bounded_volume_hierarchy != 0 && scene->n_prims > 10;
-    int n_dev = 0;
-    const bool gpus = hipGetDeviceCount(&n_dev) == hipSuccess && n_dev > 0;
-    // with GPUs present, an unusable device is refused before the (seconds-long on a
-    // million-triangle mesh) scene build; without any, the layout check still runs first
-    if (gpus) {
-      rc = zrt::check_device(int(params->device));
-      if (rc) return rc;
-    }
-    const bool have_dev = gpus && int(params->device) < n_dev;
-    zrt::HostScene h;
-    zrt::flatten_scene(&h, scene, use_bvh, have_dev ? int(params->device) : -1);
-    rc = zrt::check_device(int(params->device));
-    if (rc) return rc;
-    *out = zrt::ctx_on_device(h, int(params->device)).release();
-    return ZRT_OK;
-  } catch (const zrt::HipError& e) {
-    return zrt::hip_fail(e);
-  } catch (const zrt::Error& e) {
-    return fail(e.code, e.what());
-  } catch (const std::bad_alloc&) {
-    return fail(ZRT_E_NOMEM, "OutOfMemory");
-  }
-}
-
-int zrt_ctx_destroy(zrt_ctx* ctx) {
-  if (!ctx) return ZRT_OK;
-  (void)hipSetDevice(ctx->device);
-  if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
-  delete ctx;
-  return ZRT_OK;
-}
-
-int zrt_ctx_tile_count(const zrt_ctx* ctx, const zrt_params* params, uint32_t* n_tiles) {
-  (void)ctx;  // the partition depends on the params only; ctx may be NULL
-  if (!n_tiles) return fail(ZRT_E_INVALID, "null argument");
-  const int rc = zrt::validate_params(params);
-  if (rc) return rc;
-  *n_tiles = zrt::rank_tiles(zrt::geometry(params), params->rank, params->world_size);
-  return ZRT_OK;
-}
-
-// Valid params (zrt::validate_params) are also the context's: its device, its BVH decision.
-static int params_fit_ctx(const zrt_ctx* c, const zrt_params* p) {
-  if (int(p->device) != c->device)
-    return fail(ZRT_E_INVALID, "params->device differs from the device the context was created on");
-  if ((p->bounded_volume_hierarchy != 0 && c->n_prims > 10) != c->use_bvh)
-    return fail(ZRT_E_INVALID,
-                "params->bounded_volume_hierarchy implies another preprocessSufraces decision (raytrace.zig:124-133) "
-                "than the one the context was built with");
-  return ZRT_OK;
-}
-
-// The launch behind zrt_ctx_render_tiles (run_pass false: the whole frame, resolved by
-// finalize_kernel) and zrt_ctx_accum_pass (run_pass true: samples [c->run_done,
-// c->run_done + n_samples) of the context's run, p = its params, resolved by
-// accumulate_kernel): one launch path and one kernel choice for both.
-static int launch_frame(zrt_ctx* c, const zrt_camera* cam, const zrt_params* p, float* dev_tiles, void* hip_stream,
-                        bool run_pass, uint32_t n_samples) {
-  if (!c || !cam || !dev_tiles) return fail(ZRT_E_INVALID, "null argument");
-  zrt_pass_plan pass{};
-  int rc = zrt::plan_pass(p, run_pass ? c->run_done : 0u, run_pass ? n_samples : (p ? p->samples_per_pixel : 0u), &pass);
-  if (rc) return rc;
-  const bool first = !run_pass || c->run_passes == 0;  // the launch zeroes the counters it adds into
-  const bool adapt = run_pass && c->adapt;  // a level of an adaptive run: the active tiles only
-  rc = params_fit_ctx(c, p);
-  if (rc) return rc;
-  try {
-    HIPCHK(hipSetDevice(c->device));
-    // a device error of the previous launch that finished meanwhile is reported
-    // here (sticky), so a caller that never synchronises through the ABI still sees it
-    rc = zrt::launch_status(c, false);
-    if (rc) return rc;
-    hipStream_t st = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
-    const zrt::Geometry g = zrt::geometry(p);
-    const uint32_t my_tiles = zrt::rank_tiles(g, p->rank, p->world_size);
-    // the launch decision (zrt::plan_launch; zrt_debug_launch_plan reports the same)
-    const zrt::LaunchPlan plan = zrt::plan_launch(zrt::shape_of(c), p);
-    const int mode = plan.mode, kmode = plan.kmode;
-    const bool diag = (p->flags & ZRT_FLAG_STATS) != 0;
-    const bool stk16 = plan.stk16, pool = plan.pool, qn = plan.qn, guard_on = plan.guard_on;
-    const uint32_t stack_depth = plan.stack_depth, node_f4 = plan.node_f4;
-    const zrt::LdsPlan& lp = plan.lp;
-    // the camera inside the origin bound: so is every ray of the launch (scattered rays start at hits)
-    const bool cam_inside = zrt::camera_inside(cam, c->root_c, c->origin_bound);
-    void* kfn = zrt::select_kernel(kmode, p->prng, diag, stk16, zrt::lean_launch(plan, diag, cam_inside));
-    const uint32_t lds_rows = lp.stack_rows;
-    const size_t lds = lp.bytes;
-    int per_cu = 0;
-    HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kfn, zrt::kBlock, lds));
-    per_cu = std::max(1, std::min(per_cu, 8));
-    uint32_t grid = uint32_t(c->cu_count) * uint32_t(per_cu);
-    const uint32_t chunk = pass.chunk;
-    const uint32_t n_chunks = pass.pass_chunks;
-    const uint32_t n_act = adapt ? c->adapt_active : my_tiles;  // tiles the launch hands out
-    const uint64_t work64 = uint64_t(n_act) * n_chunks;  // units: (tile, chunk); < 2^32 (plan_pass)
-    const uint32_t work = uint32_t(work64);
-    // one wave per unit at the start; more waves than units would only idle
-    grid = std::max(1u, std::min(grid, (work + (zrt::kBlock / 64) - 1) / (zrt::kBlock / 64)));
-    const uint64_t n_partial = uint64_t(my_tiles) * 64u * n_chunks;
-    if (c->partial.n < n_partial) c->partial.alloc(n_partial);
-    const uint64_t n_lanes = uint64_t(grid) * zrt::kBlock;
-    // global attenuation rows: [row][lane], or [path][row] for the path-pool loop
-    const uint64_t n_paths = pool ? uint64_t(grid) * zrt::kBlockPaths : n_lanes;
-    if (n_paths >= (1ull << 32)) return fail(ZRT_E_UNSUPPORTED, "too many paths");
-    const zrt::BufNeed need = zrt::buffer_need(lp, p->max_depth, stack_depth, n_paths, n_lanes, stk16);
-    if (need.att_elems * sizeof(uint32_t) > (16ull << 30))
-      return fail(ZRT_E_UNSUPPORTED, "max_depth too large for the per-lane attenuation stack");
-    if (c->att.n < need.att_elems) c->att.alloc(need.att_elems);
-    if (first)
-      HIPCHK(hipMemsetAsync(c->scratch.p, 0, zrt::kScratchSlots * sizeof(unsigned long long), st));
-    else  // a run's later passes add into its counters and keep its error flag: a new work counter only
-      HIPCHK(hipMemsetAsync(c->scratch.p + zrt::kWorkSlot, 0, sizeof(unsigned long long), st));
-    if (run_pass) {
-      // the previous pass's events wait to be added into the run's times (no host wait here)
-      if (!first) {
-        zrt::fold_pass_times(c, false);  // (frees the sets of passes that have finished)
-        if (c->ev_spare.empty()) {
-          zrt_ctx::EvSet e;
-          HIPCHK(hipEventCreate(&e.pre));
-          HIPCHK(hipEventCreate(&e.e0));
-          HIPCHK(hipEventCreate(&e.e1));
-          c->ev_spare.push_back(e);
-        }
-        const zrt_ctx::EvSet e = c->ev_spare.back();
-        c->ev_spare.pop_back();
-        c->run_pending.push_back({c->ev_pre, c->ev0, c->ev1, c->pass_probed});
-        c->ev_pre = e.pre;
-        c->ev0 = e.e0;
-        c->ev1 = e.e1;
-      }
-      if (first) HIPCHK(hipMemsetAsync(c->accum.p, 0, c->accum.n * sizeof(float4), st));
-      if (first && adapt) HIPCHK(hipMemsetAsync(c->tile_done.p, 0, c->tile_done.n * sizeof(uint32_t), st));
-    }
-
-    zrt::KArgs a{};
-    a.nodes = c->nodes.p;
-    a.prims = c->prims.p;
-    a.shade = c->shade.p;
-    a.mats = c->mats.p;
-    a.texels = c->texels.p;
-    a.texels8 = c->texels8.p;
-    a.att = c->att.p;
-    a.partial = c->partial.p;
-    a.counters = c->scratch.p;
-    a.work_counter = reinterpret_cast<uint32_t*>(c->scratch.p + zrt::kWorkSlot);
-    a.error_flag = reinterpret_cast<uint32_t*>(c->scratch.p + zrt::kErrorSlot);
-    const zrt_vec3* v[4] = {&cam->origin, &cam->lower_left_corner, &cam->horizontal, &cam->vertical};
-    float* dst[4] = {a.org, a.llc, a.hor, a.ver};
-    for (int k = 0; k < 4; ++k) {
-      dst[k][0] = v[k]->x;
-      dst[k][1] = v[k]->y;
-      dst[k][2] = v[k]->z;
-    }
-    a.f_width = float(p->width);
-    a.f_height = float(p->height);
-    a.inv_width = 1.0f / a.f_width;  // IEEE RN(1/width): dev::div_core's y
-    a.inv_height = 1.0f / a.f_height;
-    a.color_scale = 1.0f / float(pass.samples_after);  // raytrace.zig:157
-    a.width = p->width;
-    a.height = p->height;
-    a.xbound = g.xbound;
-    a.spp = pass.pass_samples;
-    a.max_depth = p->max_depth;
-    a.tiles_x = g.tiles_x;
-    a.rank = p->rank;
-    a.world = p->world_size;
-    a.total_work = work;
-    a.n_list = c->use_bvh ? 0 : c->n_prims;
-    a.tri_rcp_fast = c->tri_rcp_fast;
-    a.scene_extent = c->scene_extent;
-    a.paxis_m = zrt::paxis_threshold();
-    for (int k = 0; k < 3; ++k) {
-      a.tri_c[k] = c->tri_c[k];
-      a.tri_h[k] = c->tri_h[k];
-    }
-    a.stack_depth = stack_depth;
-    a.ref_stack = std::min(c->stack_depth, stack_depth);
-    a.leaf_of_slot = c->leaf_of_slot.p;
-    a.ref_sph = c->ref_sph.p;
-    for (int k = 0; k < 3; ++k) a.root_c[k] = c->root_c[k];
-    a.origin_bound = c->origin_bound;
-    a.layout = c->layout;
-    a.graze_m = c->graze_m;
-    a.graze_leaf = c->graze_leaf;
-    a.guard = guard_on ? c->guard : 0.0f;
-    a.check_origins = cam_inside ? 0u : 1u;
-    a.wnodes = qn ? c->qnodes.p : c->wnodes.p;
-    a.wide_stride = qn ? c->q_stride : c->wide_stride;
-    a.node_f4 = node_f4;
-    a.qleaves = qn ? c->qleaves.p : nullptr;
-    a.n_qnodes = qn ? c->q_stride / zrt::kQuantNodeF4 : 0u;
-    a.n_qleaves = qn ? c->n_qleaves : 0u;
-    a.lds_rows = lds_rows;
-    if (need.ovf_bytes) {
-      if (c->stack_ovf.n < need.ovf_bytes) c->stack_ovf.alloc(need.ovf_bytes);
-      a.stack_ovf = c->stack_ovf.p;
-    }
-    a.n_lanes = uint32_t(n_lanes);
-    a.n_top = qn ? c->q_top : c->n_top;
-    a.lds_top_off = lp.top_off;
-    a.lds_att_off = lp.att_off;
-    a.att_lds_rows = lp.att_rows;
-    a.lds_mat_off = lp.mat_off;
-    a.lds_pool_off = lp.pool_off;
-    a.lds_state_off = lp.state_off;
-    a.n_paths = uint32_t(n_paths);
-    // (a loop that reads the table from LDS only and has none there - the lockstep loop
-    // at max_depth 0, which shades nothing - copies none: its plan holds no region for it)
-    a.n_mats = ZRT_MATS_LDS_ONLY && kmode == 3 && !lp.mats_in_lds ? 0u : c->n_mats;
-    a.mats_in_lds = lp.mats_in_lds;
-    a.seed_mix = p->seed * 0x9E3779B97F4A7C15ULL + pass.key_offset;
-    if (std::getenv("ZRT_DEBUG_LAUNCH"))
-      std::fprintf(stderr, "zrt launch: mode %d stk16 %d grid %u (%d blocks/CU x %d CUs) lds %zu B "
-                   "(stack rows %u, top nodes %u @%u, att rows %u @%u, mats %u @%u)\n", mode, int(stk16), grid,
-                   per_cu, c->cu_count, lds, lp.stack_rows, a.n_top, lp.top_off, lp.att_rows, lp.att_off,
-                   lp.mats_in_lds ? c->n_mats : 0u, lp.mat_off);
-    a.chunk = chunk;
-    a.n_chunks = n_chunks;
-    a.wf_thresh = 48;  // shade once 3/4 of the unit's active lanes are ready (C5: 32 -> 7.32, 48 -> 7.71, 56 -> 7.70 Gray/s)
-    if (const char* e = std::getenv("ZRT_WF_THRESH")) a.wf_thresh = std::max(1, std::min(64, std::atoi(e)));
-    // the lockstep interval: the BVH loops keep a wave's lanes on one sample (its
-    // camera rays coherent); the list loop gains nothing from that (every ray reads
-    // the same surfaces) and lets its lanes run through the unit's chunk
-    // (C2: 34.1 -> 45.4 Gray/s, profiles/r04/s1)
-    a.sync = mode == 0 ? chunk : ZRT_SYNC_SAMPLES;
-    if (const char* e = std::getenv("ZRT_SYNC"))  // A/B: lockstep interval in samples (identical images)
-      a.sync = std::max(1u, uint32_t(std::atoi(e)));
-    a.n_slots = my_tiles * 64u;
-
-    HIPCHK(hipEventRecord(c->ev_pre, st));
-    bool schedule =
-        mode == 3 && !(p->flags & ZRT_FLAG_NO_SCHEDULE) && p->samples_per_pixel >= 128 && my_tiles >= 2;
-    // (a run decides once, by its cap: its first pass probes, the later ones reuse the
-    // order and the probe's counters)
-    if (schedule && !first) {
-      schedule = c->run_ordered;
-      if (schedule) a.tile_order = c->tile_order.p;
-    } else if (schedule) {
-      schedule = zrt::schedule_tiles(c, a, p->prng, stk16, my_tiles, grid, lds, st);
-    }
-    if (run_pass && first) c->run_ordered = schedule;
-    if (adapt) {
-      // the launch hands out the active list: level 0's is the probe's order where the run
-      // is scheduled (else the identity zrt_ctx_adapt_begin uploaded), a later level's is
-      // what the previous level's compaction wrote
-      uint32_t* list = c->active[c->adapt_cur].p;
-      if (first && schedule)
-        HIPCHK(hipMemcpyAsync(list, c->tile_order.p, size_t(my_tiles) * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
-      a.tile_order = list;
-    }
-    c->pass_probed = schedule && first;
-    c->scheduled = schedule;
-    // the lockstep loop takes its interval from the probe's lane efficiency (auto_sync;
-    // ZRT_SYNC or ZRT_AUTO_SYNC=0: the fixed interval, A/B)
-    {
-      const char* as = std::getenv("ZRT_AUTO_SYNC");
-      const bool auto_on = !std::getenv("ZRT_SYNC") && !(as && std::atoi(as) == 0);
-      a.sync_probe = schedule && kmode == 3 && auto_on ? c->probe_scratch.p : nullptr;
-    }
-    c->scanline_rows = 0;
-    if (p->flags & ZRT_FLAG_SCANLINES) {  // (not the probe's: set after it)
-      if (c->scanlines.n < size_t(p->height) * 3) c->scanlines.alloc(size_t(p->height) * 3);
-      if (first) HIPCHK(hipMemsetAsync(c->scanlines.p, 0, size_t(p->height) * 3 * sizeof(unsigned long long), st));
-      a.scanlines = c->scanlines.p;
-      c->scanline_rows = p->height;
-    }
-    if (ZRT_PROFILE) {
-      c->n_waves = grid * (zrt::kBlock / 64);
-      if (c->wave_times.n < 2ull * c->n_waves) c->wave_times.alloc(2ull * c->n_waves);
-      a.wave_times = c->wave_times.p;
-    }
-    // every global row the render launch may touch lies inside its buffer (the probe
-    // may have grown them): checked on the host, and handed to the STATS flavour's
-    // device check
-    zrt::check_buffers("render launch", need, c->att.n, c->stack_ovf.n);
-    a.att = c->att.p;
-    if (need.ovf_bytes) a.stack_ovf = c->stack_ovf.p;
-    a.att_cap = c->att.n;
-    a.ovf_cap = zrt::ovf_cap_elems(c->stack_ovf.n, stk16);
-    if (diag)
-      if (const char* e = std::getenv("ZRT_DEBUG_ROW_CAP")) {  // tests: the device check reports a smaller buffer
-        const double f = std::atof(e);
-        a.att_cap = uint64_t(double(a.att_cap) * f);
-        a.ovf_cap = uint64_t(double(a.ovf_cap) * f);
-      }
-    HIPCHK(hipEventRecord(c->ev0, st));
-    if (work > 0) {
-      void* args[] = {&a};
-      HIPCHK(hipLaunchKernel(kfn, dim3(grid), dim3(zrt::kBlock), args, lds, st));
-    }
-    HIPCHK(hipEventRecord(c->ev1, st));
-    if (run_pass) {
-      HIPCHK(hipMemsetAsync(c->metrics.p, 0, zrt::kMetricWords * sizeof(unsigned long long), st));
-      if (adapt) {
-        // resolve the active tiles, decide (levels 1 .. last - 1), pack the survivors in
-        // order into the other list; the host reads their number (zrt_ctx_adapt_level)
-        const uint32_t decide = c->adapt_k >= 1 && c->adapt_k + 1 < c->adapt_levels.size() ? 1u : 0u;
-        const float prev_scale = c->run_done ? 1.0f / float(c->run_done) : 0.0f;
-        HIPCHK(hipMemsetAsync(c->active_count.p, 0, sizeof(uint32_t), st));
-        if (n_act > 0) {
-          hipLaunchKernelGGL(zrt::resolve_kernel, dim3((n_act + 3) / 4), dim3(256), 0, st, c->partial.p, c->accum.p,
-                             dev_tiles, c->active[c->adapt_cur].p, n_act, my_tiles, n_chunks, p->world_size, p->rank,
-                             g.tiles_x, g.xbound, p->height, prev_scale, a.color_scale, c->adapt_a.tolerance, decide,
-                             pass.samples_after, c->tile_done.p, c->scratch.p + zrt::kErrorSlot, c->metrics.p);
-          HIPCHK(hipGetLastError());
-          hipLaunchKernelGGL(zrt::compact_kernel, dim3(1), dim3(zrt::kCompactBlock), 0, st,
-                             c->active[c->adapt_cur].p, n_act, c->tile_done.p, c->active[c->adapt_cur ^ 1u].p,
-                             c->active_count.p);
-          HIPCHK(hipGetLastError());
-        }
-        HIPCHK(hipMemcpyAsync(c->count_host, c->active_count.p, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-      } else if (my_tiles > 0) {
-        const uint32_t n_slots = my_tiles * 64u;
-        const float prev_scale = c->run_done ? 1.0f / float(c->run_done) : 0.0f;
-        hipLaunchKernelGGL(zrt::accumulate_kernel, dim3((n_slots + 255) / 256), dim3(256), 0, st, c->partial.p,
-                           c->accum.p, dev_tiles, n_slots, n_chunks, p->world_size, p->rank, g.tiles_x, g.xbound,
-                           p->height, prev_scale, a.color_scale, c->scratch.p + zrt::kErrorSlot, c->metrics.p);
-        HIPCHK(hipGetLastError());
-      }
-      HIPCHK(hipMemcpyAsync(c->metrics_host, c->metrics.p, zrt::kMetricWords * sizeof(unsigned long long),
-                            hipMemcpyDeviceToHost, st));
-    } else if (my_tiles > 0) {
-      const uint32_t n_slots = my_tiles * 64u;
-      hipLaunchKernelGGL(zrt::finalize_kernel, dim3((n_slots + 255) / 256), dim3(256), 0, st, c->partial.p,
-                         dev_tiles, n_slots, n_chunks, p->world_size, p->rank, g.tiles_x, g.xbound, p->height,
-                         a.color_scale, c->scratch.p + zrt::kErrorSlot);
-      HIPCHK(hipGetLastError());
-    }
-    HIPCHK(hipMemcpyAsync(c->err_host, c->scratch.p + zrt::kErrorSlot, sizeof(unsigned long long),
-                          hipMemcpyDeviceToHost, st));
-    HIPCHK(hipEventRecord(c->ev_done, st));
-    c->err_reported = false;
-    // count the pixels this rank renders (for samples/pixels counters)
-    uint64_t pixels = 0;
-    for (uint32_t lt = 0; lt < my_tiles; ++lt) {
-      const uint32_t t = lt * p->world_size + p->rank;
-      const uint32_t tx = t % g.tiles_x, ty = t / g.tiles_x;
-      const uint32_t w = std::min(8u, g.xbound - tx * 8u), h = std::min(8u, p->height - ty * 8u);
-      pixels += uint64_t(w) * h;
-    }
-    c->last_pixels = uint32_t(pixels);
-    c->last_spp = pass.samples_after;
-    c->last_tiles = my_tiles;
-    c->last_rank = p->rank;
-    c->last_world = p->world_size;
-    c->last_tiles_x = g.tiles_x;
-    c->last_xbound = g.xbound;
-    c->last_stats = diag;
-    c->last_mode = mode;
-    c->last_loop = int(zrt::reported_loop(kmode));
-    c->last_qn = qn;
-    c->last_guard = a.guard;
-    c->launched = 1;
-    c->run_stats = run_pass;
-    c->last_adapt = adapt;
-    if (run_pass) {
-      c->run_done = pass.samples_after;
-      c->run_passes += 1;
-      c->pass_samples = pass.pass_samples;
-    } else {
-      c->run_live = false;  // a plain render overwrites the probe's buffers: it ends the run
-    }
-    return ZRT_OK;
-  }
-  ZRT_CATCH_ALL
-}
-
-int zrt_ctx_render_tiles(zrt_ctx* c, const zrt_camera* cam, const zrt_params* p, float* dev_tiles,
-                         void* hip_stream) {
-  return launch_frame(c, cam, p, dev_tiles, hip_stream, false, 0);
-}
-
-int zrt_ctx_accum_begin(zrt_ctx* c, const zrt_camera* cam, const zrt_params* p) {
-  if (!c || !cam) return fail(ZRT_E_INVALID, "null argument");
-  int rc = zrt::validate_params(p);
-  if (rc) return rc;
-  rc = params_fit_ctx(c, p);
-  if (rc) return rc;
-  try {
-    HIPCHK(hipSetDevice(c->device));
-    c->run_live = false;
-    const uint64_t n_slots = uint64_t(zrt::rank_tiles(zrt::geometry(p), p->rank, p->world_size)) * 64u;
-    if (c->accum.n < n_slots) c->accum.alloc(n_slots);
-    if (c->metrics.n < zrt::kMetricWords) c->metrics.alloc(zrt::kMetricWords);
-    if (!c->metrics_host) {
-      HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&c->metrics_host),
-                           zrt::kMetricWords * sizeof(unsigned long long), hipHostMallocDefault));
-      std::memset(c->metrics_host, 0, zrt::kMetricWords * sizeof(unsigned long long));
-    }
-    // (a restarted run's unread pass times are dropped; the accumulator, the counters
-    // and the error flag are zeroed by the first pass, on its stream)
-    for (const zrt_ctx::EvSet& e : c->run_pending) c->ev_spare.push_back(e);
-    c->run_pending.clear();
-    c->run_render_ms = c->run_sched_ms = 0.0;
-    c->run_cam = *cam;
-    c->run_p = *p;
-    c->run_done = 0;
-    c->run_passes = 0;
-    c->run_ordered = false;
-    c->adapt = false;
-    c->run_live = true;
-    return ZRT_OK;
-  }
-  ZRT_CATCH_ALL
-}
-
-int zrt_ctx_accum_pass(zrt_ctx* c, uint32_t n_samples, float* dev_tiles, void* hip_stream) {
-  if (!c || !dev_tiles) return fail(ZRT_E_INVALID, "null argument");
-  if (!c->run_live || c->adapt)
-    return fail(ZRT_E_INVALID, "no accumulation run is live on this context (zrt_ctx_accum_begin; a "
-                               "zrt_ctx_render_tiles ends the run)");
-  // a device error of an earlier pass is sticky for the run: its accumulator is poisoned
-  if (c->run_passes > 0 && hipEventQuery(c->ev_done) == hipSuccess && *c->err_host != 0) {
-    c->err_reported = true;
-    return fail(ZRT_E_UNSUPPORTED, zrt::device_error_msg(*c->err_host));
-  }
-  (void)hipGetLastError();
-  return launch_frame(c, &c->run_cam, &c->run_p, dev_tiles, hip_stream, true, n_samples);
-}
-
-int zrt_ctx_accum_info(zrt_ctx* c, zrt_pass_info* out) {
-  if (!c || !out) return fail(ZRT_E_INVALID, "null argument");
-  if (!c->launched || !c->run_stats) return fail(ZRT_E_INVALID, "the context's last launch was not a zrt_ctx_accum_pass");
-  try {
-    HIPCHK(hipSetDevice(c->device));
-    HIPCHK(hipEventSynchronize(c->ev_done));
-    std::memset(out, 0, sizeof(*out));
-    out->samples_done = c->run_done;
-    out->pass_samples = c->pass_samples;
-    uint32_t bits = 0;  // the shards' sum and maximum
-    for (uint32_t k = 0; k < zrt::kMetricShards; ++k) {
-      out->changed_pixels += c->metrics_host[k * zrt::kMetricStride];
-      bits = std::max(bits, uint32_t(c->metrics_host[k * zrt::kMetricStride + 1]));
-    }
-    std::memcpy(&out->max_abs_change, &bits, 4);
-    float ms = 0.0f, sched = 0.0f;
-    HIPCHK(hipEventElapsedTime(&ms, c->ev_pre, c->ev1));
-    HIPCHK(hipEventElapsedTime(&sched, c->ev_pre, c->ev0));
-    out->render_ms = ms;
-    out->schedule_ms = c->pass_probed ? sched : 0.0f;
-    return zrt::launch_status(c, true);
-  }
-  ZRT_CATCH_ALL
-}
-
-int zrt_debug_pass_plan(const zrt_params* params, uint32_t done, uint32_t n_samples, zrt_pass_plan* out) {
-  if (!out) return fail(ZRT_E_INVALID, "null argument");
-  return zrt::plan_pass(params, done, n_samples, out);
-}
-
-int zrt_debug_adapt_plan(const zrt_params* params, const zrt_adaptive* adaptive, uint32_t* levels, uint32_t cap,
-                         uint32_t* n_levels) {
-  if (!n_levels || (cap && !levels)) return fail(ZRT_E_INVALID, "null argument");
-  std::vector<uint32_t> L;
-  const int rc = zrt::plan_adapt(params, adaptive, &L);
-  if (rc) return rc;
-  *n_levels = uint32_t(L.size());
-  for (uint32_t k = 0; k < cap && k < L.size(); ++k) levels[k] = L[k];
-  return ZRT_OK;
-}
-
-int zrt_ctx_adapt_begin(zrt_ctx* c, const zrt_camera* cam, const zrt_params* p, const zrt_adaptive* ad) {
-  if (!c || !cam || !ad) return fail(ZRT_E_INVALID, "null argument");
-  std::vector<uint32_t> levels;
-  int rc = zrt::plan_adapt(p, ad, &levels);
-  if (rc) return rc;
-  rc = zrt_ctx_accum_begin(c, cam, p);  // the accumulator, the metrics, the run's state
-  if (rc) return rc;
-  try {
-    c->run_live = false;
-    const uint32_t my_tiles = zrt::rank_tiles(zrt::geometry(p), p->rank, p->world_size);
-    // (no level of an earlier run is in flight: zrt_ctx_adapt_level waits for its own)
-    std::vector<uint32_t> ids(my_tiles);
-    for (uint32_t i = 0; i < my_tiles; ++i) ids[i] = i;
-    if (c->active[0].n < my_tiles || c->active[1].n < my_tiles || c->tile_done.n < my_tiles) {
-      c->active[0].alloc(my_tiles);
-      c->active[1].alloc(my_tiles);
-      c->tile_done.alloc(my_tiles);
-    }
-    if (my_tiles)
-      HIPCHK(hipMemcpy(c->active[0].p, ids.data(), size_t(my_tiles) * sizeof(uint32_t), hipMemcpyHostToDevice));
-    if (c->active_count.n < 1) c->active_count.alloc(1);
-    if (!c->count_host)
-      HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&c->count_host), sizeof(uint32_t), hipHostMallocDefault));
-    *c->count_host = 0;
-    c->adapt_a = *ad;
-    c->adapt_levels = levels;
-    c->adapt_k = 0;
-    c->adapt_cur = 0;
-    c->adapt_active = my_tiles;
-    c->adapt_samples = 0;
-    c->adapt_tiles = nullptr;
-    c->adapt = true;
-    c->run_live = true;
-    return ZRT_OK;
-  }
-  ZRT_CATCH_ALL
-}
-
-int zrt_ctx_adapt_level(zrt_ctx* c, float* dev_tiles, void* hip_stream, zrt_level_info* out) {
-  if (!c || !dev_tiles) return fail(ZRT_E_INVALID, "null argument");
-  if (!c->run_live || !c->adapt)
-    return fail(ZRT_E_INVALID, "no adaptive run is live on this context (zrt_ctx_adapt_begin; a "
-                               "zrt_ctx_render_tiles ends the run)");
-  // a device error of an earlier level is sticky for the run (every level is waited for)
-  if (c->run_passes > 0 && *c->err_host != 0) {
-    c->err_reported = true;
-    return fail(ZRT_E_UNSUPPORTED, zrt::device_error_msg(*c->err_host));
-  }
-  if (c->adapt_k >= c->adapt_levels.size()) return fail(ZRT_E_INVALID, "the adaptive run has rendered its last level");
-  if (c->adapt_active == 0 && c->run_passes > 0) return fail(ZRT_E_INVALID, "no tile of the adaptive run is active");
-  if (c->adapt_tiles && c->adapt_tiles != dev_tiles)
-    return fail(ZRT_E_INVALID, "dev_tiles differs from the run's earlier levels' (frozen tiles live there)");
-  const uint32_t level = c->adapt_levels[c->adapt_k], rendered = c->adapt_active;
-  const uint32_t level_samples = level - c->run_done;
-  const int rc = launch_frame(c, &c->run_cam, &c->run_p, dev_tiles, hip_stream, true, level_samples);
-  if (rc) return rc;
-  try {
-    HIPCHK(hipEventSynchronize(c->ev_done));  // the one wait of the level: the surviving count is here
-    c->adapt_tiles = dev_tiles;
-    c->adapt_k += 1;
-    c->adapt_cur ^= 1u;
-    c->adapt_active = c->adapt_k < c->adapt_levels.size() ? *c->count_host : 0u;
-    uint64_t pixels = 0, changed = 0;
-    uint32_t bits = 0;
-    for (uint32_t k = 0; k < zrt::kMetricShards; ++k) {
-      changed += c->metrics_host[k * zrt::kMetricStride];
-      bits = std::max(bits, uint32_t(c->metrics_host[k * zrt::kMetricStride + 1]));
-      pixels += c->metrics_host[k * zrt::kMetricStride + 2];
-    }
-    if (*c->err_host == 0) c->adapt_samples += pixels * level_samples;
-    if (out) {
-      std::memset(out, 0, sizeof(*out));
-      out->level_samples = level;
-      out->tiles_rendered = rendered;
-      out->tiles_active_after = c->adapt_active;
-      out->samples_rendered = pixels * level_samples;
-      out->changed_pixels = changed;
-      std::memcpy(&out->max_abs_change, &bits, 4);
-      float ms = 0.0f, sched = 0.0f;
-      HIPCHK(hipEventElapsedTime(&ms, c->ev_pre, c->ev1));
-      HIPCHK(hipEventElapsedTime(&sched, c->ev_pre, c->ev0));
-      out->render_ms = ms;
-      out->schedule_ms = c->pass_probed ? sched : 0.0f;
-    }
-    return zrt::launch_status(c, true);
-  }
-  ZRT_CATCH_ALL
-}
-
-int zrt_ctx_adapt_samples(zrt_ctx* c, uint32_t* per_tile, uint32_t cap_tiles) {
-  if (!c || !per_tile) return fail(ZRT_E_INVALID, "null argument");
-  if (!c->run_live || !c->adapt) return fail(ZRT_E_INVALID, "no adaptive run is live on this context");
-  const uint32_t my_tiles = zrt::rank_tiles(zrt::geometry(&c->run_p), c->run_p.rank, c->run_p.world_size);
-  if (cap_tiles < my_tiles) return fail(ZRT_E_INVALID, "per_tile holds fewer entries than the rank has tiles");
-  try {
-    HIPCHK(hipSetDevice(c->device));
-    if (c->run_passes == 0) {
-      std::fill(per_tile, per_tile + my_tiles, 0u);
-      return ZRT_OK;
-    }
-    HIPCHK(hipEventSynchronize(c->ev_done));
-    if (my_tiles)
-      HIPCHK(hipMemcpy(per_tile, c->tile_done.p, size_t(my_tiles) * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    for (uint32_t i = 0; i < my_tiles; ++i) per_tile[i] &= ~zrt::kTileFrozen;
-    return ZRT_OK;
-  }
-  ZRT_CATCH_ALL
-}
-
-int zrt_ctx_stats(zrt_ctx* c, zrt_stats* out) {
-  if (!c || !out) return fail(ZRT_E_INVALID, "null argument");
-  if (!c->launched) return fail(ZRT_E_INVALID, "zrt_ctx_stats before any zrt_ctx_render_tiles");
-  try {
-    HIPCHK(hipSetDevice(c->device));
-    HIPCHK(hipEventSynchronize(c->ev_done));
-    unsigned long long h[zrt::kScratchSlots] = {0};
-    HIPCHK(hipMemcpy(h, c->scratch.p, sizeof(h), hipMemcpyDeviceToHost));
-    if (c->scanline_rows) {  // ZRT_FLAG_SCANLINES: the launch counted these three per row only
-      std::vector<unsigned long long> rows(size_t(c->scanline_rows) * 3);
-      HIPCHK(hipMemcpy(rows.data(), c->scanlines.p, rows.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-      for (size_t y = 0; y < c->scanline_rows; ++y) {
-        h[zrt::kDepthHits] += rows[3 * y];
-        h[zrt::kReflections] += rows[3 * y + 1];
-        h[zrt::kBackground] += rows[3 * y + 2];
-      }
-    }
-    std::memset(out, 0, sizeof(*out));
-    out->recursion_depth_hits = h[zrt::kDepthHits];
-    out->reflections = h[zrt::kReflections];
-    out->background_hits = h[zrt::kBackground];
-    // rayColor calls = samples + reflections = rays + depth-limit hits
-    // (an adaptive run: per-tile sample counts, summed level by level)
-    const uint64_t samples = c->last_adapt ? c->adapt_samples : uint64_t(c->last_pixels) * c->last_spp;
-    out->rays_processed = c->last_stats ? h[zrt::kRays] : samples + h[zrt::kReflections] - h[zrt::kDepthHits];
-    out->node_visits = h[zrt::kNodes];
-    out->prim_tests = h[zrt::kTriTests] + h[zrt::kSphereTests];
-    out->sphere_tests = h[zrt::kSphereTests];
-    out->shade_fetches = h[zrt::kShades];
-    out->texel_fetches = h[zrt::kTexels];
-    out->leaf_visits = h[zrt::kLeaves];
-    out->order_replays = h[zrt::kReplays];
-    uint32_t bt = uint32_t(h[zrt::kExcessTri]), bs = uint32_t(h[zrt::kExcessSph]);
-    std::memcpy(&out->box_excess_max_triangle, &bt, 4);
-    std::memcpy(&out->box_excess_max_sphere, &bs, 4);
-    out->box_excess_hits = h[zrt::kExcessHits];
-    // FAST: leaf boxes ride in their parent's 128 B; compressed: 64-B nodes (+ 32-B leaf records)
-    out->node_bytes = c->last_mode == 3 ? (c->last_qn ? 64 : 128) : 32;
-    out->wide_nodes = c->n_wide;
-    out->sampling_loop = uint32_t(c->last_loop);
-    out->guard = c->last_guard;
-    out->texel_bytes = c->texel_bytes;
-    out->pixels_processed = c->last_pixels;
-    out->samples_processed = samples;
-    out->preprocess_ms = c->preprocess_ms;
-    out->upload_ms = c->upload_ms;
-    float ms = 0.0f, sched = 0.0f;
-    HIPCHK(hipEventElapsedTime(&ms, c->ev_pre, c->ev1));
-    HIPCHK(hipEventElapsedTime(&sched, c->ev_pre, c->ev0));
-    out->render_ms = ms;
-    out->schedule_ms = c->scheduled ? sched : 0.0f;
-    if (c->run_stats) {  // a run: the sums over its passes (the counters above were never re-zeroed)
-      zrt::fold_pass_times(c, true);
-      out->render_ms = c->run_render_ms + ms;
-      out->schedule_ms = float(c->run_sched_ms + (c->pass_probed ? sched : 0.0f));
-    }
-    out->used_bvh = c->use_bvh ? 1 : 0;
-    out->bvh_nodes = c->n_nodes;
-    out->bvh_max_depth = c->bvh_depth;
-    out->n_gpus = 1;
-    return zrt::launch_status(c, true);
-  }
-  ZRT_CATCH_ALL
-}
-
-int zrt_ctx_sync(zrt_ctx* c) {
-  if (!c) return fail(ZRT_E_INVALID, "null argument");
-  try {
-    HIPCHK(hipSetDevice(c->device));
-    return zrt::launch_status(c, true);
-  }
-  ZRT_CATCH_ALL
-}
-
-namespace zrt {
-namespace {
-// The per-row Progress counters of c's last launch (ZRT_FLAG_SCANLINES) added
-// into out[0 .. height): this rank's pixels, samples and rays of each row and
-// the three counters the kernel counted per row.
-int add_scanlines(zrt_ctx* c, zrt_scanline* out, uint32_t height) {
-  if (!c->launched || c->scanline_rows == 0)
-    return fail(ZRT_E_INVALID, "the last launch did not count scanlines (ZRT_FLAG_SCANLINES)");
-  if (height != c->scanline_rows) return fail(ZRT_E_INVALID, "height differs from the last launch's");
-  HIPCHK(hipSetDevice(c->device));
-  HIPCHK(hipEventSynchronize(c->ev_done));
-  std::vector<unsigned long long> rows(size_t(height) * 3);
-  HIPCHK(hipMemcpy(rows.data(), c->scanlines.p, rows.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-  std::vector<uint32_t> done;  // an adaptive run: samples per pixel of each tile
-  if (c->last_adapt) {
-    done.resize(std::max(1u, c->last_tiles));
-    HIPCHK(hipMemcpy(done.data(), c->tile_done.p, size_t(c->last_tiles) * sizeof(uint32_t), hipMemcpyDeviceToHost));
-  }
-  std::vector<uint64_t> row_samples(height, 0);
-  for (uint32_t lt = 0; lt < c->last_tiles; ++lt) {  // pixels of this rank's tiles, per row
-    const uint32_t t = lt * c->last_world + c->last_rank;
-    const uint32_t tx = t % c->last_tiles_x, ty = t / c->last_tiles_x;
-    const uint32_t w = std::min(8u, c->last_xbound - tx * 8u);
-    const uint32_t spp = c->last_adapt ? done[lt] & ~kTileFrozen : c->last_spp;
-    for (uint32_t y = ty * 8u; y < std::min(height, ty * 8u + 8u); ++y) {
-      out[y].pixels += w;
-      row_samples[y] += uint64_t(w) * spp;
-    }
-  }
-  for (uint32_t y = 0; y < height; ++y) {
-    out[y].recursion_depth_hits += rows[3 * y];
-    out[y].reflections += rows[3 * y + 1];
-    out[y].background_hits += rows[3 * y + 2];
-  }
-  // samples and rays from the pixels (rays = rayColor calls - depth-limit hits)
-  for (uint32_t y = 0; y < height; ++y) {
-    out[y].samples += row_samples[y];
-    out[y].rays = out[y].samples + out[y].reflections - out[y].recursion_depth_hits;
-  }
-  return ZRT_OK;
-}
-}  // namespace
-}  // namespace zrt
-
-int zrt_ctx_scanlines(zrt_ctx* c, zrt_scanline* out, uint32_t height) {
-  if (!c || !out) return fail(ZRT_E_INVALID, "null argument");
-  try {
-    std::memset(out, 0, sizeof(zrt_scanline) * height);
-    int rc = zrt::add_scanlines(c, out, height);
-    if (rc) return rc;
-    return zrt::launch_status(c, true);
-  }
-  ZRT_CATCH_ALL
-}
-
-int zrt_ctx_debug_counters(zrt_ctx* c, uint64_t* out, uint32_t n) {
-  if (!c || !out) return fail(ZRT_E_INVALID, "null argument");
-  if (!c->launched) return fail(ZRT_E_INVALID, "no kernel launched on this context yet");
-  try {
-    HIPCHK(hipSetDevice(c->device));
-    HIPCHK(hipEventSynchronize(c->ev_done));
-    unsigned long long h[zrt::kScratchSlots] = {0};
-    HIPCHK(hipMemcpy(h, c->scratch.p, sizeof(h), hipMemcpyDeviceToHost));
-    for (uint32_t i = 0; i < n && i < uint32_t(zrt::kScratchSlots); ++i) out[i] = h[i];
-    return ZRT_OK;
-  }
-  ZRT_CATCH_ALL
-}
-
-int zrt_ctx_debug_wave_times(zrt_ctx* c, uint64_t* out, uint32_t cap, uint32_t* n_waves) {
-  if (!c || !n_waves) return fail(ZRT_E_INVALID, "null argument");
-  try {
-    HIPCHK(hipSetDevice(c->device));
-    if (c->launched) HIPCHK(hipEventSynchronize(c->ev_done));
-    *n_waves = ZRT_PROFILE ? c->n_waves : 0u;
-    const size_t n = std::min<size_t>(cap / 2, *n_waves);
-    if (n && out) HIPCHK(hipMemcpy(out, c->wave_times.p, 2 * n * sizeof(uint64_t), hipMemcpyDeviceToHost));
-    return ZRT_OK;
-  }
-  ZRT_CATCH_ALL
-}
-
-int zrt_ctx_debug_schedule(zrt_ctx* c, uint32_t* costs, uint32_t* order, uint32_t cap, uint32_t* n_tiles) {
-  if (!c || !n_tiles) return fail(ZRT_E_INVALID, "null argument");
-  if (!c->launched) return fail(ZRT_E_INVALID, "no kernel launched on this context yet");
-  try {
-    HIPCHK(hipSetDevice(c->device));
-    HIPCHK(hipEventSynchronize(c->ev_done));
-    *n_tiles = c->scheduled ? c->tile_ids_n : 0u;
-    const size_t n = std::min<size_t>(cap, *n_tiles);
-    if (n && costs) HIPCHK(hipMemcpy(costs, c->tile_cost.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    if (n && order) HIPCHK(hipMemcpy(order, c->tile_order.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    return ZRT_OK;
-  }
-  ZRT_CATCH_ALL
-}
-
-int zrt_ctx_last_kernel_ms(zrt_ctx* c, double* ms) {
-  if (!c || !ms) return fail(ZRT_E_INVALID, "null argument");
-  if (!c->launched) return fail(ZRT_E_INVALID, "no kernel launched on this context yet");
-  try {
-    HIPCHK(hipSetDevice(c->device));
-    HIPCHK(hipEventSynchronize(c->ev1));
-    float f = 0.0f;
-    HIPCHK(hipEventElapsedTime(&f, c->ev0, c->ev1));
-    *ms = f;
-    return zrt::launch_status(c, true);
-  }
-  ZRT_CATCH_ALL
-}
-
-int zrt_ctx_assemble(zrt_ctx* c, const zrt_params* p, const float* dev_gathered, float* dev_frame,
-                     void* hip_stream) {
-  return zrt::assemble(c, p, dev_gathered, 0, dev_frame, hip_stream);
-}
-
-int zrt_ctx_assemble_padded(zrt_ctx* c, const zrt_params* p, const float* dev_gathered, uint32_t stride_tiles,
-                            float* dev_frame, void* hip_stream) {
-  if (stride_tiles == 0) return fail(ZRT_E_INVALID, "stride_tiles must be > 0");
-  return zrt::assemble(c, p, dev_gathered, stride_tiles, dev_frame, hip_stream);
-}
-
-// ---- first-hit feature buffers (zrt.h "denoising") ---------------------------
-int zrt_ctx_features(zrt_ctx* c, const zrt_camera* cam, const zrt_params* p, float* dev_features, void* hip_stream) {
-  if (!c || !cam || !dev_features) return fail(ZRT_E_INVALID, "null argument");
-  int rc = zrt::validate_params(p);
-  if (rc) return rc;
-  rc = params_fit_ctx(c, p);
-  if (rc) return rc;
-  if (reinterpret_cast<uintptr_t>(dev_features) & 15u)
-    return fail(ZRT_E_INVALID, "dev_features must be 16-byte aligned");
-  try {
-    HIPCHK(hipSetDevice(c->device));
-    hipStream_t st = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
-    // the traversal of zrt_trace: the loop's own, with the grazing-triangle guard
-    const int mode = !c->use_bvh ? 0
-                     : p->traversal == ZRT_TRAVERSAL_REFERENCE ? 2
-                     : p->traversal == ZRT_TRAVERSAL_BINARY ? 1 : 3;
-    const uint32_t stack_depth = mode == 3 ? std::max(c->wide_stack, c->stack_depth) : c->stack_depth;
-    const bool stk16 = mode == 3 ? zrt::fast_stk16(c->n_wide, c->n_nodes) : c->n_nodes < 65536;
-    const bool qn = mode == 3 && c->q_ok;
-    const uint32_t node_f4 = qn ? zrt::kQuantNodeF4 : 8u;
-    const zrt::LdsPlan lp = zrt::plan_lds(c, mode, stk16, stack_depth, 0, false, false, ZRT_PRNG_XOROSHIRO128, node_f4);
-    const uint32_t tiles = ((p->width + 7u) / 8u) * ((p->height + 7u) / 8u);
-    const uint32_t grid = (tiles + zrt::kBlock / 64 - 1) / (zrt::kBlock / 64);
-    const uint64_t n_lanes = uint64_t(grid) * zrt::kBlock;
-    if (c->feat_slot_prim.n < c->slot_to_prim.size() || c->feat_slot_prim.p == nullptr)
-      c->feat_slot_prim.upload(c->slot_to_prim);
-    if (!c->feat_done) {
-      HIPCHK(hipEventCreateWithFlags(&c->feat_done, hipEventDisableTiming));
-      HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&c->feat_err_host), sizeof(unsigned long long),
-                           hipHostMallocDefault));
-      *c->feat_err_host = 0;
-    }
-    // the context's error flag: what a render launch left there stays (a run's flag is
-    // sticky); before the first launch the slots hold nothing yet
-    if (!c->launched && !c->feat_launched)
-      HIPCHK(hipMemsetAsync(c->scratch.p, 0, zrt::kScratchSlots * sizeof(unsigned long long), st));
-    zrt::KArgs a{};
-    a.nodes = c->nodes.p;
-    a.prims = c->prims.p;
-    a.shade = c->shade.p;
-    a.mats = c->mats.p;
-    a.texels = c->texels.p;
-    a.texels8 = c->texels8.p;
-    a.n_mats = c->n_mats;
-    a.wnodes = qn ? c->qnodes.p : c->wnodes.p;
-    a.wide_stride = qn ? c->q_stride : c->wide_stride;
-    a.node_f4 = node_f4;
-    a.qleaves = qn ? c->qleaves.p : nullptr;
-    a.n_qnodes = qn ? c->q_stride / zrt::kQuantNodeF4 : 0u;
-    a.n_qleaves = qn ? c->n_qleaves : 0u;
-    a.error_flag = reinterpret_cast<uint32_t*>(c->scratch.p + zrt::kErrorSlot);
-    const zrt_vec3* v[4] = {&cam->origin, &cam->lower_left_corner, &cam->horizontal, &cam->vertical};
-    float* dst[4] = {a.org, a.llc, a.hor, a.ver};
-    for (int k = 0; k < 4; ++k) {
-      dst[k][0] = v[k]->x;
-      dst[k][1] = v[k]->y;
-      dst[k][2] = v[k]->z;
-    }
-    a.f_width = float(p->width);
-    a.f_height = float(p->height);
-    a.width = p->width;
-    a.height = p->height;
-    a.xbound = zrt::geometry(p).xbound;
-    a.n_list = c->use_bvh ? 0 : c->n_prims;
-    a.tri_rcp_fast = c->tri_rcp_fast;
-    a.scene_extent = c->scene_extent;
-    a.paxis_m = zrt::paxis_threshold();
-    for (int k = 0; k < 3; ++k) {
-      a.tri_c[k] = c->tri_c[k];
-      a.tri_h[k] = c->tri_h[k];
-    }
-    a.stack_depth = stack_depth;
-    a.ref_stack = c->stack_depth;
-    a.leaf_of_slot = c->leaf_of_slot.p;
-    a.ref_sph = c->ref_sph.p;
-    for (int k = 0; k < 3; ++k) a.root_c[k] = c->root_c[k];
-    a.origin_bound = c->origin_bound;
-    a.check_origins = 1;  // any camera
-    a.layout = c->layout;
-    a.graze_m = c->graze_m;
-    a.graze_leaf = c->graze_leaf;
-    a.guard = c->guard;  // as zrt_trace
-    a.lds_rows = lp.stack_rows;
-    a.n_lanes = uint32_t(n_lanes);
-    a.n_top = qn ? c->q_top : c->n_top;
-    a.lds_top_off = lp.top_off;
-    a.lds_att_off = lp.att_off;
-    const zrt::BufNeed need = zrt::buffer_need(lp, 0, stack_depth, n_lanes, n_lanes, stk16);
-    if (need.ovf_bytes) {
-      if (c->feat_ovf.n < need.ovf_bytes) {
-        HIPCHK(hipStreamSynchronize(st));  // (an earlier feature launch may still use the old rows)
-        c->feat_ovf.alloc(need.ovf_bytes);
-      }
-      a.stack_ovf = c->feat_ovf.p;
-    }
-    zrt::check_buffers("feature launch", zrt::BufNeed{0, need.ovf_bytes}, c->att.n, c->feat_ovf.n);
-    a.att_cap = c->att.n;
-    a.ovf_cap = zrt::ovf_cap_elems(c->feat_ovf.n, stk16);
-    void* fn = nullptr;
-#define ZRT_FK(M) (stk16 ? reinterpret_cast<void*>(&zrt::features_kernel<M, uint16_t>) \
-                         : reinterpret_cast<void*>(&zrt::features_kernel<M, uint32_t>))
-#ifndef ZRT_ISA_KERNEL
-    fn = mode == 0 ? ZRT_FK(0) : mode == 1 ? ZRT_FK(1) : mode == 2 ? ZRT_FK(2) : qn ? ZRT_FK(8) : ZRT_FK(3);
-#endif
-#undef ZRT_FK
-    const uint32_t* sp = c->feat_slot_prim.p;
-    float4* out = reinterpret_cast<float4*>(dev_features);
-    void* args[] = {&a, &sp, &out};
-    HIPCHK(hipLaunchKernel(fn, dim3(grid), dim3(zrt::kBlock), args, lp.bytes, st));
-    const uint64_t n_f4 = 2ull * p->width * p->height;
-    hipLaunchKernelGGL(zrt::features_error_kernel, dim3(uint32_t(std::min<uint64_t>((n_f4 + 255) / 256, 4096))),
-                       dim3(256), 0, st, out, n_f4, c->scratch.p + zrt::kErrorSlot);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(c->feat_err_host, c->scratch.p + zrt::kErrorSlot, sizeof(unsigned long long),
-                          hipMemcpyDeviceToHost, st));
-    HIPCHK(hipEventRecord(c->feat_done, st));
-    c->feat_launched = true;
-    c->feat_err_reported = false;
-    return ZRT_OK;
-  }
-  ZRT_CATCH_ALL
-}
-
-// ---- denoising (zrt.h "denoising"; the kernels: denoise.hip) ----------------
-// the default sigmas: the winner of tools/denoise_probe.py's grid of powers of two
-// (profiles/r10/denoise/defaults.json)
-#define ZRT_DN_SIGMA_COLOR 2.0f
-#define ZRT_DN_SIGMA_NORMAL 0.125f
-#define ZRT_DN_SIGMA_ALBEDO 0x1p-12f
-#define ZRT_DN_SIGMA_DEPTH 0.015625f
-int zrt_denoise_defaults(zrt_denoise* out) {
-  if (!out) return fail(ZRT_E_INVALID, "null argument");
-  *out = zrt_denoise{};
-  out->iterations = ZRT_DEFAULT_DENOISE_ITERATIONS;
-  // the winner of tools/denoise_probe.py's grid (profiles/r10/denoise/defaults.json)
-  out->sigma_color = ZRT_DN_SIGMA_COLOR;
-  out->sigma_normal = ZRT_DN_SIGMA_NORMAL;
-  out->sigma_albedo = ZRT_DN_SIGMA_ALBEDO;
-  out->sigma_depth = ZRT_DN_SIGMA_DEPTH;
-  return ZRT_OK;
-}
-
-namespace zrt {
-namespace {
-// What zrt_ctx_denoise refuses of a zrt_denoise, and the launch it asks for otherwise.
-int plan_denoise(const zrt_params* p, const zrt_denoise* dn, DenoiseLaunch* out) {
-  if (!dn) return fail(ZRT_E_INVALID, "denoise is null");
-  int rc = validate_params(p);
-  if (rc) return rc;
-  if (dn->iterations > 8) return fail(ZRT_E_INVALID, "denoise iterations must be <= 8");
-  const float sg[4] = {dn->sigma_color, dn->sigma_normal, dn->sigma_albedo, dn->sigma_depth};
-  const char* names[4] = {"sigma_color", "sigma_normal", "sigma_albedo", "sigma_depth"};
-  float inv[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-  uint32_t terms = 0;
-  for (int k = 0; k < 4; ++k) {
-    if (!std::isfinite(sg[k]) || sg[k] < 0.0f)
-      return fail(ZRT_E_INVALID, std::string("denoise ") + names[k] + " must be finite and >= 0");
-    if (sg[k] > 0.0f) {
-      terms |= 1u << k;
-      inv[k] = 1.0f / sg[k];
-    }
-  }
-  out->width = p->width;
-  out->n = p->height;
-  out->iterations = dn->iterations ? dn->iterations : ZRT_DEFAULT_DENOISE_ITERATIONS;
-  out->terms = terms;
-  out->inv_c = inv[0];
-  out->inv_n = inv[1];
-  out->inv_a = inv[2];
-  out->inv_z = inv[3];
-  return ZRT_OK;
-}
-}  // namespace
-}  // namespace zrt
-
-int zrt_ctx_denoise(zrt_ctx* c, const zrt_params* p, const zrt_denoise* dn, const float* dev_frame,
-                    const float* dev_features, float* dev_out, void* hip_stream) {
-  zrt::DenoiseLaunch l{};
-  int rc = zrt::plan_denoise(p, dn, &l);  // (the refusals that need no context come first)
-  if (rc) return rc;
-  if (dev_out && static_cast<const float*>(dev_out) == dev_frame)
-    return fail(ZRT_E_INVALID, "denoise: dev_out must not be dev_frame");
-  if (reinterpret_cast<uintptr_t>(dev_features) & 15u)
-    return fail(ZRT_E_INVALID, "denoise: dev_features must be 16-byte aligned");
-  if (!c || !dev_frame || !dev_features || !dev_out) return fail(ZRT_E_INVALID, "null argument");
-  if (int(p->device) != c->device)
-    return fail(ZRT_E_INVALID, "params->device differs from the device the context was created on");
-  try {
-    HIPCHK(hipSetDevice(c->device));
-    hipStream_t st = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
-    const size_t plane = size_t(l.n) * l.n;
-    for (zrt::DevBuf<float4>& b : c->dn_buf)
-      if (b.n < plane) b.alloc(plane);
-    if (!c->dn_ev0) {
-      HIPCHK(hipEventCreate(&c->dn_ev0));
-      HIPCHK(hipEventCreate(&c->dn_ev1));
-    }
-    HIPCHK(hipEventRecord(c->dn_ev0, st));
-    HIPCHK(zrt::denoise_enqueue(l, dev_frame, reinterpret_cast<const float4*>(dev_features), dev_out, c->dn_buf[0].p,
-                                c->dn_buf[1].p, st));
-    HIPCHK(hipEventRecord(c->dn_ev1, st));
-    c->dn_launched = true;
-    return ZRT_OK;
-  }
-  ZRT_CATCH_ALL
-}
-
-int zrt_ctx_denoise_ms(zrt_ctx* c, double* ms) {
-  if (!c || !ms) return fail(ZRT_E_INVALID, "null argument");
-  if (!c->dn_launched) return fail(ZRT_E_INVALID, "no denoise launched on this context yet");
-  try {
-    HIPCHK(hipSetDevice(c->device));
-    HIPCHK(hipEventSynchronize(c->dn_ev1));
-    float f = 0.0f;
-    HIPCHK(hipEventElapsedTime(&f, c->dn_ev0, c->dn_ev1));
-    *ms = f;
-    return ZRT_OK;
-  }
-  ZRT_CATCH_ALL
-}
-
-namespace zrt {
-namespace {
-// What a one-shot render does with its assembled frame while it still lies on the
-// device (zrt_render_denoised): called last, with the context, the params rendered
-// with and the frame.
-using FramePost = std::function<int(zrt_ctx*, const zrt_params&, const float*)>;
-
-int render_one(const zrt_scene* scene, const zrt_camera* camera, const zrt_params* params, float* out_rgb,
-               zrt_stats* stats, zrt_scanline* rows, const FramePost* post = nullptr) {
-  if (!camera || (!out_rgb && !post)) return fail(ZRT_E_INVALID, "null argument");
-  int rc = zrt::validate_params(params);
-  if (rc) return rc;
-  zrt_params p = *params;
-  p.rank = 0;
-  p.world_size = 1;
-  if (rows) p.flags |= ZRT_FLAG_SCANLINES;
-  zrt_ctx* c = nullptr;
-  rc = zrt_ctx_create(scene, &p, &c);
-  if (rc) return rc;
-  std::unique_ptr<zrt_ctx, int (*)(zrt_ctx*)> guard(c, zrt_ctx_destroy);
-  try {
-    uint32_t n_tiles = 0;
-    rc = zrt_ctx_tile_count(c, &p, &n_tiles);
-    if (rc) return rc;
-    zrt::DevBuf<float> tiles, frame;
-    tiles.alloc(size_t(n_tiles) * 64 * 3);
-    frame.alloc(size_t(p.width) * p.height * 3);
-    rc = zrt_ctx_render_tiles(c, camera, &p, tiles.p, nullptr);
-    if (rc) return rc;
-    rc = zrt_ctx_assemble(c, &p, tiles.p, frame.p, nullptr);
-    if (rc) return rc;
-    HIPCHK(hipStreamSynchronize(c->stream));
-    if (out_rgb)
-      HIPCHK(hipMemcpy(out_rgb, frame.p, sizeof(float) * 3 * size_t(p.width) * p.height, hipMemcpyDeviceToHost));
-    zrt_stats s;
-    rc = zrt_ctx_stats(c, &s);
-    if (rc) return rc;
-    if (rows) {
-      std::memset(rows, 0, sizeof(zrt_scanline) * p.height);
-      rc = add_scanlines(c, rows, p.height);
-      if (rc) return rc;
-    }
-    if (stats) *stats = s;
-    if (post) return (*post)(c, p, frame.p);
-    return ZRT_OK;
-  }
-  ZRT_CATCH_ALL
-}
-}  // namespace
-}  // namespace zrt
-
-int zrt_render(const zrt_scene* scene, const zrt_camera* camera, const zrt_params* params,
-               float* out_rgb, zrt_stats* stats) {
-  return zrt::render_one(scene, camera, params, out_rgb, stats, nullptr);
-}
-
-int zrt_render_progress(const zrt_scene* scene, const zrt_camera* camera, const zrt_params* params,
-                        float* out_rgb, zrt_stats* stats, zrt_scanline* scanlines) {
-  if (!scanlines) return fail(ZRT_E_INVALID, "null argument");
-  return zrt::render_one(scene, camera, params, out_rgb, stats, scanlines);
-}
-
-int zrt_render_progressive(const zrt_scene* scene, const zrt_camera* camera, const zrt_params* params,
-                           uint32_t pass_samples, zrt_pass_fn on_pass, void* user, float* out_rgb,
-                           zrt_stats* stats) {
-  if (!camera || !out_rgb) return fail(ZRT_E_INVALID, "null argument");
-  int rc = zrt::validate_params(params);
-  if (rc) return rc;
-  zrt_params p = *params;
-  p.rank = 0;
-  p.world_size = 1;
-  const uint32_t chunk = p.sample_chunk ? p.sample_chunk : ZRT_DEFAULT_SAMPLE_CHUNK;
-  // whole chunks per pass (a pass must start on a chunk boundary); 0: the default
-  const uint64_t per_pass = pass_samples ? (uint64_t(pass_samples) + chunk - 1) / chunk * chunk
-                                         : uint64_t(ZRT_DEFAULT_PASS_CHUNKS) * chunk;
-  zrt_ctx* c = nullptr;
-  rc = zrt_ctx_create(scene, &p, &c);
-  if (rc) return rc;
-  std::unique_ptr<zrt_ctx, int (*)(zrt_ctx*)> guard(c, zrt_ctx_destroy);
-  try {
-    uint32_t n_tiles = 0;
-    rc = zrt_ctx_tile_count(c, &p, &n_tiles);
-    if (rc) return rc;
-    zrt::DevBuf<float> tiles, frame;
-    tiles.alloc(size_t(n_tiles) * 64 * 3);
-    frame.alloc(size_t(p.width) * p.height * 3);
-    rc = zrt_ctx_accum_begin(c, camera, &p);
-    if (rc) return rc;
-    const size_t frame_bytes = sizeof(float) * 3 * size_t(p.width) * p.height;
-    for (uint32_t done = 0; done < p.samples_per_pixel;) {
-      const uint32_t n = uint32_t(std::min<uint64_t>(per_pass, p.samples_per_pixel - done));
-      rc = zrt_ctx_accum_pass(c, n, tiles.p, nullptr);
-      if (rc) return rc;
-      rc = zrt_ctx_assemble(c, &p, tiles.p, frame.p, nullptr);
-      if (rc) return rc;
-      done += n;
-      if (!on_pass && done < p.samples_per_pixel) continue;  // nobody looks: the passes queue up
-      HIPCHK(hipStreamSynchronize(c->stream));
-      HIPCHK(hipMemcpy(out_rgb, frame.p, frame_bytes, hipMemcpyDeviceToHost));
-      if (on_pass) {
-        zrt_pass_info info;
-        rc = zrt_ctx_accum_info(c, &info);
-        if (rc) return rc;
-        if (on_pass(user, out_rgb, &info) != 0) break;
-      }
-    }
-    zrt_stats s;
-    rc = zrt_ctx_stats(c, &s);
-    if (rc) return rc;
-    if (stats) *stats = s;
-    return ZRT_OK;
-  }
-  ZRT_CATCH_ALL
-}
-
-namespace zrt {
-namespace {
-int render_adaptive(const zrt_scene* scene, const zrt_camera* camera, const zrt_params* params,
-                    const zrt_adaptive* adaptive, zrt_level_fn on_level, void* user, float* out_rgb,
-                    uint32_t* out_samples, zrt_stats* stats, zrt_scanline* rows, const FramePost* post = nullptr) {
-  if (!camera || (!out_rgb && !post) || !adaptive) return fail(ZRT_E_INVALID, "null argument");
-  if (!out_rgb && on_level) return fail(ZRT_E_INVALID, "on_level needs out_rgb");
-  std::vector<uint32_t> levels;
-  int rc = zrt::plan_adapt(params, adaptive, &levels);
-  if (rc) return rc;
-  zrt_params p = *params;
-  p.rank = 0;
-  p.world_size = 1;
-  if (rows) p.flags |= ZRT_FLAG_SCANLINES;
-  zrt_ctx* c = nullptr;
-  rc = zrt_ctx_create(scene, &p, &c);
-  if (rc) return rc;
-  std::unique_ptr<zrt_ctx, int (*)(zrt_ctx*)> guard(c, zrt_ctx_destroy);
-  try {
-    uint32_t n_tiles = 0;
-    rc = zrt_ctx_tile_count(c, &p, &n_tiles);
-    if (rc) return rc;
-    zrt::DevBuf<float> tiles, frame;
-    tiles.alloc(size_t(n_tiles) * 64 * 3);
-    frame.alloc(size_t(p.width) * p.height * 3);
-    HIPCHK(hipMemset(tiles.p, 0, sizeof(float) * tiles.n));
-    rc = zrt_ctx_adapt_begin(c, camera, &p, adaptive);
-    if (rc) return rc;
-    const size_t frame_bytes = sizeof(float) * 3 * size_t(p.width) * p.height;
-    for (size_t k = 0; k < levels.size(); ++k) {
-      zrt_level_info info;
-      rc = zrt_ctx_adapt_level(c, tiles.p, nullptr, &info);
-      if (rc) return rc;
-      const bool over = info.tiles_active_after == 0;
-      if (on_level || over) {
-        rc = zrt_ctx_assemble(c, &p, tiles.p, frame.p, nullptr);
-        if (rc) return rc;
-        HIPCHK(hipStreamSynchronize(c->stream));
-        if (out_rgb) HIPCHK(hipMemcpy(out_rgb, frame.p, frame_bytes, hipMemcpyDeviceToHost));
-      }
-      if (on_level && on_level(user, out_rgb, &info) != 0 && !over) {
-        break;
-      }
-      if (over) break;
-    }
-    if (out_samples) {
-      std::vector<uint32_t> per_tile(std::max(1u, n_tiles));
-      rc = zrt_ctx_adapt_samples(c, per_tile.data(), n_tiles);
-      if (rc) return rc;
-      const zrt::Geometry g = zrt::geometry(&p);
-      std::fill(out_samples, out_samples + size_t(p.width) * p.height, 0u);
-      for (uint32_t y = 0; y < p.height; ++y)
-        for (uint32_t x = 0; x < g.xbound; ++x)
-          out_samples[size_t(y) * p.width + x] = per_tile[(y / 8u) * g.tiles_x + x / 8u];
-    }
-    zrt_stats s;
-    rc = zrt_ctx_stats(c, &s);
-    if (rc) return rc;
-    if (rows) {
-      std::memset(rows, 0, sizeof(zrt_scanline) * p.height);
-      rc = add_scanlines(c, rows, p.height);
-      if (rc) return rc;
-    }
-    if (stats) *stats = s;
-    if (post) return (*post)(c, p, frame.p);
-    return ZRT_OK;
-  }
-  ZRT_CATCH_ALL
-}
-}  // namespace
-}  // namespace zrt
-
-int zrt_render_adaptive(const zrt_scene* scene, const zrt_camera* camera, const zrt_params* params,
-                        const zrt_adaptive* adaptive, zrt_level_fn on_level, void* user, float* out_rgb,
-                        uint32_t* out_samples, zrt_stats* stats) {
-  return zrt::render_adaptive(scene, camera, params, adaptive, on_level, user, out_rgb, out_samples, stats, nullptr);
-}
-
-int zrt_render_adaptive_progress(const zrt_scene* scene, const zrt_camera* camera, const zrt_params* params,
-                                 const zrt_adaptive* adaptive, zrt_level_fn on_level, void* user, float* out_rgb,
-                                 uint32_t* out_samples, zrt_stats* stats, zrt_scanline* scanlines) {
-  if (!scanlines) return fail(ZRT_E_INVALID, "null argument");
-  return zrt::render_adaptive(scene, camera, params, adaptive, on_level, user, out_rgb, out_samples, stats, scanlines);
-}
-
-int zrt_render_denoised(const zrt_scene* scene, const zrt_camera* camera, const zrt_params* params,
-                        const zrt_adaptive* adaptive, const zrt_denoise* dn, float* out_rgb, float* out_noisy,
-                        float* out_features, zrt_stats* stats, double* denoise_ms) {
-  if (!camera || !out_rgb) return fail(ZRT_E_INVALID, "null argument");
-  zrt_denoise d;
-  if (dn) d = *dn;
-  else zrt_denoise_defaults(&d);
-  zrt::DenoiseLaunch l{};
-  int rc = zrt::plan_denoise(params, &d, &l);  // (refused before any device work)
-  if (rc) return rc;
-  const zrt::FramePost post = [&](zrt_ctx* c, const zrt_params& p, const float* dev_frame) -> int {
-    try {
-      const size_t px = size_t(p.width) * p.height;
-      zrt::DevBuf<float> feat, outb;
-      feat.alloc(px * 8);
-      outb.alloc(px * 3);
-      int r = zrt_ctx_features(c, camera, &p, feat.p, nullptr);
-      if (r) return r;
-      r = zrt_ctx_denoise(c, &p, &d, dev_frame, feat.p, outb.p, nullptr);
-      if (r) return r;
-      HIPCHK(hipStreamSynchronize(c->stream));
-      r = zrt_ctx_sync(c);  // (a feature launch's device error)
-      if (r) return r;
-      HIPCHK(hipMemcpy(out_rgb, outb.p, sizeof(float) * 3 * px, hipMemcpyDeviceToHost));
-      if (out_features) HIPCHK(hipMemcpy(out_features, feat.p, sizeof(float) * 8 * px, hipMemcpyDeviceToHost));
-      if (denoise_ms) {
-        r = zrt_ctx_denoise_ms(c, denoise_ms);
-        if (r) return r;
-      }
-      return ZRT_OK;
-    }
-    ZRT_CATCH_ALL
+const KernelConfig& kernel_config() {
+  static const KernelConfig k = {
+      ZRT_WAVES_WIDE, ZRT_WAVES_WF, ZRT_WAVES_POOL, ZRT_WAVES_LIST, ZRT_WAVES_PER_SIMD,
+      ZRT_ATT_ROWS_LOCK, ZRT_ATT_ROWS_WF, ZRT_ATT_ROWS_POOL, ZRT_ATT_ROWS_LIST,
+      ZRT_STACK_ROWS_LOCK, ZRT_SYNC_SAMPLES, ZRT_PROBE_SPP,
+      kOctCopies,
+      {LaneState<ZRT_PRNG_XOROSHIRO128>::kWords, LaneState<ZRT_PRNG_XOSHIRO256>::kWords},
+      kBlockPaths,
+      kKernelLayout,
+      kPaxisM,
+      ZRT_LDS_TOP != 0, ZRT_LANE_LDS != 0, ZRT_MATS_LDS_ONLY != 0, ZRT_LOCK_QN != 0, ZRT_PROFILE != 0,
+      ZRT_LEAN_DEFAULT != 0, ZRT_GROW != 0, ZRT_SPHERE_SLOTS != 0,
   };
-  if (adaptive)
-    return zrt::render_adaptive(scene, camera, params, adaptive, nullptr, nullptr, out_noisy, nullptr, stats, nullptr,
-                                &post);
-  return zrt::render_one(scene, camera, params, out_noisy, stats, nullptr, &post);
+  return k;
 }
-
-// ---- several GPUs from one host thread (zrt_multi_*, zrt_render_multi) -------
-int zrt_multi_create(const zrt_scene* scene, const zrt_params* params, const uint32_t* devices,
-                     uint32_t n_devices, zrt_multi** out) {
-  if (!out || !devices) return fail(ZRT_E_INVALID, "null argument");
-  *out = nullptr;
-  if (n_devices == 0 || n_devices > 1024) return fail(ZRT_E_INVALID, "n_devices must be in 1..1024");
-  if (!params) return fail(ZRT_E_INVALID, "params is null");
-  int rc = zrt::validate_scene(scene);
-  if (rc) return rc;
-  for (uint32_t r = 0; r < n_devices; ++r) {
-    rc = zrt::check_device(int(devices[r]));
-    if (rc) return rc;
-  }
-  try {
-    std::unique_ptr<zrt_multi> m(new zrt_multi);
-    m->devices.assign(devices, devices + n_devices);
-    std::vector<uint32_t> distinct(m->devices);
-    std::sort(distinct.begin(), distinct.end());
-    distinct.erase(std::unique(distinct.begin(), distinct.end()), distinct.end());
-    m->n_distinct = uint32_t(distinct.size());
-    // RCCL only where there is something to move between GPUs: one rank per
-    // device, at least two devices (a device listed twice gathers by copies)
-    m->use_rccl = m->n_distinct == n_devices && n_devices > 1;
-    // the scene flattened once (BVH build, raytrace.zig:124-133), a copy on every GPU
-    const bool use_bvh = params->bounded_volume_hierarchy != 0 && scene->n_prims > 10;
-    zrt::HostScene host;
-    zrt::flatten_scene(&host, scene, use_bvh, int(devices[0]));
-    for (uint32_t r = 0; r < n_devices; ++r) m->ctx.emplace_back(zrt::ctx_on_device(host, int(devices[r])).release());
-    m->send.resize(n_devices);
-    if (m->use_rccl) {
-      // communicators live as long as the context (not per frame)
-      const zrt::Rccl& R = zrt::rccl();
-      m->comms.R = &R;
-      m->comms.c.assign(n_devices, nullptr);
-      std::vector<int> devs(devices, devices + n_devices);
-      NCCLCHK(R, R.comm_init_all(m->comms.c.data(), int(n_devices), devs.data()));
-    }
-    *out = m.release();
-    return ZRT_OK;
-  }
-  ZRT_CATCH_ALL
-}
-
-int zrt_multi_destroy(zrt_multi* m) {
-  if (!m) return ZRT_OK;
-  for (auto& c : m->ctx) {
-    (void)hipSetDevice(c->device);
-    (void)hipDeviceSynchronize();
-  }
-  delete m;
-  return ZRT_OK;
-}
-
-int zrt_multi_render(zrt_multi* m, const zrt_camera* camera, const zrt_params* params, float* out_rgb,
-                     zrt_stats* stats) {
-  if (!m || !camera) return fail(ZRT_E_INVALID, "null argument");  // out_rgb NULL: the frame stays on devices[0]
-  int rc = zrt::validate_params(params);
-  if (rc) return rc;
-  const uint32_t n = uint32_t(m->ctx.size());
-  try {
-    const zrt::Geometry g = zrt::geometry(params);
-    std::vector<zrt_params> rp(n, *params);
-    std::vector<uint32_t> count(n), base(n + 1, 0);
-    uint32_t max_tiles = 0;
-    for (uint32_t r = 0; r < n; ++r) {
-      rp[r].rank = r;
-      rp[r].world_size = n;
-      rp[r].device = m->devices[r];
-      count[r] = zrt::rank_tiles(g, r, n);
-      base[r + 1] = base[r] + count[r];
-      max_tiles = std::max(max_tiles, count[r]);
-    }
-    const size_t slot = 64 * 3;  // floats per tile
-    // tile buffers padded to the largest rank's (ncclGather sends equal counts)
-    for (uint32_t r = 0; r < n; ++r) {
-      HIPCHK(hipSetDevice(m->ctx[r]->device));
-      if (m->send[r].n < std::max<size_t>(1, max_tiles * slot)) m->send[r].alloc(std::max<size_t>(1, max_tiles * slot));
-    }
-    // the sampling loops, all enqueued before any is waited on
-    for (uint32_t r = 0; r < n; ++r) {
-      rc = zrt_ctx_render_tiles(m->ctx[r].get(), camera, &rp[r], m->send[r].p, nullptr);
-      if (rc) return rc;
-    }
-    zrt_stats sum;
-    std::memset(&sum, 0, sizeof(sum));
-    int device_rc = ZRT_OK;
-    std::string device_msg;
-    m->frame_n = 0;
-    m->rank_ms.assign(n, 0.0);
-    for (uint32_t r = 0; r < n; ++r) {
-      zrt_stats s;
-      rc = zrt_ctx_stats(m->ctx[r].get(), &s);  // waits for rank r's launch
-      if (rc == ZRT_E_UNSUPPORTED) {  // device error: finish the frame (NaN tiles), then report it
-        device_rc = rc;
-        device_msg = zrt_last_error();
-      }
-      else if (rc) return rc;
-      {  // the render kernel alone (ev0 -> ev1; render_ms also holds the schedule probe)
-        float ms = 0.0f;
-        HIPCHK(hipSetDevice(m->ctx[r]->device));
-        HIPCHK(hipEventElapsedTime(&ms, m->ctx[r]->ev0, m->ctx[r]->ev1));
-        m->rank_ms[r] = ms;
-      }
-      if (r == 0) {
-        sum = s;
-        continue;
-      }
-      sum.recursion_depth_hits += s.recursion_depth_hits;
-      sum.reflections += s.reflections;
-      sum.background_hits += s.background_hits;
-      sum.pixels_processed += s.pixels_processed;
-      sum.samples_processed += s.samples_processed;
-      sum.rays_processed += s.rays_processed;
-      sum.node_visits += s.node_visits;
-      sum.prim_tests += s.prim_tests;
-      sum.sphere_tests += s.sphere_tests;
-      sum.shade_fetches += s.shade_fetches;
-      sum.texel_fetches += s.texel_fetches;
-      sum.leaf_visits += s.leaf_visits;
-      sum.order_replays += s.order_replays;
-      sum.preprocess_ms = std::max(sum.preprocess_ms, s.preprocess_ms);
-      sum.upload_ms = std::max(sum.upload_ms, s.upload_ms);
-      sum.render_ms = std::max(sum.render_ms, s.render_ms);
-      sum.schedule_ms = std::max(sum.schedule_ms, s.schedule_ms);
-    }
-    // the gather to devices[0] in the padded rank-major layout (rank r at
-    // r * max_tiles tiles), which zrt_ctx_assemble_padded reads as it lies
-    const double t0 = zrt::now_ms();
-    zrt_ctx* root = m->ctx[0].get();
-    HIPCHK(hipSetDevice(root->device));
-    const size_t frame_n = size_t(params->width) * params->height * 3;
-    if (m->frame.n < frame_n) m->frame.alloc(frame_n);
-    const size_t gathered_n = std::max<size_t>(1, size_t(n) * max_tiles * slot);
-    if (m->gathered.n < gathered_n) m->gathered.alloc(gathered_n);
-    if (m->use_rccl) {
-      const zrt::Rccl& R = *m->comms.R;
-      NCCLCHK(R, R.group_start());
-      for (uint32_t r = 0; r < n; ++r)
-        NCCLCHK(R, R.gather(m->send[r].p, r == 0 ? m->gathered.p : nullptr, size_t(max_tiles) * slot, ncclFloat32, 0,
-                            m->comms.c[r], m->ctx[r]->stream));
-      NCCLCHK(R, R.group_end());
-      // every rank's part of the gather is done before the next frame reuses its buffer
-      for (uint32_t r = 1; r < n; ++r) {
-        HIPCHK(hipSetDevice(m->ctx[r]->device));
-        HIPCHK(hipStreamSynchronize(m->ctx[r]->stream));
-      }
-      HIPCHK(hipSetDevice(root->device));
-    } else {
-      // one device (or ranks sharing devices): copies; every rank's launch is done (stats above)
-      for (uint32_t r = 0; r < n; ++r)
-        if (count[r])
-          HIPCHK(hipMemcpyPeerAsync(m->gathered.p + size_t(r) * max_tiles * slot, root->device, m->send[r].p,
-                                    m->ctx[r]->device, size_t(count[r]) * slot * sizeof(float), root->stream));
-    }
-    rc = zrt_ctx_assemble_padded(root, &rp[0], m->gathered.p, std::max(1u, max_tiles), m->frame.p, nullptr);
-    if (rc) return rc;
-    HIPCHK(hipStreamSynchronize(root->stream));
-    sum.gather_ms = zrt::now_ms() - t0;
-    m->frame_n = frame_n;
-    if (out_rgb) HIPCHK(hipMemcpy(out_rgb, m->frame.p, sizeof(float) * frame_n, hipMemcpyDeviceToHost));
-    sum.n_gpus = m->n_distinct;
-    if (stats) *stats = sum;
-    if (device_rc) return fail(device_rc, device_msg);
-    return ZRT_OK;
-  }
-  ZRT_CATCH_ALL
-}
-
-int zrt_multi_frame(zrt_multi* m, float* out_rgb, uint64_t n_floats) {
-  if (!m || !out_rgb) return fail(ZRT_E_INVALID, "null argument");
-  if (m->frame_n == 0) return fail(ZRT_E_INVALID, "no frame: zrt_multi_frame before a successful zrt_multi_render");
-  if (n_floats != m->frame_n) return fail(ZRT_E_INVALID, "n_floats differs from the last frame's width * height * 3");
-  try {
-    HIPCHK(hipSetDevice(m->ctx[0]->device));
-    HIPCHK(hipMemcpy(out_rgb, m->frame.p, sizeof(float) * m->frame_n, hipMemcpyDeviceToHost));
-    return ZRT_OK;
-  }
-  ZRT_CATCH_ALL
-}
-
-int zrt_multi_rank_ms(zrt_multi* m, double* kernel_ms, uint32_t n) {
-  if (!m || !kernel_ms) return fail(ZRT_E_INVALID, "null argument");
-  if (m->rank_ms.empty()) return fail(ZRT_E_INVALID, "no frame rendered yet");
-  if (n != m->rank_ms.size()) return fail(ZRT_E_INVALID, "n differs from the context's rank count");
-  for (uint32_t r = 0; r < n; ++r) kernel_ms[r] = m->rank_ms[r];
-  return ZRT_OK;
-}
-
-int zrt_multi_scanlines(zrt_multi* m, zrt_scanline* out, uint32_t height) {
-  if (!m || !out) return fail(ZRT_E_INVALID, "null argument");
-  try {
-    std::memset(out, 0, sizeof(zrt_scanline) * height);
-    for (auto& c : m->ctx) {
-      const int rc = zrt::add_scanlines(c.get(), out, height);
-      if (rc) return rc;
-    }
-    return ZRT_OK;
-  }
-  ZRT_CATCH_ALL
-}
-
-int zrt_render_multi(const zrt_scene* scene, const zrt_camera* camera, const zrt_params* params,
-                     const uint32_t* devices, uint32_t n_devices, float* out_rgb, zrt_stats* stats) {
-  if (!camera || !out_rgb || !devices) return fail(ZRT_E_INVALID, "null argument");
-  int rc = zrt::validate_params(params);
-  if (rc) return rc;
-  zrt_multi* m = nullptr;
-  rc = zrt_multi_create(scene, params, devices, n_devices, &m);
-  if (rc) return rc;
-  rc = zrt_multi_render(m, camera, params, out_rgb, stats);
-  const std::string msg = zrt_last_error();
-  zrt_multi_destroy(m);
-  if (rc) return fail(rc, msg);
-  return ZRT_OK;
-}
-
-int zrt_trace(const zrt_scene* scene, const zrt_params* params, const float* rays, uint32_t n_rays, float* out_t,
-              int32_t* out_prim) {
-  if (!params || (n_rays && (!rays || !out_t || !out_prim))) return fail(ZRT_E_INVALID, "null argument");
-  int rc = zrt::validate_scene(scene);
-  if (rc) return rc;
-  if (params->traversal > ZRT_TRAVERSAL_BINARY) return fail(ZRT_E_INVALID, "unknown traversal");
-  rc = zrt::check_device(int(params->device));
-  if (rc) return rc;
-  if (n_rays == 0) return ZRT_OK;
-  try {
-    const bool use_bvh = params->bounded_volume_hierarchy != 0 && scene->n_prims > 10;
-    zrt::HostScene h;
-    zrt::flatten_scene(&h, scene, use_bvh, int(params->device));
-    std::unique_ptr<zrt_ctx> c = zrt::ctx_on_device(h, int(params->device));
-    const int mode = !c->use_bvh ? 0
-                     : params->traversal == ZRT_TRAVERSAL_REFERENCE ? 2
-                     : params->traversal == ZRT_TRAVERSAL_BINARY ? 1 : 3;
-    const uint32_t stack_depth = mode == 3 ? std::max(c->wide_stack, c->stack_depth) : c->stack_depth;
-    const bool stk16 = mode == 3 ? zrt::fast_stk16(c->n_wide, c->n_nodes) : c->n_nodes < 65536;
-    // FAST over compressed nodes (wide_iter_q, MODE 8) where the context built them
-    const bool qn = mode == 3 && c->q_ok;
-    const uint32_t node_f4 = qn ? zrt::kQuantNodeF4 : 8u;
-    const zrt::LdsPlan lp = zrt::plan_lds(c.get(), mode, stk16, stack_depth, 0, false, false, ZRT_PRNG_XOROSHIRO128,
-                                          node_f4);
-    const uint32_t lds_rows = lp.stack_rows;
-    const uint32_t grid = (n_rays + zrt::kBlock - 1) / zrt::kBlock;
-    const uint64_t n_lanes = uint64_t(grid) * zrt::kBlock;
-    zrt::DevBuf<float> d_rays, d_t;
-    zrt::DevBuf<int32_t> d_slot;
-    d_rays.alloc(6ull * n_rays);
-    d_t.alloc(n_rays);
-    d_slot.alloc(n_rays);
-    HIPCHK(hipMemcpy(d_rays.p, rays, sizeof(float) * 6ull * n_rays, hipMemcpyHostToDevice));
-    HIPCHK(hipMemset(c->scratch.p, 0, zrt::kScratchSlots * sizeof(unsigned long long)));
-    zrt::KArgs a{};
-    a.nodes = c->nodes.p;
-    a.prims = c->prims.p;
-    a.shade = c->shade.p;
-    a.wnodes = qn ? c->qnodes.p : c->wnodes.p;
-    a.wide_stride = qn ? c->q_stride : c->wide_stride;
-    a.node_f4 = node_f4;
-    a.qleaves = qn ? c->qleaves.p : nullptr;
-    a.n_qnodes = qn ? c->q_stride / zrt::kQuantNodeF4 : 0u;
-    a.n_qleaves = qn ? c->n_qleaves : 0u;
-    a.error_flag = reinterpret_cast<uint32_t*>(c->scratch.p + zrt::kErrorSlot);
-    a.n_list = c->use_bvh ? 0 : c->n_prims;
-    a.tri_rcp_fast = c->tri_rcp_fast;
-    a.scene_extent = c->scene_extent;
-    a.paxis_m = zrt::paxis_threshold();
-    for (int k = 0; k < 3; ++k) {
-      a.tri_c[k] = c->tri_c[k];
-      a.tri_h[k] = c->tri_h[k];
-    }
-    a.stack_depth = stack_depth;
-    a.ref_stack = c->stack_depth;
-    a.leaf_of_slot = c->leaf_of_slot.p;
-    a.ref_sph = c->ref_sph.p;
-    for (int k = 0; k < 3; ++k) a.root_c[k] = c->root_c[k];
-    a.origin_bound = c->origin_bound;
-    a.check_origins = 1;  // arbitrary ray origins
-    a.layout = c->layout;
-    a.graze_m = c->graze_m;
-    a.graze_leaf = c->graze_leaf;
-    // tests: ZRT_DEBUG_NO_GUARD=1 traces without the grazing-triangle guard (the
-    // default render kernels' traversal), to record what the guard is for
-    a.guard = std::getenv("ZRT_DEBUG_NO_GUARD") ? 0.0f : c->guard;
-    a.lds_rows = lds_rows;
-    a.n_lanes = uint32_t(n_lanes);
-    a.n_top = qn ? c->q_top : c->n_top;
-    a.lds_top_off = lp.top_off;
-    a.lds_att_off = lp.att_off;
-    const zrt::BufNeed need = zrt::buffer_need(lp, 0, stack_depth, n_lanes, n_lanes, stk16);
-    if (need.ovf_bytes) {
-      c->stack_ovf.alloc(need.ovf_bytes);
-      a.stack_ovf = c->stack_ovf.p;
-    }
-    zrt::check_buffers("trace launch", zrt::BufNeed{0, need.ovf_bytes}, c->att.n, c->stack_ovf.n);
-    a.att_cap = c->att.n;
-    a.ovf_cap = zrt::ovf_cap_elems(c->stack_ovf.n, stk16);
-    void* fn = nullptr;
-#define ZRT_TK(M) (stk16 ? reinterpret_cast<void*>(&zrt::trace_kernel<M, uint16_t>) \
-                         : reinterpret_cast<void*>(&zrt::trace_kernel<M, uint32_t>))
-#ifdef ZRT_ISA_KERNEL
-    fn = nullptr;
-#else
-    fn = mode == 0 ? ZRT_TK(0) : mode == 1 ? ZRT_TK(1) : mode == 2 ? ZRT_TK(2) : qn ? ZRT_TK(8) : ZRT_TK(3);
-#endif
-#undef ZRT_TK
-    const float* rp = d_rays.p;
-    float* tp = d_t.p;
-    int32_t* sp = d_slot.p;
-    uint32_t nn = n_rays;
-    void* args[] = {&a, &rp, &nn, &tp, &sp};
-    HIPCHK(hipLaunchKernel(fn, dim3(grid), dim3(zrt::kBlock), args, lp.bytes, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    unsigned long long err = 0;
-    HIPCHK(hipMemcpy(&err, c->scratch.p + zrt::kErrorSlot, sizeof(err), hipMemcpyDeviceToHost));
-    if (err) return fail(ZRT_E_UNSUPPORTED, zrt::device_error_msg(err));
-    std::vector<int32_t> slot(n_rays);
-    HIPCHK(hipMemcpy(out_t, d_t.p, sizeof(float) * n_rays, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(slot.data(), d_slot.p, sizeof(int32_t) * n_rays, hipMemcpyDeviceToHost));
-    for (uint32_t i = 0; i < n_rays; ++i)
-      out_prim[i] = slot[i] < 0 ? -1 : int32_t(c->slot_to_prim[size_t(slot[i])]);
-    return ZRT_OK;
-  } catch (const zrt::HipError& e) {
-    return zrt::hip_fail(e);
-  } catch (const zrt::Error& e) {
-    return fail(e.code, e.what());
-  } catch (const std::bad_alloc&) {
-    return fail(ZRT_E_NOMEM, "OutOfMemory");
-  }
-}
-
-int zrt_debug_math(int fn, const float* x, const float* y, float* out, uint32_t n, uint32_t device) {
-  if (!x || !out) return fail(ZRT_E_INVALID, "null argument");
-  int rc = zrt::check_device(int(device));
-  if (rc) return rc;
-  try {
-    HIPCHK(hipSetDevice(int(device)));
-    zrt::DevBuf<float> dx, dy, dout;
-    dx.alloc(n);
-    dout.alloc(n);
-    HIPCHK(hipMemcpy(dx.p, x, n * sizeof(float), hipMemcpyHostToDevice));
-    if (y) {
-      dy.alloc(n);
-      HIPCHK(hipMemcpy(dy.p, y, n * sizeof(float), hipMemcpyHostToDevice));
-    }
-    hipLaunchKernelGGL(zrt::debug_math_kernel, dim3((n + 255) / 256), dim3(256), 0, 0, fn, dx.p,
-                       y ? dy.p : nullptr, dout.p, n);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipMemcpy(out, dout.p, n * sizeof(float), hipMemcpyDeviceToHost));
-    return ZRT_OK;
-  }
-  ZRT_CATCH_ALL
-}
-
-int zrt_debug_lds_plans(const zrt_scene* scene, uint32_t* n_checked) {
-  if (!n_checked) return fail(ZRT_E_INVALID, "null argument");
-  *n_checked = 0;
-  int rc = zrt::validate_scene(scene);
-  if (rc) return rc;
-  try {
-    zrt::HostScene h;
-    // (the host BVH build: no device; the compressed nodes built too, so their
-    // plans are checked with the top levels they really keep in LDS)
-    zrt::flatten_scene(&h, scene, scene->n_prims > 10, -1, scene->n_prims > 10 ? 1 : 0);
-    const uint32_t n_mats = uint32_t(h.mats.size());
-    const uint32_t ref_depth = h.use_bvh ? h.bvh_depth + 2 : 0;
-    std::string where;
-    for (int mode : {0, 1, 2, 3}) {
-      for (int loop = 0; loop < (mode == 3 ? 3 : 1); ++loop) {  // lockstep, wavefront, path pool
-        for (bool stk16 : {true, false}) {
-          for (uint32_t prng : {uint32_t(ZRT_PRNG_XOROSHIRO128), uint32_t(ZRT_PRNG_XOSHIRO256)}) {
-            for (uint32_t depth : {0u, 1u, 2u, 5u, 20u, 50u}) {
-              for (uint32_t nf4 : {8u, 4u}) {  // full / compressed wide nodes (the path pool only)
-                if (nf4 == 4u && (loop != 2 || !h.q_ok)) continue;
-                // the plan as the environment has it, and (FAST, 16-bit stack) with the LDS
-                // rows capped as ZRT_STACK_LDS_ROWS16 caps them
-                for (uint32_t cap : {zrt::stack_rows_cap(), 1u, 2u, 4u}) {
-                  const bool capped = cap != zrt::stack_rows_cap();
-                  if (capped && !(mode == 3 && stk16)) continue;
-                  const uint32_t sd = mode == 3 ? std::max(h.wide_stack, ref_depth) : ref_depth;
-                  where = "mode " + std::to_string(mode) + " loop " + std::to_string(loop) + " stk16 " +
-                          std::to_string(int(stk16)) + " prng " + std::to_string(prng) + " depth " +
-                          std::to_string(depth) + " node_f4 " + std::to_string(nf4) +
-                          (capped ? " stack rows capped at " + std::to_string(cap) : std::string());
-                  try {
-                    (void)zrt::plan_lds(nf4 == 4u ? h.q_top : h.n_top, n_mats, mode, stk16, sd, depth, loop == 1,
-                                        loop == 2, prng, nf4, cap);
-                  } catch (const zrt::Error& e) {
-                    throw zrt::Error(e.code, std::string(e.what()) + " (" + where + ")");
-                  }
-                  ++*n_checked;
-                }
-              }
-            }
-          }
-        }
-      }
-    }
-    return ZRT_OK;
-  }
-  ZRT_CATCH_ALL
-}
-
-int zrt_debug_buffer_plans(const zrt_scene* scene, uint32_t legacy, uint32_t* n_checked) {
-  if (!n_checked) return fail(ZRT_E_INVALID, "null argument");
-  *n_checked = 0;
-  int rc = zrt::validate_scene(scene);
-  if (rc) return rc;
-  if (scene->n_prims <= 10) return ZRT_OK;  // no tree: no FAST launch, no probe
-  try {
-    zrt::HostScene h;
-    zrt::flatten_scene(&h, scene, true, -1, 1);
-    const uint32_t n_mats = uint32_t(h.mats.size());
-    const uint32_t sd = std::max(h.wide_stack, h.bvh_depth + 2);  // zrt_render's FAST stack depth
-    for (int loop = 0; loop < 3; ++loop) {  // the render launch: lockstep, wavefront, path pool
-      for (bool stk16 : {true, false}) {
-        for (uint32_t prng : {uint32_t(ZRT_PRNG_XOROSHIRO128), uint32_t(ZRT_PRNG_XOSHIRO256)}) {
-          for (uint32_t depth : {0u, 1u, 2u, 4u, 5u, 6u, 13u, 20u, 50u}) {
-            for (uint32_t nf4 : {8u, 4u}) {
-              if (nf4 == 4u && (loop != 2 || !h.q_ok)) continue;
-              for (uint32_t grid : {64u, 1536u, 2048u}) {  // blocks (the probe: at most the render's)
-               // the plans as the environment has them, and (16-bit stack) with the LDS rows
-               // capped as ZRT_STACK_LDS_ROWS16 caps them: more overflow rows for both launches
-               for (uint32_t cap : {zrt::stack_rows_cap(), 1u, 2u, 4u}) {
-                const bool capped = cap != zrt::stack_rows_cap();
-                if (capped && !stk16) continue;
-                const std::string where = "loop " + std::to_string(loop) + " stk16 " + std::to_string(int(stk16)) +
-                                          " prng " + std::to_string(prng) + " depth " + std::to_string(depth) +
-                                          " node_f4 " + std::to_string(nf4) + " grid " + std::to_string(grid) +
-                                          (capped ? " stack rows capped at " + std::to_string(cap) : std::string());
-                // zrt_render's sizing: the render launch's need, then (schedule_tiles) the
-                // probe's, the buffers grown to the larger of the two
-                const zrt::LdsPlan lp = zrt::plan_lds(nf4 == 4u ? h.q_top : h.n_top, n_mats, 3, stk16, sd, depth,
-                                                      loop == 1, loop == 2, prng, nf4, cap);
-                const uint64_t n_lanes = uint64_t(grid) * zrt::kBlock;
-                const uint64_t n_paths = loop == 2 ? uint64_t(grid) * zrt::kBlockPaths : n_lanes;
-                const zrt::BufNeed rn = zrt::buffer_need(lp, depth, sd, n_paths, n_lanes, stk16);
-                const zrt::LdsPlan pp = zrt::plan_lds(h.n_top, n_mats, 3, stk16, sd, depth, false, false, prng, 8, cap);
-                const zrt::BufNeed pn = zrt::buffer_need(pp, depth, sd, n_lanes, n_lanes, stk16);
-                uint64_t att = rn.att_elems, ovf = std::max(rn.ovf_bytes, pn.ovf_bytes);
-                // legacy = 1: the sizing before commit 4072f5f, where the probe shared the
-                // render launch's attenuation rows without growing them
-                if (!legacy) att = std::max(att, pn.att_elems);
-                try {
-                  zrt::check_buffers("scheduling probe", pn, att, ovf);
-                  zrt::check_buffers("render launch", rn, att, ovf);
-                } catch (const zrt::Error& e) {
-                  throw zrt::Error(e.code, std::string(e.what()) + " (" + where + ")");
-                }
-                ++*n_checked;
-               }
-              }
-            }
-          }
-        }
-      }
-    }
-    return ZRT_OK;
-  }
-  ZRT_CATCH_ALL
-}
-
-int zrt_debug_launch_plan(const zrt_scene* scene, const zrt_params* params, zrt_launch_plan* out) {
-  if (!params || !out) return fail(ZRT_E_INVALID, "null argument");
-  std::memset(out, 0, sizeof(*out));
-  int rc = zrt::validate_scene(scene);
-  if (rc) return rc;
-  if (params->traversal > ZRT_TRAVERSAL_BINARY) return fail(ZRT_E_INVALID, "unknown traversal");
-  try {
-    const bool use_bvh = params->bounded_volume_hierarchy != 0 && scene->n_prims > 10;  // (zrt_ctx_create)
-    zrt::HostScene h;
-    zrt::flatten_scene(&h, scene, use_bvh, -1);
-    const zrt::LaunchPlan P = zrt::plan_launch(zrt::shape_of(h), params);
-    out->mode = uint32_t(P.mode);
-    out->kmode = uint32_t(P.kmode);
-    out->sampling_loop = zrt::reported_loop(P.kmode);
-    out->stk16 = P.stk16;
-    out->wf = P.wf;
-    out->pool = P.pool;
-    out->qnodes = P.qn;
-    out->guard_on = P.guard_on;
-    out->stack_depth = P.stack_depth;
-    out->stack_rows = P.lp.stack_rows;
-    out->att_rows = P.lp.att_rows;
-    out->att_rows_per_path = zrt::att_rows_per_path(P.lp, params->max_depth);
-    out->mats_in_lds = P.lp.mats_in_lds;
-    out->lds_bytes = uint32_t(P.lp.bytes);
-    out->ovf_bytes_per_lane = zrt::buffer_need(P.lp, params->max_depth, P.stack_depth, 1, 1, P.stk16).ovf_bytes;
-    return ZRT_OK;
-  }
-  ZRT_CATCH_ALL
-}
-
-int zrt_debug_lean_kernel(const zrt_scene* scene, const zrt_camera* camera, const zrt_params* params, uint32_t* lean) {
-  if (!camera || !params || !lean) return fail(ZRT_E_INVALID, "null argument");
-  *lean = 0;
-  int rc = zrt::validate_scene(scene);
-  if (rc) return rc;
-  if (params->traversal > ZRT_TRAVERSAL_BINARY) return fail(ZRT_E_INVALID, "unknown traversal");
-  try {
-    const bool use_bvh = params->bounded_volume_hierarchy != 0 && scene->n_prims > 10;  // (zrt_ctx_create)
-    zrt::HostScene h;
-    zrt::flatten_scene(&h, scene, use_bvh, -1);
-    const zrt::LaunchPlan P = zrt::plan_launch(zrt::shape_of(h), params);
-    // (as zrt_ctx_render_tiles decides)
-    *lean = zrt::lean_launch(P, (params->flags & ZRT_FLAG_STATS) != 0,
-                             zrt::camera_inside(camera, h.root_c, h.origin_bound))
-                ? 1u
-                : 0u;
-    return ZRT_OK;
-  }
-  ZRT_CATCH_ALL
-}
-
-int zrt_debug_qnodes(const zrt_scene* scene, uint64_t* n_checked) {
-  if (!n_checked) return fail(ZRT_E_INVALID, "null argument");
-  *n_checked = 0;
-  int rc = zrt::validate_scene(scene);
-  if (rc) return rc;
-  if (scene->n_prims <= 10) return fail(ZRT_E_INVALID, "no BVH for <= 10 surfaces (raytrace.zig:124-133)");
-  try {
-    zrt::HostScene h;
-    zrt::flatten_scene(&h, scene, true, -1, 1);  // (the compressed nodes asked for explicitly)
-    if (!h.q_ok) return fail(ZRT_E_UNSUPPORTED, "the encoder refused this tree (a non-finite plane)");
-    const uint32_t nn = h.q_stride / zrt::kQuantNodeF4, nw = h.wide_stride / 8u;
-    if (nn != nw) return fail(ZRT_E_UNSUPPORTED, "compressed and full trees differ in node count");
-    auto bad = [](const std::string& what, uint32_t o, uint32_t i, int k) {
-      return fail(ZRT_E_UNSUPPORTED, what + " (octant " + std::to_string(o) + ", node " + std::to_string(i) + ", slot " +
-                                         std::to_string(k) + ")");
-    };
-    for (uint32_t o = 0; o < 8; ++o) {
-      for (uint32_t i = 0; i < nn; ++i) {
-        const float4* F = &h.wn[size_t(o) * h.wide_stride + 8u * i];  // full node, this octant's copy
-        uint32_t W[16];
-        std::memcpy(W, &h.qn[size_t(o) * h.q_stride + zrt::kQuantNodeF4 * i], sizeof(W));
-        float org[3], step[3];
-        std::memcpy(org, W, 12);
-        for (int a = 0; a < 3; ++a) step[a] = std::ldexp(1.0f, int((W[3] >> (8 * a)) & 0xffu) - 127);
-        int32_t fr[4], qr[4], fb[4];
-        std::memcpy(fr, &F[6], 16);
-        std::memcpy(fb, &F[7], 16);
-        std::memcpy(qr, &W[10], 16);
-        for (int k = 0; k < 4; ++k) {
-          const float* fn = reinterpret_cast<const float*>(F);
-          const bool empty = qr[k] == zrt::kEmptyRef;
-          for (int a = 0; a < 3 && !empty; ++a) {
-            const double qn = double((W[4 + a] >> (8 * k)) & 0xffu), qf = double((W[7 + a] >> (8 * k)) & 0xffu);
-            const double dn = double(org[a]) + qn * double(step[a]), df = double(org[a]) + qf * double(step[a]);
-            if (double(float(dn)) != dn || double(float(df)) != df) return bad("a plane does not decode exactly", o, i, k);
-            const bool neg = (o >> a) & 1u;  // the near plane is the max one
-            const double full_n = fn[4 * a + k], full_f = fn[4 * (3 + a) + k];
-            if (neg ? !(dn >= full_n && df <= full_f) : !(dn <= full_n && df >= full_f))
-              return bad("a decoded box does not contain the full node's", o, i, k);
-          }
-          if (!empty && qr[k] >= 0 && qr[k] != fr[k]) return bad("an inner child ref differs", o, i, k);
-          if (!empty && qr[k] < 0) {
-            const bool sph = qr[k] < -zrt::kSphereSlotBias;
-            const uint32_t L = uint32_t(-(sph ? qr[k] + zrt::kSphereSlotBias : qr[k]) - 1);
-            if (size_t(L) * zrt::kLeafRecF4 + 1 >= h.ql.size()) return bad("a leaf record index past the records", o, i, k);
-            const float4 mn = h.ql[zrt::kLeafRecF4 * size_t(L)], mx = h.ql[zrt::kLeafRecF4 * size_t(L) + 1];
-            const float m[3] = {mn.x, mn.y, mn.z}, M[3] = {mx.x, mx.y, mx.z};
-            for (int a = 0; a < 3; ++a) {
-              const bool neg = (o >> a) & 1u;
-              const float full_n = fn[4 * a + k], full_f = fn[4 * (3 + a) + k];
-              const float rn = neg ? M[a] : m[a], rf = neg ? m[a] : M[a];
-              if (std::memcmp(&rn, &full_n, 4) || std::memcmp(&rf, &full_f, 4)) return bad("a leaf record's box differs", o, i, k);
-            }
-            int32_t ra, rb;
-            std::memcpy(&ra, &mn.w, 4);
-            std::memcpy(&rb, &mx.w, 4);
-            const int32_t full_a = sph ? fr[k] + zrt::kSphereSlotBias : fr[k];
-            if (ra != full_a || rb != fb[k] || sph != (fr[k] < -zrt::kSphereSlotBias))
-              return bad("a leaf record's refs differ", o, i, k);
-          }
-          ++*n_checked;
-        }
-      }
-    }
-    return ZRT_OK;
-  }
-  ZRT_CATCH_ALL
-}
-
-int zrt_debug_division(uint64_t n, uint64_t* counts, uint32_t device) {
-  if (!counts) return fail(ZRT_E_INVALID, "null argument");
-  int rc = zrt::check_device(int(device));
-  if (rc) return rc;
-  try {
-    HIPCHK(hipSetDevice(int(device)));
-    zrt::DevBuf<unsigned long long> d;
-    d.alloc(5);
-    HIPCHK(hipMemset(d.p, 0, 5 * sizeof(unsigned long long)));
-    hipLaunchKernelGGL(zrt::debug_division_kernel, dim3(8192), dim3(256), 0, 0, n, d.p);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipMemcpy(counts, d.p, 5 * sizeof(uint64_t), hipMemcpyDeviceToHost));
-    return ZRT_OK;
-  }
-  ZRT_CATCH_ALL
-}
-
-int zrt_debug_rng(uint32_t prng, uint64_t key, uint64_t* out, uint32_t n, uint32_t device) {
-  if (!out) return fail(ZRT_E_INVALID, "null argument");
-  int rc = zrt::check_device(int(device));
-  if (rc) return rc;
-  try {
-    HIPCHK(hipSetDevice(int(device)));
-    zrt::DevBuf<unsigned long long> d;
-    d.alloc(n);
-    if (prng == ZRT_PRNG_XOSHIRO256)
-      hipLaunchKernelGGL(zrt::debug_rng_kernel<ZRT_PRNG_XOSHIRO256>, dim3(1), dim3(64), 0, 0, key, d.p, n);
-    else
-      hipLaunchKernelGGL(zrt::debug_rng_kernel<ZRT_PRNG_XOROSHIRO128>, dim3(1), dim3(64), 0, 0, key, d.p, n);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipMemcpy(out, d.p, n * sizeof(uint64_t), hipMemcpyDeviceToHost));
-    return ZRT_OK;
-  }
-  ZRT_CATCH_ALL
-}
-
-}  // extern "C"
+}  // namespace zrt
