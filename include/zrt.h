@@ -580,6 +580,55 @@ int zrt_render_adaptive_progress(const zrt_scene* scene, const zrt_camera* camer
 int zrt_debug_adapt_plan(const zrt_params* params, const zrt_adaptive* adaptive, uint32_t* levels,
                          uint32_t cap, uint32_t* n_levels);
 
+/* ---- the variance plane: what a run's chunk sums say of its noise ------------ *
+ * A pixel's accumulator is the sum of its chunk sums S_j (one per sample chunk,
+ * added in chunk order).  The run also keeps, per pixel, in f32, nothing fused,
+ * in chunk order:
+ *     l_j = (S_j.r + S_j.g) + S_j.b        Q = Q + l_j * l_j        (Q = 0 at begin)
+ * A ragged last chunk goes into the sums but not into Q, and a device error
+ * leaves NaN in Q as in the sums.  The scatter of the l_j around their mean is an
+ * unbiased estimate of the variance of the preview pixel's brightness r + g + b
+ * (the s of the adaptive rule).
+ *
+ * zrt_ctx_accum_variance reads the live plain or adaptive run and writes one f32
+ * per pixel of this rank's tiles to dev_tiles_var (a device pointer, tile-major,
+ * n_tiles*64 f32: dev_tiles' layout with one channel) on hip_stream (NULL: the
+ * context's own).  It waits for the run's last pass, then enqueues.  c = the
+ * sample chunk in use, n = the samples in the pixel's accumulator (samples_done;
+ * in an adaptive run the tile's own count, zrt_ctx_adapt_samples), k = n / c.  On
+ * the host, in f32, per distinct k (per tile in an adaptive run):
+ *     ik = 1.0f / float(k)        sc = 1.0f / (float(k - 1) * (float(c) * float(c)))
+ * Per in-frame pixel, acc = its sums, in f32, nothing fused:
+ *     M    = (acc.r + acc.g) + acc.b
+ *     mean = M * ik
+ *     v    = Q * ik - mean * mean ;  v = v > 0 ? v : 0      (a NaN M or Q gives NaN, not 0)
+ *     var  = v * sc
+ * Out-of-frame slots are 0.  Q * ik - mean * mean cancels: its relative error is
+ * about k * 2^-23 * mean^2 / v, clamped at 0.
+ * ZRT_E_INVALID: no live run, no pass yet, a tile with n % c != 0 (a ragged pass
+ * happened) or a rendered tile with k < 2.  After a device error the plane is NaN
+ * and the status is the run's sticky ZRT_E_UNSUPPORTED. */
+int zrt_ctx_accum_variance(zrt_ctx* ctx, float* dev_tiles_var, void* hip_stream);
+
+/* zrt_ctx_assemble / zrt_ctx_assemble_padded for one-channel planes: gathered
+ * tile-major planes (n_tiles*64 f32 per rank; stride_tiles 0: packed rank after
+ * rank, else rank r starts at tile r * stride_tiles) into the frame's layout,
+ * dev_frame: width*height f32, zero outside the rendered square. */
+int zrt_ctx_assemble_plane(zrt_ctx* ctx, const zrt_params* params, const float* dev_gathered,
+                           uint32_t stride_tiles, float* dev_frame, void* hip_stream);
+
+/* (c, n) -> (k, ik, sc) as zrt_ctx_accum_variance computes them, with no device
+ * (the launch path calls the same function; it returns the refusals above: n == 0,
+ * n % c != 0, k < 2).  Only params->sample_chunk is read beyond the validation of
+ * the params; n_samples need not lie under params->samples_per_pixel. */
+typedef struct zrt_variance_plan {
+  uint32_t chunk;  /* c: the sample chunk in use (sample_chunk, or 32 for 0) */
+  uint32_t k;      /* whole chunks in the accumulator */
+  float ik;        /* 1.0f / float(k) */
+  float sc;        /* 1.0f / (float(k - 1) * (float(c) * float(c))) */
+} zrt_variance_plan;
+int zrt_debug_variance_plan(const zrt_params* params, uint32_t n_samples, zrt_variance_plan* out);
+
 /* ---- denoising: first-hit feature buffers and an a-trous filter ------------- *
  * A frame of few samples is noisy; an edge-avoiding a-trous wavelet filter
  * (Dammertz et al. 2010) smooths it where the surface under a pixel's
@@ -673,6 +722,78 @@ int zrt_ctx_denoise_ms(zrt_ctx* ctx, double* ms);
 int zrt_render_denoised(const zrt_scene* scene, const zrt_camera* camera, const zrt_params* params,
                         const zrt_adaptive* adaptive, const zrt_denoise* dn, float* out_rgb, float* out_noisy,
                         float* out_features, zrt_stats* stats, double* denoise_ms);
+
+/* ---- variance-guided denoising: the a-trous filter with per-pixel variance --- *
+ * The filter above tells noise from an edge by one global sigma_color.  This one
+ * (the spatial filter of SVGF, Schied et al. 2017) takes a per-pixel variance of
+ * the brightness r + g + b - zrt_ctx_accum_variance's plane, assembled - scales
+ * its colour test by the local standard deviation, and filters the variance
+ * along with the colour.  With ZRT_DN_DEMODULATE it filters the frame divided by
+ * the first hit's albedo, so texture detail is not treated as noise.
+ *
+ * Definition.  Everything of the definition above holds except what is said
+ * here; all f32, nothing fused, IEEE sqrtf and `/`.  V_0 = the variance plane.
+ * L(x) = (x.r + x.g) + x.b.  sigma_color is in standard deviations of L, does not
+ * halve (there is no kc: the variance shrinks by itself), and 0 switches the
+ * colour term off as before; on the host sc_l = sigma_color.
+ *
+ * Demodulation (ZRT_DN_DEMODULATE only), a_min = 2^-6, per pixel p of D with
+ * id(p) != 0, A its albedo:
+ *     C_0(p).c = A.c > a_min ? frame(p).c / A.c : frame(p).c          per channel
+ *     am = ((A.r + A.g) + A.b) * (1.0f / 3.0f)
+ *     V_0(p) = am > a_min ? V(p) / (am * am) : V(p)
+ * Misses are unchanged.  After the last iteration the output's channel c is
+ * multiplied by A.c under the same per-channel test and the output variance by
+ * am * am under its test (a NaN albedo fails the tests: unchanged).
+ *
+ * Iteration i, per pixel p of D.  First the variance smoothed over 3 x 3:
+ * g = 0; dy = -1 .. 1 (outer), dx = -1 .. 1 (inner), q = p + (dx, dy) (adjacent
+ * pixels at every step), wt = 1/4 (dx = dy = 0), 1/8 (dx = 0 or dy = 0), else 1/16:
+ *     g = g + (q in D ? V_i(q) : V_i(p)) * wt
+ * Then, with the colour term on, kl = 1.0f / (sigma_color * sqrtf(g) + 0x1p-20f).
+ * vacc = 0 beside acc and wsum.  The taps are the definition's, with
+ *     t_c = 1.0f - |L(C_i(p)) - L(C_i(q))| * kl
+ * and a tap that survives with weight w also adds vacc = vacc + V_i(q) * (w * w)
+ * after wsum = wsum + w; the centre tap adds V_i(p) * (w0 * w0), w0 = h(0) * h(0).
+ *     C_(i+1)(p).c = acc.c / wsum        V_(i+1)(p) = vacc / (wsum * wsum)
+ * The outputs are C_iterations and V_iterations (the variance left in the
+ * filtered frame, under the assumption of independent pixels); pixels outside D
+ * are copied in both.
+ *
+ * NaN.  A NaN variance at p or beside it makes g and kl NaN, so every tested tap
+ * of p fails and p keeps its own colour through the untested centre tap; a NaN
+ * variance reached by a surviving tap makes V_(i+1)(p) NaN, and p's taps fail
+ * from the next iteration on.  Colours never become NaN through the variance:
+ * the NaN-frame behaviour of the filter above carries over.  (With the colour
+ * term off the variance guides nothing and is only filtered.) */
+enum { ZRT_DN_DEMODULATE = 1u };
+
+/* The default guided filter and flags (host only): the winner of the search of
+ * tools/denoise_guided_probe.py (profiles/r11/guided/defaults.json). */
+int zrt_denoise_guided_defaults(zrt_denoise* out, uint32_t* flags);
+
+/* zrt_ctx_denoise with the definition above.  dev_variance: width*height f32 in
+ * the frame's layout; dev_out_variance (may be NULL): the same, written with
+ * V_iterations.  ZRT_E_INVALID: what zrt_ctx_denoise refuses, a null dev_variance,
+ * dev_out_variance == dev_variance, an unknown flag.  zrt_ctx_denoise_ms reports
+ * the last filter of either kind. */
+int zrt_ctx_denoise_guided(zrt_ctx* ctx, const zrt_params* params, const zrt_denoise* dn, uint32_t flags,
+                           const float* dev_frame, const float* dev_features, const float* dev_variance,
+                           float* dev_out, float* dev_out_variance, void* hip_stream);
+
+/* zrt_render_denoised with the guided filter.  The noisy frame is rendered as an
+ * accumulation run of one pass (adaptive NULL) or as the adaptive run, so
+ * out_noisy stays bit for bit zrt_render's / zrt_render_adaptive's; then
+ * zrt_ctx_accum_variance, both assembles, zrt_ctx_features and
+ * zrt_ctx_denoise_guided.  dn NULL: zrt_denoise_guided_defaults' filter (flags
+ * are the caller's either way).  out_variance (may be NULL): width*height f32,
+ * the noisy frame's variance plane.  ZRT_E_INVALID before any device work when
+ * samples_per_pixel is not a multiple of the sample chunk or holds fewer than two
+ * chunks: choose a smaller params->sample_chunk. */
+int zrt_render_denoised_guided(const zrt_scene* scene, const zrt_camera* camera, const zrt_params* params,
+                               const zrt_adaptive* adaptive, const zrt_denoise* dn, uint32_t flags, float* out_rgb,
+                               float* out_noisy, float* out_features, float* out_variance, zrt_stats* stats,
+                               double* denoise_ms);
 
 /* ---- host-side scene ingestion (the caller side of the seam) ------------- *
  * Restatement of scenes.zig / obj_reader.zig / png_image.zig texture loading

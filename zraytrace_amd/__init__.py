@@ -20,7 +20,7 @@ from . import _ffi
 from ._ffi import (ZRT_PRNG_XOROSHIRO128, ZRT_PRNG_XOSHIRO256, ZRT_RNG_COUNTER,  # noqa: F401
                    ZRT_RNG_REFERENCE_STREAM, ZRT_TRAVERSAL_FAST, ZRT_TRAVERSAL_REFERENCE,
                    ZRT_TRAVERSAL_BINARY, ZRT_FLAG_STATS, ZRT_FLAG_NO_SCHEDULE, ZRT_FLAG_SCANLINES, ZRT_FLAG_GUARD,
-                   ZrtError, check)
+                   ZRT_DN_DEMODULATE, ZrtError, check)
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ASSETS = os.path.join(REPO, "assets")
@@ -254,6 +254,52 @@ def render_denoised(scene, camera: _ffi.Camera, params: RenderParams, tolerance:
     return rgb, noisy, features, stats
 
 
+def denoise_guided_defaults():
+    """The default variance-guided filter (zrt_denoise_guided_defaults; no device): (the
+    zrt_denoise tools/denoise_guided_probe.py's search chose, its flags)."""
+    out = _ffi.Denoise()
+    flags = C.c_uint32()
+    check(lib().zrt_denoise_guided_defaults(C.byref(out), C.byref(flags)))
+    return out, flags.value
+
+
+def debug_variance_plan(params: RenderParams, n_samples: int) -> dict:
+    """How the variance plane scales a pixel holding n_samples samples in chunks of
+    params.sample_chunk (zrt_debug_variance_plan; no device): chunk, k, ik, sc.  Raises
+    ZrtError for what zrt_ctx_accum_variance would refuse."""
+    out = _ffi.VariancePlan()
+    p = params.abi()
+    check(lib().zrt_debug_variance_plan(C.byref(p), n_samples, C.byref(out)))
+    return out.as_dict()
+
+
+def render_denoised_guided(scene, camera: _ffi.Camera, params: RenderParams, tolerance: float = None,
+                           first_level: int = 0, denoise: _ffi.Denoise = None, flags: int = None):
+    """render_denoised() with the variance-guided filter (zrt_render_denoised_guided; denoise
+    None: the guided defaults, flags None: their flags).  params.samples_per_pixel must be
+    two or more whole sample chunks.  Returns (rgb, noisy, features, variance float32[H, W]:
+    the noisy frame's variance plane, stats)."""
+    view = scene.view if isinstance(scene, LoadedScene) else scene
+    f = C.POINTER(C.c_float)
+    rgb = np.zeros((params.height, params.width, 3), dtype=np.float32)
+    noisy = np.zeros((params.height, params.width, 3), dtype=np.float32)
+    features = np.zeros((params.height, params.width, 8), dtype=np.float32)
+    variance = np.zeros((params.height, params.width), dtype=np.float32)
+    st = _ffi.Stats()
+    ms = C.c_double()
+    p = params.abi()
+    ad = C.byref(_adaptive(tolerance, first_level)) if tolerance is not None else None
+    if flags is None:
+        flags = denoise_guided_defaults()[1]
+    dn = C.byref(denoise) if denoise is not None else None
+    check(lib().zrt_render_denoised_guided(view, C.byref(camera), C.byref(p), ad, dn, flags, rgb.ctypes.data_as(f),
+                                           noisy.ctypes.data_as(f), features.ctypes.data_as(f),
+                                           variance.ctypes.data_as(f), C.byref(st), C.byref(ms)))
+    stats = st.as_dict()
+    stats["denoise_ms"] = ms.value
+    return rgb, noisy, features, variance, stats
+
+
 def _scanlines_np(rows) -> np.ndarray:
     """zrt_scanline[height] -> uint64 array [height, 6] (columns: _ffi.SCANLINE_FIELDS)."""
     return np.ctypeslib.as_array(rows).view(np.uint64).reshape(len(rows), 6).copy()
@@ -436,6 +482,30 @@ class RenderContext:
         p = params.abi()
         check(lib().zrt_ctx_denoise(self._h, C.byref(p), C.byref(dn), C.c_void_p(dev_frame),
                                     C.c_void_p(dev_features), C.c_void_p(dev_out), C.c_void_p(stream or None)))
+
+    def accum_variance(self, dev_tiles_var: int, stream: int = 0):
+        """The live run's variance plane (zrt_ctx_accum_variance): one f32 per pixel of this
+        rank's tiles, tile-major, at the device pointer dev_tiles_var."""
+        check(lib().zrt_ctx_accum_variance(self._h, C.c_void_p(dev_tiles_var), C.c_void_p(stream or None)))
+
+    def assemble_plane(self, params: RenderParams, dev_gathered: int, dev_frame: int, stride_tiles: int = 0,
+                       stream: int = 0):
+        """assemble() / assemble_padded() for one-channel planes (zrt_ctx_assemble_plane;
+        stride_tiles 0: packed rank after rank)."""
+        p = params.abi()
+        check(lib().zrt_ctx_assemble_plane(self._h, C.byref(p), C.c_void_p(dev_gathered), stride_tiles,
+                                           C.c_void_p(dev_frame), C.c_void_p(stream or None)))
+
+    def denoise_guided(self, params: RenderParams, dn: _ffi.Denoise, flags: int, dev_frame: int, dev_features: int,
+                       dev_variance: int, dev_out: int, dev_out_variance: int = 0, stream: int = 0):
+        """denoise() with the variance-guided filter (zrt_ctx_denoise_guided): dev_variance is
+        width * height f32 in the frame's layout, dev_out_variance (0: not wanted) receives the
+        filtered variance."""
+        p = params.abi()
+        check(lib().zrt_ctx_denoise_guided(self._h, C.byref(p), C.byref(dn), flags, C.c_void_p(dev_frame),
+                                           C.c_void_p(dev_features), C.c_void_p(dev_variance or None),
+                                           C.c_void_p(dev_out), C.c_void_p(dev_out_variance or None),
+                                           C.c_void_p(stream or None)))
 
     def denoise_ms(self) -> float:
         """Device time of the last denoise() in ms (zrt_ctx_denoise_ms; waits for it)."""

@@ -34,6 +34,7 @@ ZRT_FLAG_STATS = 1
 ZRT_FLAG_NO_SCHEDULE = 2
 ZRT_FLAG_SCANLINES = 4
 ZRT_FLAG_GUARD = 8
+ZRT_DN_DEMODULATE = 1
 
 
 class Vec3(C.Structure):
@@ -171,6 +172,13 @@ class Denoise(C.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_ if name != "reserved"}
 
 
+class VariancePlan(C.Structure):
+    _fields_ = [("chunk", C.c_uint32), ("k", C.c_uint32), ("ik", C.c_float), ("sc", C.c_float)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
 class BvhNode(C.Structure):
     _fields_ = [("min", Vec3), ("left", C.c_int32), ("max", Vec3), ("right", C.c_int32)]
 
@@ -238,6 +246,16 @@ SIGNATURES = [
     ("zrt_denoise_defaults", C.c_int, [C.POINTER(Denoise)]),
     ("zrt_ctx_denoise", C.c_int, [_P, C.POINTER(Params), C.POINTER(Denoise), _P, _P, _P, _P]),
     ("zrt_ctx_denoise_ms", C.c_int, [_P, C.POINTER(C.c_double)]),
+    ("zrt_ctx_accum_variance", C.c_int, [_P, _P, _P]),
+    ("zrt_ctx_assemble_plane", C.c_int, [_P, C.POINTER(Params), _P, C.c_uint32, _P, _P]),
+    ("zrt_debug_variance_plan", C.c_int, [C.POINTER(Params), C.c_uint32, C.POINTER(VariancePlan)]),
+    ("zrt_denoise_guided_defaults", C.c_int, [C.POINTER(Denoise), C.POINTER(C.c_uint32)]),
+    ("zrt_ctx_denoise_guided", C.c_int, [_P, C.POINTER(Params), C.POINTER(Denoise), C.c_uint32, _P, _P, _P, _P, _P,
+                                         _P]),
+    ("zrt_render_denoised_guided", C.c_int, [C.POINTER(Scene), C.POINTER(Camera), C.POINTER(Params),
+                                             C.POINTER(Adaptive), C.POINTER(Denoise), C.c_uint32,
+                                             C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                             C.POINTER(C.c_float), C.POINTER(Stats), C.POINTER(C.c_double)]),
     ("zrt_scene_load", C.c_int, [C.c_uint32, C.c_char_p, C.POINTER(_P), C.POINTER(Camera)]),
     ("zrt_scene_view", C.POINTER(Scene), [_P]),
     ("zrt_scene_free", None, [_P]),

@@ -27,6 +27,10 @@
 // the PNG is the denoised frame, $ZRT_DENOISE_NOISY=<file.png> also receives the
 // unfiltered one.  It composes with $ZRT_ADAPTIVE_TOL (no level or scanline lines then,
 // and no sample map) and is refused with $ZRT_DEVICES or $ZRT_PASS_SAMPLES.
+// $ZRT_DENOISE_VARIANCE=1 beside $ZRT_DENOISE selects the variance-guided filter
+// (zrt_render_denoised_guided; $ZRT_DENOISE=1: its own defaults), =2 adds albedo
+// demodulation; the samples must then be two or more whole sample chunks
+// ($ZRT_SAMPLE_CHUNK sets params.sample_chunk, default 32).
 #include <unistd.h>
 
 #include <chrono>
@@ -164,6 +168,7 @@ int main(int argc, char** argv) {
   params.seed = 42;  // DefaultPrng.init(42) in every scene
   params.world_size = 1;
   if (const char* dev = std::getenv("ZRT_DEVICE")) params.device = uint32_t(std::atoi(dev));
+  if (const char* chunk = std::getenv("ZRT_SAMPLE_CHUNK")) params.sample_chunk = uint32_t(std::strtoul(chunk, nullptr, 10));
   // $ZRT_DEVICES="0,1,...,7": tiles over those GPUs, one RCCL gather (zrt_render_multi)
   std::vector<uint32_t> devices;
   if (const char* list = std::getenv("ZRT_DEVICES")) {
@@ -195,6 +200,8 @@ int main(int argc, char** argv) {
   // output file is the a-trous-filtered frame (zrt_render_denoised); $ZRT_DENOISE_NOISY=path
   // also writes the unfiltered one
   const char* dn_env = std::getenv("ZRT_DENOISE");
+  const char* var_env = dn_env ? std::getenv("ZRT_DENOISE_VARIANCE") : nullptr;
+  uint32_t dn_flags = 0;
   zrt_denoise dn;
   if (dn_env) {
     if (pass_env || !devices.empty()) {
@@ -203,7 +210,19 @@ int main(int argc, char** argv) {
       zrt_scene_free(data);
       return 1;
     }
-    zrt_denoise_defaults(&dn);
+    if (var_env) {
+      const int v = std::atoi(var_env);
+      if (v != 1 && v != 2) {
+        std::fprintf(stderr, "error: ZRT_DENOISE_VARIANCE is 1 (variance-guided) or 2 (with albedo demodulation)\n");
+        zrt_scene_free(data);
+        return 1;
+      }
+      uint32_t default_flags = 0;
+      zrt_denoise_guided_defaults(&dn, &default_flags);
+      dn_flags = v == 2 ? uint32_t(ZRT_DN_DEMODULATE) : 0u;
+    } else {
+      zrt_denoise_defaults(&dn);
+    }
     if (std::strchr(dn_env, ',')) {
       unsigned iters = 0;
       if (std::sscanf(dn_env, "%u,%f,%f,%f,%f", &iters, &dn.sigma_color, &dn.sigma_normal, &dn.sigma_albedo,
@@ -237,8 +256,12 @@ int main(int argc, char** argv) {
     if (tol_env) ad.tolerance = std::strtof(tol_env, nullptr);
     if (const char* first = std::getenv("ZRT_ADAPTIVE_FIRST")) ad.first_level = uint32_t(std::strtoul(first, nullptr, 10));
     noisy.assign(image.size(), 0.0f);
-    rc = zrt_render_denoised(scene, &camera, &params, tol_env ? &ad : nullptr, &dn, image.data(), noisy.data(), nullptr,
-                             &stats, &denoise_ms);
+    if (var_env)
+      rc = zrt_render_denoised_guided(scene, &camera, &params, tol_env ? &ad : nullptr, &dn, dn_flags, image.data(),
+                                      noisy.data(), nullptr, nullptr, &stats, &denoise_ms);
+    else
+      rc = zrt_render_denoised(scene, &camera, &params, tol_env ? &ad : nullptr, &dn, image.data(), noisy.data(),
+                               nullptr, &stats, &denoise_ms);
   } else if (tol_env) {
     zrt_adaptive ad;
     std::memset(&ad, 0, sizeof(ad));
@@ -301,8 +324,9 @@ int main(int argc, char** argv) {
                double(stats.rays_processed) / render_runtime / 1e6, call, stats.n_gpus);
 
   if (dn_env)
-    std::fprintf(stderr, "  Denoise:               %u iterations, %.3f ms\n",
-                 dn.iterations ? dn.iterations : unsigned(ZRT_DEFAULT_DENOISE_ITERATIONS), denoise_ms);
+    std::fprintf(stderr, "  Denoise:               %u iterations, %.3f ms%s\n",
+                 dn.iterations ? dn.iterations : unsigned(ZRT_DEFAULT_DENOISE_ITERATIONS), denoise_ms,
+                 !var_env ? "" : dn_flags ? " (variance-guided, demodulated)" : " (variance-guided)");
 
   rc = zrt_image_write_png(filename, image.data(), width, height);
   if (const char* path = std::getenv("ZRT_DENOISE_NOISY"); path && dn_env && rc == ZRT_OK)

@@ -351,8 +351,9 @@ std::unique_ptr<zrt_ctx> ctx_on_device(const HostScene& h, int device) {
   return c;
 }
 
+// channels: 3 (the frame) or 1 (a plane, zrt_ctx_assemble_plane)
 static int assemble(zrt_ctx* c, const zrt_params* p, const float* dev_gathered, uint32_t stride_tiles, float* dev_frame,
-             void* hip_stream) {
+             void* hip_stream, uint32_t channels = 3) {
   if (!c || !dev_gathered || !dev_frame) return fail(ZRT_E_INVALID, "null argument");
   const int rc = validate_params(p);
   if (rc) return rc;
@@ -373,10 +374,11 @@ static int assemble(zrt_ctx* c, const zrt_params* p, const float* dev_gathered, 
       c->rank_base.upload(base);
       total = base[p->world_size];
     }
-    HIPCHK(hipMemsetAsync(dev_frame, 0, sizeof(float) * 3 * size_t(p->width) * p->height, st));
+    HIPCHK(hipMemsetAsync(dev_frame, 0, sizeof(float) * channels * size_t(p->width) * p->height, st));
     if (total) {
-      HIPCHK(launch_assemble(st, dev_gathered, dev_frame, stride_tiles ? nullptr : c->rank_base.p, p->world_size,
-                             g.tiles_x, g.xbound, p->height, p->width, total, stride_tiles * 64u, g.n_tiles));
+      HIPCHK((channels == 1 ? launch_assemble_plane : launch_assemble)(
+          st, dev_gathered, dev_frame, stride_tiles ? nullptr : c->rank_base.p, p->world_size, g.tiles_x, g.xbound,
+          p->height, p->width, total, stride_tiles * 64u, g.n_tiles));
     }
     return ZRT_OK;
   }
@@ -646,6 +648,8 @@ static int launch_frame(zrt_ctx* c, const zrt_camera* cam, const zrt_params* p, 
     HIPCHK(hipEventRecord(c->ev1, st));
     if (run_pass) {
       HIPCHK(hipMemsetAsync(c->metrics.p, 0, zrt::kMetricWords * sizeof(unsigned long long), st));
+      // the chunk sums that enter the second moment: all but a ragged last one (zrt.h "the variance plane")
+      const uint32_t q_chunks = n_chunks - (pass.last_chunk < chunk ? 1u : 0u);
       if (adapt) {
         // resolve the active tiles, decide (levels 1 .. last - 1), pack the survivors in
         // order into the other list; the host reads their number (zrt_ctx_adapt_level)
@@ -655,7 +659,8 @@ static int launch_frame(zrt_ctx* c, const zrt_camera* cam, const zrt_params* p, 
         if (n_act > 0) {
           HIPCHK(zrt::launch_resolve(st, c->partial.p, c->accum.p, dev_tiles, c->active[c->adapt_cur].p, n_act, my_tiles,
                                      n_chunks, p->world_size, p->rank, g.tiles_x, g.xbound, p->height, prev_scale,
-                                     a.color_scale, c->adapt_a.tolerance, decide, pass.samples_after, c->tile_done.p,
+                                     a.color_scale, q_chunks, c->adapt_a.tolerance, decide, pass.samples_after,
+                                     c->tile_done.p,
                                      c->scratch.p + zrt::kErrorSlot, c->metrics.p));
           HIPCHK(zrt::launch_compact(st, c->active[c->adapt_cur].p, n_act, c->tile_done.p,
                                      c->active[c->adapt_cur ^ 1u].p, c->active_count.p));
@@ -665,7 +670,7 @@ static int launch_frame(zrt_ctx* c, const zrt_camera* cam, const zrt_params* p, 
         const uint32_t n_slots = my_tiles * 64u;
         const float prev_scale = c->run_done ? 1.0f / float(c->run_done) : 0.0f;
         HIPCHK(zrt::launch_accumulate(st, c->partial.p, c->accum.p, dev_tiles, n_slots, n_chunks, p->world_size, p->rank,
-                                      g.tiles_x, g.xbound, p->height, prev_scale, a.color_scale,
+                                      g.tiles_x, g.xbound, p->height, prev_scale, a.color_scale, q_chunks,
                                       c->scratch.p + zrt::kErrorSlot, c->metrics.p));
       }
       HIPCHK(hipMemcpyAsync(c->metrics_host, c->metrics.p, zrt::kMetricWords * sizeof(unsigned long long),
@@ -1095,6 +1100,66 @@ int zrt_ctx_assemble_padded(zrt_ctx* c, const zrt_params* p, const float* dev_ga
   return zrt::assemble(c, p, dev_gathered, stride_tiles, dev_frame, hip_stream);
 }
 
+int zrt_ctx_assemble_plane(zrt_ctx* c, const zrt_params* p, const float* dev_gathered, uint32_t stride_tiles,
+                           float* dev_frame, void* hip_stream) {
+  return zrt::assemble(c, p, dev_gathered, stride_tiles, dev_frame, hip_stream, 1);
+}
+
+// ---- the variance plane of the live run (zrt.h "the variance plane") ----------
+int zrt_ctx_accum_variance(zrt_ctx* c, float* dev_tiles_var, void* hip_stream) {
+  if (!c || !dev_tiles_var) return fail(ZRT_E_INVALID, "null argument");
+  if (!c->run_live)
+    return fail(ZRT_E_INVALID, "no run is live on this context (zrt_ctx_accum_begin / zrt_ctx_adapt_begin; a "
+                               "zrt_ctx_render_tiles ends the run)");
+  if (c->run_passes == 0) return fail(ZRT_E_INVALID, "variance: the run has rendered no pass yet");
+  try {
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t st = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
+    const zrt_params* p = &c->run_p;
+    const zrt::Geometry g = zrt::geometry(p);
+    const uint32_t my_tiles = zrt::rank_tiles(g, p->rank, p->world_size);
+    const uint32_t n_slots = my_tiles * 64u;
+    HIPCHK(hipEventSynchronize(c->ev_done));  // the last pass: its error flag, an adaptive run's tile counts
+    const bool dev_err = *c->err_host != 0;
+    c->var_plan_host.assign(std::max(1u, my_tiles), make_float2(0.0f, 0.0f));
+    if (!dev_err) {
+      zrt_variance_plan vp{};
+      if (c->adapt) {
+        std::vector<uint32_t> done(std::max(1u, my_tiles));
+        if (my_tiles)
+          HIPCHK(hipMemcpy(done.data(), c->tile_done.p, size_t(my_tiles) * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        uint32_t last_n = 0;
+        for (uint32_t lt = 0; lt < my_tiles; ++lt) {
+          const uint32_t n = done[lt] & ~zrt::kTileFrozen;
+          if (n != last_n) {  // (ik and sc per distinct k)
+            const int rc = zrt::plan_variance(p, n, &vp);
+            if (rc) return rc;
+            last_n = n;
+          }
+          c->var_plan_host[lt] = make_float2(vp.ik, vp.sc);
+        }
+      } else {
+        const int rc = zrt::plan_variance(p, c->run_done, &vp);
+        if (rc) return rc;
+        for (uint32_t lt = 0; lt < my_tiles; ++lt) c->var_plan_host[lt] = make_float2(vp.ik, vp.sc);
+      }
+    }
+    if (c->var_plan.n < c->var_plan_host.size()) c->var_plan.alloc(c->var_plan_host.size());
+    // (a blocking copy: the table may be rewritten by the next call)
+    HIPCHK(hipMemcpy(c->var_plan.p, c->var_plan_host.data(), c->var_plan_host.size() * sizeof(float2),
+                     hipMemcpyHostToDevice));
+    if (n_slots)
+      HIPCHK(zrt::launch_variance(st, c->accum.p, c->var_plan.p, dev_tiles_var, n_slots, p->world_size, p->rank,
+                                  g.tiles_x, g.xbound, p->height, c->scratch.p + zrt::kErrorSlot));
+    if (dev_err) {
+      c->err_reported = true;
+      return fail(ZRT_E_UNSUPPORTED, zrt::device_error_msg(*c->err_host));
+    }
+    return ZRT_OK;
+  }
+  ZRT_CATCH_ALL
+}
+
 // ---- first-hit feature buffers (zrt.h "denoising") ---------------------------
 int zrt_ctx_features(zrt_ctx* c, const zrt_camera* cam, const zrt_params* p, float* dev_features, void* hip_stream) {
   if (!c || !cam || !dev_features) return fail(ZRT_E_INVALID, "null argument");
@@ -1187,6 +1252,63 @@ int zrt_ctx_denoise(zrt_ctx* c, const zrt_params* p, const zrt_denoise* dn, cons
     HIPCHK(hipEventRecord(c->dn_ev0, st));
     HIPCHK(zrt::denoise_enqueue(l, dev_frame, reinterpret_cast<const float4*>(dev_features), dev_out, c->dn_buf[0].p,
                                 c->dn_buf[1].p, st));
+    HIPCHK(hipEventRecord(c->dn_ev1, st));
+    c->dn_launched = true;
+    return ZRT_OK;
+  }
+  ZRT_CATCH_ALL
+}
+
+// the default guided filter: the winner of tools/denoise_guided_probe.py's search
+// (profiles/r11/guided/defaults.json)
+#define ZRT_DG_SIGMA_COLOR 4.0f
+#define ZRT_DG_SIGMA_NORMAL 0.0625f
+#define ZRT_DG_SIGMA_ALBEDO 0x1p-12f
+#define ZRT_DG_SIGMA_DEPTH 0.015625f
+#define ZRT_DG_FLAGS ZRT_DN_DEMODULATE
+int zrt_denoise_guided_defaults(zrt_denoise* out, uint32_t* flags) {
+  if (!out || !flags) return fail(ZRT_E_INVALID, "null argument");
+  *out = zrt_denoise{};
+  out->iterations = ZRT_DEFAULT_DENOISE_ITERATIONS;
+  out->sigma_color = ZRT_DG_SIGMA_COLOR;
+  out->sigma_normal = ZRT_DG_SIGMA_NORMAL;
+  out->sigma_albedo = ZRT_DG_SIGMA_ALBEDO;
+  out->sigma_depth = ZRT_DG_SIGMA_DEPTH;
+  *flags = ZRT_DG_FLAGS;
+  return ZRT_OK;
+}
+
+int zrt_ctx_denoise_guided(zrt_ctx* c, const zrt_params* p, const zrt_denoise* dn, uint32_t flags,
+                           const float* dev_frame, const float* dev_features, const float* dev_variance,
+                           float* dev_out, float* dev_out_variance, void* hip_stream) {
+  zrt::DenoiseLaunch l{};
+  int rc = zrt::plan_denoise(p, dn, &l);  // (the refusals that need no context come first)
+  if (rc) return rc;
+  if (flags & ~uint32_t(ZRT_DN_DEMODULATE)) return fail(ZRT_E_INVALID, "denoise: unknown flag");
+  if (dev_out && static_cast<const float*>(dev_out) == dev_frame)
+    return fail(ZRT_E_INVALID, "denoise: dev_out must not be dev_frame");
+  if (reinterpret_cast<uintptr_t>(dev_features) & 15u)
+    return fail(ZRT_E_INVALID, "denoise: dev_features must be 16-byte aligned");
+  if (!dev_variance) return fail(ZRT_E_INVALID, "denoise: dev_variance is null");
+  if (dev_out_variance && static_cast<const float*>(dev_out_variance) == dev_variance)
+    return fail(ZRT_E_INVALID, "denoise: dev_out_variance must not be dev_variance");
+  if (!c || !dev_frame || !dev_features || !dev_out) return fail(ZRT_E_INVALID, "null argument");
+  if (int(p->device) != c->device)
+    return fail(ZRT_E_INVALID, "params->device differs from the device the context was created on");
+  try {
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t st = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
+    const size_t plane = size_t(l.n) * l.n;
+    for (zrt::DevBuf<float4>& b : c->dn_buf)
+      if (b.n < plane) b.alloc(plane);
+    if (!c->dn_ev0) {
+      HIPCHK(hipEventCreate(&c->dn_ev0));
+      HIPCHK(hipEventCreate(&c->dn_ev1));
+    }
+    HIPCHK(hipEventRecord(c->dn_ev0, st));
+    HIPCHK(zrt::denoise_guided_enqueue(l, dn->sigma_color, (flags & ZRT_DN_DEMODULATE) != 0, dev_frame,
+                                       reinterpret_cast<const float4*>(dev_features), dev_variance, dev_out,
+                                       dev_out_variance, c->dn_buf[0].p, c->dn_buf[1].p, st));
     HIPCHK(hipEventRecord(c->dn_ev1, st));
     c->dn_launched = true;
     return ZRT_OK;

@@ -144,6 +144,9 @@ struct zrt_ctx {
   zrt::DevBuf<float4> dn_buf[2];
   hipEvent_t dn_ev0 = nullptr, dn_ev1 = nullptr;
   bool dn_launched = false;
+  // ---- the variance plane (zrt_ctx_accum_variance): each local tile's {ik, sc} ----
+  zrt::DevBuf<float2> var_plan;
+  std::vector<float2> var_plan_host;
   // ---- first-hit feature buffers (zrt_ctx_features): the launch's own deep stack rows,
   // the slot -> primitive table, and its device error status behind feat_done ----
   zrt::DevBuf<uint8_t> feat_ovf;

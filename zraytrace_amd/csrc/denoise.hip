@@ -182,7 +182,231 @@ hipError_t launch_iter(bool last, dim3 grid, hipStream_t st, const float4* cin, 
   return hipGetLastError();
 }
 
+// ---- the variance-guided filter (zrt.h "variance-guided denoising") -------------------
+// The same plan with the variance V in the colour planes' fourth lane: a tap stays
+// three 16-byte loads and the LDS footprint is unchanged.  The 3 x 3 smoothing of V
+// reads adjacent pixels: inside the staged halo (2 S >= 1) for the LDS steps, eight
+// 4-byte loads for the memory steps.
+
+constexpr float kDnAlbedoMin = 0.015625f;  // a_min = 2^-6
+
+// dn_tap with the guided colour test on L = (r + g) + b, scaled by the centre's kl,
+// and the variance sum.
+__device__ __forceinline__ void dg_tap(const DnCentre& p, float lum_p, float kl, const float4 cq, const float4 f0q,
+                                       const float4 f1q, float w, uint32_t terms, float inv_n, float inv_a, float& ar,
+                                       float& ag, float& ab, float& wsum, float& vacc) {
+  const bool hit_q = __float_as_uint(f1q.w) != 0u;
+  if (p.hit != hit_q) return;
+  if (terms & kDnColor) {
+    const float t = 1.0f - fabsf(lum_p - ((cq.x + cq.y) + cq.z)) * kl;
+    if (!(t > 0.0f)) return;
+    w = w * t;
+  }
+  if (terms & kDnNormal) {
+    const float dx = p.f0.x - f0q.x, dy = p.f0.y - f0q.y, dz = p.f0.z - f0q.z;
+    const float t = 1.0f - ((dx * dx + dy * dy) + dz * dz) * inv_n;
+    if (!(t > 0.0f)) return;
+    w = w * t;
+  }
+  if (terms & kDnAlbedo) {
+    const float t = 1.0f - ((fabsf(p.f1.x - f1q.x) + fabsf(p.f1.y - f1q.y)) + fabsf(p.f1.z - f1q.z)) * inv_a;
+    if (!(t > 0.0f)) return;
+    w = w * t;
+  }
+  if (terms & kDnDepth) {
+    const float t = 1.0f - fabsf(p.f0.w - f0q.w) * p.kz;
+    if (!(t > 0.0f)) return;
+    w = w * t;
+  }
+  if (!(w > 0.0f)) return;
+  ar = ar + cq.x * w;
+  ag = ag + cq.y * w;
+  ab = ab + cq.z * w;
+  wsum = wsum + w;
+  vacc = vacc + cq.w * (w * w);
+}
+
+// S, LAST as atrous_kernel's.  LAST also multiplies the albedo back (demod) and
+// writes the variance to out_var when it is given.
+template <int S, bool LAST>
+__global__ void __launch_bounds__(kDnBX* kDnBY)
+    guided_kernel(const float4* __restrict__ cin, const float4* __restrict__ feat, float4* __restrict__ cout,
+                  float* __restrict__ out, float* __restrict__ out_var, uint32_t n, uint32_t width, int step,
+                  uint32_t terms, float sigma_c, float inv_n, float inv_a, float inv_z, uint32_t demod) {
+  constexpr int RW = kDnBX + 4 * S, RH = kDnBY + 4 * S;
+  __shared__ float4 s_c[S ? RW * RH : 1], s_f0[S ? RW * RH : 1], s_f1[S ? RW * RH : 1];
+  const int x0 = int(blockIdx.x) * kDnBX, y0 = int(blockIdx.y) * kDnBY;
+  const int px = x0 + int(threadIdx.x), py = y0 + int(threadIdx.y);
+  const int ni = int(n);
+  if (S) {
+    const int tid = int(threadIdx.y) * kDnBX + int(threadIdx.x);
+    for (int i = tid; i < RW * RH; i += kDnBX * kDnBY) {
+      const int gx = x0 - 2 * S + i % RW, gy = y0 - 2 * S + i / RW;
+      float4 c = make_float4(0.0f, 0.0f, 0.0f, 0.0f), f0 = c, f1 = c;
+      if (gx >= 0 && gx < ni && gy >= 0 && gy < ni) {
+        c = cin[size_t(gy) * n + size_t(gx)];
+        const size_t f = (size_t(gy) * width + size_t(gx)) * 2;
+        f0 = feat[f];
+        f1 = feat[f + 1];
+      }
+      s_c[i] = c;
+      s_f0[i] = f0;
+      s_f1[i] = f1;
+    }
+    __syncthreads();
+  }
+  if (px >= ni || py >= ni) return;
+  const int s = S ? S : step;
+  const int lc = (int(threadIdx.y) + 2 * S) * RW + int(threadIdx.x) + 2 * S;  // the centre's LDS slot
+  DnCentre p;
+  if (S) {
+    p.c = s_c[lc];
+    p.f0 = s_f0[lc];
+    p.f1 = s_f1[lc];
+  } else {
+    p.c = cin[size_t(py) * n + size_t(px)];
+    const size_t f = (size_t(py) * width + size_t(px)) * 2;
+    p.f0 = feat[f];
+    p.f1 = feat[f + 1];
+  }
+  p.hit = __float_as_uint(p.f1.w) != 0u;
+  const float rz = p.hit ? 1.0f / p.f0.w : 0.0f;
+  p.kz = inv_z * rz;
+  // the variance smoothed over the 3 x 3 adjacent pixels (a neighbour outside D: the centre's)
+  float g = 0.0f;
+#pragma unroll
+  for (int dy = -1; dy <= 1; ++dy) {
+#pragma unroll
+    for (int dx = -1; dx <= 1; ++dx) {
+      const float wt = (dx == 0 && dy == 0) ? 0.25f : (dx == 0 || dy == 0) ? 0.125f : 0.0625f;
+      const int qx = px + dx, qy = py + dy;
+      float v = p.c.w;
+      if ((dx != 0 || dy != 0) && qx >= 0 && qx < ni && qy >= 0 && qy < ni)
+        v = S ? s_c[lc + dy * RW + dx].w : reinterpret_cast<const float*>(cin)[(size_t(qy) * n + size_t(qx)) * 4 + 3];
+      g = g + v * wt;
+    }
+  }
+  const float kl = (terms & kDnColor) ? 1.0f / (sigma_c * __builtin_sqrtf(g) + 0x1p-20f) : 0.0f;
+  const float lum_p = (p.c.x + p.c.y) + p.c.z;
+  float ar = 0.0f, ag = 0.0f, ab = 0.0f, wsum = 0.0f, vacc = 0.0f;
+#pragma unroll
+  for (int dy = -2; dy <= 2; ++dy) {
+#pragma unroll
+    for (int dx = -2; dx <= 2; ++dx) {
+      if (dx == 0 && dy == 0) {  // the centre tap: no tests
+        const float w = 0.375f * 0.375f;
+        ar = ar + p.c.x * w;
+        ag = ag + p.c.y * w;
+        ab = ab + p.c.z * w;
+        wsum = wsum + w;
+        vacc = vacc + p.c.w * (w * w);
+        continue;
+      }
+      const int qx = px + s * dx, qy = py + s * dy;
+      if (qx < 0 || qx >= ni || qy < 0 || qy >= ni) continue;
+      float4 cq, f0q, f1q;
+      if (S) {
+        const int l = lc + S * dy * RW + S * dx;
+        cq = s_c[l];
+        f0q = s_f0[l];
+        f1q = s_f1[l];
+      } else {
+        cq = cin[size_t(qy) * n + size_t(qx)];
+        const size_t f = (size_t(qy) * width + size_t(qx)) * 2;
+        f0q = feat[f];
+        f1q = feat[f + 1];
+      }
+      dg_tap(p, lum_p, kl, cq, f0q, f1q, dn_h(dx) * dn_h(dy), terms, inv_n, inv_a, ar, ag, ab, wsum, vacc);
+    }
+  }
+  float r = ar / wsum, gg = ag / wsum, b = ab / wsum, v = vacc / (wsum * wsum);
+  if (LAST) {
+    if (demod && p.hit) {
+      if (p.f1.x > kDnAlbedoMin) r = r * p.f1.x;
+      if (p.f1.y > kDnAlbedoMin) gg = gg * p.f1.y;
+      if (p.f1.z > kDnAlbedoMin) b = b * p.f1.z;
+      const float am = ((p.f1.x + p.f1.y) + p.f1.z) * (1.0f / 3.0f);
+      if (am > kDnAlbedoMin) v = v * (am * am);
+    }
+    float* o = out + (size_t(py) * width + size_t(px)) * 3;
+    o[0] = r;
+    o[1] = gg;
+    o[2] = b;
+    if (out_var) out_var[size_t(py) * width + size_t(px)] = v;
+  } else {
+    cout[size_t(py) * n + size_t(px)] = make_float4(r, gg, b, v);
+  }
+}
+
+// {C_0, V_0}: dn_pack_kernel with the variance in the fourth lane, demodulated when asked.
+__global__ void dg_pack_kernel(const float* __restrict__ frame, const float4* __restrict__ feat,
+                               const float* __restrict__ var, float4* __restrict__ c0, float* __restrict__ out,
+                               float* __restrict__ out_var, uint32_t n, uint32_t width, uint32_t demod) {
+  const size_t i = size_t(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (i >= size_t(width) * n) return;
+  const uint32_t x = uint32_t(i % width), y = uint32_t(i / width);
+  float r = frame[3 * i], g = frame[3 * i + 1], b = frame[3 * i + 2], v = var[i];
+  if (x < n) {
+    if (demod) {
+      const float4 a = feat[2 * i + 1];
+      if (__float_as_uint(a.w) != 0u) {
+        if (a.x > kDnAlbedoMin) r = r / a.x;
+        if (a.y > kDnAlbedoMin) g = g / a.y;
+        if (a.z > kDnAlbedoMin) b = b / a.z;
+        const float am = ((a.x + a.y) + a.z) * (1.0f / 3.0f);
+        if (am > kDnAlbedoMin) v = v / (am * am);
+      }
+    }
+    c0[size_t(y) * n + x] = make_float4(r, g, b, v);
+  } else {
+    out[3 * i] = r;
+    out[3 * i + 1] = g;
+    out[3 * i + 2] = b;
+    if (out_var) out_var[i] = v;
+  }
+}
+
+template <int S>
+hipError_t launch_guided(bool last, dim3 grid, hipStream_t st, const float4* cin, const float4* feat, float4* cout,
+                         float* out, float* out_var, const DenoiseLaunch& l, int step, float sigma_c, uint32_t demod) {
+  const dim3 block(kDnBX, kDnBY);
+  if (last)
+    hipLaunchKernelGGL((guided_kernel<S, true>), grid, block, 0, st, cin, feat, cout, out, out_var, l.n, l.width, step,
+                       l.terms, sigma_c, l.inv_n, l.inv_a, l.inv_z, demod);
+  else
+    hipLaunchKernelGGL((guided_kernel<S, false>), grid, block, 0, st, cin, feat, cout, out, out_var, l.n, l.width,
+                       step, l.terms, sigma_c, l.inv_n, l.inv_a, l.inv_z, demod);
+  return hipGetLastError();
+}
+
 }  // namespace
+
+hipError_t denoise_guided_enqueue(const DenoiseLaunch& l, float sigma_c, bool demodulate, const float* frame,
+                                  const float4* feat, const float* var, float* out, float* out_var, float4* buf0,
+                                  float4* buf1, hipStream_t st) {
+  if (l.n == 0 || l.width < l.n || l.iterations == 0 || l.iterations > 8) return hipErrorInvalidValue;
+  const size_t pixels = size_t(l.width) * l.n;
+  const uint32_t demod = demodulate ? 1u : 0u;
+  hipLaunchKernelGGL(dg_pack_kernel, dim3(uint32_t((pixels + 255) / 256)), dim3(256), 0, st, frame, feat, var, buf0, out,
+                     out_var, l.n, l.width, demod);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  const dim3 grid((l.n + kDnBX - 1) / kDnBX, (l.n + kDnBY - 1) / kDnBY);
+  float4* cur = buf0;
+  float4* nxt = buf1;
+  for (uint32_t i = 0; i < l.iterations; ++i) {
+    const int step = 1 << i;
+    const bool last = i + 1 == l.iterations;
+    e = step == 1   ? launch_guided<1>(last, grid, st, cur, feat, nxt, out, out_var, l, step, sigma_c, demod)
+        : step == 2 ? launch_guided<2>(last, grid, st, cur, feat, nxt, out, out_var, l, step, sigma_c, demod)
+                    : launch_guided<0>(last, grid, st, cur, feat, nxt, out, out_var, l, step, sigma_c, demod);
+    if (e != hipSuccess) return e;
+    float4* t = cur;
+    cur = nxt;
+    nxt = t;
+  }
+  return hipSuccess;
+}
 
 hipError_t denoise_enqueue(const DenoiseLaunch& l, const float* frame, const float4* feat, float* out, float4* buf0,
                            float4* buf1, hipStream_t st) {

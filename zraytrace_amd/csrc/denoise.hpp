@@ -25,4 +25,12 @@ struct DenoiseLaunch {
 hipError_t denoise_enqueue(const DenoiseLaunch& l, const float* frame, const float4* feat, float* out,
                            float4* buf0, float4* buf1, hipStream_t st);
 
+// The variance-guided filter (zrt.h "variance-guided denoising"): the same passes
+// with the variance in the colour planes' fourth lane.  sigma_c: sigma_color itself
+// (l.inv_c is not read); demodulate: ZRT_DN_DEMODULATE.  var: width * n floats;
+// out_var (may be null): the same, written with the filtered variance.
+hipError_t denoise_guided_enqueue(const DenoiseLaunch& l, float sigma_c, bool demodulate, const float* frame,
+                                  const float4* feat, const float* var, float* out, float* out_var, float4* buf0,
+                                  float4* buf1, hipStream_t st);
+
 }  // namespace zrt

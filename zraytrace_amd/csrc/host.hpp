@@ -127,6 +127,7 @@ uint32_t reported_loop(int kmode);
 LaunchPlan plan_launch(const SceneShape& s, const zrt_params* p);
 int plan_pass(const zrt_params* p, uint32_t done, uint32_t n_samples, zrt_pass_plan* out);
 int plan_adapt(const zrt_params* p, const zrt_adaptive* ad, std::vector<uint32_t>* levels);
+int plan_variance(const zrt_params* p, uint32_t n, zrt_variance_plan* out);
 int plan_denoise(const zrt_params* p, const zrt_denoise* dn, DenoiseLaunch* out);
 
 // ---- flatten.cpp ----

@@ -182,18 +182,24 @@ hipError_t launch_finalize(hipStream_t st, const float4* partial, float* out, ui
                            float color_scale, const unsigned long long* error_flag);
 hipError_t launch_accumulate(hipStream_t st, const float4* partial, float4* accum, float* out, uint32_t n_slots,
                              uint32_t pass_chunks, uint32_t world, uint32_t rank, uint32_t tiles_x, uint32_t xbound,
-                             uint32_t height, float prev_scale, float new_scale, const unsigned long long* error_flag,
-                             unsigned long long* metrics);
+                             uint32_t height, float prev_scale, float new_scale, uint32_t q_chunks,
+                             const unsigned long long* error_flag, unsigned long long* metrics);
 hipError_t launch_resolve(hipStream_t st, const float4* partial, float4* accum, float* out, const uint32_t* active,
                           uint32_t n_active, uint32_t my_tiles, uint32_t pass_chunks, uint32_t world, uint32_t rank,
                           uint32_t tiles_x, uint32_t xbound, uint32_t height, float prev_scale, float new_scale,
-                          float tolerance, uint32_t decide, uint32_t level_samples, uint32_t* tile_done,
-                          const unsigned long long* error_flag, unsigned long long* metrics);
+                          uint32_t q_chunks, float tolerance, uint32_t decide, uint32_t level_samples,
+                          uint32_t* tile_done, const unsigned long long* error_flag, unsigned long long* metrics);
 hipError_t launch_compact(hipStream_t st, const uint32_t* in, uint32_t n, const uint32_t* tile_done, uint32_t* out,
                           uint32_t* count);
 hipError_t launch_assemble(hipStream_t st, const float* gathered, float* frame, const uint32_t* rank_base,
                            uint32_t world, uint32_t tiles_x, uint32_t xbound, uint32_t height, uint32_t width,
                            uint32_t total, uint32_t stride_px, uint32_t n_tiles);
+hipError_t launch_variance(hipStream_t st, const float4* accum, const float2* tile_plan, float* out, uint32_t n_slots,
+                           uint32_t world, uint32_t rank, uint32_t tiles_x, uint32_t xbound, uint32_t height,
+                           const unsigned long long* error_flag);
+hipError_t launch_assemble_plane(hipStream_t st, const float* gathered, float* frame, const uint32_t* rank_base,
+                                 uint32_t world, uint32_t tiles_x, uint32_t xbound, uint32_t height, uint32_t width,
+                                 uint32_t total, uint32_t stride_px, uint32_t n_tiles);
 hipError_t launch_features_error(hipStream_t st, float4* out, uint64_t n_f4, const unsigned long long* error_flag);
 hipError_t launch_debug_math(int fn, const float* x, const float* y, float* out, uint32_t n);
 hipError_t launch_debug_division(uint64_t n, unsigned long long* counts);

@@ -210,6 +210,105 @@ int zrt_render_adaptive_progress(const zrt_scene* scene, const zrt_camera* camer
   return zrt::render_adaptive(scene, camera, params, adaptive, on_level, user, out_rgb, out_samples, stats, scanlines);
 }
 
+namespace zrt {
+namespace {
+// render_one as an accumulation run of one pass: zrt_render's frame and counters,
+// with the run (its accumulator and second moment) still live for `post`.
+int render_one_pass(const zrt_scene* scene, const zrt_camera* camera, const zrt_params* params, float* out_rgb,
+                    zrt_stats* stats, const FramePost& post) {
+  if (!camera) return fail(ZRT_E_INVALID, "null argument");
+  int rc = zrt::validate_params(params);
+  if (rc) return rc;
+  zrt_params p = *params;
+  p.rank = 0;
+  p.world_size = 1;
+  zrt_ctx* c = nullptr;
+  rc = zrt_ctx_create(scene, &p, &c);
+  if (rc) return rc;
+  std::unique_ptr<zrt_ctx, int (*)(zrt_ctx*)> guard(c, zrt_ctx_destroy);
+  try {
+    uint32_t n_tiles = 0;
+    rc = zrt_ctx_tile_count(c, &p, &n_tiles);
+    if (rc) return rc;
+    zrt::DevBuf<float> tiles, frame;
+    tiles.alloc(size_t(n_tiles) * 64 * 3);
+    frame.alloc(size_t(p.width) * p.height * 3);
+    rc = zrt_ctx_accum_begin(c, camera, &p);
+    if (rc) return rc;
+    rc = zrt_ctx_accum_pass(c, p.samples_per_pixel, tiles.p, nullptr);
+    if (rc) return rc;
+    rc = zrt_ctx_assemble(c, &p, tiles.p, frame.p, nullptr);
+    if (rc) return rc;
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (out_rgb)
+      HIPCHK(hipMemcpy(out_rgb, frame.p, sizeof(float) * 3 * size_t(p.width) * p.height, hipMemcpyDeviceToHost));
+    zrt_stats s;
+    rc = zrt_ctx_stats(c, &s);
+    if (rc) return rc;
+    if (stats) *stats = s;
+    return post(c, p, frame.p);
+  }
+  ZRT_CATCH_ALL
+}
+}  // namespace
+}  // namespace zrt
+
+int zrt_render_denoised_guided(const zrt_scene* scene, const zrt_camera* camera, const zrt_params* params,
+                               const zrt_adaptive* adaptive, const zrt_denoise* dn, uint32_t flags, float* out_rgb,
+                               float* out_noisy, float* out_features, float* out_variance, zrt_stats* stats,
+                               double* denoise_ms) {
+  if (!camera || !out_rgb) return fail(ZRT_E_INVALID, "null argument");
+  zrt_denoise d;
+  uint32_t default_flags = 0;
+  if (dn) d = *dn;
+  else zrt_denoise_guided_defaults(&d, &default_flags);
+  zrt::DenoiseLaunch l{};
+  int rc = zrt::plan_denoise(params, &d, &l);  // (refused before any device work)
+  if (rc) return rc;
+  if (flags & ~uint32_t(ZRT_DN_DEMODULATE)) return fail(ZRT_E_INVALID, "denoise: unknown flag");
+  // every tile ends on whole chunks, two at least: a frozen tile holds a doubled level, the others the cap
+  zrt_variance_plan vp{};
+  rc = zrt::plan_variance(params, params->samples_per_pixel, &vp);
+  if (rc) return rc;
+  const zrt::FramePost post = [&](zrt_ctx* c, const zrt_params& p, const float* dev_frame) -> int {
+    try {
+      const size_t px = size_t(p.width) * p.height;
+      uint32_t n_tiles = 0;
+      int r = zrt_ctx_tile_count(c, &p, &n_tiles);
+      if (r) return r;
+      zrt::DevBuf<float> feat, outb, var_tiles, var;
+      feat.alloc(px * 8);
+      outb.alloc(px * 3);
+      var_tiles.alloc(size_t(n_tiles) * 64);
+      var.alloc(px);
+      r = zrt_ctx_accum_variance(c, var_tiles.p, nullptr);
+      if (r) return r;
+      r = zrt_ctx_assemble_plane(c, &p, var_tiles.p, 0, var.p, nullptr);
+      if (r) return r;
+      r = zrt_ctx_features(c, camera, &p, feat.p, nullptr);
+      if (r) return r;
+      r = zrt_ctx_denoise_guided(c, &p, &d, flags, dev_frame, feat.p, var.p, outb.p, nullptr, nullptr);
+      if (r) return r;
+      HIPCHK(hipStreamSynchronize(c->stream));
+      r = zrt_ctx_sync(c);  // (a feature launch's device error)
+      if (r) return r;
+      HIPCHK(hipMemcpy(out_rgb, outb.p, sizeof(float) * 3 * px, hipMemcpyDeviceToHost));
+      if (out_features) HIPCHK(hipMemcpy(out_features, feat.p, sizeof(float) * 8 * px, hipMemcpyDeviceToHost));
+      if (out_variance) HIPCHK(hipMemcpy(out_variance, var.p, sizeof(float) * px, hipMemcpyDeviceToHost));
+      if (denoise_ms) {
+        r = zrt_ctx_denoise_ms(c, denoise_ms);
+        if (r) return r;
+      }
+      return ZRT_OK;
+    }
+    ZRT_CATCH_ALL
+  };
+  if (adaptive)
+    return zrt::render_adaptive(scene, camera, params, adaptive, nullptr, nullptr, out_noisy, nullptr, stats, nullptr,
+                                &post);
+  return zrt::render_one_pass(scene, camera, params, out_noisy, stats, post);
+}
+
 int zrt_render_denoised(const zrt_scene* scene, const zrt_camera* camera, const zrt_params* params,
                         const zrt_adaptive* adaptive, const zrt_denoise* dn, float* out_rgb, float* out_noisy,
                         float* out_features, zrt_stats* stats, double* denoise_ms) {

@@ -407,6 +407,30 @@ int plan_adapt(const zrt_params* p, const zrt_adaptive* ad, std::vector<uint32_t
   return ZRT_OK;
 }
 
+// The host half of the variance plane (zrt.h "the variance plane";
+// zrt_debug_variance_plan reports the same): n samples in chunks of c are k = n / c
+// chunk sums; ik and sc in f32 as the header states them.  Refused: no sample, a
+// ragged n (its last chunk sum is missing from Q), fewer than two chunks.
+int plan_variance(const zrt_params* p, uint32_t n, zrt_variance_plan* out) {
+  const int rc = validate_params(p);
+  if (rc) return rc;
+  const uint32_t chunk = p->sample_chunk ? p->sample_chunk : ZRT_DEFAULT_SAMPLE_CHUNK;
+  if (n == 0) return fail(ZRT_E_INVALID, "variance: no samples in the accumulator");
+  if (n % chunk != 0)
+    return fail(ZRT_E_INVALID, "variance: " + std::to_string(n) + " samples are not whole chunks of " +
+                                   std::to_string(chunk) + " (a ragged pass happened; choose a sample_chunk that "
+                                   "divides the samples)");
+  const uint32_t k = n / chunk;
+  if (k < 2)
+    return fail(ZRT_E_INVALID, "variance: " + std::to_string(n) + " samples are fewer than two chunks of " +
+                                   std::to_string(chunk) + " (choose a smaller sample_chunk)");
+  out->chunk = chunk;
+  out->k = k;
+  out->ik = 1.0f / float(k);
+  out->sc = 1.0f / (float(k - 1) * (float(chunk) * float(chunk)));
+  return ZRT_OK;
+}
+
 // What zrt_ctx_denoise refuses of a zrt_denoise, and the launch it asks for otherwise.
 int plan_denoise(const zrt_params* p, const zrt_denoise* dn, DenoiseLaunch* out) {
   if (!dn) return fail(ZRT_E_INVALID, "denoise is null");

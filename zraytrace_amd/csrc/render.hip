@@ -3745,6 +3745,9 @@ __device__ __forceinline__ uint32_t png_channel_dev(float c) {
 // frame of that many samples (raytrace.zig:157, 177, 182).  Out-of-frame slots
 // stay 0.  A nonzero device error flag leaves NaN in every pixel and in every
 // slot of accum, so no later pass resolves a clean frame from it.
+// accum[i].w is Q, the second moment of the slot's chunk sums (zrt.h "the variance
+// plane"): per chunk sum S_j of the first q_chunks of the pass (all of them but a
+// ragged last one), l = (S_j.r + S_j.g) + S_j.b, Q = Q + l * l, in chunk order.
 // metrics: kMetricShards pairs, kMetricStride words apart (a block adds into pair
 // blockIdx.x % kMetricShards: one word takes some 90 atomics per microsecond, and a
 // 2048 x 2048 frame has 65 536 waves; the host adds the pairs up).  Word 0: in-frame
@@ -3757,7 +3760,7 @@ __device__ __forceinline__ uint32_t png_channel_dev(float c) {
 __global__ void accumulate_kernel(const float4* __restrict__ partial, float4* __restrict__ accum,
                                   float* __restrict__ out, uint32_t n_slots, uint32_t pass_chunks, uint32_t world,
                                   uint32_t rank, uint32_t tiles_x, uint32_t xbound, uint32_t height, float prev_scale,
-                                  float new_scale, const unsigned long long* __restrict__ error_flag,
+                                  float new_scale, uint32_t q_chunks, const unsigned long long* __restrict__ error_flag,
                                   unsigned long long* __restrict__ metrics) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   const bool live = i < n_slots;
@@ -3770,19 +3773,24 @@ __global__ void accumulate_kernel(const float4* __restrict__ partial, float4* __
   bool changed = false;
   if (live && *error_flag != 0ull) {
     r = g = b = __builtin_nanf("");
-    accum[i] = make_float4(r, g, b, 0.0f);
+    accum[i] = make_float4(r, g, b, r);
   } else if (live && px < xbound && py < height) {
     const float4 before = accum[i];
     r = before.x;
     g = before.y;
     b = before.z;
+    float q = before.w;
     for (uint32_t j = 0; j < pass_chunks; ++j) {  // [chunk][slot], as finalize_kernel reads them
       const float4 v = partial[(size_t)j * n_slots + i];
       r += v.x;
       g += v.y;
       b += v.z;
+      if (j < q_chunks) {  // (a ragged last chunk is left out of the second moment)
+        const float l = (v.x + v.y) + v.z;
+        q = q + l * l;
+      }
     }
-    accum[i] = make_float4(r, g, b, 0.0f);
+    accum[i] = make_float4(r, g, b, q);
     r *= new_scale;
     g *= new_scale;
     b *= new_scale;
@@ -3828,7 +3836,7 @@ __global__ void resolve_kernel(const float4* __restrict__ partial, float4* __res
                                float* __restrict__ out, const uint32_t* __restrict__ active, uint32_t n_active,
                                uint32_t my_tiles, uint32_t pass_chunks, uint32_t world, uint32_t rank,
                                uint32_t tiles_x, uint32_t xbound, uint32_t height, float prev_scale, float new_scale,
-                               float tolerance, uint32_t decide, uint32_t level_samples,
+                               uint32_t q_chunks, float tolerance, uint32_t decide, uint32_t level_samples,
                                uint32_t* __restrict__ tile_done, const unsigned long long* __restrict__ error_flag,
                                unsigned long long* __restrict__ metrics) {
   const uint32_t w = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, p = threadIdx.x & 63u;
@@ -3838,7 +3846,7 @@ __global__ void resolve_kernel(const float4* __restrict__ partial, float4* __res
     const float nan = __builtin_nanf("");
     for (uint32_t lt = w; lt < my_tiles; lt += n_active) {
       const size_t i = size_t(lt) * 64u + p;
-      accum[i] = make_float4(nan, nan, nan, 0.0f);
+      accum[i] = make_float4(nan, nan, nan, nan);
       out[3ull * i + 0] = nan;
       out[3ull * i + 1] = nan;
       out[3ull * i + 2] = nan;
@@ -3860,13 +3868,18 @@ __global__ void resolve_kernel(const float4* __restrict__ partial, float4* __res
     r = before.x;
     g = before.y;
     b = before.z;
+    float q = before.w;
     for (uint32_t j = 0; j < pass_chunks; ++j) {  // [chunk][slot] over all the rank's slots
       const float4 v = partial[(size_t)j * n_slots + i];
       r += v.x;
       g += v.y;
       b += v.z;
+      if (j < q_chunks) {  // (as accumulate_kernel)
+        const float l = (v.x + v.y) + v.z;
+        q = q + l * l;
+      }
     }
-    accum[i] = make_float4(r, g, b, 0.0f);
+    accum[i] = make_float4(r, g, b, q);
     r *= new_scale;
     g *= new_scale;
     b *= new_scale;
@@ -3941,6 +3954,8 @@ __global__ void __launch_bounds__(kCompactBlock) compact_kernel(const uint32_t* 
 // Scatter gathered rank tiles into the framebuffer (raytrace.zig:182 layout).
 // Packed (stride_px == 0): rank r's tiles start at rank_base[r].  Padded: rank r
 // starts at r * stride_px, as a gather of equal per-rank counts leaves them.
+// CH: floats per pixel, 3 (the frame) or 1 (a plane, zrt_ctx_assemble_plane).
+template <uint32_t CH>
 __global__ void assemble_kernel(const float* __restrict__ gathered, float* __restrict__ frame,
                                 const uint32_t* __restrict__ rank_base, uint32_t world,
                                 uint32_t tiles_x, uint32_t xbound, uint32_t height, uint32_t width,
@@ -3962,10 +3977,39 @@ __global__ void assemble_kernel(const float* __restrict__ gathered, float* __res
   const uint32_t px = (t % tiles_x) * 8u + (p & 7u);
   const uint32_t py = (t / tiles_x) * 8u + (p >> 3);
   if (px >= xbound || py >= height) return;
-  const size_t o = ((size_t)py * width + px) * 3;
-  frame[o + 0] = gathered[3ull * i + 0];
-  frame[o + 1] = gathered[3ull * i + 1];
-  frame[o + 2] = gathered[3ull * i + 2];
+  const size_t o = ((size_t)py * width + px) * CH;
+#pragma unroll
+  for (uint32_t c = 0; c < CH; ++c) frame[o + c] = gathered[(size_t)CH * i + c];
+}
+
+// The variance plane of a run (zrt_ctx_accum_variance; the definition: zrt.h "the variance
+// plane"): per in-frame slot, from the accumulator's sums and second moment Q and the
+// tile's host-computed {ik, sc} (plan_variance), in f32, nothing fused:
+// mean = M ik, v = Q ik - mean mean clamped at 0 (a NaN stays), var = v sc.
+// Out-of-frame slots are 0; a nonzero device error flag leaves NaN in every slot.
+__global__ void variance_kernel(const float4* __restrict__ accum, const float2* __restrict__ tile_plan,
+                                float* __restrict__ out, uint32_t n_slots, uint32_t world, uint32_t rank,
+                                uint32_t tiles_x, uint32_t xbound, uint32_t height,
+                                const unsigned long long* __restrict__ error_flag) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n_slots) return;
+  const uint32_t lt = i >> 6, p = i & 63u;
+  const uint32_t t = lt * world + rank;
+  const uint32_t px = (t % tiles_x) * 8u + (p & 7u);
+  const uint32_t py = (t / tiles_x) * 8u + (p >> 3);
+  float var = 0.0f;
+  if (*error_flag != 0ull) {
+    var = __builtin_nanf("");
+  } else if (px < xbound && py < height) {
+    const float4 a = accum[i];
+    const float2 k = tile_plan[lt];
+    const float m = (a.x + a.y) + a.z;
+    const float mean = m * k.x;
+    float v = a.w * k.x - mean * mean;
+    v = (v > 0.0f || v != v) ? v : 0.0f;
+    var = v * k.y;
+  }
+  out[i] = var;
 }
 
 // Device evaluation of the path's math (parity probes against the oracle).
@@ -4170,19 +4214,19 @@ hipError_t launch_finalize(hipStream_t st, const float4* partial, float* out, ui
 }
 hipError_t launch_accumulate(hipStream_t st, const float4* partial, float4* accum, float* out, uint32_t n_slots,
                              uint32_t pass_chunks, uint32_t world, uint32_t rank, uint32_t tiles_x, uint32_t xbound,
-                             uint32_t height, float prev_scale, float new_scale, const unsigned long long* error_flag,
-                             unsigned long long* metrics) {
+                             uint32_t height, float prev_scale, float new_scale, uint32_t q_chunks,
+                             const unsigned long long* error_flag, unsigned long long* metrics) {
   return launch(accumulate_kernel, (n_slots + 255) / 256, 256, st, partial, accum, out, n_slots, pass_chunks, world,
-                    rank, tiles_x, xbound, height, prev_scale, new_scale, error_flag, metrics);
+                    rank, tiles_x, xbound, height, prev_scale, new_scale, q_chunks, error_flag, metrics);
 }
 hipError_t launch_resolve(hipStream_t st, const float4* partial, float4* accum, float* out, const uint32_t* active,
                           uint32_t n_active, uint32_t my_tiles, uint32_t pass_chunks, uint32_t world, uint32_t rank,
                           uint32_t tiles_x, uint32_t xbound, uint32_t height, float prev_scale, float new_scale,
-                          float tolerance, uint32_t decide, uint32_t level_samples, uint32_t* tile_done,
-                          const unsigned long long* error_flag, unsigned long long* metrics) {
+                          uint32_t q_chunks, float tolerance, uint32_t decide, uint32_t level_samples,
+                          uint32_t* tile_done, const unsigned long long* error_flag, unsigned long long* metrics) {
   return launch(resolve_kernel, (n_active + 3) / 4, 256, st, partial, accum, out, active, n_active, my_tiles,
-                    pass_chunks, world, rank, tiles_x, xbound, height, prev_scale, new_scale, tolerance, decide,
-                    level_samples, tile_done, error_flag, metrics);
+                    pass_chunks, world, rank, tiles_x, xbound, height, prev_scale, new_scale, q_chunks, tolerance,
+                    decide, level_samples, tile_done, error_flag, metrics);
 }
 hipError_t launch_compact(hipStream_t st, const uint32_t* in, uint32_t n, const uint32_t* tile_done, uint32_t* out,
                           uint32_t* count) {
@@ -4191,7 +4235,19 @@ hipError_t launch_compact(hipStream_t st, const uint32_t* in, uint32_t n, const 
 hipError_t launch_assemble(hipStream_t st, const float* gathered, float* frame, const uint32_t* rank_base,
                            uint32_t world, uint32_t tiles_x, uint32_t xbound, uint32_t height, uint32_t width,
                            uint32_t total, uint32_t stride_px, uint32_t n_tiles) {
-  return launch(assemble_kernel, (total + 255) / 256, 256, st, gathered, frame, rank_base, world, tiles_x, xbound,
+  return launch(assemble_kernel<3>, (total + 255) / 256, 256, st, gathered, frame, rank_base, world, tiles_x, xbound,
+                    height, width, total, stride_px, n_tiles);
+}
+hipError_t launch_variance(hipStream_t st, const float4* accum, const float2* tile_plan, float* out, uint32_t n_slots,
+                           uint32_t world, uint32_t rank, uint32_t tiles_x, uint32_t xbound, uint32_t height,
+                           const unsigned long long* error_flag) {
+  return launch(variance_kernel, (n_slots + 255) / 256, 256, st, accum, tile_plan, out, n_slots, world, rank, tiles_x,
+                    xbound, height, error_flag);
+}
+hipError_t launch_assemble_plane(hipStream_t st, const float* gathered, float* frame, const uint32_t* rank_base,
+                                 uint32_t world, uint32_t tiles_x, uint32_t xbound, uint32_t height, uint32_t width,
+                                 uint32_t total, uint32_t stride_px, uint32_t n_tiles) {
+  return launch(assemble_kernel<1>, (total + 255) / 256, 256, st, gathered, frame, rank_base, world, tiles_x, xbound,
                     height, width, total, stride_px, n_tiles);
 }
 hipError_t launch_features_error(hipStream_t st, float4* out, uint64_t n_f4, const unsigned long long* error_flag) {
