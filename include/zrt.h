@@ -795,6 +795,133 @@ int zrt_render_denoised_guided(const zrt_scene* scene, const zrt_camera* camera,
                                float* out_noisy, float* out_features, float* out_variance, zrt_stats* stats,
                                double* denoise_ms);
 
+/* ---- temporal accumulation: the last frame reprojected under a moving camera --- *
+ * The filters above treat a frame as the only frame there is.  This step (the
+ * temporal half of SVGF, Schied et al. 2017) finds, for every pixel, where its
+ * first-hit surface point was in the previous frame of the same scene, decides
+ * from the feature buffers whether that history shows the same surface, and blends
+ * the history into the frame.  The variance plane is propagated through the blend
+ * exactly, so zrt_ctx_denoise_guided's colour test tightens by itself on the
+ * accumulated frame.  A context keeps the state: the previous camera, and per
+ * pixel of D the previous features, a history {r, g, b, V} and a history length.
+ *
+ * The reprojection plan (host, f32, nothing fused).  o, llc, H, W = the previous
+ * camera's origin, lower_left_corner, horizontal, vertical; b = llc - o;
+ *     cross(a, c) = (a.y*c.z - a.z*c.y, a.z*c.x - a.x*c.z, a.x*c.y - a.y*c.x)
+ *     dot(a, c)   = (a.x*c.x + a.y*c.y) + a.z*c.z
+ *     rn = cross(W, H)    ru = cross(b, W)    rv = cross(H, b)    s = dot(b, rn)
+ * Camera.init's vectors give s > 0 (H x W points backwards, W x H forwards); s < 0 - a
+ * left-handed camera - negates rn, ru and rv.  s == 0 or NaN: valid = 0, and a temporal
+ * call with such a plan has no history.
+ * A point P = o + l (b + u H + v W) has d = P - o with dot(d, rn) = l |s|,
+ * dot(d, ru) = l u |s|, dot(d, rv) = l v |s|: it lies in front of the previous
+ * camera iff den = dot(d, rn) > 0, at the pixel coordinates
+ *     fx = (dot(d, ru) / den) * float(width)    fy = (dot(d, rv) / den) * float(height)
+ * (pixel centres are the integers: zrt_ctx_features shoots pixel x at u = float(x) /
+ * float(width)). */
+typedef struct zrt_reproject_plan {
+  zrt_vec3 origin;  /* o */
+  zrt_vec3 rn, ru, rv;
+  float s;          /* dot(b, rn) before the sign rule */
+  uint32_t valid;
+} zrt_reproject_plan;
+/* Only params->width / height are read beyond the validation of the params (they
+ * scale fx / fy in the kernel; the plan's vectors do not depend on them). */
+int zrt_debug_reproject_plan(const zrt_camera* prev, const zrt_params* params, zrt_reproject_plan* out);
+
+/* Definition.  All f32, nothing fused, IEEE `/` and sqrtf, in this order.  D, the
+ * feature buffer, a_min = 2^-6 and the demodulation rule are the guided filter's.
+ * n_D = height.  On the host inv_n = 1.0f / sigma_normal, inv_z = 1.0f / sigma_depth
+ * for the terms that are on.  Pixels outside D are copied (colour and variance),
+ * their length is 0 and they are never a tap.  Per pixel p = (x, y) of D:
+ *  1. c = frame(p), v = variance(p).  With ZRT_TA_DEMODULATE and id(p) != 0:
+ *     c.c = A.c > a_min ? c.c / A.c : c.c per channel, am = ((A.r + A.g) + A.b) *
+ *     (1.0f / 3.0f), v = am > a_min ? v / (am * am) : v.  The history then holds
+ *     demodulated values.
+ *  2. No history - out = c, outv = v, n = 1 - when the context holds no state (the
+ *     first call, after zrt_ctx_temporal_reset, after a change of width, height or
+ *     ZRT_TA_DEMODULATE, a previous camera whose plan has valid = 0) or id(p) == 0:
+ *     the background is a function of the direction and carries no noise.
+ *  3. Where the point was.  The camera equal to the previous one byte for byte
+ *     (decided on the host): fx = float(x), fy = float(y), te = t(p).  Otherwise the
+ *     pixel-centre ray as zrt_ctx_features builds it: u = float(x) / float(width),
+ *     v = float(y) / float(height), e = ((llc + H * u) + W * v) - o per component
+ *     (camera.zig:46-51), dir = e / sqrtf((e.x*e.x + e.y*e.y) + e.z*e.z) (Ray.init);
+ *     P = o + dir * t(p) per component (ray.zig:14-16); d = P - o_prev; den, fx, fy
+ *     as above; te = sqrtf(dot(d, d)); and there is no history unless den > 0,
+ *     fx > -1.0f, fx < float(n_D), fy > -1.0f, fy < float(n_D) (a NaN fails).
+ *  4. x0f = floorf(fx), a = fx - x0f, likewise y0f, bb; kz = inv_z * (1.0f / te).
+ *     nmin = 2^32 - 1.  Four taps (i, j) = (0,0), (1,0), (0,1), (1,1) at q = (x0 + i,
+ *     y0 + j) with w = (i ? a : 1.0f - a) * (j ? bb : 1.0f - bb).  A tap is skipped
+ *     unless q is in D, w > 0, len(q) != 0, id_prev(q) != 0, with the normal term
+ *     on 1.0f - ((dNx*dNx + dNy*dNy) + dNz*dNz) * inv_n > 0 for dN = N(p) - N_prev(q),
+ *     with the depth term on 1.0f - |te - t_prev(q)| * kz > 0, and no lane of the
+ *     history {r, g, b, V} at q is NaN.  A surviving tap adds acc.c = acc.c +
+ *     Hc(q).c * w, vacc = vacc + Hv(q) * w, wsum = wsum + w, nmin = min(nmin, len(q)).
+ *     Surface ids are not compared: adjacent triangles of one mesh differ in id.
+ *  5. No tap survived: as in 2.  Else h.c = acc.c / wsum, hv = vacc / wsum,
+ *     n = min(nmin + 1, max_history), r = 1.0f / float(n), al = r > alpha_min ? r :
+ *     alpha_min, om = 1.0f - al, out.c = h.c * om + c.c * al,
+ *     outv = hv * (om * om) + v * (al * al).
+ *  6. The history at p becomes {out, outv}, len(p) = n, and the previous features
+ *     at p the features at p.  The outputs are out - with ZRT_TA_DEMODULATE and
+ *     id(p) != 0 channel c times A.c where A.c > a_min - outv (times am * am where
+ *     am > a_min) and n.
+ * The variance line of step 5 assumes the history and the frame are independent:
+ * change params->seed from frame to frame.  The bilinear weights interpolate the
+ * history's variance as a value; they do not claim its taps are independent.
+ * NaN: a NaN pixel of the frame gives a NaN output and a NaN history entry, which
+ * the next frame skips as a tap - the NaN frame of a device error stays
+ * recognisable and does not outlive one frame. */
+typedef struct zrt_temporal {
+  float alpha_min;       /* in [0, 1]: the least weight of the new frame in the blend */
+  uint32_t max_history;  /* 1 .. 65535; 0 selects ZRT_DEFAULT_TEMPORAL_HISTORY */
+  float sigma_normal;    /* each: finite > 0 = on, 0 = that test off */
+  float sigma_depth;     /* relative: a fraction of the reprojected distance te */
+  uint32_t flags;        /* ZRT_TA_* */
+  uint32_t reserved[3];
+} zrt_temporal;
+enum { ZRT_TA_DEMODULATE = 1u };
+enum { ZRT_DEFAULT_TEMPORAL_HISTORY = 32u };
+
+/* The default temporal step (host only): the winner of the grid search of
+ * tools/temporal_probe.py (profiles/r12/temporal/defaults.json). */
+int zrt_temporal_defaults(zrt_temporal* out);
+
+/* One frame of the definition above on hip_stream (NULL: the context's own).
+ * Asynchronous, one launch; the state belongs to the context, so the calls of a
+ * sequence go to one stream (or to streams the caller orders).  camera and params:
+ * what dev_features was made with.  dev_frame, dev_out: width*height*3 f32;
+ * dev_features: width*height*8 f32, 16-byte aligned; dev_variance: width*height f32;
+ * dev_out_variance (may be NULL): the same; dev_out_len (may be NULL): width*height
+ * uint32.  The state is allocated on first use and again when width or height
+ * change.  ZRT_E_INVALID: what zrt_ctx_denoise_guided refuses of its pointers and
+ * params, alpha_min outside [0, 1] or NaN, a negative, NaN or infinite sigma,
+ * max_history > 65535, an unknown flag, dev_out == dev_frame. */
+int zrt_ctx_temporal(zrt_ctx* ctx, const zrt_camera* camera, const zrt_params* params, const zrt_temporal* tp,
+                     const float* dev_frame, const float* dev_features, const float* dev_variance,
+                     float* dev_out, float* dev_out_variance, uint32_t* dev_out_len, void* hip_stream);
+/* Drops the history: the next zrt_ctx_temporal is a first call. */
+int zrt_ctx_temporal_reset(zrt_ctx* ctx);
+/* Device time of the last zrt_ctx_temporal in ms (HIP events; waits for it). */
+int zrt_ctx_temporal_ms(zrt_ctx* ctx, double* ms);
+
+/* A sequence of n_frames frames of one scene on one GPU (params->device), cameras[k]
+ * the camera of frame k.  Frame k: an accumulation run of one pass with seed
+ * params->seed + k, zrt_ctx_accum_variance, both assembles, zrt_ctx_features,
+ * zrt_ctx_temporal (tp NULL: zrt_temporal_defaults), then zrt_ctx_denoise_guided
+ * on its colour and variance (dn NULL: the guided defaults' filter; dn_flags are
+ * the caller's either way).  on_frame (may be NULL) receives each filtered frame
+ * (width*height*3 f32; it is out_rgb) and its index; a nonzero return stops the
+ * sequence.  out_rgb: the last filtered frame; stats (may be NULL): the last
+ * frame's.  ZRT_E_INVALID before any device work: zrt_render_denoised_guided's
+ * refusal of a ragged or single-chunk samples_per_pixel, n_frames == 0, and what
+ * zrt_ctx_temporal refuses of tp. */
+typedef int (*zrt_frame_fn)(void* user, const float* rgb, uint32_t frame);
+int zrt_render_temporal(const zrt_scene* scene, const zrt_camera* cameras, uint32_t n_frames,
+                        const zrt_params* params, const zrt_temporal* tp, const zrt_denoise* dn, uint32_t dn_flags,
+                        zrt_frame_fn on_frame, void* user, float* out_rgb, zrt_stats* stats);
+
 /* ---- host-side scene ingestion (the caller side of the seam) ------------- *
  * Restatement of scenes.zig / obj_reader.zig / png_image.zig texture loading
  * so tests and bench can build the reference's scenes without Zig.  Assets are

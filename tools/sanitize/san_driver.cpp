@@ -256,6 +256,34 @@ static void pass_and_adapt_plans() {
         "adapt plan: null arguments accepted");
 }
 
+// plan_reproject at the cases of tests/test_temporal_host.py: a scene's camera, the
+// same mirrored (s changes sign, the plan stays valid), parallel axes, a NaN, nulls
+static void reproject_plans(const std::string& assets) {
+  zrt_scene_data* d = nullptr;
+  zrt_camera cam;
+  CHECK(zrt_scene_load(1, assets.c_str(), &d, &cam) == ZRT_OK, "scene 1: %s", zrt_last_error());
+  zrt_scene_free(d);
+  const zrt_params p = params(24, 24, 1, 1, ZRT_RNG_COUNTER);
+  zrt_reproject_plan a, b;
+  CHECK(zrt_debug_reproject_plan(&cam, &p, &a) == ZRT_OK && a.valid == 1, "reproject plan: scene camera");
+  zrt_camera m = cam;
+  m.lower_left_corner = {cam.lower_left_corner.x + cam.horizontal.x, cam.lower_left_corner.y + cam.horizontal.y,
+                         cam.lower_left_corner.z + cam.horizontal.z};
+  m.horizontal = {-cam.horizontal.x, -cam.horizontal.y, -cam.horizontal.z};
+  CHECK(zrt_debug_reproject_plan(&m, &p, &b) == ZRT_OK && b.valid == 1 && (a.s < 0.0f) != (b.s < 0.0f),
+        "reproject plan: mirrored camera (s %g, %g)", double(a.s), double(b.s));
+  m = cam;
+  m.vertical = m.horizontal;
+  CHECK(zrt_debug_reproject_plan(&m, &p, &b) == ZRT_OK && b.valid == 0, "reproject plan: parallel axes are valid");
+  m = cam;
+  m.origin.y = NAN;
+  CHECK(zrt_debug_reproject_plan(&m, &p, &b) == ZRT_OK && b.valid == 0, "reproject plan: a NaN origin is valid");
+  CHECK(zrt_debug_reproject_plan(nullptr, &p, &b) == ZRT_E_INVALID &&
+            zrt_debug_reproject_plan(&cam, nullptr, &b) == ZRT_E_INVALID &&
+            zrt_debug_reproject_plan(&cam, &p, nullptr) == ZRT_E_INVALID,
+        "reproject plan: null arguments accepted");
+}
+
 int main(int argc, char** argv) {
   if (argc < 3) {
     std::fprintf(stderr, "usage: %s ASSETS_DIR TMP_DIR\n", argv[0]);
@@ -264,6 +292,7 @@ int main(int argc, char** argv) {
   const std::string assets = argv[1], tmp = argv[2];
   for (uint32_t i : {0u, 1u, 2u, 3u, 4u}) one_scene(i, assets, tmp);
   pass_and_adapt_plans();
+  reproject_plans(assets);
 
   // error paths: unknown scene index, missing files, a truncated binary scene
   zrt_scene_data* d = nullptr;

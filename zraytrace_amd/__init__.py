@@ -20,7 +20,7 @@ from . import _ffi
 from ._ffi import (ZRT_PRNG_XOROSHIRO128, ZRT_PRNG_XOSHIRO256, ZRT_RNG_COUNTER,  # noqa: F401
                    ZRT_RNG_REFERENCE_STREAM, ZRT_TRAVERSAL_FAST, ZRT_TRAVERSAL_REFERENCE,
                    ZRT_TRAVERSAL_BINARY, ZRT_FLAG_STATS, ZRT_FLAG_NO_SCHEDULE, ZRT_FLAG_SCANLINES, ZRT_FLAG_GUARD,
-                   ZRT_DN_DEMODULATE, ZrtError, check)
+                   ZRT_DN_DEMODULATE, ZRT_TA_DEMODULATE, ZrtError, check)
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ASSETS = os.path.join(REPO, "assets")
@@ -300,6 +300,48 @@ def render_denoised_guided(scene, camera: _ffi.Camera, params: RenderParams, tol
     return rgb, noisy, features, variance, stats
 
 
+def temporal_defaults() -> _ffi.Temporal:
+    """The default temporal step (zrt_temporal_defaults; no device): what
+    tools/temporal_probe.py's grid search chose."""
+    out = _ffi.Temporal()
+    check(lib().zrt_temporal_defaults(C.byref(out)))
+    return out
+
+
+def debug_reproject_plan(prev: _ffi.Camera, params: RenderParams) -> _ffi.ReprojectPlan:
+    """The reprojection plan of a previous camera (zrt_debug_reproject_plan; no device)."""
+    out = _ffi.ReprojectPlan()
+    p = params.abi()
+    check(lib().zrt_debug_reproject_plan(C.byref(prev), C.byref(p), C.byref(out)))
+    return out
+
+
+def render_temporal(scene, cameras, params: RenderParams, temporal: _ffi.Temporal = None,
+                    denoise: _ffi.Denoise = None, flags: int = None, on_frame=None):
+    """A sequence of frames, cameras[k] the camera of frame k, through the temporal step
+    and the guided filter (zrt_render_temporal; temporal None: temporal_defaults(), denoise
+    None: the guided defaults, flags None: their flags).  on_frame(rgb float32[H, W, 3], k)
+    is called with each filtered frame; a true return stops the sequence.  Returns (the
+    last filtered frame, the last frame's stats)."""
+    view = scene.view if isinstance(scene, LoadedScene) else scene
+    cams = (_ffi.Camera * len(cameras))(*cameras)
+    rgb = np.zeros((params.height, params.width, 3), dtype=np.float32)
+    st = _ffi.Stats()
+    p = params.abi()
+    if flags is None:
+        flags = denoise_guided_defaults()[1]
+
+    def cb(_user, ptr, k):
+        return 1 if on_frame(rgb.copy(), k) else 0
+
+    fn = _ffi.FRAME_FN(cb) if on_frame is not None else C.cast(None, _ffi.FRAME_FN)
+    check(lib().zrt_render_temporal(view, cams, len(cameras), C.byref(p),
+                                    C.byref(temporal) if temporal is not None else None,
+                                    C.byref(denoise) if denoise is not None else None, flags, fn, None,
+                                    rgb.ctypes.data_as(C.POINTER(C.c_float)), C.byref(st)))
+    return rgb, st.as_dict()
+
+
 def _scanlines_np(rows) -> np.ndarray:
     """zrt_scanline[height] -> uint64 array [height, 6] (columns: _ffi.SCANLINE_FIELDS)."""
     return np.ctypeslib.as_array(rows).view(np.uint64).reshape(len(rows), 6).copy()
@@ -506,6 +548,27 @@ class RenderContext:
                                            C.c_void_p(dev_features), C.c_void_p(dev_variance or None),
                                            C.c_void_p(dev_out), C.c_void_p(dev_out_variance or None),
                                            C.c_void_p(stream or None)))
+
+    def temporal(self, camera, params: RenderParams, tp: _ffi.Temporal, dev_frame: int, dev_features: int,
+                 dev_variance: int, dev_out: int, dev_out_variance: int = 0, dev_out_len: int = 0, stream: int = 0):
+        """One frame of the temporal accumulation (zrt_ctx_temporal; device pointers,
+        asynchronous; the definition: zrt.h): the context's history reprojected from the
+        previous call's camera and blended into the frame at dev_frame."""
+        p = params.abi()
+        check(lib().zrt_ctx_temporal(self._h, C.byref(camera), C.byref(p), C.byref(tp), C.c_void_p(dev_frame or None),
+                                     C.c_void_p(dev_features or None), C.c_void_p(dev_variance or None),
+                                     C.c_void_p(dev_out or None), C.c_void_p(dev_out_variance or None),
+                                     C.c_void_p(dev_out_len or None), C.c_void_p(stream or None)))
+
+    def temporal_reset(self):
+        """Drop the temporal history (zrt_ctx_temporal_reset)."""
+        check(lib().zrt_ctx_temporal_reset(self._h))
+
+    def temporal_ms(self) -> float:
+        """Device time of the last temporal() in ms (zrt_ctx_temporal_ms; waits for it)."""
+        ms = C.c_double()
+        check(lib().zrt_ctx_temporal_ms(self._h, C.byref(ms)))
+        return ms.value
 
     def denoise_ms(self) -> float:
         """Device time of the last denoise() in ms (zrt_ctx_denoise_ms; waits for it)."""

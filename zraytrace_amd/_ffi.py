@@ -35,6 +35,7 @@ ZRT_FLAG_NO_SCHEDULE = 2
 ZRT_FLAG_SCANLINES = 4
 ZRT_FLAG_GUARD = 8
 ZRT_DN_DEMODULATE = 1
+ZRT_TA_DEMODULATE = 1
 
 
 class Vec3(C.Structure):
@@ -179,6 +180,22 @@ class VariancePlan(C.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_}
 
 
+class ReprojectPlan(C.Structure):
+    _fields_ = [("origin", Vec3), ("rn", Vec3), ("ru", Vec3), ("rv", Vec3), ("s", C.c_float), ("valid", C.c_uint32)]
+
+
+class Temporal(C.Structure):
+    _fields_ = [("alpha_min", C.c_float), ("max_history", C.c_uint32), ("sigma_normal", C.c_float),
+                ("sigma_depth", C.c_float), ("flags", C.c_uint32), ("reserved", C.c_uint32 * 3)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_ if name != "reserved"}
+
+
+# zrt_frame_fn: int (*)(void* user, const float* rgb, uint32_t frame)
+FRAME_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_float), C.c_uint32)
+
+
 class BvhNode(C.Structure):
     _fields_ = [("min", Vec3), ("left", C.c_int32), ("max", Vec3), ("right", C.c_int32)]
 
@@ -256,6 +273,15 @@ SIGNATURES = [
                                              C.POINTER(Adaptive), C.POINTER(Denoise), C.c_uint32,
                                              C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float),
                                              C.POINTER(C.c_float), C.POINTER(Stats), C.POINTER(C.c_double)]),
+    ("zrt_debug_reproject_plan", C.c_int, [C.POINTER(Camera), C.POINTER(Params), C.POINTER(ReprojectPlan)]),
+    ("zrt_temporal_defaults", C.c_int, [C.POINTER(Temporal)]),
+    ("zrt_ctx_temporal", C.c_int, [_P, C.POINTER(Camera), C.POINTER(Params), C.POINTER(Temporal), _P, _P, _P, _P, _P,
+                                   _P, _P]),
+    ("zrt_ctx_temporal_reset", C.c_int, [_P]),
+    ("zrt_ctx_temporal_ms", C.c_int, [_P, C.POINTER(C.c_double)]),
+    ("zrt_render_temporal", C.c_int, [C.POINTER(Scene), C.POINTER(Camera), C.c_uint32, C.POINTER(Params),
+                                      C.POINTER(Temporal), C.POINTER(Denoise), C.c_uint32, FRAME_FN, _P,
+                                      C.POINTER(C.c_float), C.POINTER(Stats)]),
     ("zrt_scene_load", C.c_int, [C.c_uint32, C.c_char_p, C.POINTER(_P), C.POINTER(Camera)]),
     ("zrt_scene_view", C.POINTER(Scene), [_P]),
     ("zrt_scene_free", None, [_P]),

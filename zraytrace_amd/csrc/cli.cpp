@@ -31,6 +31,13 @@
 // (zrt_render_denoised_guided; $ZRT_DENOISE=1: its own defaults), =2 adds albedo
 // demodulation; the samples must then be two or more whole sample chunks
 // ($ZRT_SAMPLE_CHUNK sets params.sample_chunk, default 32).
+// $ZRT_TEMPORAL_FRAMES=n renders a sequence of n frames through the temporal step and the
+// guided filter (zrt_render_temporal, both at their defaults; the samples as for
+// $ZRT_DENOISE_VARIANCE) and writes the last filtered frame; $ZRT_TEMPORAL_TRUCK=<delta>
+// (default 0: a static camera) moves the camera sideways: frame k's origin and
+// lower_left_corner are the scene's plus (float(k) * delta) * horizontal per component, in
+// f32.  One line per frame on stderr in place of the scanline lines.  It is refused with
+// every other mode above.
 #include <unistd.h>
 
 #include <chrono>
@@ -114,6 +121,11 @@ int on_pass(void* user, const float* rgb, const zrt_pass_info* info) {
                double(pv->pixels) * info->pass_samples / (double(info->render_ms) / 1000.0) / 1e6);
   // (an unwritable preview stops the run; the final write below reports the error)
   return zrt_image_write_png(pv->filename, rgb, pv->width, pv->height) != ZRT_OK;
+}
+
+int on_frame(void*, const float*, uint32_t frame) {
+  std::fprintf(stderr, "Frame: %u\n", frame + 1);
+  return 0;
 }
 
 int on_level(void*, const float*, const zrt_level_info* info) {
@@ -235,6 +247,37 @@ int main(int argc, char** argv) {
     }
   }
 
+  // $ZRT_TEMPORAL_FRAMES=n [$ZRT_TEMPORAL_TRUCK=delta]: n frames through zrt_render_temporal
+  const char* tf_env = std::getenv("ZRT_TEMPORAL_FRAMES");
+  std::vector<zrt_camera> cameras;
+  if (tf_env) {
+    if (pass_env || tol_env || dn_env || !devices.empty()) {
+      std::fprintf(stderr, "error: ZRT_TEMPORAL_FRAMES renders its own sequence on one GPU: unset ZRT_DEVICES, "
+                           "ZRT_PASS_SAMPLES, ZRT_ADAPTIVE_TOL and ZRT_DENOISE (or ZRT_TEMPORAL_FRAMES)\n");
+      zrt_scene_free(data);
+      return 1;
+    }
+    const unsigned long n = std::strtoul(tf_env, nullptr, 10);
+    const char* truck = std::getenv("ZRT_TEMPORAL_TRUCK");
+    const float delta = truck ? std::strtof(truck, nullptr) : 0.0f;
+    if (n == 0 || n > 65535) {
+      std::fprintf(stderr, "error: ZRT_TEMPORAL_FRAMES is a frame count, 1 .. 65535\n");
+      zrt_scene_free(data);
+      return 1;
+    }
+    for (unsigned long k = 0; k < n; ++k) {
+      zrt_camera ck = camera;
+      const float f = float(k) * delta;
+      ck.origin.x = camera.origin.x + f * camera.horizontal.x;
+      ck.origin.y = camera.origin.y + f * camera.horizontal.y;
+      ck.origin.z = camera.origin.z + f * camera.horizontal.z;
+      ck.lower_left_corner.x = camera.lower_left_corner.x + f * camera.horizontal.x;
+      ck.lower_left_corner.y = camera.lower_left_corner.y + f * camera.horizontal.y;
+      ck.lower_left_corner.z = camera.lower_left_corner.z + f * camera.horizontal.z;
+      cameras.push_back(ck);
+    }
+  }
+
   std::fprintf(stderr, "Raytrace start\n");
   std::fprintf(stderr, " - Surfaces:                 %u\n", scene->n_prims);
   std::fprintf(stderr, " - Pixels:                   %ux%u\n", unsigned(width), unsigned(height));
@@ -250,7 +293,11 @@ int main(int argc, char** argv) {
   std::vector<uint32_t> sample_map;
   std::vector<float> noisy;
   double denoise_ms = 0.0;
-  if (dn_env) {
+  if (tf_env) {
+    zrt_denoise_guided_defaults(&dn, &dn_flags);
+    rc = zrt_render_temporal(scene, cameras.data(), uint32_t(cameras.size()), &params, nullptr, &dn, dn_flags,
+                             on_frame, nullptr, image.data(), &stats);
+  } else if (dn_env) {
     zrt_adaptive ad;
     std::memset(&ad, 0, sizeof(ad));
     if (tol_env) ad.tolerance = std::strtof(tol_env, nullptr);
@@ -298,7 +345,7 @@ int main(int argc, char** argv) {
   // printProgress after every scanline (raytrace.zig:37-50, 184)
   const double pixels_per_second = double(stats.pixels_processed) / render_runtime;
   unsigned long long pixels = 0, samples_sum = 0, rays = 0;
-  for (uint32_t y = 0; y < height && !pass_env && !dn_env; ++y) {
+  for (uint32_t y = 0; y < height && !pass_env && !dn_env && !tf_env; ++y) {
     pixels += rows[y].pixels;
     samples_sum += rows[y].samples;
     rays += rows[y].rays;
@@ -327,6 +374,10 @@ int main(int argc, char** argv) {
     std::fprintf(stderr, "  Denoise:               %u iterations, %.3f ms%s\n",
                  dn.iterations ? dn.iterations : unsigned(ZRT_DEFAULT_DENOISE_ITERATIONS), denoise_ms,
                  !var_env ? "" : dn_flags ? " (variance-guided, demodulated)" : " (variance-guided)");
+
+  if (tf_env)
+    std::fprintf(stderr, "  Temporal:              %u frames (the counters above are the last frame's)\n",
+                 unsigned(cameras.size()));
 
   rc = zrt_image_write_png(filename, image.data(), width, height);
   if (const char* path = std::getenv("ZRT_DENOISE_NOISY"); path && dn_env && rc == ZRT_OK)

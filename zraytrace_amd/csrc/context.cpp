@@ -1330,6 +1330,120 @@ int zrt_ctx_denoise_ms(zrt_ctx* c, double* ms) {
   ZRT_CATCH_ALL
 }
 
+// ---- temporal accumulation (zrt.h "temporal accumulation"; the kernel: temporal.hip) ----
+// the default step: the winner of tools/temporal_probe.py's grid
+// (profiles/r12/temporal/defaults.json)
+#define ZRT_TA_ALPHA_MIN 0.0f
+#define ZRT_TA_MAX_HISTORY 2u
+#define ZRT_TA_SIGMA_NORMAL 0.0f
+#define ZRT_TA_SIGMA_DEPTH 0.0f
+#define ZRT_TA_FLAGS 0u
+int zrt_temporal_defaults(zrt_temporal* out) {
+  if (!out) return fail(ZRT_E_INVALID, "null argument");
+  *out = zrt_temporal{};
+  out->alpha_min = ZRT_TA_ALPHA_MIN;
+  out->max_history = ZRT_TA_MAX_HISTORY;
+  out->sigma_normal = ZRT_TA_SIGMA_NORMAL;
+  out->sigma_depth = ZRT_TA_SIGMA_DEPTH;
+  out->flags = ZRT_TA_FLAGS;
+  return ZRT_OK;
+}
+
+int zrt_ctx_temporal(zrt_ctx* c, const zrt_camera* cam, const zrt_params* p, const zrt_temporal* tp,
+                     const float* dev_frame, const float* dev_features, const float* dev_variance, float* dev_out,
+                     float* dev_out_variance, uint32_t* dev_out_len, void* hip_stream) {
+  zrt::TemporalLaunch l{};
+  int rc = zrt::plan_temporal(p, tp, &l);  // (the refusals that need no context come first)
+  if (rc) return rc;
+  if (dev_out && static_cast<const float*>(dev_out) == dev_frame)
+    return fail(ZRT_E_INVALID, "temporal: dev_out must not be dev_frame");
+  if (reinterpret_cast<uintptr_t>(dev_features) & 15u)
+    return fail(ZRT_E_INVALID, "temporal: dev_features must be 16-byte aligned");
+  if (!dev_variance) return fail(ZRT_E_INVALID, "temporal: dev_variance is null");
+  if (dev_out_variance && static_cast<const float*>(dev_out_variance) == dev_variance)
+    return fail(ZRT_E_INVALID, "temporal: dev_out_variance must not be dev_variance");
+  if (!c || !cam || !dev_frame || !dev_features || !dev_out) return fail(ZRT_E_INVALID, "null argument");
+  if (int(p->device) != c->device)
+    return fail(ZRT_E_INVALID, "params->device differs from the device the context was created on");
+  try {
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t st = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
+    const size_t plane = size_t(l.n) * l.n;
+    if (c->ta_width != p->width || c->ta_height != p->height || c->ta_hist[0].n < plane) {
+      for (int k = 0; k < 2; ++k) {  // (hipFree waits for the frames in flight)
+        c->ta_hist[k].alloc(plane);
+        c->ta_feat[k].alloc(2 * plane);
+        c->ta_len[k].alloc(plane);
+      }
+      c->ta_width = p->width;
+      c->ta_height = p->height;
+      c->ta_live = false;
+    }
+    if (c->ta_demod != l.demod) c->ta_live = false;
+    if (c->ta_live) {
+      zrt_reproject_plan rp{};
+      rc = zrt::plan_reproject(&c->ta_cam, p, &rp);
+      if (rc) return rc;
+      l.history = rp.valid;
+      l.static_cam = std::memcmp(cam, &c->ta_cam, sizeof(zrt_camera)) == 0 ? 1u : 0u;
+      const zrt_vec3* src[4] = {&rp.origin, &rp.rn, &rp.ru, &rp.rv};
+      float* dst[4] = {l.porg, l.rn, l.ru, l.rv};
+      for (int k = 0; k < 4; ++k) {
+        dst[k][0] = src[k]->x;
+        dst[k][1] = src[k]->y;
+        dst[k][2] = src[k]->z;
+      }
+    }
+    {
+      const zrt_vec3* src[4] = {&cam->origin, &cam->lower_left_corner, &cam->horizontal, &cam->vertical};
+      float* dst[4] = {l.org, l.llc, l.hor, l.ver};
+      for (int k = 0; k < 4; ++k) {
+        dst[k][0] = src[k]->x;
+        dst[k][1] = src[k]->y;
+        dst[k][2] = src[k]->z;
+      }
+    }
+    if (!c->ta_ev0) {
+      HIPCHK(hipEventCreate(&c->ta_ev0));
+      HIPCHK(hipEventCreate(&c->ta_ev1));
+    }
+    const uint32_t cur = c->ta_cur, nxt = cur ^ 1u;
+    const zrt::TemporalPlanes prev{c->ta_hist[cur].p, c->ta_feat[cur].p, c->ta_len[cur].p};
+    const zrt::TemporalPlanes next{c->ta_hist[nxt].p, c->ta_feat[nxt].p, c->ta_len[nxt].p};
+    HIPCHK(hipEventRecord(c->ta_ev0, st));
+    HIPCHK(zrt::temporal_enqueue(l, dev_frame, reinterpret_cast<const float4*>(dev_features), dev_variance, prev, next,
+                                 dev_out, dev_out_variance, dev_out_len, st));
+    HIPCHK(hipEventRecord(c->ta_ev1, st));
+    c->ta_cur = nxt;
+    c->ta_cam = *cam;
+    c->ta_demod = l.demod;
+    c->ta_live = true;
+    c->ta_launched = true;
+    return ZRT_OK;
+  }
+  ZRT_CATCH_ALL
+}
+
+int zrt_ctx_temporal_reset(zrt_ctx* c) {
+  if (!c) return fail(ZRT_E_INVALID, "null argument");
+  c->ta_live = false;
+  return ZRT_OK;
+}
+
+int zrt_ctx_temporal_ms(zrt_ctx* c, double* ms) {
+  if (!c || !ms) return fail(ZRT_E_INVALID, "null argument");
+  if (!c->ta_launched) return fail(ZRT_E_INVALID, "no temporal step launched on this context yet");
+  try {
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipEventSynchronize(c->ta_ev1));
+    float f = 0.0f;
+    HIPCHK(hipEventElapsedTime(&f, c->ta_ev0, c->ta_ev1));
+    *ms = f;
+    return ZRT_OK;
+  }
+  ZRT_CATCH_ALL
+}
+
 int zrt_trace(const zrt_scene* scene, const zrt_params* params, const float* rays, uint32_t n_rays, float* out_t,
               int32_t* out_prim) {
   if (!params || (n_rays && (!rays || !out_t || !out_prim))) return fail(ZRT_E_INVALID, "null argument");

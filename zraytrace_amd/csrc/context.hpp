@@ -144,6 +144,16 @@ struct zrt_ctx {
   zrt::DevBuf<float4> dn_buf[2];
   hipEvent_t dn_ev0 = nullptr, dn_ev1 = nullptr;
   bool dn_launched = false;
+  // ---- temporal accumulation (zrt_ctx_temporal): the previous frame's camera and, in D's
+  // layout (n * n, n = the frame's height), its history, features and history lengths,
+  // double-buffered: a frame reads [ta_cur] and writes [ta_cur ^ 1] ----
+  zrt::DevBuf<float4> ta_hist[2], ta_feat[2];
+  zrt::DevBuf<uint32_t> ta_len[2];
+  uint32_t ta_cur = 0, ta_width = 0, ta_height = 0, ta_demod = 0;
+  bool ta_live = false;  // [ta_cur] holds a frame rendered through ta_cam
+  zrt_camera ta_cam{};
+  hipEvent_t ta_ev0 = nullptr, ta_ev1 = nullptr;
+  bool ta_launched = false;
   // ---- the variance plane (zrt_ctx_accum_variance): each local tile's {ik, sc} ----
   zrt::DevBuf<float2> var_plan;
   std::vector<float2> var_plan_host;
@@ -157,6 +167,8 @@ struct zrt_ctx {
   ~zrt_ctx() {
     if (feat_done) (void)hipEventDestroy(feat_done);
     if (feat_err_host) (void)hipHostFree(feat_err_host);
+    if (ta_ev0) (void)hipEventDestroy(ta_ev0);
+    if (ta_ev1) (void)hipEventDestroy(ta_ev1);
     if (dn_ev0) (void)hipEventDestroy(dn_ev0);
     if (dn_ev1) (void)hipEventDestroy(dn_ev1);
     if (count_host) (void)hipHostFree(count_host);

@@ -32,6 +32,11 @@ int zrt_debug_variance_plan(const zrt_params* params, uint32_t n_samples, zrt_va
   return zrt::plan_variance(params, n_samples, out);
 }
 
+int zrt_debug_reproject_plan(const zrt_camera* prev, const zrt_params* params, zrt_reproject_plan* out) {
+  if (!out) return fail(ZRT_E_INVALID, "null argument");
+  return zrt::plan_reproject(prev, params, out);
+}
+
 int zrt_debug_lds_plans(const zrt_scene* scene, uint32_t* n_checked) {
   if (!n_checked) return fail(ZRT_E_INVALID, "null argument");
   *n_checked = 0;

@@ -12,6 +12,7 @@
 
 #include "denoise.hpp"
 #include "kernels.hpp"
+#include "temporal.hpp"
 #include "zrt.hpp"
 
 namespace zrt {
@@ -129,6 +130,8 @@ int plan_pass(const zrt_params* p, uint32_t done, uint32_t n_samples, zrt_pass_p
 int plan_adapt(const zrt_params* p, const zrt_adaptive* ad, std::vector<uint32_t>* levels);
 int plan_variance(const zrt_params* p, uint32_t n, zrt_variance_plan* out);
 int plan_denoise(const zrt_params* p, const zrt_denoise* dn, DenoiseLaunch* out);
+int plan_reproject(const zrt_camera* prev, const zrt_params* p, zrt_reproject_plan* out);
+int plan_temporal(const zrt_params* p, const zrt_temporal* tp, TemporalLaunch* out);
 
 // ---- flatten.cpp ----
 // `device` >= 0: the GPU that may build the reference BVH (bvh_gpu.hip); a failed

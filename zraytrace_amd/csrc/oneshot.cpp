@@ -347,3 +347,85 @@ int zrt_render_denoised(const zrt_scene* scene, const zrt_camera* camera, const 
                                 &post);
   return zrt::render_one(scene, camera, params, out_noisy, stats, nullptr, &post);
 }
+
+// A sequence of frames of one scene through the temporal step and the guided filter
+// (zrt.h "temporal accumulation"): one context, one set of device buffers, frame k
+// an accumulation run of one pass with seed + k.
+int zrt_render_temporal(const zrt_scene* scene, const zrt_camera* cameras, uint32_t n_frames,
+                        const zrt_params* params, const zrt_temporal* tp, const zrt_denoise* dn, uint32_t dn_flags,
+                        zrt_frame_fn on_frame, void* user, float* out_rgb, zrt_stats* stats) {
+  if (!cameras || !out_rgb) return fail(ZRT_E_INVALID, "null argument");
+  zrt_denoise d;
+  uint32_t default_flags = 0;
+  if (dn) d = *dn;
+  else zrt_denoise_guided_defaults(&d, &default_flags);
+  zrt_temporal t;
+  if (tp) t = *tp;
+  else zrt_temporal_defaults(&t);
+  zrt::DenoiseLaunch l{};
+  int rc = zrt::plan_denoise(params, &d, &l);  // (refused before any device work)
+  if (rc) return rc;
+  if (dn_flags & ~uint32_t(ZRT_DN_DEMODULATE)) return fail(ZRT_E_INVALID, "denoise: unknown flag");
+  zrt::TemporalLaunch tl{};
+  rc = zrt::plan_temporal(params, &t, &tl);
+  if (rc) return rc;
+  zrt_variance_plan vp{};
+  rc = zrt::plan_variance(params, params->samples_per_pixel, &vp);
+  if (rc) return rc;
+  if (n_frames == 0) return fail(ZRT_E_INVALID, "temporal: n_frames must be > 0");
+  zrt_params p = *params;
+  p.rank = 0;
+  p.world_size = 1;
+  zrt_ctx* c = nullptr;
+  rc = zrt_ctx_create(scene, &p, &c);
+  if (rc) return rc;
+  std::unique_ptr<zrt_ctx, int (*)(zrt_ctx*)> guard(c, zrt_ctx_destroy);
+  try {
+    const size_t px = size_t(p.width) * p.height;
+    uint32_t n_tiles = 0;
+    rc = zrt_ctx_tile_count(c, &p, &n_tiles);
+    if (rc) return rc;
+    zrt::DevBuf<float> tiles, frame, feat, var_tiles, var, acc, acc_var, outb;
+    tiles.alloc(size_t(n_tiles) * 64 * 3);
+    frame.alloc(px * 3);
+    feat.alloc(px * 8);
+    var_tiles.alloc(size_t(n_tiles) * 64);
+    var.alloc(px);
+    acc.alloc(px * 3);
+    acc_var.alloc(px);
+    outb.alloc(px * 3);
+    for (uint32_t k = 0; k < n_frames; ++k) {
+      zrt_params pk = p;
+      pk.seed = p.seed + k;  // the blend's variance assumes independent frames
+      const zrt_camera* cam = &cameras[k];
+      rc = zrt_ctx_accum_begin(c, cam, &pk);
+      if (rc) return rc;
+      rc = zrt_ctx_accum_pass(c, pk.samples_per_pixel, tiles.p, nullptr);
+      if (rc) return rc;
+      rc = zrt_ctx_accum_variance(c, var_tiles.p, nullptr);
+      if (rc) return rc;
+      rc = zrt_ctx_assemble(c, &pk, tiles.p, frame.p, nullptr);
+      if (rc) return rc;
+      rc = zrt_ctx_assemble_plane(c, &pk, var_tiles.p, 0, var.p, nullptr);
+      if (rc) return rc;
+      rc = zrt_ctx_features(c, cam, &pk, feat.p, nullptr);
+      if (rc) return rc;
+      rc = zrt_ctx_temporal(c, cam, &pk, &t, frame.p, feat.p, var.p, acc.p, acc_var.p, nullptr, nullptr);
+      if (rc) return rc;
+      rc = zrt_ctx_denoise_guided(c, &pk, &d, dn_flags, acc.p, feat.p, acc_var.p, outb.p, nullptr, nullptr);
+      if (rc) return rc;
+      if (!on_frame && k + 1 < n_frames) continue;  // nobody looks: the frames queue up
+      HIPCHK(hipStreamSynchronize(c->stream));
+      rc = zrt_ctx_sync(c);  // (a feature launch's device error)
+      if (rc) return rc;
+      HIPCHK(hipMemcpy(out_rgb, outb.p, sizeof(float) * 3 * px, hipMemcpyDeviceToHost));
+      if (on_frame && on_frame(user, out_rgb, k) != 0) break;
+    }
+    zrt_stats s;
+    rc = zrt_ctx_stats(c, &s);
+    if (rc) return rc;
+    if (stats) *stats = s;
+    return ZRT_OK;
+  }
+  ZRT_CATCH_ALL
+}

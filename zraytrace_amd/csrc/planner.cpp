@@ -459,4 +459,70 @@ int plan_denoise(const zrt_params* p, const zrt_denoise* dn, DenoiseLaunch* out)
   out->inv_z = inv[3];
   return ZRT_OK;
 }
+
+// The reprojection plan of a previous camera (zrt.h "temporal accumulation";
+// zrt_debug_reproject_plan reports the same): every cross product component is one
+// a*b - c*d, the dot product (x + y) + z, all f32 (this file is built unfused).
+int plan_reproject(const zrt_camera* prev, const zrt_params* p, zrt_reproject_plan* out) {
+  if (!prev) return fail(ZRT_E_INVALID, "null argument");
+  const int rc = validate_params(p);
+  if (rc) return rc;
+  const zrt_vec3 o = prev->origin, H = prev->horizontal, W = prev->vertical;
+  const zrt_vec3 b = {prev->lower_left_corner.x - o.x, prev->lower_left_corner.y - o.y,
+                      prev->lower_left_corner.z - o.z};
+  const auto cross = [](const zrt_vec3& a, const zrt_vec3& c) {
+    return zrt_vec3{a.y * c.z - a.z * c.y, a.z * c.x - a.x * c.z, a.x * c.y - a.y * c.x};
+  };
+  zrt_vec3 rn = cross(W, H), ru = cross(b, W), rv = cross(H, b);
+  const float s = (b.x * rn.x + b.y * rn.y) + b.z * rn.z;
+  if (s < 0.0f) {
+    rn = zrt_vec3{-rn.x, -rn.y, -rn.z};
+    ru = zrt_vec3{-ru.x, -ru.y, -ru.z};
+    rv = zrt_vec3{-rv.x, -rv.y, -rv.z};
+  }
+  out->origin = o;
+  out->rn = rn;
+  out->ru = ru;
+  out->rv = rv;
+  out->s = s;
+  out->valid = (s < 0.0f || s > 0.0f) ? 1u : 0u;  // (0 and NaN: no)
+  return ZRT_OK;
+}
+
+// What zrt_ctx_temporal refuses of a zrt_temporal, and the camera-independent part
+// of the launch it asks for otherwise.
+int plan_temporal(const zrt_params* p, const zrt_temporal* tp, TemporalLaunch* out) {
+  if (!tp) return fail(ZRT_E_INVALID, "temporal is null");
+  const int rc = validate_params(p);
+  if (rc) return rc;
+  if (!(tp->alpha_min >= 0.0f && tp->alpha_min <= 1.0f))
+    return fail(ZRT_E_INVALID, "temporal alpha_min must lie in [0, 1]");
+  if (tp->max_history > 65535u) return fail(ZRT_E_INVALID, "temporal max_history must be <= 65535");
+  if (tp->flags & ~uint32_t(ZRT_TA_DEMODULATE)) return fail(ZRT_E_INVALID, "temporal: unknown flag");
+  const float sg[2] = {tp->sigma_normal, tp->sigma_depth};
+  const char* names[2] = {"sigma_normal", "sigma_depth"};
+  const uint32_t bit[2] = {kDnNormal, kDnDepth};
+  float inv[2] = {0.0f, 0.0f};
+  uint32_t terms = 0;
+  for (int k = 0; k < 2; ++k) {
+    if (!std::isfinite(sg[k]) || sg[k] < 0.0f)
+      return fail(ZRT_E_INVALID, std::string("temporal ") + names[k] + " must be finite and >= 0");
+    if (sg[k] > 0.0f) {
+      terms |= bit[k];
+      inv[k] = 1.0f / sg[k];
+    }
+  }
+  *out = TemporalLaunch{};
+  out->width = p->width;
+  out->n = p->height;
+  out->terms = terms;
+  out->demod = (tp->flags & ZRT_TA_DEMODULATE) ? 1u : 0u;
+  out->max_history = tp->max_history ? tp->max_history : uint32_t(ZRT_DEFAULT_TEMPORAL_HISTORY);
+  out->alpha_min = tp->alpha_min;
+  out->inv_n = inv[0];
+  out->inv_z = inv[1];
+  out->f_width = float(p->width);
+  out->f_height = float(p->height);
+  return ZRT_OK;
+}
 }  // namespace zrt
