@@ -174,7 +174,12 @@ enum { ZRT_DEFAULT_SAMPLE_CHUNK = 32u };
  * launch renders 1 sample per pixel of every tile (results discarded) and
  * records each tile's cost; the tiles are radix-sorted by descending cost on
  * the device and the render launch hands out units costliest first, so no long
- * unit starts at the end of the launch.  Images do not depend on it. */
+ * unit starts at the end of the launch.  Images do not depend on it.
+ * A context keeps the last probe's order: a later frame with the same camera
+ * (compared bitwise), width, height, max_depth, rank, world_size, traversal, guard
+ * flag and tile count - whatever its samples_per_pixel, seed or prng - skips the
+ * probe and the sort, and reports schedule_ms = 0.  ZRT_ORDER_CACHE=0 in the
+ * environment probes every frame (A/B). */
 
 /* ZRT_FLAG_GUARD (FAST traversal): the grazing-triangle guard (DESIGN.md
  * section 3 "Triangles"): every box is widened by the reach of the rounded
@@ -218,7 +223,8 @@ typedef struct zrt_stats {
   uint32_t wide_nodes;    /* FAST traversal: 4-wide nodes over the reference leaves */
   uint32_t texel_bytes;   /* bytes per texel on the device: 4 when every image is exact 8-bit
                              (c == k/255, png_image.zig:76-89), else 12 (f32 RGB); 0: no images */
-  float schedule_ms;       /* probe + sort before the render launch (included in render_ms) */
+  float schedule_ms;       /* probe + sort before the render launch (included in render_ms); 0 when the
+                            * context's kept tile order was reused */
   uint64_t order_replays;  /* FAST: rays re-traced the reference's way for an order hazard (diagnostic) */
   /* REFERENCE traversal + ZRT_FLAG_STATS (diagnostic, DESIGN.md §3 "Exactness"):
    * over every primitive of every leaf the reference opens, the largest
@@ -1072,6 +1078,14 @@ int zrt_debug_lean_kernel(const zrt_scene* scene, const zrt_camera* camera, cons
  * for bit.  n_checked: the slots checked.  ZRT_E_UNSUPPORTED names the first
  * violation (or a tree the encoder refused). */
 int zrt_debug_qnodes(const zrt_scene* scene, uint64_t* n_checked);
+/* The size check context creation makes on a flattened wide tree (no device
+ * needed): a ray's octant copy lies oct * stride_f4 float4s into the nodes and
+ * oct * n_top * node_f4 into the top levels in LDS, and the kernels form both
+ * products from the factors' low 24 bits.  ZRT_E_UNSUPPORTED when stride_f4 or
+ * n_top * node_f4 reaches 2^24 (zrt_ctx_create returns the same for such a scene),
+ * ZRT_OK otherwise - and always for a library built with ZRT_OCT_MUL24=0.
+ * (tests only) */
+int zrt_debug_octant_offsets(uint32_t stride_f4, uint32_t n_top, uint32_t node_f4);
 
 #ifdef __cplusplus
 }

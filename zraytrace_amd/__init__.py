@@ -772,3 +772,10 @@ def debug_qnodes(scene) -> int:
     n = C.c_uint64()
     check(lib().zrt_debug_qnodes(view, C.byref(n)))
     return n.value
+
+
+def debug_octant_offsets(stride_f4: int, n_top: int, node_f4: int = 8) -> None:
+    """The size check context creation makes on a flattened wide tree
+    (zrt_debug_octant_offsets; no device): raises ZrtError(ZRT_E_UNSUPPORTED) for a
+    tree whose octant stride or LDS top levels reach 2^24 float4s."""
+    check(lib().zrt_debug_octant_offsets(stride_f4, n_top, node_f4))

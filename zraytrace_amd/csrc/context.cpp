@@ -589,11 +589,34 @@ static int launch_frame(zrt_ctx* c, const zrt_camera* cam, const zrt_params* p, 
         mode == 3 && !(p->flags & ZRT_FLAG_NO_SCHEDULE) && p->samples_per_pixel >= 128 && my_tiles >= 2;
     // (a run decides once, by its cap: its first pass probes, the later ones reuse the
     // order and the probe's counters)
+    bool order_hit = false;  // the context holds the order of a probe with this launch's key
     if (schedule && !first) {
       schedule = c->run_ordered;
       if (schedule) a.tile_order = c->tile_order.p;
     } else if (schedule) {
-      schedule = zrt::schedule_tiles(c, a, p->prng, stk16, my_tiles, grid, st);
+      // (the order cannot change a frame - chunk sums land in fixed slots - so a frame
+      // with another seed, sample count or PRNG takes it too; ZRT_ORDER_CACHE=0: A/B)
+      zrt_ctx::OrderKey key{};
+      key.cam = *cam;
+      key.width = p->width;
+      key.height = p->height;
+      key.max_depth = p->max_depth;
+      key.rank = p->rank;
+      key.world_size = p->world_size;
+      key.traversal = p->traversal;
+      key.guard_on = guard_on ? 1u : 0u;
+      key.tiles = my_tiles;
+      const char* oc = std::getenv("ZRT_ORDER_CACHE");
+      order_hit = !(oc && std::atoi(oc) == 0) && c->order_valid &&
+                  std::memcmp(&key, &c->order_key, sizeof(key)) == 0;
+      if (order_hit) {
+        a.tile_order = c->tile_order.p;
+      } else {
+        c->order_valid = false;  // (the probe overwrites the order, whether or not it completes)
+        schedule = zrt::schedule_tiles(c, a, p->prng, stk16, my_tiles, grid, st);
+        c->order_key = key;
+        c->order_valid = schedule;
+      }
     }
     if (run_pass && first) c->run_ordered = schedule;
     if (adapt) {
@@ -605,7 +628,7 @@ static int launch_frame(zrt_ctx* c, const zrt_camera* cam, const zrt_params* p, 
         HIPCHK(hipMemcpyAsync(list, c->tile_order.p, size_t(my_tiles) * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
       a.tile_order = list;
     }
-    c->pass_probed = schedule && first;
+    c->pass_probed = schedule && first && !order_hit;
     c->scheduled = schedule;
     // the lockstep loop takes its interval from the probe's lane efficiency (auto_sync;
     // ZRT_SYNC or ZRT_AUTO_SYNC=0: the fixed interval, A/B)
@@ -956,7 +979,7 @@ int zrt_ctx_stats(zrt_ctx* c, zrt_stats* out) {
     HIPCHK(hipEventElapsedTime(&ms, c->ev_pre, c->ev1));
     HIPCHK(hipEventElapsedTime(&sched, c->ev_pre, c->ev0));
     out->render_ms = ms;
-    out->schedule_ms = c->scheduled ? sched : 0.0f;
+    out->schedule_ms = c->pass_probed ? sched : 0.0f;  // (0 when a kept order was reused)
     if (c->run_stats) {  // a run: the sums over its passes (the counters above were never re-zeroed)
       zrt::fold_pass_times(c, true);
       out->render_ms = c->run_render_ms + ms;

@@ -89,6 +89,15 @@ struct zrt_ctx {
   zrt::DevBuf<uint32_t> tile_cost, tile_ids, cost_sorted, tile_order;
   zrt::DevBuf<uint8_t> sort_temp;
   uint32_t tile_ids_n = 0;
+  // what the probe behind tile_order / probe_scratch saw: a launch with the same key
+  // takes them as they are (launch_frame).  The order is a cost estimate only, so the
+  // key leaves out the sample count, the seed and the PRNG.
+  struct OrderKey {
+    zrt_camera cam;  // compared bitwise
+    uint32_t width, height, max_depth, rank, world_size, traversal, guard_on, tiles;
+  };
+  OrderKey order_key{};
+  bool order_valid = false;
   zrt::DevBuf<unsigned long long> wave_times;  // ZRT_PROFILE builds
   uint32_t n_waves = 0;
   zrt::DevBuf<unsigned long long> scanlines;  // ZRT_FLAG_SCANLINES: [row][3] of the last launch

@@ -37,6 +37,14 @@ int zrt_debug_reproject_plan(const zrt_camera* prev, const zrt_params* params, z
   return zrt::plan_reproject(prev, params, out);
 }
 
+int zrt_debug_octant_offsets(uint32_t stride_f4, uint32_t n_top, uint32_t node_f4) {
+  try {
+    zrt::check_octant_offsets(stride_f4, n_top, node_f4);
+    return ZRT_OK;
+  }
+  ZRT_CATCH_HOST
+}
+
 int zrt_debug_lds_plans(const zrt_scene* scene, uint32_t* n_checked) {
   if (!n_checked) return fail(ZRT_E_INVALID, "null argument");
   *n_checked = 0;

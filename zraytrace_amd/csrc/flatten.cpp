@@ -221,6 +221,9 @@ void flatten_scene(HostScene* c, const zrt_scene* s, bool use_bvh, int device, i
     c->n_wide = wide.n_nodes;
     c->n_leaves = wide.n_leaves;
     c->n_top = wide.level_end.empty() ? 0u : wide.level_end[std::min<size_t>(2, wide.level_end.size()) - 1];
+    // (either node format's octant offsets within the kernels' multiply)
+    check_octant_offsets(uint32_t(std::min<size_t>(nw, 0xffffffffu)), c->n_top, 8u);
+    if (c->q_ok) check_octant_offsets(c->q_stride, c->q_top, kQuantNodeF4);
     c->layout = wide.layout;
     if (const char* e = std::getenv("ZRT_DEBUG_TREE_LAYOUT"))  // tests: a tree another kernel would have to decode
       c->layout ^= uint32_t(std::strtoul(e, nullptr, 0));

@@ -110,6 +110,7 @@ int validate_params(const zrt_params* p);
 Geometry geometry(const zrt_params* p);
 uint32_t rank_tiles(const Geometry& g, uint32_t rank, uint32_t world);
 float paxis_threshold();
+void check_octant_offsets(uint32_t stride_f4, uint32_t n_top, uint32_t node_f4);
 bool want_qnodes(uint32_t n_wide);
 uint32_t qtop_levels();
 constexpr uint32_t kNoRowsCap = 0xffffffffu;

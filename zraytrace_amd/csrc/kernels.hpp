@@ -166,6 +166,7 @@ struct KernelConfig {
   float paxis_m;                                      // kPaxisM
   // ZRT_LDS_TOP, ZRT_LANE_LDS, ZRT_MATS_LDS_ONLY, ZRT_LOCK_QN, ZRT_PROFILE, ZRT_LEAN_DEFAULT, ZRT_GROW, ZRT_SPHERE_SLOTS
   bool lds_top, lane_lds, mats_lds_only, lock_qn, profile, lean_default, grow, sphere_slots;
+  bool oct_mul24;  // ZRT_OCT_MUL24 (with octant copies): zrt::check_octant_offsets bounds the trees
 };
 const KernelConfig& kernel_config();
 

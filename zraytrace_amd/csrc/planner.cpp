@@ -95,6 +95,20 @@ float paxis_threshold() {
   if (const char* e = std::getenv("ZRT_PAXIS_M")) return float(std::atof(e));
   return kernel_config().paxis_m;
 }
+// A ray's octant copy starts oct * stride_f4 float4s into the nodes and oct * n_top *
+// node_f4 into the LDS top levels (render.hip wide_view).  Kernels built with
+// ZRT_OCT_MUL24 form both by a 24-bit multiply, which reads the low 24 bits of each
+// factor only: a tree whose stride or top levels reach 2^24 float4s (2 M full nodes
+// per copy; the C5 mesh has 3.7 M float4s) is refused before anything is uploaded.
+void check_octant_offsets(uint32_t stride_f4, uint32_t n_top, uint32_t node_f4) {
+  if (!kernel_config().oct_mul24) return;
+  constexpr uint64_t lim = 1ull << 24;
+  const uint64_t top = uint64_t(n_top) * node_f4;
+  if (stride_f4 >= lim || top >= lim)
+    throw Error(ZRT_E_UNSUPPORTED, "wide tree too large for the kernels' 24-bit octant offsets: " +
+                                       std::to_string(stride_f4) + " float4s per octant copy, " + std::to_string(top) +
+                                       " in its top levels (each must be below 2^24)");
+}
 // The path-pool loop (render_loop_pool, MODE 5) instead of the wavefront loop?
 // ZRT_POOL=0/1 forces it.  Default: the wavefront loop's cases (trees past the
 // 16-bit stack), where it is 4 % faster at C5's full size (8.30 -> 8.65 Gray/s,

@@ -49,6 +49,36 @@ __device__ __forceinline__ bool row_ok(const KArgs& a, uint64_t idx, uint64_t ca
   return false;
 }
 
+#ifndef ZRT_RARE_ARGS
+#define ZRT_RARE_ARGS 1  // kernel arguments that only rare branches of the FAST loop read (the error flag, the
+                         // stack's overflow rows, the replay's reference tree) are loaded from the argument
+                         // block inside those branches, through a pointer the compiler cannot trace: they no
+                         // longer sit in (spilled) SGPRs across the sampling loop
+#endif
+// The kernel's arguments as a rare branch reads them.  Every kernel that reaches these
+// paths takes its KArgs by value as its first parameter, so the argument block starts
+// with it; the empty asm hides where the pointer came from, which keeps each load - a
+// scalar load from the constant address space - inside the branch that asked for it.
+#if ZRT_RARE_ARGS && defined(__HIP_DEVICE_COMPILE__)
+typedef const __attribute__((address_space(4))) KArgs* RareArgs;
+__device__ __forceinline__ RareArgs rare_args(const KArgs& a) {
+  (void)a;
+  RareArgs p = (RareArgs)__builtin_amdgcn_kernarg_segment_ptr();
+  asm volatile("" : "+s"(p));
+  return p;
+}
+#else
+typedef const KArgs* RareArgs;
+__device__ __forceinline__ RareArgs rare_args(const KArgs& a) { return &a; }
+#endif
+// the device error flag raised (stack overflow, a tree the kernel does not decode, ...)
+__device__ __forceinline__ void raise_error(const KArgs& a, uint32_t bits) { atomicOr(rare_args(a)->error_flag, bits); }
+// lane gl's column of the FAST stack's rows past the LDS part ([row][lane] in global memory)
+template <class StackT>
+__device__ __forceinline__ StackT* ovf_column(const KArgs& a, uint32_t gl) {
+  return reinterpret_cast<StackT*>(rare_args(a)->stack_ovf) + gl;
+}
+
 // ZRT_PROFILE builds (diagnostic only, never the shipped library) add s_memtime
 // cycle sums per loop section into counters[kProfSlot + section].
 #ifndef ZRT_PROFILE
@@ -125,6 +155,18 @@ __device__ __forceinline__ uint64_t prof_stamp() {
 #endif
 #ifndef ZRT_LEAN_DEFAULT
 #define ZRT_LEAN_DEFAULT 1  // an eligible launch takes the lean kernel unless ZRT_LEAN=0 (0: only with ZRT_LEAN=1)
+#endif
+// Per-ray scalar overhead of the FAST traversal's prologue (every kernel that
+// traverses the wide tree; exact by construction, one switch each for A/B):
+#ifndef ZRT_OCT_MASKS_LOCAL
+#define ZRT_OCT_MASKS_LOCAL 1  // the three sign masks of 1/d are formed where a rare path reads them (the
+                               // order-hazard replay's box test), behind a value the compiler cannot trace
+                               // back to the ray's start: it no longer parks them in six spill lanes per ray
+#endif
+#ifndef ZRT_OCT_MUL24
+#define ZRT_OCT_MUL24 1  // the octant copy's offsets by a full-rate 24-bit multiply (v_mul_u32_u24) instead of
+                         // the quarter-rate v_mul_lo_u32: wide_stride and n_top * node_f4 are below 2^24
+                         // (flatten_scene refuses larger trees: zrt::check_octant_offsets)
 #endif
 template <bool LEAN>
 struct Lean {
@@ -702,10 +744,24 @@ __device__ __forceinline__ bool ray_origin_ok(const KArgs& a, const RayT& r) {
 // grazing slack) - except boxes holding a sphere, whose rounded
 // test reaches beyond the sphere (KArgs::ref_sph); false: the reference's test alone.
 template <class StackT>
-__device__ ZRT_REPLAY_ATTR void reference_replay(const KArgs& a, const RayT& r, StackT* __restrict__ stk, uint32_t gl,
+__device__ ZRT_REPLAY_ATTR void reference_replay(const KArgs& a, const RayT& ray, StackT* __restrict__ stk, uint32_t gl,
                                               float& best_t, int& best, bool narrow = true) {
-  const uint32_t rows = a.lds_rows, cap = a.ref_stack;
-  StackT* __restrict__ ovf = reinterpret_cast<StackT*>(a.stack_ovf) + gl;
+#if ZRT_OCT_MASKS_LOCAL && defined(__HIP_DEVICE_COMPILE__)
+  // box_test swaps each axis' planes by the sign of 1/d: the same comparisons as the
+  // octant's (wide_view), which the compiler would make once per ray and keep - spilled
+  // to lanes - for this branch almost no ray takes.  The copies below hold the same
+  // values, but their comparisons are made here.
+  RayT r = ray;
+  asm volatile("" : "+v"(r.ix), "+v"(r.iy), "+v"(r.iz));
+#else
+  const RayT& r = ray;
+#endif
+  // (the reference tree, its stack depth and the overflow rows are read here only)
+  const RareArgs ra = rare_args(a);
+  const uint32_t rows = a.lds_rows, cap = ra->ref_stack;
+  StackT* __restrict__ ovf = reinterpret_cast<StackT*>(ra->stack_ovf) + gl;
+  const float4* __restrict__ nodes = ra->nodes;
+  const uint8_t* __restrict__ ref_sph = ra->ref_sph;
   const float slack = ray_slack(r, a.scene_extent, ray_m(r));
   const float gw = ZRT_GUARD && r.gk > 0.0f ? guard_grow(a, r) : 0.0f;  // the grazing-triangle guard
   best_t = __builtin_inff();
@@ -716,13 +772,13 @@ __device__ ZRT_REPLAY_ATTR void reference_replay(const KArgs& a, const RayT& r, 
   while (sp > 0) {
     --sp;
     const int idx = sp < rows ? (int)stk[sp * kBlock] : (int)ovf[(size_t)(sp - rows) * a.n_lanes];
-    const float4 lo = a.nodes[2 * idx], hi = a.nodes[2 * idx + 1];
+    const float4 lo = nodes[2 * idx], hi = nodes[2 * idx + 1];
     float e;
     // the reference's loose test against the current best, and FAST's narrowed
     // emptiness test (a box the ray does not cross holds no hit):
     // left-first with the reference's t_max, so every leaf is accepted or
     // rejected exactly as the reference does it, in ~1 % of its node visits
-    if (!box_test<ZRT_REPLAY_NARROW>(lo, hi, r, best_t, &e, slack, narrow && a.ref_sph[idx] == 0, gw)) continue;
+    if (!box_test<ZRT_REPLAY_NARROW>(lo, hi, r, best_t, &e, slack, narrow && ref_sph[idx] == 0, gw)) continue;
     const int left = as_int(lo.w), right = as_int(hi.w);
     if (left < 0) {
       prim_test<false, false>(a.prims, left, r, best_t, best, c_tri, c_sph);
@@ -736,7 +792,7 @@ __device__ ZRT_REPLAY_ATTR void reference_replay(const KArgs& a, const RayT& r, 
       }
       sp += 2;
     } else {
-      atomicOr(a.error_flag, kErrOverflow);
+      atomicOr(ra->error_flag, kErrOverflow);
     }
   }
 }
@@ -1119,22 +1175,35 @@ struct WideView {
   const float4* __restrict__ top;  // this octant's copy of the top nodes in LDS
   uint32_t base;                   // float4 offset of this octant's copy (< 2^32)
   uint32_t n_top;
-  bool sx, sy, sz;
 };
+// (the octant's three sign masks are no part of it: with octant copies only rare
+// paths read them, and form them there - OctSigns - instead of carrying them)
+struct OctSigns {
+  bool sx, sy, sz;
+  __device__ __forceinline__ explicit OctSigns(const RayT& r) : sx(r.ix < 0.0f), sy(r.iy < 0.0f), sz(r.iz < 0.0f) {}
+};
+
+// oct * n for an octant (< 8) and a float4 count the host keeps below 2^24
+// (zrt::check_octant_offsets): the product is below 2^27, exact in either form
+__device__ __forceinline__ uint32_t oct_times(uint32_t oct, uint32_t n) {
+#if ZRT_OCT_MUL24 && defined(__HIP_DEVICE_COMPILE__)
+  return __umul24(oct, n);
+#else
+  return oct * n;
+#endif
+}
 
 __device__ __forceinline__ WideView wide_view(const KArgs& a, const RayT& r, const float4* __restrict__ lds_top) {
   WideView v;
-  v.sx = r.ix < 0.0f;
-  v.sy = r.iy < 0.0f;
-  v.sz = r.iz < 0.0f;
 #if ZRT_OCT_COPIES
-  const uint32_t oct = (v.sx ? 1u : 0u) | (v.sy ? 2u : 0u) | (v.sz ? 4u : 0u);
-  v.base = oct * a.wide_stride;
+  const OctSigns s(r);
+  const uint32_t oct = (s.sx ? 1u : 0u) | (s.sy ? 2u : 0u) | (s.sz ? 4u : 0u);
+  v.base = oct_times(oct, a.wide_stride);
 #else
   const uint32_t oct = 0;
   v.base = 0;
 #endif
-  v.top = lds_top + (ZRT_OCT_COPIES ? oct : 0u) * (a.n_top * a.node_f4);
+  v.top = lds_top + oct_times(oct, a.n_top * a.node_f4);
   v.n_top = ZRT_LDS_TOP ? a.n_top : 0u;
   return v;
 }
@@ -1174,9 +1243,9 @@ __device__ __forceinline__ bool wide_iter(const KArgs& a, const RayT& r, const W
   // the first rows in LDS, the rest in global memory (a.lds_rows: zrt::plan_lds)
   constexpr bool kOvf = true;
   const uint32_t rows = a.lds_rows;
-  StackT* __restrict__ ovf = reinterpret_cast<StackT*>(a.stack_ovf) + gl;
   const float inf = __builtin_inff();
-  const bool sx = v.sx, sy = v.sy, sz = v.sz;
+  const OctSigns os(r);  // (read by rare paths only: wide_load ignores them with octant copies)
+  const bool sx = os.sx, sy = os.sy, sz = os.sz;
   int r0 = as_int(w.ra.x), r1 = as_int(w.ra.y), r2 = as_int(w.ra.z), r3 = as_int(w.ra.w);
   const float tb = __builtin_fabsf(best_t) * kOpen;
   const float m = ray_m(r), rel = ray_rel(r, m), slk = ray_slack(r, a.scene_extent, m);
@@ -1348,7 +1417,7 @@ __device__ __forceinline__ bool wide_iter(const KArgs& a, const RayT& r, const W
         stk[(sp + 1) * stride] = (StackT)(n == 4 ? r2 : r1);
         stk[(sp + 2) * stride] = (StackT)r1;
         const uint32_t nsp = sp + n - 1;
-        if (__builtin_expect(nsp > cap - 3, 0)) atomicOr(a.error_flag, kErrOverflow);
+        if (__builtin_expect(nsp > cap - 3, 0)) raise_error(a, kErrOverflow);
         sp = min(nsp, cap - 3);
         next = r0;
       } else if (sp != 0) {
@@ -1374,7 +1443,7 @@ __device__ __forceinline__ bool wide_iter(const KArgs& a, const RayT& r, const W
       stk[(sp + 2) * stride] = (StackT)r1;
       const uint32_t nsp = sp + n - 1;
       if (__builtin_expect(__ballot(n != 0 && nsp > cap - 3) != 0ull, 0)) {
-        if (n != 0 && nsp > cap - 3) atomicOr(a.error_flag, kErrOverflow);
+        if (n != 0 && nsp > cap - 3) raise_error(a, kErrOverflow);
       }
       next = n != 0 ? r0 : sp != 0 ? top : -1;
       sp = n != 0 ? min(nsp, cap - 3) : psp;
@@ -1389,7 +1458,7 @@ __device__ __forceinline__ bool wide_iter(const KArgs& a, const RayT& r, const W
       next = k0 != inf ? r0 : k1 != inf ? r1 : k2 != inf ? r2 : r3;
     } else if (sp != 0) {
       --sp;
-      next = kOvf && sp >= rows ? (row_ok<STATS>(a, (uint64_t)(sp - rows) * a.n_lanes + gl, a.ovf_cap) ? (int32_t)ovf[(size_t)(sp - rows) * a.n_lanes] : -1)
+      next = kOvf && sp >= rows ? (row_ok<STATS>(a, (uint64_t)(sp - rows) * a.n_lanes + gl, a.ovf_cap) ? (int32_t)ovf_column<StackT>(a, gl)[(size_t)(sp - rows) * a.n_lanes] : -1)
                                   : (int32_t)stk[sp * stride];
     }
   } else {
@@ -1418,7 +1487,7 @@ __device__ __forceinline__ bool wide_iter(const KArgs& a, const RayT& r, const W
           stk[(sp + j) * stride] = e[j];
         } else {
           if (row_ok<STATS>(a, (uint64_t)(sp + j - rows) * a.n_lanes + gl, a.ovf_cap))
-            ovf[(size_t)(sp + j - rows) * a.n_lanes] = e[j];
+            ovf_column<StackT>(a, gl)[(size_t)(sp + j - rows) * a.n_lanes] = e[j];
           if (STATS) ++coh.ovfw;
         }
       }
@@ -1426,12 +1495,12 @@ __device__ __forceinline__ bool wide_iter(const KArgs& a, const RayT& r, const W
     const uint32_t nsp = sp + n - 1;
     // the host sizes cap = the tree's deepest stack + 3, so this never fires
     // unless the stack was sized too small: then entries would be lost
-    if (__builtin_expect(nsp > cap - 3, 0)) atomicOr(a.error_flag, kErrOverflow);
+    if (__builtin_expect(nsp > cap - 3, 0)) raise_error(a, kErrOverflow);
     sp = min(nsp, cap - 3);
     next = r0;
   } else if (sp != 0) {
     --sp;
-    next = kOvf && sp >= rows ? (row_ok<STATS>(a, (uint64_t)(sp - rows) * a.n_lanes + gl, a.ovf_cap) ? (int32_t)ovf[(size_t)(sp - rows) * a.n_lanes] : -1)
+    next = kOvf && sp >= rows ? (row_ok<STATS>(a, (uint64_t)(sp - rows) * a.n_lanes + gl, a.ovf_cap) ? (int32_t)ovf_column<StackT>(a, gl)[(size_t)(sp - rows) * a.n_lanes] : -1)
                                   : (int32_t)stk[sp * stride];
   }
 #if ZRT_SORT_SKIP
@@ -1621,7 +1690,8 @@ __device__ __forceinline__ bool wide_iter_q(const KArgs& a, const RayT& r, const
   const uint32_t rows = a.lds_rows;  // the first rows in LDS, the rest in global memory (either stack width)
   StackT* __restrict__ ovf = reinterpret_cast<StackT*>(a.stack_ovf) + gl;
   const float inf = __builtin_inff();
-  const bool sx = v.sx, sy = v.sy, sz = v.sz;
+  const OctSigns os(r);  // (a leaf record holds the reference's box: its planes are picked per ray)
+  const bool sx = os.sx, sy = os.sy, sz = os.sz;
   int r0 = as_int(w.f2.z), r1 = as_int(w.f2.w), r2 = as_int(w.f3.x), r3 = as_int(w.f3.y);
   const float ox = w.f0.x, oy = w.f0.y, oz = w.f0.z;
   const uint32_t ee = __float_as_uint(w.f0.w);
@@ -1831,9 +1901,13 @@ __device__ __forceinline__ bool wide_iter_q(const KArgs& a, const RayT& r, const
 
 // the suspended node of a wavefront / pool lane (re)loaded, in either format
 template <bool QN, class W>
-__device__ __forceinline__ void node_load(const float4* q, const WideView& v, W& w) {
-  if constexpr (QN) qnode_load(q, w);
-  else wide_load(q, v.sx, v.sy, v.sz, w);
+__device__ __forceinline__ void node_load(const float4* q, const RayT& r, W& w) {
+  if constexpr (QN) {
+    qnode_load(q, w);
+  } else {
+    const OctSigns os(r);
+    wide_load(q, os.sx, os.sy, os.sz, w);
+  }
 }
 
 // zrt_trace over compressed nodes (MODE 8): traverse_wide with wide_iter_q; LOCK: the
@@ -1864,7 +1938,8 @@ __device__ __forceinline__ void traverse_wide(const KArgs& a, const RayT& r, Sta
   // the root is node 0 of this octant's copy (in LDS when the top levels are)
   const float4* q = ZRT_LDS_TOP && !ZRT_Q_GLOBAL ? v.top : a.wnodes + v.base;
   WideNode w;
-  wide_load(ZRT_LDS_TOP ? v.top : a.wnodes + v.base, v.sx, v.sy, v.sz, w);
+  const OctSigns os(r);
+  wide_load(ZRT_LDS_TOP ? v.top : a.wnodes + v.base, os.sx, os.sy, os.sz, w);
   while (wide_iter<STATS, StackT, ZRT_SCALAR_NODES, PAXIS, true, ZRT_Q_GLOBAL != 0>(
       a, r, v, stk, gl, w, q, sp, best_t, best, c_nodes, c_leaves, c_tri, c_sph, coh)) {
   }
@@ -2676,7 +2751,8 @@ __device__ __forceinline__ void render_loop_wf(const KArgs& a) {
       WideNode w;
       if (trav) {
         v = wide_view(a, r, lds_top);
-        wide_load(q, v.sx, v.sy, v.sz, w);  // the suspended node (re)loaded
+        const OctSigns os(r);
+        wide_load(q, os.sx, os.sy, os.sz, w);  // the suspended node (re)loaded
       }
       for (;;) {
         if (trav) {
@@ -2927,7 +3003,7 @@ __device__ __forceinline__ void render_loop_pool(const KArgs& a) {
       std::conditional_t<QN, WideNodeQ, WideNode> w;
       if (trav) {
         v = wide_view(a, r, lds_top);
-        node_load<QN>(q, v, w);  // the suspended node (re)loaded
+        node_load<QN>(q, r, w);  // the suspended node (re)loaded
       }
       for (;;) {
         const uint64_t idle = __ballot(!trav);
@@ -2949,7 +3025,7 @@ __device__ __forceinline__ void render_loop_pool(const KArgs& a) {
             sp = 0;
             v = wide_view(a, r, lds_top);
             q = ZRT_LDS_TOP ? v.top : a.wnodes + v.base;
-            node_load<QN>(q, v, w);
+            node_load<QN>(q, r, w);
             trav = true;
           }
           const uint32_t n_idle = (uint32_t)__builtin_popcountll(idle);
@@ -4277,6 +4353,7 @@ const KernelConfig& kernel_config() {
       kPaxisM,
       ZRT_LDS_TOP != 0, ZRT_LANE_LDS != 0, ZRT_MATS_LDS_ONLY != 0, ZRT_LOCK_QN != 0, ZRT_PROFILE != 0,
       ZRT_LEAN_DEFAULT != 0, ZRT_GROW != 0, ZRT_SPHERE_SLOTS != 0,
+      ZRT_OCT_MUL24 != 0 && ZRT_OCT_COPIES != 0,
   };
   return k;
 }
