@@ -11,7 +11,7 @@ of tools/denoise_probe.py.
     is the lowest mean among the points that lower every scene's RMSE (the condition of
     tests/test_gpu_denoise_guided.py).  The plain default filter (zrt_denoise_defaults) is
     scored on the same frames.  defaults.json; zrt_denoise_guided_defaults returns the winner
-    (context.cpp ZRT_DG_*).
+    (post.cpp ZRT_DG_*).
 (b) bunny: config C4's frame (scene 2, 2048 x 2048) at 8 spp in chunks of 4: the device time
     of the plain default filter and of the guided default filter (zrt_ctx_denoise_ms),
     interleaved, the median of --reps calls each, and of zrt_ctx_accum_variance +

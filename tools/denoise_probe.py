@@ -9,7 +9,7 @@
     scene's RMSE (the quality condition of tests/test_gpu_denoise.py); the grid, the
     winner, its per-scene ratios, each sigma value's best score and the ten best points
     go to defaults.json.  zrt_denoise_defaults returns
-    the winner (context.cpp ZRT_DN_SIGMA_*).
+    the winner (post.cpp ZRT_DN_SIGMA_*).
 (b) bunny: config C4's frame (scene 2, 2048 x 2048) at 8 spp: the device time of
     zrt_ctx_features, of the render, and of zrt_ctx_denoise with the default sigmas for
     1 .. 8 iterations (zrt_ctx_denoise_ms, the median of --reps calls); iteration k's

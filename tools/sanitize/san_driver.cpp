@@ -10,7 +10,7 @@
 //   accel_build.cpp  the wide tree over the reference leaves (render.hip's FAST layout)
 //   planner.cpp, flatten.cpp, debug_plans.cpp  the LDS / buffer / launch / pass /
 //                  adaptive planners and the scene flattener, through the zrt_debug_*
-//                  entry points that need no device
+//                  entry points that need no device; the per-tile walk directly
 //   oracle/        oracle_render (both RNG modes), oracle_render_scanlines,
 //                  oracle_trace, oracle_bvh_build
 //
@@ -30,6 +30,7 @@
 #include "../../oracle/oracle.h"
 #include "../../zraytrace_amd/csrc/accel_build.hpp"
 #include "../../zraytrace_amd/csrc/bvh_build.hpp"
+#include "../../zraytrace_amd/csrc/host.hpp"
 #include "../../zraytrace_amd/csrc/kernels.hpp"
 
 namespace zrt {
@@ -284,6 +285,35 @@ static void reproject_plans(const std::string& assets) {
         "reproject plan: null arguments accepted");
 }
 
+// for_rank_tiles (the pixel count of a launch, zrt_ctx_scanlines) against a count over
+// the frame's pixels: ragged frames, world sizes 1 - 3, every rank, a rank with no tile
+static void tile_walks() {
+  struct Case { uint32_t w, h, world; };
+  for (const Case& k : {Case{13, 21, 1}, Case{13, 21, 2}, Case{13, 21, 3}, Case{20, 13, 3}, Case{5, 5, 3}})
+    for (uint32_t rank = 0; rank < k.world; ++rank) {
+      const zrt_params p = params(k.w, k.h, 1, 1, ZRT_RNG_COUNTER);
+      const zrt::Geometry g = zrt::geometry(&p);
+      std::vector<uint32_t> want(k.h, 0), got(k.h, 0);  // this rank's pixels in each row
+      uint32_t want_tiles = 0;
+      for (uint32_t y = 0; y < k.h; ++y)
+        for (uint32_t x = 0; x < g.xbound; ++x) {
+          const uint32_t t = (y / 8) * g.tiles_x + x / 8;
+          if (t % k.world != rank) continue;
+          want[y] += 1;
+          want_tiles += (x % 8 == 0 && y % 8 == 0) ? 1 : 0;
+        }
+      uint32_t n = 0;
+      bool in_order = true;
+      zrt::for_rank_tiles(g, k.h, rank, k.world, [&](uint32_t lt, uint32_t w, uint32_t h, uint32_t y0) {
+        in_order = in_order && lt == n && w >= 1 && w <= 8 && h >= 1 && h <= 8 && y0 + h <= k.h;
+        ++n;
+        for (uint32_t y = y0; y < y0 + h && y < k.h; ++y) got[y] += w;
+      });
+      CHECK(in_order && n == want_tiles && n == zrt::rank_tiles(g, rank, k.world) && got == want,
+            "tile walk %u x %u, rank %u of %u: %u tiles (%u expected)", k.w, k.h, rank, k.world, n, want_tiles);
+    }
+}
+
 int main(int argc, char** argv) {
   if (argc < 3) {
     std::fprintf(stderr, "usage: %s ASSETS_DIR TMP_DIR\n", argv[0]);
@@ -293,6 +323,7 @@ int main(int argc, char** argv) {
   for (uint32_t i : {0u, 1u, 2u, 3u, 4u}) one_scene(i, assets, tmp);
   pass_and_adapt_plans();
   reproject_plans(assets);
+  tile_walks();
 
   // error paths: unknown scene index, missing files, a truncated binary scene
   zrt_scene_data* d = nullptr;

@@ -15,7 +15,7 @@ sibling of tools/denoise_guided_probe.py.
     the seven others and picks the shortest history of the grid; that winner is recorded too).
     The winner is the lowest score among the points whose static sequences all have a ratio
     below 1 (the condition of tests/test_gpu_temporal.py).  defaults.json, with every point's
-    ratios; zrt_temporal_defaults returns the winner (context.cpp ZRT_TA_*).
+    ratios; zrt_temporal_defaults returns the winner (post.cpp ZRT_TA_*).
     quality.json: the winner's ratios per scene and sequence, the parallax of the truck
     (pixels between the first and the last camera, from the last frame's depths), and the
     spread: the sequences rendered again from two other base seeds, (max - min) of each

@@ -1,11 +1,14 @@
 // context.hpp - private to the host files that talk to the HIP runtime
-// (context.cpp, multi.cpp, oneshot.cpp): the HIP error type, device buffers, the
-// context behind zrt_ctx_* and the catch clauses of their entry points.
+// (context.cpp, runs.cpp, post.cpp, debug_device.cpp, multi.cpp, oneshot.cpp): the
+// HIP error type, the owning handles, the context behind zrt_ctx_*, what those
+// files share of its launch path, and the catch clauses of their entry points.
 #pragma once
 #include <hip/hip_runtime_api.h>
 
+#include <cstring>
 #include <memory>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "host.hpp"
@@ -45,156 +48,226 @@ struct DevBuf {
     HIPCHK(hipMalloc(&p, count * sizeof(T)));
     n = count;
   }
+  void grow(size_t count) {  // at least `count` elements; the contents are not kept
+    if (n < count) alloc(count);
+  }
   void upload(const std::vector<T>& v) {
     alloc(v.size());
     if (!v.empty()) HIPCHK(hipMemcpy(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
   }
 };
-}  // namespace zrt
 
-struct zrt_ctx {
-  int device = 0;
-  hipStream_t stream = nullptr;
-  bool use_bvh = false;
-  uint32_t n_prims = 0, n_nodes = 0, bvh_depth = 0, stack_depth = 0;
-  uint32_t n_wide = 0, n_leaves = 0, wide_stack = 0, wide_stride = 0, n_top = 0, n_mats = 0;
+// The other handles, owned the same way: move-only, created on first use (create /
+// alloc do nothing on a live handle), released with their owner.
+template <class H, hipError_t (*Destroy)(H)>
+struct Handle {
+  H h = nullptr;
+  Handle() = default;
+  Handle(Handle&& o) noexcept : h(std::exchange(o.h, nullptr)) {}
+  Handle& operator=(Handle&& o) noexcept {
+    std::swap(h, o.h);
+    return *this;
+  }
+  ~Handle() {
+    if (h) (void)Destroy(h);
+  }
+  operator H() const { return h; }
+};
+struct Event : Handle<hipEvent_t, hipEventDestroy> {
+  void create(unsigned flags = hipEventDefault) {  // hipEventDisableTiming: a completion mark only
+    if (!h) HIPCHK(hipEventCreateWithFlags(&h, flags));
+  }
+};
+struct Stream : Handle<hipStream_t, hipStreamDestroy> {
+  // a blocking stream: work a caller enqueues on the legacy default stream (NULL,
+  // e.g. torch's default stream) after a render on this one waits for it
+  void create() {
+    if (!h) HIPCHK(hipStreamCreateWithFlags(&h, hipStreamDefault));
+  }
+};
+
+// A value (or an array) in pinned host memory, zeroed: what a launch copies back behind an event.
+template <class T>
+struct Pinned : Handle<void*, hipHostFree> {
+  void alloc(size_t count = 1) {
+    if (h) return;
+    HIPCHK(hipHostMalloc(&h, count * sizeof(T), hipHostMallocDefault));
+    std::memset(h, 0, count * sizeof(T));
+  }
+  T* get() const { return static_cast<T*>(h); }
+  T& operator*() const { return *get(); }
+  T& operator[](size_t i) const { return get()[i]; }
+};
+
+// The events around one launch: pre .. e1 is its render_ms, e0 .. e1 the render kernel alone.
+struct EvSet {
+  Event pre, e0, e1;
+  bool probed = false;  // the launch ran the scheduling probe (pre .. e0 is its schedule_ms)
+  void create() {
+    pre.create();
+    e0.create();
+    e1.create();
+  }
+};
+
+// A launch's device error flag, copied into pinned host memory behind `done` on
+// the stream the launch was enqueued on (the caller's, or the context's).
+struct Completion {
+  Event done;
+  Pinned<unsigned long long> err;
+  bool launched = false;
+  bool reported = false;  // the launch's device error was returned to the caller
+  void create() {
+    done.create(hipEventDisableTiming);
+    err.alloc();
+  }
+};
+
+// The uploaded scene: its buffers and counts, and the constants a launch passes on (KArgs).
+struct Scene {
+  SceneShape shape;  // its counts and depths: what the launch decision reads of the scene (plan_launch)
+  uint32_t n_prims = 0, bvh_depth = 0, wide_stride = 0;
   std::vector<uint32_t> slot_to_prim;  // device primitive slot -> reference list index
-  zrt::SceneShape shape;               // what the launch decision reads of the scene (plan_launch)
-  zrt::DevBuf<float4> wnodes;
-  zrt::DevBuf<float4> qnodes, qleaves;  // compressed wide nodes + leaf records (q_ok)
-  bool q_ok = false;
-  uint32_t q_stride = 0, q_top = 0, n_qleaves = 0;
-  zrt::DevBuf<float4> nodes, prims, shade;
-  zrt::DevBuf<zrt::DevMaterial> mats;
-  zrt::DevBuf<float> texels;
-  zrt::DevBuf<uint32_t> texels8;
-  zrt::DevBuf<uint32_t> leaf_of_slot;
-  zrt::DevBuf<uint8_t> ref_sph;
+  DevBuf<float4> wnodes;
+  DevBuf<float4> qnodes, qleaves;  // compressed wide nodes + leaf records (q_ok)
+  uint32_t q_stride = 0, n_qleaves = 0;
+  DevBuf<float4> nodes, prims, shade;
+  DevBuf<DevMaterial> mats;
+  DevBuf<float> texels;
+  DevBuf<uint32_t> texels8;
+  DevBuf<uint32_t> leaf_of_slot;
+  DevBuf<uint8_t> ref_sph;
   float root_c[3] = {0.0f, 0.0f, 0.0f}, origin_bound = 0.0f;
   uint32_t layout = 0;  // the wide tree's encoding (KArgs::layout)
   float graze_m = 0x1p-18f, graze_leaf = 0x1p-18f;  // KArgs::graze_m / graze_leaf
-  float guard = 0.0f;                                // KArgs::guard
   uint32_t texel_bytes = 0;
   uint32_t tri_rcp_fast = 1;
   float scene_extent = 1.0f;
   float tri_c[3] = {0.0f, 0.0f, 0.0f}, tri_h[3] = {0.0f, 0.0f, 0.0f};  // KArgs::tri_c / tri_h
+  double preprocess_ms = 0, upload_ms = 0;
+};
+
+// What the probe behind Probe::tile_order / scratch saw: a launch with the same key
+// takes them as they are (launch_frame).  The order is a cost estimate only, so the
+// key leaves out the sample count, the seed and the PRNG.
+struct OrderKey {
+  zrt_camera cam;  // compared bitwise
+  uint32_t width, height, max_depth, rank, world_size, traversal, guard_on, tiles;
+};
+static_assert(sizeof(OrderKey) == sizeof(zrt_camera) + 8 * sizeof(uint32_t), "OrderKey is compared bitwise: no padding");
+// scheduling probe: its own partial sums + counters, per-tile costs, the sort
+struct Probe {
+  DevBuf<float4> partial;
+  DevBuf<unsigned long long> scratch;
+  DevBuf<uint32_t> tile_cost, tile_ids, cost_sorted, tile_order;
+  DevBuf<uint8_t> sort_temp;
+  uint32_t tile_ids_n = 0;
+  OrderKey order_key{};
+  bool order_valid = false;
+};
+
+// The last launch, as the reporting calls read it: assigned as one value at its end.
+struct LastLaunch {
+  Geometry g{};
+  uint32_t height = 0, rank = 0, world = 1, tiles = 0, pixels = 0, spp = 0;
+  // STATS flavour; it read compressed nodes; it was a pass: zrt_ctx_stats reports the run's
+  // sums; it was a level: stats / scanlines count per-tile samples; it took a tile order
+  bool stats = false, qn = false, run = false, adapt = false, scheduled = false;
+  int mode = 0, loop = 0;  // loop: zrt_stats::sampling_loop
+  float guard = 0.0f;      // zrt_stats::guard
+  uint32_t scanline_rows = 0;  // rows it counted (0: not flagged)
+  uint32_t n_waves = 0;        // ZRT_PROFILE builds
+};
+
+// ---- the accumulation run (zrt_ctx_accum_*): at most one per context ----
+struct AccumRun {
+  bool live = false;         // between zrt_ctx_accum_begin and the next plain render
+  zrt_camera cam{};
+  zrt_params p{};
+  uint32_t done = 0;         // samples per pixel in accum
+  uint32_t passes = 0;       // passes enqueued
+  bool ordered = false;      // the first pass's probe left tile_order and the probe's scratch for the later ones
+  uint32_t pass_samples = 0; // the last pass's
+  DevBuf<float4> accum;      // [slot] running chunk sums (rank's tile-major layout)
+  DevBuf<unsigned long long> metrics;  // accumulate_kernel's {changed pixels, max change bits} shards
+  Pinned<unsigned long long> metrics_host;  // ... of the last pass, copied behind the launch's done event
+  // earlier passes' events not yet added into render_ms / sched_ms, and spare sets
+  std::vector<EvSet> pending, spare;
+  double render_ms = 0, sched_ms = 0;
+};
+
+// ---- an adaptive run (zrt_ctx_adapt_*): an accumulation run over the active tiles ----
+struct AdaptRun {
+  bool on = false;             // the live run is adaptive
+  zrt_adaptive a{};
+  std::vector<uint32_t> levels;  // L_0 .. (zrt::plan_adapt)
+  uint32_t k = 0;              // the next level
+  uint32_t n_active = 0;       // tiles in active[cur]
+  uint32_t cur = 0;            // the list the next level's launch reads (the other one is written)
+  uint64_t samples = 0;        // sum over tiles of in-frame pixels x samples so far
+  float* tiles = nullptr;      // the run's dev_tiles
+  DevBuf<uint32_t> active[2], tile_done, active_count;
+  Pinned<uint32_t> count_host;  // the surviving count of the last level
+};
+
+// The events around a post-processing step, for its *_ms call.
+struct StepTimer {
+  Event e0, e1;
+  bool launched = false;
+};
+// ---- the a-trous filter (zrt_ctx_denoise): its ping-pong colour planes and its events ----
+struct DenoiseState {
+  DevBuf<float4> buf[2];
+  StepTimer timer;
+};
+// ---- temporal accumulation (zrt_ctx_temporal): the previous frame's camera and, in D's
+// layout (n * n, n = the frame's height), its history, features and history lengths,
+// double-buffered: a frame reads [cur] and writes [cur ^ 1] ----
+struct TemporalState {
+  DevBuf<float4> hist[2], feat[2];
+  DevBuf<uint32_t> len[2];
+  uint32_t cur = 0, width = 0, height = 0, demod = 0;
+  bool live = false;  // [cur] holds a frame rendered through cam
+  zrt_camera cam{};
+  StepTimer timer;
+};
+// ---- the variance plane (zrt_ctx_accum_variance): each local tile's {ik, sc} ----
+struct VariancePlan {
+  DevBuf<float2> dev;
+  std::vector<float2> host;
+};
+// ---- first-hit feature buffers (zrt_ctx_features): the launch's own deep stack rows,
+// the slot -> primitive table, and its device error status ----
+struct FeatureState {
+  DevBuf<uint8_t> ovf;
+  DevBuf<uint32_t> slot_prim;
+  Completion done;
+};
+}  // namespace zrt
+
+struct zrt_ctx {
+  int device = 0;
+  int cu_count = 0;
+  zrt::Stream stream;  // first, so released last: after every buffer and event below (zrt_ctx_destroy drains it)
+  zrt::Scene scene;
+  // what the launches of a frame share and later frames reuse (BufNeed)
   zrt::DevBuf<uint32_t> att;  // attenuation rows past the LDS ones (att codes)
   zrt::DevBuf<uint8_t> stack_ovf;  // FAST stack rows beyond the LDS part (deep trees)
   zrt::DevBuf<unsigned long long> scratch;  // counters, work counter, error flag (kScratchSlots)
   zrt::DevBuf<float4> partial;
   zrt::DevBuf<uint32_t> rank_base;
-  // scheduling probe: its own partial sums + counters, per-tile costs, the sort
-  zrt::DevBuf<float4> probe_partial;
-  zrt::DevBuf<unsigned long long> probe_scratch;
-  zrt::DevBuf<uint32_t> tile_cost, tile_ids, cost_sorted, tile_order;
-  zrt::DevBuf<uint8_t> sort_temp;
-  uint32_t tile_ids_n = 0;
-  // what the probe behind tile_order / probe_scratch saw: a launch with the same key
-  // takes them as they are (launch_frame).  The order is a cost estimate only, so the
-  // key leaves out the sample count, the seed and the PRNG.
-  struct OrderKey {
-    zrt_camera cam;  // compared bitwise
-    uint32_t width, height, max_depth, rank, world_size, traversal, guard_on, tiles;
-  };
-  OrderKey order_key{};
-  bool order_valid = false;
   zrt::DevBuf<unsigned long long> wave_times;  // ZRT_PROFILE builds
-  uint32_t n_waves = 0;
-  zrt::DevBuf<unsigned long long> scanlines;  // ZRT_FLAG_SCANLINES: [row][3] of the last launch
-  uint32_t scanline_rows = 0;                 // rows counted by the last launch (0: not flagged)
-  bool scheduled = false;
-  hipEvent_t ev_pre = nullptr, ev0 = nullptr, ev1 = nullptr, ev_done = nullptr;
-  double preprocess_ms = 0, upload_ms = 0;
-  // last launch: its device error flag, copied into pinned host memory behind
-  // ev_done on the stream it was enqueued on (the caller's, or `stream`)
-  unsigned long long* err_host = nullptr;
-  bool err_reported = false;  // the last launch's device error was returned to the caller
-  uint32_t last_pixels = 0, last_spp = 0, launched = 0;
-  uint32_t last_tiles = 0, last_rank = 0, last_world = 1, last_tiles_x = 0, last_xbound = 0;
-  bool last_stats = false;
-  int last_mode = 0;
-  bool last_qn = false;  // the last launch read compressed nodes
-  int last_loop = 0;  // zrt_stats::sampling_loop
-  float last_guard = 0.0f;  // zrt_stats::guard
-  int cu_count = 0;
-  // ---- the accumulation run (zrt_ctx_accum_*): at most one per context ----
-  struct EvSet {
-    hipEvent_t pre = nullptr, e0 = nullptr, e1 = nullptr;
-    bool probed = false;  // the pass ran the scheduling probe (pre .. e0 is its schedule_ms)
-  };
-  bool run_live = false;       // between zrt_ctx_accum_begin and the next plain render
-  bool run_stats = false;      // the last launch was a pass: zrt_ctx_stats reports the run's sums
-  zrt_camera run_cam{};
-  zrt_params run_p{};
-  uint32_t run_done = 0;       // samples per pixel in accum
-  uint32_t run_passes = 0;     // passes enqueued
-  bool run_ordered = false;    // the first pass's probe left tile_order and probe_scratch for the later ones
-  bool pass_probed = false;    // the last pass ran the probe
-  uint32_t pass_samples = 0;   // the last pass's
-  zrt::DevBuf<float4> accum;   // [slot] running chunk sums (rank's tile-major layout)
-  zrt::DevBuf<unsigned long long> metrics;  // accumulate_kernel's {changed pixels, max change bits} shards
-  unsigned long long* metrics_host = nullptr;  // ... of the last pass, pinned, copied behind ev_done
-  // earlier passes' events not yet added into run_render_ms / run_sched_ms, and spare sets
-  std::vector<EvSet> run_pending, ev_spare;
-  double run_render_ms = 0, run_sched_ms = 0;
-  // ---- an adaptive run (zrt_ctx_adapt_*): an accumulation run over the active tiles ----
-  bool adapt = false;          // the live run is adaptive
-  bool last_adapt = false;     // the last launch was a level: stats / scanlines count per-tile samples
-  zrt_adaptive adapt_a{};
-  std::vector<uint32_t> adapt_levels;  // L_0 .. (zrt::plan_adapt)
-  uint32_t adapt_k = 0;        // the next level
-  uint32_t adapt_active = 0;   // tiles in active[adapt_cur]
-  uint32_t adapt_cur = 0;      // the list the next level's launch reads (the other one is written)
-  uint64_t adapt_samples = 0;  // sum over tiles of in-frame pixels x samples so far
-  float* adapt_tiles = nullptr;  // the run's dev_tiles
-  zrt::DevBuf<uint32_t> active[2], tile_done, active_count;
-  uint32_t* count_host = nullptr;  // the surviving count of the last level, pinned
-  // ---- the a-trous filter (zrt_ctx_denoise): its ping-pong colour planes and its events ----
-  zrt::DevBuf<float4> dn_buf[2];
-  hipEvent_t dn_ev0 = nullptr, dn_ev1 = nullptr;
-  bool dn_launched = false;
-  // ---- temporal accumulation (zrt_ctx_temporal): the previous frame's camera and, in D's
-  // layout (n * n, n = the frame's height), its history, features and history lengths,
-  // double-buffered: a frame reads [ta_cur] and writes [ta_cur ^ 1] ----
-  zrt::DevBuf<float4> ta_hist[2], ta_feat[2];
-  zrt::DevBuf<uint32_t> ta_len[2];
-  uint32_t ta_cur = 0, ta_width = 0, ta_height = 0, ta_demod = 0;
-  bool ta_live = false;  // [ta_cur] holds a frame rendered through ta_cam
-  zrt_camera ta_cam{};
-  hipEvent_t ta_ev0 = nullptr, ta_ev1 = nullptr;
-  bool ta_launched = false;
-  // ---- the variance plane (zrt_ctx_accum_variance): each local tile's {ik, sc} ----
-  zrt::DevBuf<float2> var_plan;
-  std::vector<float2> var_plan_host;
-  // ---- first-hit feature buffers (zrt_ctx_features): the launch's own deep stack rows,
-  // the slot -> primitive table, and its device error status behind feat_done ----
-  zrt::DevBuf<uint8_t> feat_ovf;
-  zrt::DevBuf<uint32_t> feat_slot_prim;
-  unsigned long long* feat_err_host = nullptr;
-  hipEvent_t feat_done = nullptr;
-  bool feat_launched = false, feat_err_reported = false;
-  ~zrt_ctx() {
-    if (feat_done) (void)hipEventDestroy(feat_done);
-    if (feat_err_host) (void)hipHostFree(feat_err_host);
-    if (ta_ev0) (void)hipEventDestroy(ta_ev0);
-    if (ta_ev1) (void)hipEventDestroy(ta_ev1);
-    if (dn_ev0) (void)hipEventDestroy(dn_ev0);
-    if (dn_ev1) (void)hipEventDestroy(dn_ev1);
-    if (count_host) (void)hipHostFree(count_host);
-    for (const std::vector<EvSet>* v : {&run_pending, &ev_spare})
-      for (const EvSet& e : *v) {
-        (void)hipEventDestroy(e.pre);
-        (void)hipEventDestroy(e.e0);
-        (void)hipEventDestroy(e.e1);
-      }
-    if (metrics_host) (void)hipHostFree(metrics_host);
-    if (ev_pre) (void)hipEventDestroy(ev_pre);
-    if (ev0) (void)hipEventDestroy(ev0);
-    if (ev1) (void)hipEventDestroy(ev1);
-    if (ev_done) (void)hipEventDestroy(ev_done);
-    if (err_host) (void)hipHostFree(err_host);
-    if (stream) (void)hipStreamDestroy(stream);
-  }
+  zrt::DevBuf<unsigned long long> scanlines;   // ZRT_FLAG_SCANLINES: [row][3] of the last launch
+  zrt::Probe probe;
+  zrt::EvSet ev;           // the last launch's events
+  zrt::Completion render;  // the last launch's completion
+  zrt::LastLaunch last;
+  zrt::AccumRun run;
+  zrt::AdaptRun adapt;
+  zrt::DenoiseState dn;
+  zrt::TemporalState ta;
+  zrt::VariancePlan var;
+  zrt::FeatureState feat;
 };
 
 namespace zrt {
@@ -205,6 +278,37 @@ void flatten_for_device(HostScene* h, const zrt_scene* s, bool use_bvh, int devi
 // A context on `device` holding an uploaded copy of a flattened scene.
 std::unique_ptr<zrt_ctx> ctx_on_device(const HostScene& h, int device);
 int add_scanlines(zrt_ctx* c, zrt_scanline* out, uint32_t height);
+
+// ---- context.cpp, for the files above it ----
+inline hipStream_t stream_of(const zrt_ctx* c, void* hip_stream) {
+  return hip_stream ? static_cast<hipStream_t>(hip_stream) : hipStream_t(c->stream);
+}
+int params_fit_ctx(const zrt_ctx* c, const zrt_params* p);
+int launch_frame(zrt_ctx* c, const zrt_camera* cam, const zrt_params* p, float* dev_tiles, void* hip_stream,
+                 bool run_pass, uint32_t n_samples);
+int launch_status(zrt_ctx* c, bool wait);
+const char* device_error_msg(unsigned long long flag);
+// A finished launch's times from its event set (schedule_ms: 0 unless it ran the probe).
+struct LaunchTimes {
+  float render_ms, schedule_ms, kernel_ms;
+};
+LaunchTimes launch_times(const EvSet& e);
+void fold_pass_times(zrt_ctx* c, bool wait);
+void fill_camera(KArgs& a, const zrt_camera* cam, const zrt_params* p);
+inline void copy3(float dst[3], const zrt_vec3& v) {
+  dst[0] = v.x;
+  dst[1] = v.y;
+  dst[2] = v.z;
+}
+// The launch of zrt_trace and zrt_ctx_features (context.cpp).
+struct TracePlan {
+  int kmode = 0;
+  bool stk16 = false;
+  LdsPlan lp;
+};
+TracePlan fill_trace(KArgs& a, const zrt_ctx* c, uint32_t traversal);
+void trace_rows(KArgs& a, const zrt_ctx* c, const TracePlan& t, uint64_t n_lanes, DevBuf<uint8_t>& ovf, hipStream_t st,
+                const char* launch);
 }  // namespace zrt
 
 // The catch clauses of every C entry point: no exception crosses the ABI.

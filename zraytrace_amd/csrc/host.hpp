@@ -7,6 +7,7 @@
 
 #include <cstddef>
 #include <cstdint>
+#include <functional>
 #include <new>
 #include <vector>
 
@@ -109,6 +110,9 @@ int validate_scene(const zrt_scene* s);
 int validate_params(const zrt_params* p);
 Geometry geometry(const zrt_params* p);
 uint32_t rank_tiles(const Geometry& g, uint32_t rank, uint32_t world);
+// A rank's tiles in local order: f(local tile, in-frame width, in-frame height, first row).
+void for_rank_tiles(const Geometry& g, uint32_t height, uint32_t rank, uint32_t world,
+                    const std::function<void(uint32_t lt, uint32_t w, uint32_t h, uint32_t y0)>& f);
 float paxis_threshold();
 void check_octant_offsets(uint32_t stride_f4, uint32_t n_top, uint32_t node_f4);
 bool want_qnodes(uint32_t n_wide);

@@ -180,12 +180,9 @@ int zrt_multi_render(zrt_multi* m, const zrt_camera* camera, const zrt_params* p
         device_msg = zrt_last_error();
       }
       else if (rc) return rc;
-      {  // the render kernel alone (ev0 -> ev1; render_ms also holds the schedule probe)
-        float ms = 0.0f;
-        HIPCHK(hipSetDevice(m->ctx[r]->device));
-        HIPCHK(hipEventElapsedTime(&ms, m->ctx[r]->ev0, m->ctx[r]->ev1));
-        m->rank_ms[r] = ms;
-      }
+      // the render kernel alone (render_ms also holds the schedule probe)
+      HIPCHK(hipSetDevice(m->ctx[r]->device));
+      m->rank_ms[r] = zrt::launch_times(m->ctx[r]->ev).kernel_ms;
       if (r == 0) {
         sum = s;
         continue;

@@ -1,6 +1,6 @@
 // oneshot.cpp - the one-shot renders (zrt_render*): a context, the frame, the
-// copy back.  They call the C ABI of context.cpp and hold device buffers; nothing
-// else.
+// copy back.  They call the C ABI of context.cpp, runs.cpp and post.cpp and hold
+// device buffers; nothing else.
 #include <algorithm>
 #include <cstring>
 #include <functional>
@@ -17,44 +17,79 @@ namespace {
 // with and the frame.
 using FramePost = std::function<int(zrt_ctx*, const zrt_params&, const float*)>;
 
-int render_one(const zrt_scene* scene, const zrt_camera* camera, const zrt_params* params, float* out_rgb,
-               zrt_stats* stats, zrt_scanline* rows, const FramePost* post = nullptr) {
-  if (!camera || (!out_rgb && !post)) return fail(ZRT_E_INVALID, "null argument");
-  int rc = zrt::validate_params(params);
-  if (rc) return rc;
-  zrt_params p = *params;
-  p.rank = 0;
-  p.world_size = 1;
-  if (rows) p.flags |= ZRT_FLAG_SCANLINES;
-  zrt_ctx* c = nullptr;
-  rc = zrt_ctx_create(scene, &p, &c);
-  if (rc) return rc;
-  std::unique_ptr<zrt_ctx, int (*)(zrt_ctx*)> guard(c, zrt_ctx_destroy);
-  try {
-    uint32_t n_tiles = 0;
-    rc = zrt_ctx_tile_count(c, &p, &n_tiles);
+// One one-shot render: a context for the params as rank 0 of 1, its tile count and
+// the tiles / frame device buffers (released before the context).  Its methods may
+// throw HipError: a session lives inside its entry point's try block.
+struct Session {
+  zrt_params p{};
+  std::unique_ptr<zrt_ctx, int (*)(zrt_ctx*)> ctx{nullptr, zrt_ctx_destroy};
+  uint32_t n_tiles = 0;
+  DevBuf<float> tiles, frame;
+
+  zrt_ctx* c() const { return ctx.get(); }
+  size_t px() const { return size_t(p.width) * p.height; }
+  int open(const zrt_scene* scene, const zrt_params* params, uint32_t extra_flags = 0) {
+    p = *params;
+    p.rank = 0;
+    p.world_size = 1;
+    p.flags |= extra_flags;
+    zrt_ctx* made = nullptr;
+    int rc = zrt_ctx_create(scene, &p, &made);
     if (rc) return rc;
-    zrt::DevBuf<float> tiles, frame;
+    ctx.reset(made);
+    rc = zrt_ctx_tile_count(c(), &p, &n_tiles);
+    if (rc) return rc;
     tiles.alloc(size_t(n_tiles) * 64 * 3);
-    frame.alloc(size_t(p.width) * p.height * 3);
-    rc = zrt_ctx_render_tiles(c, camera, &p, tiles.p, nullptr);
+    frame.alloc(px() * 3);
+    return ZRT_OK;
+  }
+  // the frame from the tiles (q: the params they were rendered with), enqueued
+  int assemble(const zrt_params& q) { return zrt_ctx_assemble(c(), &q, tiles.p, frame.p, nullptr); }
+  // ... waited for and copied out (out may be null: the frame stays on the device)
+  void copy_out(float* out) {
+    HIPCHK(hipStreamSynchronize(c()->stream));
+    if (out) HIPCHK(hipMemcpy(out, frame.p, sizeof(float) * 3 * px(), hipMemcpyDeviceToHost));
+  }
+  int fetch(float* out) {
+    const int rc = assemble(p);
     if (rc) return rc;
-    rc = zrt_ctx_assemble(c, &p, tiles.p, frame.p, nullptr);
-    if (rc) return rc;
-    HIPCHK(hipStreamSynchronize(c->stream));
-    if (out_rgb)
-      HIPCHK(hipMemcpy(out_rgb, frame.p, sizeof(float) * 3 * size_t(p.width) * p.height, hipMemcpyDeviceToHost));
+    copy_out(out);
+    return ZRT_OK;
+  }
+  // the stats (and the scanlines) of what the context rendered, then `post`
+  int finish(zrt_stats* stats, zrt_scanline* rows = nullptr, const FramePost* post = nullptr) {
     zrt_stats s;
-    rc = zrt_ctx_stats(c, &s);
+    int rc = zrt_ctx_stats(c(), &s);
     if (rc) return rc;
     if (rows) {
       std::memset(rows, 0, sizeof(zrt_scanline) * p.height);
-      rc = add_scanlines(c, rows, p.height);
+      rc = add_scanlines(c(), rows, p.height);
       if (rc) return rc;
     }
     if (stats) *stats = s;
-    if (post) return (*post)(c, p, frame.p);
-    return ZRT_OK;
+    return post ? (*post)(c(), p, frame.p) : ZRT_OK;
+  }
+};
+
+// one_pass: the frame as an accumulation run of one pass - zrt_render's frame and counters,
+// with the run (its accumulator and second moment) still live for `post`
+int render_one(const zrt_scene* scene, const zrt_camera* camera, const zrt_params* params, float* out_rgb,
+               zrt_stats* stats, zrt_scanline* rows, const FramePost* post = nullptr, bool one_pass = false) {
+  if (!camera || (!out_rgb && !post)) return fail(ZRT_E_INVALID, "null argument");
+  int rc = zrt::validate_params(params);
+  if (rc) return rc;
+  try {
+    Session s;
+    rc = s.open(scene, params, rows ? ZRT_FLAG_SCANLINES : 0u);
+    if (rc) return rc;
+    if (one_pass) rc = zrt_ctx_accum_begin(s.c(), camera, &s.p);
+    if (rc) return rc;
+    rc = one_pass ? zrt_ctx_accum_pass(s.c(), s.p.samples_per_pixel, s.tiles.p, nullptr)
+                  : zrt_ctx_render_tiles(s.c(), camera, &s.p, s.tiles.p, nullptr);
+    if (rc) return rc;
+    rc = s.fetch(out_rgb);
+    if (rc) return rc;
+    return s.finish(stats, rows, post);
   }
   ZRT_CATCH_ALL
 }
@@ -78,37 +113,27 @@ int zrt_render_progressive(const zrt_scene* scene, const zrt_camera* camera, con
   if (!camera || !out_rgb) return fail(ZRT_E_INVALID, "null argument");
   int rc = zrt::validate_params(params);
   if (rc) return rc;
-  zrt_params p = *params;
-  p.rank = 0;
-  p.world_size = 1;
-  const uint32_t chunk = p.sample_chunk ? p.sample_chunk : ZRT_DEFAULT_SAMPLE_CHUNK;
+  const uint32_t chunk = params->sample_chunk ? params->sample_chunk : ZRT_DEFAULT_SAMPLE_CHUNK;
   // whole chunks per pass (a pass must start on a chunk boundary); 0: the default
   const uint64_t per_pass = pass_samples ? (uint64_t(pass_samples) + chunk - 1) / chunk * chunk
                                          : uint64_t(ZRT_DEFAULT_PASS_CHUNKS) * chunk;
-  zrt_ctx* c = nullptr;
-  rc = zrt_ctx_create(scene, &p, &c);
-  if (rc) return rc;
-  std::unique_ptr<zrt_ctx, int (*)(zrt_ctx*)> guard(c, zrt_ctx_destroy);
   try {
-    uint32_t n_tiles = 0;
-    rc = zrt_ctx_tile_count(c, &p, &n_tiles);
+    zrt::Session s;
+    rc = s.open(scene, params);
     if (rc) return rc;
-    zrt::DevBuf<float> tiles, frame;
-    tiles.alloc(size_t(n_tiles) * 64 * 3);
-    frame.alloc(size_t(p.width) * p.height * 3);
+    const zrt_params& p = s.p;
+    zrt_ctx* c = s.c();
     rc = zrt_ctx_accum_begin(c, camera, &p);
     if (rc) return rc;
-    const size_t frame_bytes = sizeof(float) * 3 * size_t(p.width) * p.height;
     for (uint32_t done = 0; done < p.samples_per_pixel;) {
       const uint32_t n = uint32_t(std::min<uint64_t>(per_pass, p.samples_per_pixel - done));
-      rc = zrt_ctx_accum_pass(c, n, tiles.p, nullptr);
+      rc = zrt_ctx_accum_pass(c, n, s.tiles.p, nullptr);
       if (rc) return rc;
-      rc = zrt_ctx_assemble(c, &p, tiles.p, frame.p, nullptr);
+      rc = s.assemble(p);
       if (rc) return rc;
       done += n;
       if (!on_pass && done < p.samples_per_pixel) continue;  // nobody looks: the passes queue up
-      HIPCHK(hipStreamSynchronize(c->stream));
-      HIPCHK(hipMemcpy(out_rgb, frame.p, frame_bytes, hipMemcpyDeviceToHost));
+      s.copy_out(out_rgb);
       if (on_pass) {
         zrt_pass_info info;
         rc = zrt_ctx_accum_info(c, &info);
@@ -116,11 +141,7 @@ int zrt_render_progressive(const zrt_scene* scene, const zrt_camera* camera, con
         if (on_pass(user, out_rgb, &info) != 0) break;
       }
     }
-    zrt_stats s;
-    rc = zrt_ctx_stats(c, &s);
-    if (rc) return rc;
-    if (stats) *stats = s;
-    return ZRT_OK;
+    return s.finish(stats);
   }
   ZRT_CATCH_ALL
 }
@@ -135,62 +156,37 @@ int render_adaptive(const zrt_scene* scene, const zrt_camera* camera, const zrt_
   std::vector<uint32_t> levels;
   int rc = zrt::plan_adapt(params, adaptive, &levels);
   if (rc) return rc;
-  zrt_params p = *params;
-  p.rank = 0;
-  p.world_size = 1;
-  if (rows) p.flags |= ZRT_FLAG_SCANLINES;
-  zrt_ctx* c = nullptr;
-  rc = zrt_ctx_create(scene, &p, &c);
-  if (rc) return rc;
-  std::unique_ptr<zrt_ctx, int (*)(zrt_ctx*)> guard(c, zrt_ctx_destroy);
   try {
-    uint32_t n_tiles = 0;
-    rc = zrt_ctx_tile_count(c, &p, &n_tiles);
+    Session s;
+    rc = s.open(scene, params, rows ? ZRT_FLAG_SCANLINES : 0u);
     if (rc) return rc;
-    zrt::DevBuf<float> tiles, frame;
-    tiles.alloc(size_t(n_tiles) * 64 * 3);
-    frame.alloc(size_t(p.width) * p.height * 3);
-    HIPCHK(hipMemset(tiles.p, 0, sizeof(float) * tiles.n));
+    const zrt_params& p = s.p;
+    zrt_ctx* c = s.c();
+    HIPCHK(hipMemset(s.tiles.p, 0, sizeof(float) * s.tiles.n));
     rc = zrt_ctx_adapt_begin(c, camera, &p, adaptive);
     if (rc) return rc;
-    const size_t frame_bytes = sizeof(float) * 3 * size_t(p.width) * p.height;
     for (size_t k = 0; k < levels.size(); ++k) {
       zrt_level_info info;
-      rc = zrt_ctx_adapt_level(c, tiles.p, nullptr, &info);
+      rc = zrt_ctx_adapt_level(c, s.tiles.p, nullptr, &info);
       if (rc) return rc;
       const bool over = info.tiles_active_after == 0;
       if (on_level || over) {
-        rc = zrt_ctx_assemble(c, &p, tiles.p, frame.p, nullptr);
+        rc = s.fetch(out_rgb);
         if (rc) return rc;
-        HIPCHK(hipStreamSynchronize(c->stream));
-        if (out_rgb) HIPCHK(hipMemcpy(out_rgb, frame.p, frame_bytes, hipMemcpyDeviceToHost));
       }
-      if (on_level && on_level(user, out_rgb, &info) != 0 && !over) {
-        break;
-      }
-      if (over) break;
+      if ((on_level && on_level(user, out_rgb, &info) != 0) || over) break;
     }
     if (out_samples) {
-      std::vector<uint32_t> per_tile(std::max(1u, n_tiles));
-      rc = zrt_ctx_adapt_samples(c, per_tile.data(), n_tiles);
+      std::vector<uint32_t> per_tile(std::max(1u, s.n_tiles));
+      rc = zrt_ctx_adapt_samples(c, per_tile.data(), s.n_tiles);
       if (rc) return rc;
       const zrt::Geometry g = zrt::geometry(&p);
-      std::fill(out_samples, out_samples + size_t(p.width) * p.height, 0u);
+      std::fill(out_samples, out_samples + s.px(), 0u);
       for (uint32_t y = 0; y < p.height; ++y)
         for (uint32_t x = 0; x < g.xbound; ++x)
           out_samples[size_t(y) * p.width + x] = per_tile[(y / 8u) * g.tiles_x + x / 8u];
     }
-    zrt_stats s;
-    rc = zrt_ctx_stats(c, &s);
-    if (rc) return rc;
-    if (rows) {
-      std::memset(rows, 0, sizeof(zrt_scanline) * p.height);
-      rc = add_scanlines(c, rows, p.height);
-      if (rc) return rc;
-    }
-    if (stats) *stats = s;
-    if (post) return (*post)(c, p, frame.p);
-    return ZRT_OK;
+    return s.finish(stats, rows, post);
   }
   ZRT_CATCH_ALL
 }
@@ -212,41 +208,55 @@ int zrt_render_adaptive_progress(const zrt_scene* scene, const zrt_camera* camer
 
 namespace zrt {
 namespace {
-// render_one as an accumulation run of one pass: zrt_render's frame and counters,
-// with the run (its accumulator and second moment) still live for `post`.
-int render_one_pass(const zrt_scene* scene, const zrt_camera* camera, const zrt_params* params, float* out_rgb,
-                    zrt_stats* stats, const FramePost& post) {
-  if (!camera) return fail(ZRT_E_INVALID, "null argument");
-  int rc = zrt::validate_params(params);
+// The guided filter's settings (dn NULL: the defaults), refused before any device work.
+int guided_settings(const zrt_params* params, const zrt_denoise* dn, uint32_t flags, zrt_denoise* d) {
+  uint32_t default_flags = 0;
+  if (dn) *d = *dn;
+  else zrt_denoise_guided_defaults(d, &default_flags);
+  DenoiseLaunch l{};
+  const int rc = plan_denoise(params, d, &l);
   if (rc) return rc;
-  zrt_params p = *params;
-  p.rank = 0;
-  p.world_size = 1;
-  zrt_ctx* c = nullptr;
-  rc = zrt_ctx_create(scene, &p, &c);
-  if (rc) return rc;
-  std::unique_ptr<zrt_ctx, int (*)(zrt_ctx*)> guard(c, zrt_ctx_destroy);
+  if (flags & ~uint32_t(ZRT_DN_DEMODULATE)) return fail(ZRT_E_INVALID, "denoise: unknown flag");
+  return ZRT_OK;
+}
+
+// zrt_render_denoised*'s FramePost: the frame's features and (guided) the live run's
+// variance plane, the filter, and the copies out.
+struct DenoisedOut {
+  float *rgb, *features, *variance;
+  double* ms;
+};
+int denoise_frame(zrt_ctx* c, const zrt_params& p, const zrt_camera* camera, const float* dev_frame,
+                  const zrt_denoise& d, bool guided, uint32_t flags, const DenoisedOut& o) {
   try {
-    uint32_t n_tiles = 0;
-    rc = zrt_ctx_tile_count(c, &p, &n_tiles);
-    if (rc) return rc;
-    zrt::DevBuf<float> tiles, frame;
-    tiles.alloc(size_t(n_tiles) * 64 * 3);
-    frame.alloc(size_t(p.width) * p.height * 3);
-    rc = zrt_ctx_accum_begin(c, camera, &p);
-    if (rc) return rc;
-    rc = zrt_ctx_accum_pass(c, p.samples_per_pixel, tiles.p, nullptr);
-    if (rc) return rc;
-    rc = zrt_ctx_assemble(c, &p, tiles.p, frame.p, nullptr);
-    if (rc) return rc;
+    const size_t px = size_t(p.width) * p.height;
+    DevBuf<float> feat, outb, var_tiles, var;
+    feat.alloc(px * 8);
+    outb.alloc(px * 3);
+    int r = ZRT_OK;
+    if (guided) {
+      uint32_t n_tiles = 0;
+      r = zrt_ctx_tile_count(c, &p, &n_tiles);
+      if (r) return r;
+      var_tiles.alloc(size_t(n_tiles) * 64);
+      var.alloc(px);
+      r = zrt_ctx_accum_variance(c, var_tiles.p, nullptr);
+      if (r) return r;
+      r = zrt_ctx_assemble_plane(c, &p, var_tiles.p, 0, var.p, nullptr);
+      if (r) return r;
+    }
+    r = zrt_ctx_features(c, camera, &p, feat.p, nullptr);
+    if (r) return r;
+    r = guided ? zrt_ctx_denoise_guided(c, &p, &d, flags, dev_frame, feat.p, var.p, outb.p, nullptr, nullptr)
+               : zrt_ctx_denoise(c, &p, &d, dev_frame, feat.p, outb.p, nullptr);
+    if (r) return r;
     HIPCHK(hipStreamSynchronize(c->stream));
-    if (out_rgb)
-      HIPCHK(hipMemcpy(out_rgb, frame.p, sizeof(float) * 3 * size_t(p.width) * p.height, hipMemcpyDeviceToHost));
-    zrt_stats s;
-    rc = zrt_ctx_stats(c, &s);
-    if (rc) return rc;
-    if (stats) *stats = s;
-    return post(c, p, frame.p);
+    r = zrt_ctx_sync(c);  // (a feature launch's device error)
+    if (r) return r;
+    HIPCHK(hipMemcpy(o.rgb, outb.p, sizeof(float) * 3 * px, hipMemcpyDeviceToHost));
+    if (o.features) HIPCHK(hipMemcpy(o.features, feat.p, sizeof(float) * 8 * px, hipMemcpyDeviceToHost));
+    if (guided && o.variance) HIPCHK(hipMemcpy(o.variance, var.p, sizeof(float) * px, hipMemcpyDeviceToHost));
+    return o.ms ? zrt_ctx_denoise_ms(c, o.ms) : ZRT_OK;
   }
   ZRT_CATCH_ALL
 }
@@ -259,54 +269,19 @@ int zrt_render_denoised_guided(const zrt_scene* scene, const zrt_camera* camera,
                                double* denoise_ms) {
   if (!camera || !out_rgb) return fail(ZRT_E_INVALID, "null argument");
   zrt_denoise d;
-  uint32_t default_flags = 0;
-  if (dn) d = *dn;
-  else zrt_denoise_guided_defaults(&d, &default_flags);
-  zrt::DenoiseLaunch l{};
-  int rc = zrt::plan_denoise(params, &d, &l);  // (refused before any device work)
+  int rc = zrt::guided_settings(params, dn, flags, &d);
   if (rc) return rc;
-  if (flags & ~uint32_t(ZRT_DN_DEMODULATE)) return fail(ZRT_E_INVALID, "denoise: unknown flag");
   // every tile ends on whole chunks, two at least: a frozen tile holds a doubled level, the others the cap
   zrt_variance_plan vp{};
   rc = zrt::plan_variance(params, params->samples_per_pixel, &vp);
   if (rc) return rc;
-  const zrt::FramePost post = [&](zrt_ctx* c, const zrt_params& p, const float* dev_frame) -> int {
-    try {
-      const size_t px = size_t(p.width) * p.height;
-      uint32_t n_tiles = 0;
-      int r = zrt_ctx_tile_count(c, &p, &n_tiles);
-      if (r) return r;
-      zrt::DevBuf<float> feat, outb, var_tiles, var;
-      feat.alloc(px * 8);
-      outb.alloc(px * 3);
-      var_tiles.alloc(size_t(n_tiles) * 64);
-      var.alloc(px);
-      r = zrt_ctx_accum_variance(c, var_tiles.p, nullptr);
-      if (r) return r;
-      r = zrt_ctx_assemble_plane(c, &p, var_tiles.p, 0, var.p, nullptr);
-      if (r) return r;
-      r = zrt_ctx_features(c, camera, &p, feat.p, nullptr);
-      if (r) return r;
-      r = zrt_ctx_denoise_guided(c, &p, &d, flags, dev_frame, feat.p, var.p, outb.p, nullptr, nullptr);
-      if (r) return r;
-      HIPCHK(hipStreamSynchronize(c->stream));
-      r = zrt_ctx_sync(c);  // (a feature launch's device error)
-      if (r) return r;
-      HIPCHK(hipMemcpy(out_rgb, outb.p, sizeof(float) * 3 * px, hipMemcpyDeviceToHost));
-      if (out_features) HIPCHK(hipMemcpy(out_features, feat.p, sizeof(float) * 8 * px, hipMemcpyDeviceToHost));
-      if (out_variance) HIPCHK(hipMemcpy(out_variance, var.p, sizeof(float) * px, hipMemcpyDeviceToHost));
-      if (denoise_ms) {
-        r = zrt_ctx_denoise_ms(c, denoise_ms);
-        if (r) return r;
-      }
-      return ZRT_OK;
-    }
-    ZRT_CATCH_ALL
+  const zrt::FramePost post = [&](zrt_ctx* c, const zrt_params& p, const float* dev_frame) {
+    return zrt::denoise_frame(c, p, camera, dev_frame, d, true, flags, {out_rgb, out_features, out_variance, denoise_ms});
   };
   if (adaptive)
     return zrt::render_adaptive(scene, camera, params, adaptive, nullptr, nullptr, out_noisy, nullptr, stats, nullptr,
                                 &post);
-  return zrt::render_one_pass(scene, camera, params, out_noisy, stats, post);
+  return zrt::render_one(scene, camera, params, out_noisy, stats, nullptr, &post, true);
 }
 
 int zrt_render_denoised(const zrt_scene* scene, const zrt_camera* camera, const zrt_params* params,
@@ -319,28 +294,8 @@ int zrt_render_denoised(const zrt_scene* scene, const zrt_camera* camera, const 
   zrt::DenoiseLaunch l{};
   int rc = zrt::plan_denoise(params, &d, &l);  // (refused before any device work)
   if (rc) return rc;
-  const zrt::FramePost post = [&](zrt_ctx* c, const zrt_params& p, const float* dev_frame) -> int {
-    try {
-      const size_t px = size_t(p.width) * p.height;
-      zrt::DevBuf<float> feat, outb;
-      feat.alloc(px * 8);
-      outb.alloc(px * 3);
-      int r = zrt_ctx_features(c, camera, &p, feat.p, nullptr);
-      if (r) return r;
-      r = zrt_ctx_denoise(c, &p, &d, dev_frame, feat.p, outb.p, nullptr);
-      if (r) return r;
-      HIPCHK(hipStreamSynchronize(c->stream));
-      r = zrt_ctx_sync(c);  // (a feature launch's device error)
-      if (r) return r;
-      HIPCHK(hipMemcpy(out_rgb, outb.p, sizeof(float) * 3 * px, hipMemcpyDeviceToHost));
-      if (out_features) HIPCHK(hipMemcpy(out_features, feat.p, sizeof(float) * 8 * px, hipMemcpyDeviceToHost));
-      if (denoise_ms) {
-        r = zrt_ctx_denoise_ms(c, denoise_ms);
-        if (r) return r;
-      }
-      return ZRT_OK;
-    }
-    ZRT_CATCH_ALL
+  const zrt::FramePost post = [&](zrt_ctx* c, const zrt_params& p, const float* dev_frame) {
+    return zrt::denoise_frame(c, p, camera, dev_frame, d, false, 0, {out_rgb, out_features, nullptr, denoise_ms});
   };
   if (adaptive)
     return zrt::render_adaptive(scene, camera, params, adaptive, nullptr, nullptr, out_noisy, nullptr, stats, nullptr,
@@ -356,16 +311,11 @@ int zrt_render_temporal(const zrt_scene* scene, const zrt_camera* cameras, uint3
                         zrt_frame_fn on_frame, void* user, float* out_rgb, zrt_stats* stats) {
   if (!cameras || !out_rgb) return fail(ZRT_E_INVALID, "null argument");
   zrt_denoise d;
-  uint32_t default_flags = 0;
-  if (dn) d = *dn;
-  else zrt_denoise_guided_defaults(&d, &default_flags);
+  int rc = zrt::guided_settings(params, dn, dn_flags, &d);
+  if (rc) return rc;
   zrt_temporal t;
   if (tp) t = *tp;
   else zrt_temporal_defaults(&t);
-  zrt::DenoiseLaunch l{};
-  int rc = zrt::plan_denoise(params, &d, &l);  // (refused before any device work)
-  if (rc) return rc;
-  if (dn_flags & ~uint32_t(ZRT_DN_DEMODULATE)) return fail(ZRT_E_INVALID, "denoise: unknown flag");
   zrt::TemporalLaunch tl{};
   rc = zrt::plan_temporal(params, &t, &tl);
   if (rc) return rc;
@@ -373,23 +323,16 @@ int zrt_render_temporal(const zrt_scene* scene, const zrt_camera* cameras, uint3
   rc = zrt::plan_variance(params, params->samples_per_pixel, &vp);
   if (rc) return rc;
   if (n_frames == 0) return fail(ZRT_E_INVALID, "temporal: n_frames must be > 0");
-  zrt_params p = *params;
-  p.rank = 0;
-  p.world_size = 1;
-  zrt_ctx* c = nullptr;
-  rc = zrt_ctx_create(scene, &p, &c);
-  if (rc) return rc;
-  std::unique_ptr<zrt_ctx, int (*)(zrt_ctx*)> guard(c, zrt_ctx_destroy);
   try {
-    const size_t px = size_t(p.width) * p.height;
-    uint32_t n_tiles = 0;
-    rc = zrt_ctx_tile_count(c, &p, &n_tiles);
+    zrt::Session s;
+    rc = s.open(scene, params);
     if (rc) return rc;
-    zrt::DevBuf<float> tiles, frame, feat, var_tiles, var, acc, acc_var, outb;
-    tiles.alloc(size_t(n_tiles) * 64 * 3);
-    frame.alloc(px * 3);
+    const zrt_params& p = s.p;
+    zrt_ctx* c = s.c();
+    const size_t px = s.px();
+    zrt::DevBuf<float> feat, var_tiles, var, acc, acc_var, outb;
     feat.alloc(px * 8);
-    var_tiles.alloc(size_t(n_tiles) * 64);
+    var_tiles.alloc(size_t(s.n_tiles) * 64);
     var.alloc(px);
     acc.alloc(px * 3);
     acc_var.alloc(px);
@@ -400,17 +343,17 @@ int zrt_render_temporal(const zrt_scene* scene, const zrt_camera* cameras, uint3
       const zrt_camera* cam = &cameras[k];
       rc = zrt_ctx_accum_begin(c, cam, &pk);
       if (rc) return rc;
-      rc = zrt_ctx_accum_pass(c, pk.samples_per_pixel, tiles.p, nullptr);
+      rc = zrt_ctx_accum_pass(c, pk.samples_per_pixel, s.tiles.p, nullptr);
       if (rc) return rc;
       rc = zrt_ctx_accum_variance(c, var_tiles.p, nullptr);
       if (rc) return rc;
-      rc = zrt_ctx_assemble(c, &pk, tiles.p, frame.p, nullptr);
+      rc = s.assemble(pk);
       if (rc) return rc;
       rc = zrt_ctx_assemble_plane(c, &pk, var_tiles.p, 0, var.p, nullptr);
       if (rc) return rc;
       rc = zrt_ctx_features(c, cam, &pk, feat.p, nullptr);
       if (rc) return rc;
-      rc = zrt_ctx_temporal(c, cam, &pk, &t, frame.p, feat.p, var.p, acc.p, acc_var.p, nullptr, nullptr);
+      rc = zrt_ctx_temporal(c, cam, &pk, &t, s.frame.p, feat.p, var.p, acc.p, acc_var.p, nullptr, nullptr);
       if (rc) return rc;
       rc = zrt_ctx_denoise_guided(c, &pk, &d, dn_flags, acc.p, feat.p, acc_var.p, outb.p, nullptr, nullptr);
       if (rc) return rc;
@@ -421,11 +364,7 @@ int zrt_render_temporal(const zrt_scene* scene, const zrt_camera* cameras, uint3
       HIPCHK(hipMemcpy(out_rgb, outb.p, sizeof(float) * 3 * px, hipMemcpyDeviceToHost));
       if (on_frame && on_frame(user, out_rgb, k) != 0) break;
     }
-    zrt_stats s;
-    rc = zrt_ctx_stats(c, &s);
-    if (rc) return rc;
-    if (stats) *stats = s;
-    return ZRT_OK;
+    return s.finish(stats);
   }
   ZRT_CATCH_ALL
 }

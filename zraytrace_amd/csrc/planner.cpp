@@ -77,6 +77,14 @@ Geometry geometry(const zrt_params* p) {
 uint32_t rank_tiles(const Geometry& g, uint32_t rank, uint32_t world) {
   return g.n_tiles > rank ? (g.n_tiles - rank + world - 1) / world : 0;
 }
+void for_rank_tiles(const Geometry& g, uint32_t height, uint32_t rank, uint32_t world,
+                    const std::function<void(uint32_t lt, uint32_t w, uint32_t h, uint32_t y0)>& f) {
+  const uint32_t n = rank_tiles(g, rank, world);
+  for (uint32_t lt = 0; lt < n; ++lt) {
+    const uint32_t t = lt * world + rank, tx = t % g.tiles_x, ty = t / g.tiles_x;
+    f(lt, std::min(8u, g.xbound - tx * 8u), std::min(8u, height - ty * 8u), ty * 8u);
+  }
+}
 
 // The wavefront loop (render_loop_wf) for this scene?  ZRT_WF=0/1 forces it.
 // It doubles the traversal lane efficiency where traversal lengths diverge
