@@ -1013,6 +1013,16 @@ int zrt_bvh_build_device(const zrt_scene* scene, uint32_t device, zrt_bvh_node**
 int zrt_debug_math(int fn, const float* x, const float* y, float* out, uint32_t n, uint32_t device);
 int zrt_debug_rng(uint32_t prng, uint64_t key, uint64_t* out, uint32_t n, uint32_t device);
 int zrt_debug_division(uint64_t n, uint64_t* counts, uint32_t device);
+/* One launch of the adaptive run's compaction (compact_kernel) on its own: the
+ * entries of list (n of them, each < n_tiles) whose tile_done word (n_tiles words:
+ * samples per pixel, bit 31 set once frozen, as resolve_kernel leaves them) has bit
+ * 31 clear, packed in list order.  out (n entries) is uploaded as the output
+ * buffer's initial content and copied back after the launch, so entries past
+ * *count keep what the caller put there; *count: the entries written.
+ * ZRT_E_INVALID: a null pointer, n == 0, or a list entry >= n_tiles (checked on
+ * the host: the kernel indexes tile_done with the entries). */
+int zrt_debug_compact(const uint32_t* list, uint32_t n, const uint32_t* tile_done, uint32_t n_tiles,
+                      uint32_t* out, uint32_t* count, uint32_t device);
 /* Host-side check of the kernels' LDS layouts for this scene (no device
  * needed): the scene is flattened as zrt_ctx_create does, then every plan the
  * launch code can make - each sampling loop, stack width, PRNG and a range of

@@ -8,7 +8,8 @@ the same key skips the probe and the sort: its schedule_ms is 0 and its frame is
 same, whatever its seed, sample count or generator.  ZRT_ORDER_CACHE=0 probes every
 frame.
 
-Scene 2 at 64 x 64 (64 tiles), 128 samples, depth 6.
+Scene 2 at 64 x 64 (64 tiles), 128 samples, depth 6.  The order itself is compared with
+the stable descending sort of the probe's costs there and at 264 x 264 (1089 tiles).
 
 Run on an MI355X: ``pytest -m gpu``.
 """
@@ -62,12 +63,18 @@ def moved(cam):
     return c
 
 
+def costliest_first(costs):
+    """The order zrt.h promises for these probe costs: descending cost, ties in tile order."""
+    return np.argsort(-costs.astype(np.int64), kind="stable")
+
+
 def test_second_frame_skips_the_probe(scenes, monkeypatch):
     monkeypatch.delenv("ZRT_ORDER_CACHE", raising=False)
     s = scenes(2)
     ctx = z.RenderContext(s, BASE)
     try:
         a, sa, oa = frame(ctx, s, s.camera, BASE)
+        costs = ctx.debug_schedule()[0]
         b, sb, ob = frame(ctx, s, s.camera, BASE)
         c, sc, oc = frame(ctx, s, s.camera, dataclasses.replace(BASE, flags=z.ZRT_FLAG_STATS))
     finally:
@@ -81,6 +88,41 @@ def test_second_frame_skips_the_probe(scenes, monkeypatch):
     np.testing.assert_array_equal(oa, oc)
     for k in P.COUNTERS:
         assert sa[k] == sb[k] == sc[k], k
+    # the order is the sort of the probe's own costs, not just some permutation
+    print(f"64 tiles: {len(costs) - len(np.unique(costs))} tiles repeat another's cost")
+    assert len(costs) == 64 and costs.max() > costs.min()
+    np.testing.assert_array_equal(oa, costliest_first(costs))
+
+
+@pytest.mark.parametrize("max_depth", [2, 20])
+def test_order_is_the_stable_sort_of_the_costs(scenes, max_depth, monkeypatch):
+    """Scene 2 at 264 x 264 (33 x 33 = 1089 tiles: the device sort runs more than one block),
+    128 samples, no oracle: the order a scheduled launch used is the stable descending sort of
+    the costs its probe recorded.  Any permutation renders the same frame, so nothing else
+    notices a sort that stopped sorting.  Ties in tile order are only tested if tiles tie: the
+    costs must hold a repeated value.  Seen on an MI355X: at depth 2 the probe's costs take 3
+    values and every tile shares its cost with another (the largest tie 527
+    tiles), so the order is stability almost alone; at depth 20 they take 6 values, 1088 tiles
+    tie and one tile's cost is its own.  (The 64 tiles of test_second_frame_skips_the_probe:
+    5 values, 59 tiles repeat another's.)
+    """
+    monkeypatch.delenv("ZRT_ORDER_CACHE", raising=False)
+    s = scenes(2)
+    p = z.RenderParams(264, 264, 128, max_depth)
+    ctx = z.RenderContext(s, p)
+    try:
+        _, st, order = frame(ctx, s, s.camera, p)
+        costs = ctx.debug_schedule()[0]
+    finally:
+        ctx.close()
+    assert st["schedule_ms"] > 0
+    assert len(costs) == len(order) == 1089 and sorted(order) == list(range(1089))
+    values, counts = np.unique(costs, return_counts=True)
+    print(f"1089 tiles: {len(values)} distinct costs, {int((counts > 1).sum())} of them repeated, "
+          f"{int(counts[counts > 1].sum())} tiles in ties, the largest tie {int(counts.max())} tiles")
+    assert costs.max() > costs.min()
+    assert (counts > 1).any(), "no two tiles tie: the order's stability is not tested"
+    np.testing.assert_array_equal(order, costliest_first(costs))
 
 
 @pytest.mark.parametrize("change", [{"seed": 7}, {"samples_per_pixel": 160}, {"prng": z.ZRT_PRNG_XOSHIRO256},

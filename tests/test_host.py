@@ -138,6 +138,29 @@ def test_param_validation_without_device(scenes):
             assert e.value.code == _ffi.ZRT_E_NODEVICE
 
 
+def test_debug_compact_refusals():
+    """zrt_debug_compact checks its list on the host, before any device is asked for: the
+    kernel indexes tile_done with the entries.  A null pointer, an empty list, an entry at or
+    past n_tiles: ZRT_E_INVALID; a good list with no GPU: ZRT_E_NODEVICE."""
+    u32p = C.POINTER(C.c_uint32)
+    lst, done, out, count = (C.c_uint32 * 3)(0, 2, 1), (C.c_uint32 * 3)(), (C.c_uint32 * 3)(), C.c_uint32()
+    f = z.lib().zrt_debug_compact
+    for args in ((None, 3, done, 3, out, C.byref(count), 0), (lst, 3, None, 3, out, C.byref(count), 0),
+                 (lst, 3, done, 3, None, C.byref(count), 0), (lst, 3, done, 3, out, None, 0),
+                 (lst, 0, done, 3, out, C.byref(count), 0), (lst, 3, done, 2, out, C.byref(count), 0)):
+        assert f(*args) == _ffi.ZRT_E_INVALID, args
+    for bad in ([], [3], [0, 1, 2 ** 32 - 1]):
+        with pytest.raises(z.ZrtError) as e:
+            z.debug_compact(bad, [0, 0, 0])
+        assert e.value.code == _ffi.ZRT_E_INVALID, bad
+    assert C.cast(out, u32p)[0] == 0  # (refused before anything is written)
+    import torch
+    if not torch.cuda.is_available():
+        with pytest.raises(z.ZrtError) as e:
+            z.debug_compact([0, 2, 1], [0, 0, 0])
+        assert e.value.code == _ffi.ZRT_E_NODEVICE
+
+
 def test_tree_layout_mismatch_is_refused(scenes, monkeypatch):
     """a wide tree whose encoding is not the one the kernels
     decode (accel_build.hpp kLayout*, render.hip kKernelLayout) is refused with

@@ -695,6 +695,21 @@ def debug_rng(prng: int, key: int, n: int, device: int = 0):
     return out
 
 
+def debug_compact(list_, tile_done, fill: int = 0xFFFFFFFF, device: int = 0):
+    """One launch of the adaptive run's compaction (zrt_debug_compact) over list_ (entries
+    index tile_done; bit 31 of a tile_done word = frozen).  The output buffer starts as
+    len(list_) words of `fill`.  Returns (out, count): the whole buffer after the launch
+    and the number of entries the kernel reports written."""
+    u32p = C.POINTER(C.c_uint32)
+    lst = np.ascontiguousarray(list_, dtype=np.uint32)
+    done = np.ascontiguousarray(tile_done, dtype=np.uint32)
+    out = np.full(lst.size, fill, dtype=np.uint32)
+    count = C.c_uint32()
+    check(lib().zrt_debug_compact(lst.ctypes.data_as(u32p), lst.size, done.ctypes.data_as(u32p), done.size,
+                                  out.ctypes.data_as(u32p), C.byref(count), device))
+    return out, count.value
+
+
 def read_png(path: str):
     """png_image.readFile (zrt_image_read_png): float32[height, width, 3], row 0 = bottom, c/255."""
     w, h, px = C.c_uint32(), C.c_uint32(), C.POINTER(C.c_float)()

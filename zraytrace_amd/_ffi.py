@@ -303,6 +303,8 @@ SIGNATURES = [
     ("zrt_debug_rng", C.c_int, [C.c_uint32, C.c_uint64, C.POINTER(C.c_uint64),
                                 C.c_uint32, C.c_uint32]),
     ("zrt_debug_division", C.c_int, [C.c_uint64, C.POINTER(C.c_uint64), C.c_uint32]),
+    ("zrt_debug_compact", C.c_int, [C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(C.c_uint32), C.c_uint32,
+                                    C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_uint32]),
     ("zrt_debug_lds_plans", C.c_int, [C.POINTER(Scene), C.POINTER(C.c_uint32)]),
     ("zrt_debug_buffer_plans", C.c_int, [C.POINTER(Scene), C.c_uint32, C.POINTER(C.c_uint32)]),
     ("zrt_debug_launch_plan", C.c_int, [C.POINTER(Scene), C.POINTER(Params), C.POINTER(LaunchPlan)]),

@@ -139,6 +139,35 @@ int zrt_debug_division(uint64_t n, uint64_t* counts, uint32_t device) {
   ZRT_CATCH_ALL
 }
 
+int zrt_debug_compact(const uint32_t* list, uint32_t n, const uint32_t* tile_done, uint32_t n_tiles, uint32_t* out,
+                      uint32_t* count, uint32_t device) {
+  if (!list || !tile_done || !out || !count) return fail(ZRT_E_INVALID, "null argument");
+  if (n == 0) return fail(ZRT_E_INVALID, "compact: an empty list");
+  // (the kernel reads tile_done[list[i]]: no entry may point past it)
+  for (uint32_t i = 0; i < n; ++i)
+    if (list[i] >= n_tiles) return fail(ZRT_E_INVALID, "compact: a list entry is not below n_tiles");
+  int rc = zrt::check_device(int(device));
+  if (rc) return rc;
+  try {
+    HIPCHK(hipSetDevice(int(device)));
+    zrt::DevBuf<uint32_t> d_list, d_done, d_out, d_count;
+    d_list.alloc(n);
+    d_done.alloc(n_tiles);
+    d_out.alloc(n);
+    d_count.alloc(1);
+    HIPCHK(hipMemcpy(d_list.p, list, size_t(n) * sizeof(uint32_t), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_done.p, tile_done, size_t(n_tiles) * sizeof(uint32_t), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_out.p, out, size_t(n) * sizeof(uint32_t), hipMemcpyHostToDevice));
+    HIPCHK(hipMemset(d_count.p, 0, sizeof(uint32_t)));
+    HIPCHK(zrt::launch_compact(nullptr, d_list.p, n, d_done.p, d_out.p, d_count.p));
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(out, d_out.p, size_t(n) * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(count, d_count.p, sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return ZRT_OK;
+  }
+  ZRT_CATCH_ALL
+}
+
 int zrt_debug_rng(uint32_t prng, uint64_t key, uint64_t* out, uint32_t n, uint32_t device) {
   if (!out) return fail(ZRT_E_INVALID, "null argument");
   int rc = zrt::check_device(int(device));
