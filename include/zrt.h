@@ -113,6 +113,16 @@ typedef struct zrt_image {
   const float* pixels;
 } zrt_image;
 
+/* Degenerate geometry is accepted and traced as the reference traces it: zero-area
+ * and zero-size primitives, duplicates, leaves whose box is flat on an axis (which the
+ * reference BVH never opens), coordinates up to FLT_MAX, +-inf and NaN vertices.
+ * One thing is refused, by every entry point that takes a scene, with
+ * ZRT_E_UNSUPPORTED and a message naming the primitive: a primitive whose bounding
+ * box (sphere.zig:24-29, triangle.zig:33) has a NaN midpoint on some axis - a NaN
+ * bound (a NaN sphere centre or radius) or a box from -inf to +inf (an infinite
+ * radius).  The reference sorts midpoints with `<` (bvh.zig:85-120), which does not
+ * order a NaN: its tree is then an accident of the sort algorithm, and no two
+ * implementations of "the reference's BVH" agree on it.  Nothing finite is refused. */
 typedef struct zrt_scene {
   const zrt_prim* prims;         /* reference list order (scenes.zig append order) */
   uint32_t n_prims;

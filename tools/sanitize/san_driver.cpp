@@ -14,11 +14,15 @@
 //   oracle/        oracle_render (both RNG modes), oracle_render_scanlines,
 //                  oracle_trace, oracle_bvh_build
 //
+// and, after the reference scenes, the degenerate families of tests/degenerate_scenes.py
+// (flat leaves, duplicates, zero-size and non-finite boxes) through the same calls.
+//
 // Device code is not built here (GPU sanitizers are not available on the pool);
 // build_bvh_device is stubbed to "not available", which is what the host build
 // path does without a GPU, and kernel_config() (render.hip's) returns the values the
 // shipped kernels are built with.  Any sanitizer report aborts with a non-zero status
 // (-fno-sanitize-recover=all); tests/test_sanitizers.py builds and runs this.
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -314,6 +318,332 @@ static void tile_walks() {
     }
 }
 
+// ---- degenerate geometry (tests/degenerate_scenes.py's families, built here again) ------
+//
+// Flat leaves, duplicates, zero-size and non-finite boxes through the host BVH build
+// (against the oracle's), the wide-tree builder, the planners, the compressed-node
+// encoder and the oracle's two closest-hit paths, with the oracle-side conditions of
+// tests/test_degenerate_host.py.  Rays: an LCG's, aimed into the family's box.
+namespace degenerate {
+
+struct Family {
+  std::string name;
+  std::vector<zrt_prim> prims;
+  std::vector<uint32_t> marked;  // flat / point / sliver / non-finite primitives
+  float lo[3], hi[3];            // the box rays are aimed into
+  int flat_axis = -1;            // flat-*: the grid's axis
+  float level = 0.0f;
+  bool from_above = false, from_front = false;
+  uint32_t n_materials = 3;
+};
+
+static zrt_vec3 v3(double x, double y, double z) { return {float(x), float(y), float(z)}; }
+
+static zrt_prim sphere(zrt_vec3 c, float r) {
+  zrt_prim p;
+  std::memset(&p, 0, sizeof p);
+  p.kind = ZRT_PRIM_SPHERE;
+  p.center = c;
+  p.radius = r;
+  return p;
+}
+
+static zrt_prim tri(zrt_vec3 a, zrt_vec3 b, zrt_vec3 c) {
+  zrt_prim p;
+  std::memset(&p, 0, sizeof p);
+  p.kind = ZRT_PRIM_TRIANGLE;
+  p.a = a, p.b = b, p.c = c;
+  return p;
+}
+
+// n x n quads in the plane coordinate[axis] == level over [lo, hi]^2 (+ shift); e1 x e2 along +axis
+static void quad_grid(std::vector<zrt_prim>& out, int axis, double level, int n, double lo, double hi, double su = 0.0,
+                      double sv = 0.0) {
+  int u = axis == 0 ? 1 : 0, v = axis == 2 ? 1 : 2;
+  if (axis == 1) std::swap(u, v);
+  auto pt = [&](double a, double b) {
+    double p[3] = {0.0, 0.0, 0.0};
+    p[axis] = level, p[u] = a + su, p[v] = b + sv;
+    return v3(p[0], p[1], p[2]);
+  };
+  std::vector<double> xs;
+  for (int k = 0; k <= n; ++k) xs.push_back(lo + (hi - lo) * k / n);
+  for (int i = 0; i < n; ++i)
+    for (int j = 0; j < n; ++j) {
+      out.push_back(tri(pt(xs[i], xs[j]), pt(xs[i + 1], xs[j]), pt(xs[i + 1], xs[j + 1])));
+      out.push_back(tri(pt(xs[i], xs[j]), pt(xs[i + 1], xs[j + 1]), pt(xs[i], xs[j + 1])));
+    }
+}
+
+static void scatter(std::vector<zrt_prim>& out, int n, double phase) {
+  for (int i = 0; i < n; ++i)
+    out.push_back(sphere(v3(1.2 * std::sin(1.7 * i + phase), 0.5 * std::sin(2.3 * i + 0.5 * phase), 1.2 * std::cos(1.1 * i + phase)),
+                         float(0.15 + 0.025 * ((7 * i + int(phase)) % 10))));
+}
+
+static void box(Family& f, double x0, double y0, double z0, double x1, double y1, double z1) {
+  f.lo[0] = float(x0), f.lo[1] = float(y0), f.lo[2] = float(z0);
+  f.hi[0] = float(x1), f.hi[1] = float(y1), f.hi[2] = float(z1);
+}
+
+static Family build(const std::string& name) {
+  Family f;
+  f.name = name;
+  box(f, -2.0, -1.0, -2.0, 2.0, 1.5, 2.0);
+  std::vector<zrt_prim>& P = f.prims;
+  if (name == "eleven" || name == "ten") {
+    const zrt_prim s[5] = {sphere(v3(0.0, -100.5, 0.0), 100.0f), sphere(v3(-1.2, 0.0, 0.3), 0.5f),
+                           sphere(v3(1.1, -0.1, -0.4), 0.4f), sphere(v3(0.0, 0.9, -1.0), 0.35f),
+                           sphere(v3(0.3, -0.3, 1.0), 0.2f)};
+    const zrt_prim t[6] = {tri(v3(-0.6, -0.5, -0.2), v3(0.4, -0.5, 0.6), v3(0.0, 0.5, 0.0)),
+                           tri(v3(0.4, -0.5, 0.6), v3(0.7, -0.5, -0.5), v3(0.0, 0.5, 0.0)),
+                           tri(v3(0.7, -0.5, -0.5), v3(-0.6, -0.5, -0.2), v3(0.0, 0.5, 0.0)),
+                           tri(v3(-2.0, -0.45, 1.0), v3(-1.0, -0.45, 1.6), v3(-1.6, 0.4, 1.2)),
+                           tri(v3(1.5, -0.4, 0.8), v3(2.2, -0.4, 0.2), v3(1.9, 0.6, 0.6)),
+                           tri(v3(-0.5, 1.0, 0.5), v3(0.5, 1.0, 0.5), v3(0.0, 1.4, -0.2))};
+    P = {s[0], t[0], s[1], t[1], t[2], s[2], t[3], s[3], t[4], s[4], t[5]};
+    if (name == "ten") P.pop_back();
+  } else if (name.rfind("flat-", 0) == 0) {
+    f.flat_axis = name[5] - 'x';
+    f.level = 0.25f;
+    quad_grid(P, f.flat_axis, 0.25, 6, -1.5, 1.5);
+    for (uint32_t i = 0; i < 72; ++i) f.marked.push_back(i);
+    box(f, -2.0, -2.0, -2.0, 2.0, 2.0, 2.0);
+  } else if (name == "terraces") {
+    const double ys[3] = {-0.5, 0.0, 0.5};
+    for (int k = 0; k < 3; ++k) quad_grid(P, 1, ys[k], 3, -0.9, 0.9, 0.7 * (k - 1), -0.5 * (k - 1));
+    for (uint32_t i = 0; i < P.size(); ++i) f.marked.push_back(i);
+    P.push_back(tri(v3(-2.0, -0.6, -1.8), v3(-2.0, -0.2, -0.6), v3(-1.0, -0.6, -1.8)));
+    P.push_back(tri(v3(1.6, -0.4, 1.0), v3(1.6, 0.3, 2.0), v3(2.4, -0.4, 1.0)));
+    P.push_back(tri(v3(-1.8, 0.1, 1.2), v3(-1.8, 0.6, 2.0), v3(-0.8, 0.1, 1.2)));
+    P.push_back(tri(v3(0.9, 0.6, -2.0), v3(0.9, 0.9, -1.2), v3(1.9, 0.6, -2.0)));
+    P.push_back(tri(v3(-0.3, -0.9, 1.6), v3(-0.3, -0.7, 2.4), v3(0.6, -0.9, 1.6)));
+    P.push_back(tri(v3(-2.4, 0.7, -0.2), v3(-2.4, 0.9, 0.5), v3(-1.6, 0.7, -0.2)));
+    P.push_back(sphere(v3(1.6, 0.0, -0.4), 0.45f));
+    f.from_above = true;
+    box(f, -2.5, -1.0, -2.5, 2.5, 1.0, 2.5);
+  } else if (name == "duplicates") {
+    for (int i = 0; i < 9; ++i) P.push_back(sphere(v3(-0.6, 0.0, 0.0), 0.55f));
+    for (int i = 0; i < 40; ++i) P.push_back(tri(v3(0.1, -0.6, -0.3), v3(1.5, -0.6, 0.2), v3(0.7, 0.8, 0.0)));
+    f.n_materials = 4;
+    box(f, -1.3, -0.8, -0.6, 1.6, 0.9, 0.6);
+  } else if (name == "points") {
+    const zrt_vec3 pt = v3(0.25, 0.125, -0.5);
+    for (int i = 0; i < 8; ++i) {
+      for (int k = 0; k < 3; ++k) f.marked.push_back(uint32_t(P.size())), P.push_back(sphere(pt, 0.0f));
+      f.marked.push_back(uint32_t(P.size())), P.push_back(tri(pt, pt, pt));
+      if (i == 3) {
+        P.push_back(sphere(v3(-0.7, 0.0, 0.0), 0.6f));
+        P.push_back(tri(v3(0.0, -0.7, -0.4), v3(1.6, -0.7, 0.0), v3(0.8, 0.9, -0.2)));
+      }
+    }
+    box(f, -1.4, -0.8, -0.7, 1.7, 1.0, 0.7);
+  } else if (name == "slivers") {
+    for (int k = 0; k < 12; ++k) {
+      const double x0 = -1.5 + 0.25 * k, x1 = -1.0 + 0.25 * k, zc = 0.25 * (k % 3) - 0.25;
+      const zrt_vec3 a = v3(x0, -0.5, zc), b = v3(x1, -0.5, zc), c = v3(x0, 0.75, zc - 0.5);
+      P.push_back(tri(a, b, c));
+      f.marked.push_back(uint32_t(P.size()));
+      if (k % 3 == 0) P.push_back(tri(a, b, v3(0.5 * (x0 + x1), -0.5, zc)));
+      else if (k % 3 == 1) P.push_back(tri(a, a, c));
+      else P.push_back(tri(v3(x0, 0.0, 0.5), v3(x0 + 0.5, 0.25, 0.5), v3(x0 + 1.0, 0.5, 0.5)));
+    }
+    f.from_front = true;
+    box(f, -1.6, -0.6, -0.9, 1.6, 0.8, 0.6);
+  } else if (name == "range") {
+    const double big = 8.0e18;
+    P.push_back(sphere(v3(1e-30, 1e-30, 1e-30), 1e-38f));
+    scatter(P, 12, 3.0);
+    P.push_back(tri(v3(3.0e38, -1.0, -3.0e38), v3(2.0e38, -1.0, 3.0e38), v3(3.2e38, -1.0, 0.0)));
+    P.push_back(tri(v3(-big, -0.75, -big), v3(-big, -0.75, big), v3(big, -0.75, -big)));
+    f.marked = {0, 13};
+    box(f, -1.5, -0.7, -1.5, 1.5, 0.8, 1.5);
+  } else if (name == "inf-vertex" || name == "inf-radius") {
+    scatter(P, 20, 5.0);
+    const zrt_prim odd = name == "inf-vertex" ? tri(v3(0.0, -0.5, 0.0), v3(INFINITY, -0.5, 0.0), v3(0.0, 0.5, -1.0))
+                                              : sphere(v3(0.0, 0.0, -3.0), INFINITY);
+    P.insert(P.begin() + 10, odd);
+    f.marked = {10};
+    box(f, -1.6, -1.0, -1.6, 1.6, 1.0, 1.6);
+  } else {  // nan-vertex, nan-center
+    for (int j = 0; j < 4; ++j)
+      for (int i = 0; i < 5; ++i) P.push_back(sphere(v3(-1.2 + 0.6 * i, -0.45 + 0.45 * j, -0.3 * (i % 2)), 0.2f));
+    if (name == "nan-vertex") P.push_back(tri(v3(0.0, 0.0, -1.0), v3(NAN, 0.0, -1.0), v3(0.0, 1.0, -1.0)));
+    else P.push_back(sphere(v3(NAN, 0.3, -0.6), 0.25f));
+    f.marked = {20};
+    box(f, -1.5, -0.8, -0.8, 1.5, 1.2, 0.4);
+  }
+  for (uint32_t i = 0; i < P.size(); ++i) P[i].material = i % f.n_materials;
+  return f;
+}
+
+struct Lcg {
+  uint64_t s;
+  double next() {  // [0, 1)
+    s = s * 6364136223846793005ull + 1442695040888963407ull;
+    return double(s >> 11) * (1.0 / 9007199254740992.0);
+  }
+};
+
+// 6000 rays: from a shell around the box at points inside it (flat-*: on the plane);
+// every 20th ray of a flat family lies in the plane (d_k = 0, o_k on it: NaN slabs)
+static std::vector<float> rays_of(const Family& f, uint32_t n) {
+  Lcg g{0x9e3779b97f4a7c15ull + f.name.size() * 1000003ull + uint64_t(f.name[f.name.size() - 1])};
+  double span = 0.0;
+  for (int k = 0; k < 3; ++k) span = std::max(span, double(f.hi[k]) - double(f.lo[k]));
+  std::vector<float> r;
+  for (uint32_t i = 0; i < n; ++i) {
+    double t[3], v[3], len = 0.0;
+    for (int k = 0; k < 3; ++k) t[k] = f.lo[k] + (double(f.hi[k]) - f.lo[k]) * g.next();
+    if (f.flat_axis >= 0) t[f.flat_axis] = f.level;
+    do {
+      len = 0.0;
+      for (int k = 0; k < 3; ++k) v[k] = 2.0 * g.next() - 1.0, len += v[k] * v[k];
+    } while (len > 1.0 || len < 1e-3);
+    len = std::sqrt(len);
+    for (int k = 0; k < 3; ++k) v[k] /= len;
+    if (f.from_above) v[1] = std::fabs(v[1]) + 0.3;
+    if (f.from_front) v[2] = std::fabs(v[2]) + 0.2;
+    const bool in_plane = f.flat_axis >= 0 && i % 20 == 0;
+    if (in_plane) v[f.flat_axis] = 0.0;
+    const double dist = span * (0.6 + 0.8 * g.next());
+    float o[3], d[3];
+    for (int k = 0; k < 3; ++k) {
+      o[k] = float(t[k] + v[k] * dist);
+      d[k] = in_plane && k == f.flat_axis ? 0.0f : float(t[k]) - o[k];
+    }
+    r.insert(r.end(), o, o + 3);
+    r.insert(r.end(), d, d + 3);
+  }
+  return r;
+}
+
+static bool is_marked(const Family& f, int32_t prim) {
+  return prim >= 0 && std::find(f.marked.begin(), f.marked.end(), uint32_t(prim)) != f.marked.end();
+}
+
+static void one_family(const std::string& name) {
+  const Family f = build(name);
+  const char* nm = name.c_str();
+  const zrt_texture texs[4] = {{ZRT_TEX_COLOR, 0, {0.8f, 0.2f, 0.15f}, 0.f, 0.f}, {ZRT_TEX_COLOR, 0, {0.8f, 0.8f, 0.85f}, 0.f, 0.f},
+                               {ZRT_TEX_COLOR, 0, {0.2f, 0.7f, 0.25f}, 0.f, 0.f}, {ZRT_TEX_COLOR, 0, {0.9f, 0.9f, 0.2f}, 0.f, 0.f}};
+  const zrt_material mats[4] = {{ZRT_MAT_LAMBERTIAN, 0, 0.f}, {ZRT_MAT_METAL, 1, 0.f}, {ZRT_MAT_LAMBERTIAN, 2, 0.f},
+                                {ZRT_MAT_METAL, 3, 0.f}};
+  zrt_scene sc;
+  std::memset(&sc, 0, sizeof sc);
+  sc.prims = f.prims.data();
+  sc.n_prims = uint32_t(f.prims.size());
+  sc.materials = mats;
+  sc.n_materials = f.n_materials;
+  sc.textures = texs;
+  sc.n_textures = 4;
+  const zrt_scene* s = &sc;
+  const bool bvh = sc.n_prims > 10;
+  const bool nan_mid = name == "inf-radius" || name == "nan-center";  // refused by validate_scene
+  CHECK(name == "ten" ? sc.n_prims == 10 : sc.n_prims >= 11 && sc.n_prims <= 300, "%s: %u primitives", nm, sc.n_prims);
+
+  // the host tree == the oracle's (nan-center: NaN sort keys, no tree to agree on); the wide tree
+  uint32_t n_leaves = 0, n_flat = 0;
+  if (bvh) {
+    zrt_bvh_node *nodes = nullptr, *onodes = nullptr;
+    uint32_t n_nodes = 0, depth = 0, on = 0, od = 0;
+    int rc = zrt_bvh_build(s, &nodes, &n_nodes, &depth);
+    CHECK(rc == ZRT_OK && n_nodes > 0, "%s bvh: %s", nm, zrt_last_error());
+    rc = oracle_bvh_build(s, &onodes, &on, &od);
+    CHECK(rc == 0 && on == n_nodes && od == depth, "%s: oracle tree of %u nodes, host %u", nm, on, n_nodes);
+    if (name != "nan-center")
+      CHECK(on == n_nodes && std::memcmp(nodes, onodes, sizeof(zrt_bvh_node) * on) == 0, "%s: host BVH differs from the oracle's", nm);
+    for (uint32_t i = 0; i < on; ++i)
+      if (onodes[i].left < 0) {
+        ++n_leaves;
+        n_flat += (onodes[i].min.x == onodes[i].max.x || onodes[i].min.y == onodes[i].max.y || onodes[i].min.z == onodes[i].max.z);
+      }
+    zrt_free(nodes);
+    oracle_free(onodes);
+    const zrt::BuiltBvh built = zrt::build_bvh(sc.prims, sc.n_prims);
+    CHECK(built.nodes.size() == n_nodes && wide_tree(built) > 0, "%s: wide tree", nm);
+  }
+
+  // the planners and the encoder
+  uint32_t n_plans = 0;
+  uint64_t n_slots = 0;
+  zrt_params p = params(24, 24, 4, 6, ZRT_RNG_COUNTER);
+  zrt_launch_plan lp;
+  auto refused = [&](int rc) {
+    return rc == ZRT_E_UNSUPPORTED && std::strstr(zrt_last_error(), ("primitive " + std::to_string(f.marked[0]) + ":").c_str());
+  };
+  if (nan_mid) {
+    CHECK(refused(zrt_debug_lds_plans(s, &n_plans)) && refused(zrt_debug_buffer_plans(s, 0, &n_plans)) &&
+              refused(zrt_debug_launch_plan(s, &p, &lp)) && refused(zrt_debug_qnodes(s, &n_slots)),
+          "%s: a NaN midpoint is not refused: %s", nm, zrt_last_error());
+  } else {
+    CHECK(zrt_debug_lds_plans(s, &n_plans) == ZRT_OK && n_plans > 0, "%s lds plans: %s", nm, zrt_last_error());
+    CHECK(zrt_debug_buffer_plans(s, 0, &n_plans) == ZRT_OK, "%s buffer plans: %s", nm, zrt_last_error());
+    for (uint32_t trav : {uint32_t(ZRT_TRAVERSAL_FAST), uint32_t(ZRT_TRAVERSAL_BINARY), uint32_t(ZRT_TRAVERSAL_REFERENCE)})
+      for (uint32_t use_bvh : {1u, 0u}) {
+        p.traversal = trav;
+        p.bounded_volume_hierarchy = use_bvh;
+        CHECK(zrt_debug_launch_plan(s, &p, &lp) == ZRT_OK && lp.lds_bytes <= (160u << 10), "%s launch plan: %s", nm, zrt_last_error());
+        if (!bvh || !use_bvh) CHECK(lp.sampling_loop == 0 || lp.sampling_loop == 6, "%s: not a list loop (%u)", nm, lp.sampling_loop);
+      }
+    if (bvh) {
+      const int rc = zrt_debug_qnodes(s, &n_slots);
+      if (name == "inf-vertex")
+        CHECK(rc == ZRT_E_UNSUPPORTED && std::strstr(zrt_last_error(), "refused"), "%s qnodes: rc %d %s", nm, rc, zrt_last_error());
+      else
+        CHECK(rc == ZRT_OK && n_slots > 0, "%s qnodes: %s", nm, zrt_last_error());
+      // a launch that asks for compressed nodes gets them, or (a refused tree) the full ones
+      setenv("ZRT_QNODES", "1", 1);
+      setenv("ZRT_POOL", "1", 1);
+      p = params(24, 24, 4, 6, ZRT_RNG_COUNTER);
+      CHECK(zrt_debug_launch_plan(s, &p, &lp) == ZRT_OK && lp.sampling_loop == 5 && lp.qnodes == (name == "inf-vertex" ? 0u : 1u),
+            "%s: launch plan under ZRT_QNODES=1: loop %u qnodes %u", nm, lp.sampling_loop, lp.qnodes);
+      unsetenv("ZRT_QNODES");
+      unsetenv("ZRT_POOL");
+    }
+  }
+
+  // the oracle's closest hits through the BVH and through the list
+  const uint32_t n = 6000;
+  const std::vector<float> rays = rays_of(f, n);
+  std::vector<float> t(n);
+  std::vector<int32_t> pb(n, -1), pl(n, -1);
+  CHECK(oracle_trace(s, 0, rays.data(), n, t.data(), pl.data()) == 0, "%s: oracle_trace (list)", nm);
+  if (bvh) CHECK(oracle_trace(s, 1, rays.data(), n, t.data(), pb.data()) == 0, "%s: oracle_trace (bvh)", nm);
+  uint32_t hits_b = 0, hits_l = 0, flat_b = 0, flat_l = 0, marked_wins = 0;
+  std::vector<int32_t> wb, wl;
+  for (uint32_t i = 0; i < n; ++i) {
+    hits_b += pb[i] >= 0, hits_l += pl[i] >= 0;
+    flat_b += is_marked(f, pb[i]), flat_l += is_marked(f, pl[i]);
+    marked_wins += is_marked(f, pb[i]) || is_marked(f, pl[i]);
+    if (pb[i] >= 0 && std::find(wb.begin(), wb.end(), pb[i]) == wb.end()) wb.push_back(pb[i]);
+    if (pl[i] >= 0 && std::find(wl.begin(), wl.end(), pl[i]) == wl.end()) wl.push_back(pl[i]);
+  }
+  std::sort(wb.begin(), wb.end());
+  std::sort(wl.begin(), wl.end());
+  std::printf("degenerate %s: %u primitives, %u of %u leaves flat, %u BVH hits and %u list hits of %u rays (%u and %u on marked)\n", nm,
+              sc.n_prims, n_flat, n_leaves, hits_b, hits_l, n, flat_b, flat_l);
+  if (f.flat_axis >= 0)
+    CHECK(hits_b == 0 && 4 * hits_l >= n && n_flat == n_leaves, "%s: %u BVH hits, %u list hits, %u of %u leaves flat", nm, hits_b,
+          hits_l, n_flat, n_leaves);
+  else if (name == "terraces")
+    CHECK(n_flat >= 20 && n_flat < n_leaves && flat_l - flat_b >= 1000, "%s: %u flat leaves, %u - %u hits on flat triangles", nm,
+          n_flat, flat_l, flat_b);
+  else if (name == "duplicates")
+    CHECK(wb != wl && wb.size() == 2 && wl.size() == 2, "%s: the BVH's winners are the list's", nm);
+  else if (name == "points" || name == "slivers" || name == "range" || name == "eleven")
+    CHECK(5 * hits_b >= n, "%s: %u BVH hits of %u rays", nm, hits_b, n);
+  if (name == "slivers") CHECK(marked_wins == 0, "%s: %u rays won by a sliver", nm, marked_wins);
+}
+
+static void all() {
+  for (const char* name : {"eleven", "ten", "flat-x", "flat-y", "flat-z", "terraces", "duplicates", "points", "slivers", "range",
+                           "inf-vertex", "inf-radius", "nan-vertex", "nan-center"})
+    one_family(name);
+}
+
+}  // namespace degenerate
+
 int main(int argc, char** argv) {
   if (argc < 3) {
     std::fprintf(stderr, "usage: %s ASSETS_DIR TMP_DIR\n", argv[0]);
@@ -324,6 +654,7 @@ int main(int argc, char** argv) {
   pass_and_adapt_plans();
   reproject_plans(assets);
   tile_walks();
+  degenerate::all();
 
   // error paths: unknown scene index, missing files, a truncated binary scene
   zrt_scene_data* d = nullptr;

@@ -9,6 +9,7 @@
 #include <string>
 
 #include "accel_build.hpp"
+#include "bvh_build.hpp"
 #include "host.hpp"
 
 namespace zrt {
@@ -29,6 +30,14 @@ int validate_scene(const zrt_scene* s) {
     const zrt_prim& p = s->prims[i];
     if (p.kind != ZRT_PRIM_SPHERE && p.kind != ZRT_PRIM_TRIANGLE) return fail(ZRT_E_INVALID, "unknown primitive kind");
     if (p.material >= s->n_materials) return fail(ZRT_E_INVALID, "material index out of range");
+    // A NaN midpoint (a NaN bound, or a box from -inf to +inf: a NaN centre or radius, an
+    // infinite radius) has no place under the `<` the reference sorts midpoints by
+    // (bvh.zig:85-120): the tree then depends on the sort's algorithm, not on the scene.
+    const Box b = prim_box(p);
+    if (std::isnan(b.mid[0]) || std::isnan(b.mid[1]) || std::isnan(b.mid[2]))
+      return fail(ZRT_E_UNSUPPORTED, "primitive " + std::to_string(i) +
+                                         ": its bounding box has a NaN midpoint (a NaN or unbounded coordinate), "
+                                         "which the reference's BVH sort does not order");
   }
   for (uint32_t i = 0; i < s->n_materials; ++i) {
     const zrt_material& m = s->materials[i];
