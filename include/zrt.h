@@ -189,7 +189,13 @@ enum { ZRT_DEFAULT_SAMPLE_CHUNK = 32u };
  * (compared bitwise), width, height, max_depth, rank, world_size, traversal, guard
  * flag and tile count - whatever its samples_per_pixel, seed or prng - skips the
  * probe and the sort, and reports schedule_ms = 0.  ZRT_ORDER_CACHE=0 in the
- * environment probes every frame (A/B). */
+ * environment probes every frame (A/B).
+ * All-sky tiles (the lockstep FAST loop, max_depth >= 1, no ZRT_FLAG_SCANLINES or
+ * ZRT_FLAG_GUARD, a frame or a progressive pass): the tiles the host proves no
+ * primary ray can hit anything in (zrt_debug_tile_classes) render in a kernel of
+ * their own without traversal; the frame and the counters are the same bit for bit.
+ * The classes are kept under the same key as the order; classifying counts into
+ * schedule_ms of a launch that probes.  ZRT_SKY_TILES=0 turns the split off (A/B). */
 
 /* ZRT_FLAG_GUARD (FAST traversal): the grazing-triangle guard (DESIGN.md
  * section 3 "Triangles"): every box is widened by the reach of the rounded
@@ -1106,6 +1112,23 @@ int zrt_debug_qnodes(const zrt_scene* scene, uint64_t* n_checked);
  * ZRT_OK otherwise - and always for a library built with ZRT_OCT_MUL24=0.
  * (tests only) */
 int zrt_debug_octant_offsets(uint32_t stride_f4, uint32_t n_top, uint32_t node_f4);
+/* The class of each of this rank's tiles as zrt_ctx_render_tiles would split them,
+ * with no device: classes[lt] for local tile lt (at most cap words are written), 0
+ * for a general tile, ZRT_TILE_SKY for a tile no primary ray of which can return a
+ * hit from the reference's closest-hit query, whatever the jitter, the seed, the
+ * sample count or the generator (such tiles render in a kernel without traversal;
+ * the frame is the same bit for bit).  Every tile is general unless the launch is the
+ * lockstep FAST loop with max_depth >= 1, without ZRT_FLAG_SCANLINES and
+ * ZRT_FLAG_GUARD, from a camera inside the scene's ray-origin bound, over a scene
+ * with no non-finite plane; and when the environment says ZRT_SKY_TILES=0.
+ * margins (4 doubles, or NULL): the largest distance past a sphere's surface and past
+ * a triangle at which the classifier still counts a ray as a possible hit, and the
+ * triangles' two coefficients (reach = k_ao |ao| + k_c).  n_sky: the rank's sky tiles.
+ * zrt_ctx_debug_counters slot 47 of a context's last launch holds the same count.
+ * (tests only) */
+#define ZRT_TILE_SKY 0x80000000u
+int zrt_debug_tile_classes(const zrt_scene* scene, const zrt_camera* camera, const zrt_params* params,
+                           uint32_t* classes, uint32_t cap, uint32_t* n_tiles, uint32_t* n_sky, double* margins);
 
 #ifdef __cplusplus
 }

@@ -184,7 +184,25 @@ static void one_scene(uint32_t index, const std::string& assets, const std::stri
         uint32_t lean = 0;
         rc = zrt_debug_lean_kernel(s, &cam, &p, &lean);
         CHECK(rc == ZRT_OK, "scene %u lean kernel: %s", index, zrt_last_error());
+        // the tile classifier (tile_class.cpp), ragged tiles, one rank and the second of three
+        for (uint32_t world : {1u, 3u}) {
+          zrt_params q = p;
+          q.world_size = world;
+          q.rank = world - 1;
+          std::vector<uint32_t> cls(64);
+          uint32_t n_tiles = 0, n_sky = 0;
+          double margins[4];
+          rc = zrt_debug_tile_classes(s, &cam, &q, cls.data(), uint32_t(cls.size()), &n_tiles, &n_sky, margins);
+          CHECK(rc == ZRT_OK && n_sky <= n_tiles, "scene %u tile classes: %s", index, zrt_last_error());
+        }
       }
+  {  // ... and a frame large enough for its threads (1024 x 1024: 16 squares of 32 x 32 tiles)
+    zrt_params q = params(1024, 1024, 4, 20, ZRT_RNG_COUNTER);
+    uint32_t n_tiles = 0, n_sky = 0;
+    rc = zrt_debug_tile_classes(s, &cam, &q, nullptr, 0, &n_tiles, &n_sky, nullptr);
+    CHECK(rc == ZRT_OK && n_tiles == 16384 && n_sky <= n_tiles, "scene %u tile classes at 1024 x 1024: %s", index,
+          zrt_last_error());
+  }
   if (s->n_prims > 10) {
     uint64_t n_slots = 0;
     rc = zrt_debug_qnodes(s, &n_slots);

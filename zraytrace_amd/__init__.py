@@ -780,6 +780,28 @@ def debug_lean_kernel(scene, camera, params) -> bool:
     return bool(out.value)
 
 
+ZRT_TILE_SKY = 0x80000000
+
+
+def debug_tile_classes(scene, camera, params):
+    """The class word of each of this rank's 8x8 tiles as a render of this scene from
+    this camera with these params would split them (zrt_debug_tile_classes; no device),
+    under the environment knobs a real launch reads (ZRT_SKY_TILES among them): a
+    uint32 array (0 general, ZRT_TILE_SKY all sky) and a dict of the classifier's
+    margins (sphere_reach, tri_reach, k_ao, k_c)."""
+    view = scene.view if isinstance(scene, LoadedScene) else scene
+    p = params.abi()
+    n, n_sky = C.c_uint32(), C.c_uint32()
+    m = (C.c_double * 4)()
+    check(lib().zrt_debug_tile_classes(view, C.byref(camera), C.byref(p), None, 0, C.byref(n), C.byref(n_sky), m))
+    out = np.zeros(max(1, n.value), dtype=np.uint32)
+    check(lib().zrt_debug_tile_classes(view, C.byref(camera), C.byref(p), out.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                       n.value, C.byref(n), C.byref(n_sky), m))
+    out = out[:n.value]
+    assert int((out == ZRT_TILE_SKY).sum()) == n_sky.value
+    return out, dict(sphere_reach=m[0], tri_reach=m[1], k_ao=m[2], k_c=m[3])
+
+
 def debug_qnodes(scene) -> int:
     """Host-side check of the scene's compressed wide nodes (zrt_debug_qnodes; no
     device): returns the number of slots checked, raises ZrtError on a violation."""

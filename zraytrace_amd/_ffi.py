@@ -311,6 +311,9 @@ SIGNATURES = [
     ("zrt_debug_lean_kernel", C.c_int, [C.POINTER(Scene), C.POINTER(Camera), C.POINTER(Params),
                                         C.POINTER(C.c_uint32)]),
     ("zrt_debug_qnodes", C.c_int, [C.POINTER(Scene), C.POINTER(C.c_uint64)]),
+    ("zrt_debug_tile_classes", C.c_int, [C.POINTER(Scene), C.POINTER(Camera), C.POINTER(Params),
+                                         C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(C.c_uint32),
+                                         C.POINTER(C.c_uint32), C.POINTER(C.c_double)]),
     ("zrt_debug_octant_offsets", C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32]),
 ]
 

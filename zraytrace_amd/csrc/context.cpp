@@ -250,6 +250,7 @@ static bool schedule_tiles(zrt_ctx* c, KArgs& a, uint32_t prng, bool stk16, uint
   HIPCHK(sort_tiles(pr.sort_temp.p, &bytes, pr.tile_cost.p, pr.cost_sorted.p, pr.tile_ids.p, pr.tile_order.p, my_tiles,
                     st));
   a.tile_order = pr.tile_order.p;
+  ++pr.order_gen;
   return true;
 }
 
@@ -330,6 +331,7 @@ std::unique_ptr<zrt_ctx> ctx_on_device(const HostScene& h, int device) {
   HIPCHK(hipGetDeviceProperties(&prop, c->device));
   c->cu_count = prop.multiProcessorCount;
   upload_scene(c->scene, h);
+  build_sky_scene(&c->sky.scene, h);
   c->scratch.alloc(kScratchSlots);
   return c;
 }
@@ -390,6 +392,8 @@ struct LaunchEnv {
   uint32_t sync = 0;          // ZRT_SYNC: A/B, the lockstep interval in samples (identical images); 0: unset
   bool order_cache = true;    // ZRT_ORDER_CACHE=0: A/B, probe every frame
   bool auto_sync = true;      // ZRT_SYNC or ZRT_AUTO_SYNC=0: the fixed interval, A/B
+  bool sky_tiles = true;      // ZRT_SKY_TILES=0: A/B, every tile through the render kernel
+  bool sky_by_render = false; // ZRT_SKY_TILES=2: measurement, the sky list through a second launch of the render kernel
   bool cap_rows = false;      // ZRT_DEBUG_ROW_CAP: tests, the STATS device check reports a smaller buffer
   double row_cap = 1.0;
 };
@@ -402,6 +406,8 @@ LaunchEnv read_launch_env() {
   v.order_cache = !(oc && std::atoi(oc) == 0);
   const char* as = std::getenv("ZRT_AUTO_SYNC");
   v.auto_sync = !v.sync && !(as && std::atoi(as) == 0);
+  v.sky_tiles = sky_tiles_wanted();
+  if (const char* e = std::getenv("ZRT_SKY_TILES")) v.sky_by_render = std::atoi(e) == 2;
   if (const char* e = std::getenv("ZRT_DEBUG_ROW_CAP")) {
     v.cap_rows = true;
     v.row_cap = std::atof(e);
@@ -599,6 +605,70 @@ bool choose_order(zrt_ctx* c, const Frame& f, const FrameSize& z, const LaunchEn
   return schedule;
 }
 
+// 6b. The all-sky tiles split off (tile_class.cpp proves them; sky_kernel renders them
+// without traversal): the render launch keeps the general tiles, in the order chosen
+// above, and its work shrinks to match.  The classes and the lists are kept under the
+// order cache's key: a frame with a matching key classifies nothing, and a run's later
+// pass takes its first pass's.  Classification runs here, behind the enqueued probe and
+// before e0, so a scheduled launch's schedule_ms covers it.  An adaptive level does not
+// take the split (its active list changes from level to level on the device).
+// Returns the sky tiles (0: no split; a.tile_order and a.total_work are as they were).
+uint32_t split_sky(zrt_ctx* c, const Frame& f, const LaunchEnv& env, KArgs& a) {
+  const zrt_params* p = f.p;
+  SkySplit& sp = c->sky;
+  if (!env.sky_tiles || f.adapt || f.my_tiles == 0 || !sp.scene.ok || !sky_split_allowed(f.plan, p, f.cam_inside))
+    return 0;
+  const OrderKey key{*f.cam, p->width, p->height, p->max_depth, p->rank, p->world_size, p->traversal,
+                     f.plan.guard_on ? 1u : 0u, f.my_tiles};
+  const bool hit = sp.valid && std::memcmp(&key, &sp.key, sizeof(key)) == 0 && (env.order_cache || !f.first);
+  if (!hit) {
+    sp.valid = false;
+    const double t0 = now_ms();
+    classify_tiles(sp.scene, f.cam, p, &sp.cls, &sp.n_sky);
+    if (env.debug)
+      std::fprintf(stderr, "zrt launch: %u of %u tiles all sky, classified in %.2f ms\n", sp.n_sky, f.my_tiles,
+                   now_ms() - t0);
+    sp.sky_host.clear();
+    sp.gen_host.clear();
+    for (uint32_t lt = 0; lt < f.my_tiles; ++lt) (sp.cls[lt] == kTileSky ? sp.sky_host : sp.gen_host).push_back(lt);
+    if (sp.n_sky) {
+      // (stream-ordered behind the previous launch, which may still read the old lists)
+      if (sp.cls_dev.n < f.my_tiles) {
+        HIPCHK(hipStreamSynchronize(f.st));
+        sp.cls_dev.alloc(f.my_tiles);
+        sp.sky_list.alloc(f.my_tiles);
+        sp.gen_list.alloc(f.my_tiles);
+        sp.gen_sorted.alloc(f.my_tiles);
+        sp.count.alloc(1);
+      }
+      const auto up = [&](DevBuf<uint32_t>& d, const std::vector<uint32_t>& h) {
+        if (!h.empty()) HIPCHK(hipMemcpyAsync(d.p, h.data(), h.size() * sizeof(uint32_t), hipMemcpyHostToDevice, f.st));
+      };
+      up(sp.cls_dev, sp.cls);
+      up(sp.sky_list, sp.sky_host);
+      up(sp.gen_list, sp.gen_host);
+      HIPCHK(hipStreamSynchronize(f.st));  // (the host vectors are rewritten by the next classification)
+    }
+    sp.sorted_valid = false;
+    sp.key = key;
+    sp.valid = true;
+  }
+  if (sp.n_sky == 0) return 0;
+  const uint32_t n_gen = f.my_tiles - sp.n_sky;
+  if (a.tile_order) {  // the probe's cost order, without the sky tiles
+    if (!sp.sorted_valid || sp.sorted_gen != c->probe.order_gen) {
+      HIPCHK(launch_compact(f.st, c->probe.tile_order.p, f.my_tiles, sp.cls_dev.p, sp.gen_sorted.p, sp.count.p));
+      sp.sorted_gen = c->probe.order_gen;
+      sp.sorted_valid = true;
+    }
+    a.tile_order = sp.gen_sorted.p;
+  } else {
+    a.tile_order = sp.gen_list.p;
+  }
+  a.total_work = uint32_t(uint64_t(n_gen) * f.pass.pass_chunks);
+  return sp.n_sky;
+}
+
 // 7. The lockstep interval's probe, the scanline and wave-time outputs, and - the
 // probe may have grown them - the global rows' buffers and their bounds.
 void optional_outputs(zrt_ctx* c, const Frame& f, const FrameSize& z, const LaunchEnv& env, bool schedule, KArgs& a) {
@@ -629,13 +699,26 @@ void optional_outputs(zrt_ctx* c, const Frame& f, const FrameSize& z, const Laun
 
 // 8. The kernel between its events, and what resolves its chunk sums into dev_tiles:
 // finalize (a frame), accumulate (a pass), or resolve and compact (an adaptive level).
-void enqueue(zrt_ctx* c, const Frame& f, const FrameSize& z, KArgs& a) {
+void enqueue(zrt_ctx* c, const Frame& f, const FrameSize& z, const LaunchEnv& env, KArgs& a, uint32_t n_sky) {
   const zrt_params* p = f.p;
   const Geometry& g = f.g;
   const uint32_t n_chunks = f.pass.pass_chunks, n_slots = f.my_tiles * 64u;
   unsigned long long* err = c->scratch.p + kErrorSlot;
   HIPCHK(hipEventRecord(c->ev.e0, f.st));
-  if (z.work > 0) {
+  if (n_sky > 0) {  // the all-sky tiles: one wave per unit at the most, no LDS
+    KArgs sa = a;
+    sa.tile_order = c->sky.sky_list.p;
+    sa.total_work = uint32_t(uint64_t(n_sky) * n_chunks);
+    const uint32_t grid = std::max(1u, std::min(uint32_t(c->cu_count) * 8u, (sa.total_work + kBlock / 64 - 1) / (kBlock / 64)));
+    void* args[] = {&sa};
+    if (env.sky_by_render) {  // (what the sky tiles cost in the render kernel: its own launch, its own work counter)
+      HIPCHK(hipLaunchKernel(f.kfn, dim3(z.grid), dim3(kBlock), args, f.plan.lp.bytes, f.st));
+      HIPCHK(hipMemsetAsync(c->scratch.p + kWorkSlot, 0, sizeof(unsigned long long), f.st));
+    } else {
+      HIPCHK(hipLaunchKernel(sky_kernel_ptr(p->prng, f.diag), dim3(grid), dim3(kBlock), args, 0, f.st));
+    }
+  }
+  if (a.total_work > 0) {
     void* args[] = {&a};
     HIPCHK(hipLaunchKernel(f.kfn, dim3(z.grid), dim3(kBlock), args, f.plan.lp.bytes, f.st));
   }
@@ -674,7 +757,7 @@ void enqueue(zrt_ctx* c, const Frame& f, const FrameSize& z, KArgs& a) {
 }
 
 // 9. The error flag copied back behind the done event; the launch recorded; the run advanced.
-void finish(zrt_ctx* c, const Frame& f, const FrameSize& z, const KArgs& a, bool schedule) {
+void finish(zrt_ctx* c, const Frame& f, const FrameSize& z, const KArgs& a, bool schedule, uint32_t n_sky) {
   HIPCHK(hipMemcpyAsync(c->render.err.get(), c->scratch.p + kErrorSlot, sizeof(unsigned long long), hipMemcpyDeviceToHost,
                         f.st));
   HIPCHK(hipEventRecord(c->render.done, f.st));
@@ -701,6 +784,7 @@ void finish(zrt_ctx* c, const Frame& f, const FrameSize& z, const KArgs& a, bool
   l.guard = a.guard;
   l.scanline_rows = (f.p->flags & ZRT_FLAG_SCANLINES) ? f.p->height : 0u;
   l.n_waves = K.profile ? z.grid * (kBlock / 64) : 0u;
+  l.sky_tiles = n_sky;
   c->last = l;
   if (f.run_pass) {
     c->run.done = f.pass.samples_after;
@@ -730,9 +814,10 @@ int launch_frame(zrt_ctx* c, const zrt_camera* cam, const zrt_params* p, float* 
     if (run_pass && !f.first) rotate_events(c);
     KArgs a = fill_args(c, f, z, env);
     const bool schedule = choose_order(c, f, z, env, a);
+    const uint32_t n_sky = split_sky(c, f, env, a);
     optional_outputs(c, f, z, env, schedule, a);
-    enqueue(c, f, z, a);
-    finish(c, f, z, a, schedule);
+    enqueue(c, f, z, env, a, n_sky);
+    finish(c, f, z, a, schedule, n_sky);
     return ZRT_OK;
   }
   ZRT_CATCH_ALL

@@ -164,6 +164,23 @@ struct Probe {
   uint32_t tile_ids_n = 0;
   OrderKey order_key{};
   bool order_valid = false;
+  uint64_t order_gen = 0;  // counts the probes that wrote tile_order (SkySplit::sorted_gen)
+};
+
+// ---- the all-sky tiles (tile_class.cpp): what the classifier keeps of the scene, and,
+// under the order cache's key, the last classified frame's classes and tile lists ----
+struct SkySplit {
+  SkyScene scene;
+  OrderKey key{};
+  bool valid = false;  // cls / the lists are `key`'s
+  uint32_t n_sky = 0;
+  std::vector<uint32_t> cls, sky_host, gen_host;  // per local tile; the sky / general tiles in tile order
+  DevBuf<uint32_t> cls_dev, sky_list, gen_list;
+  // the general tiles in the probe's cost order: Probe::tile_order without the sky tiles
+  // (compact_kernel), valid while sorted_gen == Probe::order_gen and sorted_valid
+  DevBuf<uint32_t> gen_sorted, count;
+  uint64_t sorted_gen = 0;
+  bool sorted_valid = false;
 };
 
 // The last launch, as the reporting calls read it: assigned as one value at its end.
@@ -177,6 +194,7 @@ struct LastLaunch {
   float guard = 0.0f;      // zrt_stats::guard
   uint32_t scanline_rows = 0;  // rows it counted (0: not flagged)
   uint32_t n_waves = 0;        // ZRT_PROFILE builds
+  uint32_t sky_tiles = 0;      // tiles the launch rendered in sky_kernel (zrt_ctx_debug_counters slot kSkyTilesSlot)
 };
 
 // ---- the accumulation run (zrt_ctx_accum_*): at most one per context ----
@@ -259,6 +277,7 @@ struct zrt_ctx {
   zrt::DevBuf<unsigned long long> wave_times;  // ZRT_PROFILE builds
   zrt::DevBuf<unsigned long long> scanlines;   // ZRT_FLAG_SCANLINES: [row][3] of the last launch
   zrt::Probe probe;
+  zrt::SkySplit sky;
   zrt::EvSet ev;           // the last launch's events
   zrt::Completion render;  // the last launch's completion
   zrt::LastLaunch last;

@@ -3,6 +3,8 @@
 // make no HIP runtime call, so a host sanitizer build links and drives them
 // (tools/sanitize).
 #include <cmath>
+#include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <string>
 
@@ -200,6 +202,38 @@ int zrt_debug_lean_kernel(const zrt_scene* scene, const zrt_camera* camera, cons
                              zrt::camera_inside(camera, h.root_c, h.origin_bound))
                 ? 1u
                 : 0u;
+    return ZRT_OK;
+  }
+  ZRT_CATCH_HOST
+}
+
+int zrt_debug_tile_classes(const zrt_scene* scene, const zrt_camera* camera, const zrt_params* params,
+                           uint32_t* classes, uint32_t cap, uint32_t* n_tiles, uint32_t* n_sky, double* margins) {
+  if (!camera || !n_tiles || !n_sky || (cap && !classes)) return fail(ZRT_E_INVALID, "null argument");
+  *n_tiles = *n_sky = 0;
+  int rc = zrt::validate_scene(scene);
+  if (rc) return rc;
+  rc = zrt::validate_params(params);
+  if (rc) return rc;
+  try {
+    const bool use_bvh = params->bounded_volume_hierarchy != 0 && scene->n_prims > 10;  // (zrt_ctx_create)
+    zrt::HostScene h;
+    zrt::flatten_scene(&h, scene, use_bvh, -1);
+    const zrt::LaunchPlan P = zrt::plan_launch(zrt::shape_of(h), params);
+    std::vector<uint32_t> cls(zrt::rank_tiles(zrt::geometry(params), params->rank, params->world_size), zrt::kTileGeneral);
+    if (margins) margins[0] = margins[1] = margins[2] = margins[3] = 0.0;
+    // (as zrt_ctx_render_tiles decides)
+    if (zrt::sky_tiles_wanted() &&
+        zrt::sky_split_allowed(P, params, zrt::camera_inside(camera, h.root_c, h.origin_bound))) {
+      zrt::SkyScene sky;
+      zrt::build_sky_scene(&sky, h);
+      const double t0 = zrt::now_ms();
+      zrt::classify_tiles(sky, camera, params, &cls, n_sky, margins);
+      if (std::getenv("ZRT_DEBUG_LAUNCH"))
+        std::fprintf(stderr, "zrt tile classes: %u of %zu tiles sky in %.2f ms\n", *n_sky, cls.size(), zrt::now_ms() - t0);
+    }
+    *n_tiles = uint32_t(cls.size());
+    for (uint32_t i = 0; i < cap && i < cls.size(); ++i) classes[i] = cls[i];
     return ZRT_OK;
   }
   ZRT_CATCH_HOST

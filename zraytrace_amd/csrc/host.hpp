@@ -138,6 +138,35 @@ int plan_denoise(const zrt_params* p, const zrt_denoise* dn, DenoiseLaunch* out)
 int plan_reproject(const zrt_camera* prev, const zrt_params* p, zrt_reproject_plan* out);
 int plan_temporal(const zrt_params* p, const zrt_temporal* tp, TemporalLaunch* out);
 
+// ---- tile_class.cpp: the all-sky tiles of a frame (DESIGN.md §3 "All-sky tiles") ----
+// A tile's class word: bit 31 (kTileFrozen's bit, so compact_kernel drops such tiles
+// from a tile order) marks a tile no primary ray of which can hit anything; the low
+// bits are free for later classes.
+constexpr uint32_t kTileGeneral = 0u, kTileSky = kTileFrozen;
+struct SkyNode {  // a reference-tree node: its box's bounding sphere and its children (KArgs::nodes refs)
+  double c[3], r;
+  int32_t left, right;
+};
+struct SkyPrim {  // a primitive slot's bounding sphere; sphere_index >= 0: a sphere (r: its radius)
+  double c[3], r;
+  int32_t sphere_index;
+};
+// What the classifier keeps of a flattened scene (a context keeps it past the upload).
+struct SkyScene {
+  bool ok = false;  // false: every tile is general (no tree, a non-finite plane, a tree too large to keep)
+  bool has_tri = false;
+  std::vector<SkyNode> nodes;
+  std::vector<SkyPrim> prims;
+  std::vector<uint32_t> spheres;  // the slots that hold spheres
+  double k_ao = 0, k_c = 0;       // the triangles' reach k_ao |ao| + k_c (tools/tri_reach_bound.py, doubled)
+  double tri_c[3] = {0, 0, 0}, tri_r = 0;  // the triangles' bounding sphere
+};
+bool sky_tiles_wanted();  // ZRT_SKY_TILES (default on)
+bool sky_split_allowed(const LaunchPlan& P, const zrt_params* p, bool cam_inside);
+void build_sky_scene(SkyScene* s, const HostScene& h);
+void classify_tiles(const SkyScene& s, const zrt_camera* cam, const zrt_params* p, std::vector<uint32_t>* cls,
+                    uint32_t* n_sky, double* margins = nullptr);
+
 // ---- flatten.cpp ----
 // `device` >= 0: the GPU that may build the reference BVH (bvh_gpu.hip); a failed
 // device build falls back to the host's and sets c->device_bvh_failed

@@ -145,6 +145,9 @@ constexpr int kVNodeTrips = 32, kVNodeLines = 33, kSNodeTrips = 34, kRbTrips = 3
               kVPrimLines = 37, kSPrimTrips = 38, kVShadeTrips = 39, kAttWTrips = 40, kAttRTrips = 41,
               kVNodeCost = 42, kVPrimCost = 43;
 
+// zrt_ctx_debug_counters: the tiles the last launch rendered in sky_kernel (filled in on the host)
+constexpr int kSkyTilesSlot = 47;
+
 constexpr int kBlock = 256;
 // accumulate_kernel / resolve_kernel's metrics: kMetricShards shards, kMetricStride words apart (render.hip)
 constexpr uint32_t kMetricShards = 64, kMetricStride = 16, kMetricWords = kMetricShards * kMetricStride;
@@ -174,6 +177,7 @@ const KernelConfig& kernel_config();
 // stats, stack width, lean>; the others by traversal mode (8: FAST over compressed nodes).
 void* select_kernel(int kmode, uint32_t prng, bool stats, bool stk16, bool lean);
 void* probe_kernel(uint32_t prng, bool stk16);
+void* sky_kernel_ptr(uint32_t prng, bool stats);  // the all-sky tiles' kernel (tile_class.cpp proves them)
 void* trace_kernel_ptr(int mode, bool stk16);
 void* features_kernel_ptr(int mode, bool stk16);
 

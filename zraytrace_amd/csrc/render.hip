@@ -3652,6 +3652,52 @@ __global__ void __launch_bounds__(kBlock, ZRT_WAVES_WIDE) schedule_probe_kernel(
   render_loop<3, PRNG, false, StackT, true>(a);
 }
 
+// The sky kernel: the tiles the host proved all sky (tile_class.cpp: no primary ray
+// of the tile can hit anything), with no traversal.  Every sample of such a tile is
+// one camera ray that ends in the background, so what is left of render_loop's
+// sample is its seed, its two draws, Camera.getRay's unit(), background(d) and the
+// add - the same expressions in the same order, so the chunk sums are the render
+// loop's bit for bit (att_product over zero rows returns L itself).  One wave per
+// unit (tile x chunk) of a.tile_order (the sky list), lane p = pixel p, units dealt
+// round-robin; the sums go to the same partial[chunk][slot], the samples to
+// kBackground (STATS: and to kRays).  No LDS, no scene arrays.
+template <int PRNG, bool STATS>
+__global__ void __launch_bounds__(kBlock) sky_kernel(const KArgs a) {
+  const uint32_t lane = __lane_id();
+  const uint32_t n_waves = gridDim.x * (kBlock / 64);
+  const V3 llc = mk(a.llc[0], a.llc[1], a.llc[2]);
+  const V3 hor = mk(a.hor[0], a.hor[1], a.hor[2]);
+  const V3 ver = mk(a.ver[0], a.ver[1], a.ver[2]);
+  const V3 o = mk(a.org[0], a.org[1], a.org[2]);
+  uint32_t c_bg = 0;
+  for (uint32_t u = blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6); u < a.total_work; u += n_waves) {
+    const uint32_t ord = u / a.n_chunks, g = u - ord * a.n_chunks;
+    const uint32_t lt = a.tile_order[ord];
+    const uint32_t t = lt * a.world + a.rank;
+    const uint32_t px = (t % a.tiles_x) * 8u + (lane & 7u), py = (t / a.tiles_x) * 8u + (lane >> 3);
+    const uint32_t first = g * a.chunk, end = min(first + a.chunk, a.spp);
+    float acc_r = 0.0f, acc_g = 0.0f, acc_b = 0.0f;
+    if (px < a.xbound && py < a.height) {  // off-frame lanes stay idle (finalize writes black)
+      const uint64_t offset = (uint64_t)py * a.width + px;
+      for (uint32_t sample = first; sample < end; ++sample) {
+        Rng<PRNG> rng;
+        rng.init(((offset << 16) | (uint64_t)sample) + a.seed_mix);
+        const float su = dev::div_known((float)px + rand_float(rng) - 0.5f, a.f_width, a.inv_width);
+        const float sv = dev::div_known((float)py + rand_float(rng) - 0.5f, a.f_height, a.inv_height);
+        const V3 d = unit(sub(add(add(llc, scale(hor, su)), scale(ver, sv)), o));
+        const V3 L = background(d);
+        acc_r += L.x;
+        acc_g += L.y;
+        acc_b += L.z;
+      }
+      c_bg += end - first;
+    }
+    a.partial[g * a.n_slots + lt * 64u + lane] = make_float4(acc_r, acc_g, acc_b, 0.0f);
+  }
+  wave_add_u64(&a.counters[kBackground], c_bg);
+  if (STATS) wave_add_u64(&a.counters[kRays], c_bg);
+}
+
 // The closest hit of one ray whose direction Ray.init has normalised: the
 // top-level query of rayColor (raytrace.zig:71-81, t_min 0.001, t_max shrinking)
 // through the same traversal code as the render loop.  best < 0: a miss.
@@ -4259,6 +4305,17 @@ void* select_kernel(int mode, uint32_t prng, bool stats, bool stk16, bool lean) 
 void* probe_kernel(uint32_t prng, bool stk16) {
   return prng == ZRT_PRNG_XOSHIRO256 ? ZRT_STK(schedule_probe_kernel, ZRT_PRNG_XOSHIRO256)
                                      : ZRT_STK(schedule_probe_kernel, ZRT_PRNG_XOROSHIRO128);
+}
+void* sky_kernel_ptr(uint32_t prng, bool stats) {
+#ifdef ZRT_ISA_KERNEL
+  return nullptr;
+#else
+  if (prng == ZRT_PRNG_XOSHIRO256)
+    return stats ? reinterpret_cast<void*>(&sky_kernel<ZRT_PRNG_XOSHIRO256, true>)
+                 : reinterpret_cast<void*>(&sky_kernel<ZRT_PRNG_XOSHIRO256, false>);
+  return stats ? reinterpret_cast<void*>(&sky_kernel<ZRT_PRNG_XOROSHIRO128, true>)
+               : reinterpret_cast<void*>(&sky_kernel<ZRT_PRNG_XOROSHIRO128, false>);
+#endif
 }
 hipError_t sort_tiles(void* temp, size_t* temp_bytes, const uint32_t* cost, uint32_t* cost_sorted, const uint32_t* ids,
                       uint32_t* order, uint32_t n, hipStream_t st) {
