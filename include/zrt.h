@@ -944,6 +944,56 @@ int zrt_render_temporal(const zrt_scene* scene, const zrt_camera* cameras, uint3
                         const zrt_params* params, const zrt_temporal* tp, const zrt_denoise* dn, uint32_t dn_flags,
                         zrt_frame_fn on_frame, void* user, float* out_rgb, zrt_stats* stats);
 
+/* ---- ray queries: closest hit and any hit on a resident context -------------- *
+ * zrt_trace builds the BVH, uploads and tears down for every batch.  These calls
+ * ask the scene a zrt_ctx already holds: device pointers, a stream (NULL: the
+ * context's own), asynchronous as zrt_ctx_features.  params supplies traversal,
+ * device and bounded_volume_hierarchy, which must fit the context (ZRT_E_INVALID
+ * otherwise); every traversal and the surface list (no BVH) are served.  Rays are
+ * n x {origin xyz, direction xyz}; Ray.init normalises the direction
+ * (ray.zig:11-13).  n == 0: ZRT_OK, nothing is enqueued.  A null or misaligned
+ * (4-byte) pointer: ZRT_E_INVALID.  A query has deep stack rows, an error flag and a
+ * completion of its own, so it disturbs neither a render or accumulation run nor a
+ * feature launch on the same context; one query is in flight per context.  A
+ * traversal stack overflow is reported by zrt_ctx_sync, or by the next call that
+ * looks at the context's launches, as ZRT_E_UNSUPPORTED (once); the outputs of
+ * that launch are overwritten: t = NaN, prim = -1, every occlusion byte = 0xFF.
+ *
+ * "Occluded" is what the reference's own code returns: the top-level surface loop
+ * of rayColor (raytrace.zig:71-81) started with t_min = 0.001 and t_max = the
+ * caller's value instead of +inf, as closest_hit != null.  Over the list: some
+ * primitive's hit(ray, 0.001, t_max) is non-null; the bounds are strict (t < t_max,
+ * sphere.zig:43/57, triangle.zig:62).  Under the BVH it is BVHNode.hit(ray, 0.001,
+ * t_max) (bvh.zig:187-205): until the first hit t_max never shrinks and after it
+ * the answer is "yes", so it equals: some leaf whose box, and all of whose
+ * ancestors' boxes, pass hitAabb(ray, 0.001, t_max) (aabb.zig:109-127, each axis on
+ * its own) holds a primitive that hits in (0.001, t_max).  That is neither "some
+ * primitive is hit below t_max" nor "the closest hit lies below t_max": a rounded
+ * hit can lie outside its own leaf's box, and a finite t_max clips slabs the
+ * infinite one lets through (DESIGN.md section 5 "Ray queries").  Every traversal
+ * returns this answer; FAST walks the full 128-B wide nodes (any-hit has no flavour
+ * over the compressed ones) with the grazing-triangle guard on, as zrt_trace.  A
+ * t_max that is NaN or <= 0.001 gives 0. */
+
+/* Closest hit of n rays on a resident context: zrt_trace's query, with device pointers,
+ * on a stream, asynchronous.  dev_rays: n x {origin xyz, direction xyz}; dev_t: n f32
+ * (+inf on a miss); dev_prim: n i32, index into scene->prims (-1 on a miss), mapped on the device. */
+int zrt_ctx_trace(zrt_ctx* ctx, const zrt_params* params, const float* dev_rays, uint32_t n,
+                  float* dev_t, int32_t* dev_prim, void* hip_stream);
+
+/* Any hit in (0.001, t_max): what rayColor's surface loop (raytrace.zig:71-81) returns when started
+ * with t_max instead of +inf, as != null.  dev_t_max: n f32, or NULL = +inf for every ray.
+ * dev_out: n bytes, 1 occluded / 0 not. */
+int zrt_ctx_occluded(zrt_ctx* ctx, const zrt_params* params, const float* dev_rays, const float* dev_t_max,
+                     uint32_t n, uint8_t* dev_out, void* hip_stream);
+
+/* One-shot, host pointers, like zrt_trace. */
+int zrt_occluded(const zrt_scene* scene, const zrt_params* params, const float* rays, const float* t_max,
+                 uint32_t n, uint8_t* out);
+
+/* ms between the events around the last query launch of the context (as zrt_ctx_denoise_ms). */
+int zrt_ctx_query_ms(zrt_ctx* ctx, double* ms);
+
 /* ---- host-side scene ingestion (the caller side of the seam) ------------- *
  * Restatement of scenes.zig / obj_reader.zig / png_image.zig texture loading
  * so tests and bench can build the reference's scenes without Zig.  Assets are

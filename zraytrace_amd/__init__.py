@@ -445,6 +445,24 @@ def trace(scene, params: RenderParams, origins, directions):
     return t, prim
 
 
+def occluded(scene, params: RenderParams, origins, directions, t_max=None):
+    """Any hit of each ray in (0.001, t_max) (zrt_occluded; the definition: zrt.h "ray queries"):
+    bool[n].  t_max: float32[n], or None = +inf for every ray."""
+    view = scene.view if isinstance(scene, LoadedScene) else scene
+    rays = np.ascontiguousarray(np.concatenate([np.asarray(origins, np.float32).reshape(-1, 3),
+                                                np.asarray(directions, np.float32).reshape(-1, 3)], axis=1))
+    n = rays.shape[0]
+    out = np.zeros(n, np.uint8)
+    tm = None
+    if t_max is not None:
+        tm = np.ascontiguousarray(np.broadcast_to(np.asarray(t_max, np.float32), (n,)))
+    p = params.abi()
+    check(lib().zrt_occluded(view, C.byref(p), rays.ctypes.data_as(C.POINTER(C.c_float)),
+                             tm.ctypes.data_as(C.POINTER(C.c_float)) if tm is not None else None, n,
+                             out.ctypes.data_as(C.POINTER(C.c_uint8))))
+    return out != 0
+
+
 class RenderContext:
     """Device-resident scene (zrt_ctx_*): build + upload once, render many."""
 
@@ -516,6 +534,27 @@ class RenderContext:
         p = params.abi()
         check(lib().zrt_ctx_features(self._h, C.byref(camera), C.byref(p), C.c_void_p(dev_ptr),
                                      C.c_void_p(stream or None)))
+
+    def trace(self, params: RenderParams, dev_rays: int, n: int, dev_t: int, dev_prim: int, stream: int = 0):
+        """Closest hit of n rays on the resident scene (zrt_ctx_trace; device pointers,
+        asynchronous): rays n x {origin, direction} f32, t f32[n] (+inf on a miss), prim
+        int32[n] (the index in the scene's list, -1 on a miss)."""
+        p = params.abi()
+        check(lib().zrt_ctx_trace(self._h, C.byref(p), C.c_void_p(dev_rays or None), n, C.c_void_p(dev_t or None),
+                                  C.c_void_p(dev_prim or None), C.c_void_p(stream or None)))
+
+    def occluded(self, params: RenderParams, dev_rays: int, dev_t_max: int, n: int, dev_out: int, stream: int = 0):
+        """Any hit of n rays in (0.001, t_max) (zrt_ctx_occluded; device pointers, asynchronous):
+        dev_t_max f32[n] or 0 = +inf for every ray; dev_out n bytes, 1 occluded / 0 not."""
+        p = params.abi()
+        check(lib().zrt_ctx_occluded(self._h, C.byref(p), C.c_void_p(dev_rays or None), C.c_void_p(dev_t_max or None),
+                                     n, C.c_void_p(dev_out or None), C.c_void_p(stream or None)))
+
+    def query_ms(self) -> float:
+        """Device time of the last trace() / occluded() kernel in ms (zrt_ctx_query_ms; waits for it)."""
+        ms = C.c_double()
+        check(lib().zrt_ctx_query_ms(self._h, C.byref(ms)))
+        return ms.value
 
     def denoise(self, params: RenderParams, dn: _ffi.Denoise, dev_frame: int, dev_features: int, dev_out: int,
                 stream: int = 0):

@@ -282,6 +282,11 @@ SIGNATURES = [
     ("zrt_render_temporal", C.c_int, [C.POINTER(Scene), C.POINTER(Camera), C.c_uint32, C.POINTER(Params),
                                       C.POINTER(Temporal), C.POINTER(Denoise), C.c_uint32, FRAME_FN, _P,
                                       C.POINTER(C.c_float), C.POINTER(Stats)]),
+    ("zrt_ctx_trace", C.c_int, [_P, C.POINTER(Params), _P, C.c_uint32, _P, _P, _P]),
+    ("zrt_ctx_occluded", C.c_int, [_P, C.POINTER(Params), _P, _P, C.c_uint32, _P, _P]),
+    ("zrt_occluded", C.c_int, [C.POINTER(Scene), C.POINTER(Params), C.POINTER(C.c_float), C.POINTER(C.c_float),
+                               C.c_uint32, C.POINTER(C.c_uint8)]),
+    ("zrt_ctx_query_ms", C.c_int, [_P, C.POINTER(C.c_double)]),
     ("zrt_scene_load", C.c_int, [C.c_uint32, C.c_char_p, C.POINTER(_P), C.POINTER(Camera)]),
     ("zrt_scene_view", C.POINTER(Scene), [_P]),
     ("zrt_scene_free", None, [_P]),

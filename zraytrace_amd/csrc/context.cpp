@@ -142,11 +142,11 @@ static void fill_lds(KArgs& a, const LdsPlan& lp) {
 // The launch of zrt_trace and zrt_ctx_features: one lane per ray over the loop's own
 // traversal (FAST: over the compressed nodes where the context built them, MODE 8),
 // with the grazing-triangle guard, any ray origin and no attenuation rows.
-TracePlan fill_trace(KArgs& a, const zrt_ctx* c, uint32_t traversal) {
+TracePlan fill_trace(KArgs& a, const zrt_ctx* c, uint32_t traversal, bool full_nodes) {
   const Scene& s = c->scene;
   const int mode = !s.shape.use_bvh ? 0 : traversal == ZRT_TRAVERSAL_REFERENCE ? 2 : traversal == ZRT_TRAVERSAL_BINARY ? 1 : 3;
   const uint32_t stack_depth = mode == 3 ? std::max(s.shape.wide_stack, s.shape.stack_depth) : s.shape.stack_depth;
-  const bool qn = mode == 3 && s.shape.q_ok;
+  const bool qn = mode == 3 && s.shape.q_ok && !full_nodes;
   TracePlan t;
   t.kmode = qn ? 8 : mode;
   t.stk16 = mode == 3 ? fast_stk16(s.shape.n_wide, s.shape.n_nodes) : s.shape.n_nodes < 65536;
@@ -157,6 +157,11 @@ TracePlan fill_trace(KArgs& a, const zrt_ctx* c, uint32_t traversal) {
   a.check_origins = 1;
   a.guard = s.shape.guard;
   return t;
+}
+const uint32_t* slot_prim_table(zrt_ctx* c) {
+  Scene& s = c->scene;
+  if (s.slot_prim.n < s.slot_to_prim.size() || s.slot_prim.p == nullptr) s.slot_prim.upload(s.slot_to_prim);
+  return s.slot_prim.p;
 }
 // Its deep stack rows in `ovf`, grown once `st` has drained (an earlier launch may
 // still use the old rows), and the bounds the STATS check would read.
@@ -281,11 +286,12 @@ static int completion_status(Completion& k, bool wait, bool once) {
   k.reported = true;
   return fail(ZRT_E_UNSUPPORTED, device_error_msg(*k.err));
 }
-// The device errors of the context's launches: a feature launch's first, reported
-// once; then the last render launch's - every waiting call reports it,
-// render_tiles' sticky check (wait false) only until some call has.
+// The device errors of the context's launches: a feature launch's first, then a ray
+// query's, each reported once; then the last render launch's - every waiting call
+// reports it, render_tiles' sticky check (wait false) only until some call has.
 int launch_status(zrt_ctx* c, bool wait) {
-  const int rc = completion_status(c->feat.done, wait, true);
+  int rc = completion_status(c->feat.done, wait, true);
+  if (!rc) rc = completion_status(c->query.done, wait, true);
   return rc ? rc : completion_status(c->render, wait, false);
 }
 

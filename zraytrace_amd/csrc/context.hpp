@@ -1,5 +1,5 @@
 // context.hpp - private to the host files that talk to the HIP runtime
-// (context.cpp, runs.cpp, post.cpp, debug_device.cpp, multi.cpp, oneshot.cpp): the
+// (context.cpp, runs.cpp, post.cpp, queries.cpp, debug_device.cpp, multi.cpp, oneshot.cpp): the
 // HIP error type, the owning handles, the context behind zrt_ctx_*, what those
 // files share of its launch path, and the catch clauses of their entry points.
 #pragma once
@@ -128,6 +128,7 @@ struct Scene {
   SceneShape shape;  // its counts and depths: what the launch decision reads of the scene (plan_launch)
   uint32_t n_prims = 0, bvh_depth = 0, wide_stride = 0;
   std::vector<uint32_t> slot_to_prim;  // device primitive slot -> reference list index
+  DevBuf<uint32_t> slot_prim;          // ... on the device, uploaded on first use (slot_prim_table)
   DevBuf<float4> wnodes;
   DevBuf<float4> qnodes, qleaves;  // compressed wide nodes + leaf records (q_ok)
   uint32_t q_stride = 0, n_qleaves = 0;
@@ -254,12 +255,20 @@ struct VariancePlan {
   DevBuf<float2> dev;
   std::vector<float2> host;
 };
-// ---- first-hit feature buffers (zrt_ctx_features): the launch's own deep stack rows,
-// the slot -> primitive table, and its device error status ----
+// ---- first-hit feature buffers (zrt_ctx_features): the launch's own deep stack rows
+// and its device error status ----
 struct FeatureState {
   DevBuf<uint8_t> ovf;
-  DevBuf<uint32_t> slot_prim;
   Completion done;
+};
+// ---- ray queries (zrt_ctx_trace / zrt_ctx_occluded, queries.cpp): the launch's own deep
+// stack rows, an error flag of its own (a query neither reads nor sets the flag a render
+// run keeps in scratch), its completion and the events around its kernel ----
+struct QueryState {
+  DevBuf<uint8_t> ovf;
+  DevBuf<unsigned long long> err;
+  Completion done;
+  StepTimer timer;
 };
 }  // namespace zrt
 
@@ -287,6 +296,7 @@ struct zrt_ctx {
   zrt::TemporalState ta;
   zrt::VariancePlan var;
   zrt::FeatureState feat;
+  zrt::QueryState query;
 };
 
 namespace zrt {
@@ -319,13 +329,16 @@ inline void copy3(float dst[3], const zrt_vec3& v) {
   dst[1] = v.y;
   dst[2] = v.z;
 }
-// The launch of zrt_trace and zrt_ctx_features (context.cpp).
+// The launch of zrt_trace, zrt_ctx_features and the ray queries (context.cpp).
 struct TracePlan {
   int kmode = 0;
   bool stk16 = false;
   LdsPlan lp;
 };
-TracePlan fill_trace(KArgs& a, const zrt_ctx* c, uint32_t traversal);
+// full_nodes: FAST over the full wide nodes even where the context holds compressed ones (any-hit)
+TracePlan fill_trace(KArgs& a, const zrt_ctx* c, uint32_t traversal, bool full_nodes = false);
+// The device copy of Scene::slot_to_prim, uploaded on first use (features, queries).
+const uint32_t* slot_prim_table(zrt_ctx* c);
 void trace_rows(KArgs& a, const zrt_ctx* c, const TracePlan& t, uint64_t n_lanes, DevBuf<uint8_t>& ovf, hipStream_t st,
                 const char* launch);
 }  // namespace zrt

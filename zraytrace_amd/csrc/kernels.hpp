@@ -180,6 +180,9 @@ void* probe_kernel(uint32_t prng, bool stk16);
 void* sky_kernel_ptr(uint32_t prng, bool stats);  // the all-sky tiles' kernel (tile_class.cpp proves them)
 void* trace_kernel_ptr(int mode, bool stk16);
 void* features_kernel_ptr(int mode, bool stk16);
+// anyhit_kernel<mode, stack width> (zrt_ctx_occluded): 0 list, 1 BINARY, 2 REFERENCE, 3 FAST over the
+// full 128-B wide nodes - any-hit has no flavour over the compressed nodes
+void* anyhit_kernel_ptr(int mode, bool stk16);
 
 // One launch function per small kernel (the arguments are the kernel's, render.hip).
 hipError_t launch_finalize(hipStream_t st, const float4* partial, float* out, uint32_t n_slots, uint32_t n_chunks,
@@ -206,6 +209,11 @@ hipError_t launch_assemble_plane(hipStream_t st, const float* gathered, float* f
                                  uint32_t world, uint32_t tiles_x, uint32_t xbound, uint32_t height, uint32_t width,
                                  uint32_t total, uint32_t stride_px, uint32_t n_tiles);
 hipError_t launch_features_error(hipStream_t st, float4* out, uint64_t n_f4, const unsigned long long* error_flag);
+// zrt_ctx_trace's end: slot -> list index, or NaN / -1 behind a launch that set *error_flag
+hipError_t launch_trace_finish(hipStream_t st, float* t, int32_t* prim, uint32_t n, const uint32_t* slot_prim,
+                               const unsigned long long* error_flag);
+// zrt_ctx_occluded's: 0xFF in every byte behind a launch that set *error_flag
+hipError_t launch_anyhit_error(hipStream_t st, uint8_t* out, uint32_t n, const unsigned long long* error_flag);
 hipError_t launch_debug_math(int fn, const float* x, const float* y, float* out, uint32_t n);
 hipError_t launch_debug_division(uint64_t n, unsigned long long* counts);
 hipError_t launch_debug_rng(uint32_t prng, uint64_t key, unsigned long long* out, uint32_t n);

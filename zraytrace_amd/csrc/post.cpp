@@ -23,8 +23,7 @@ int zrt_ctx_features(zrt_ctx* c, const zrt_camera* cam, const zrt_params* p, flo
     const uint32_t tiles = ((p->width + 7u) / 8u) * ((p->height + 7u) / 8u);
     const uint32_t grid = (tiles + zrt::kBlock / 64 - 1) / (zrt::kBlock / 64);
     const uint64_t n_lanes = uint64_t(grid) * zrt::kBlock;
-    if (f.slot_prim.n < c->scene.slot_to_prim.size() || f.slot_prim.p == nullptr)
-      f.slot_prim.upload(c->scene.slot_to_prim);
+    const uint32_t* sp = zrt::slot_prim_table(c);
     f.done.create();
     // the context's error flag: what a render launch left there stays (a run's flag is
     // sticky); before the first launch the slots hold nothing yet
@@ -35,7 +34,6 @@ int zrt_ctx_features(zrt_ctx* c, const zrt_camera* cam, const zrt_params* p, flo
     zrt::fill_camera(a, cam, p);
     zrt::trace_rows(a, c, t, n_lanes, f.ovf, st, "feature launch");
     void* fn = zrt::features_kernel_ptr(t.kmode, t.stk16);
-    const uint32_t* sp = f.slot_prim.p;
     float4* out = reinterpret_cast<float4*>(dev_features);
     void* args[] = {&a, &sp, &out};
     HIPCHK(hipLaunchKernel(fn, dim3(grid), dim3(zrt::kBlock), args, t.lp.bytes, st));

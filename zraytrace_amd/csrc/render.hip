@@ -3757,6 +3757,228 @@ __global__ void __launch_bounds__(kBlock) trace_kernel(const KArgs a, const floa
   out_slot[gl] = best;
 }
 
+// The end of a resident closest-hit query (zrt_ctx_trace) behind trace_kernel: the
+// device slot mapped to the index in the reference's list (slot_prim), or, after a
+// launch that set its error flag (a traversal stack overflow), t = NaN and prim = -1.
+__global__ void trace_finish_kernel(float* __restrict__ t, int32_t* __restrict__ prim, uint32_t n,
+                                    const uint32_t* __restrict__ slot_prim,
+                                    const unsigned long long* __restrict__ error_flag) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  if (*error_flag != 0ull) {
+    t[i] = __builtin_nanf("");
+    prim[i] = -1;
+    return;
+  }
+  const int32_t s = prim[i];
+  prim[i] = s < 0 ? -1 : (int32_t)slot_prim[s];
+}
+
+// ---------------------------------------------------------------------------
+// Any-hit (zrt_ctx_occluded; DESIGN.md §5 "Ray queries"): is some primitive hit
+// in (0.001, t_max) as rayColor's surface loop (raytrace.zig:71-81) started with
+// t_max would find it.  Under the BVH (bvh.zig:187-205 with a t_max that never
+// shrinks before the answer is "yes") that is: a primitive whose own leaf, and
+// every ancestor of it, passes hitAabb(ray, 0.001, t_max) and whose hit test
+// passes with the strict bounds t_min < t < t_max.
+// ---------------------------------------------------------------------------
+// One primitive against the fixed interval: the reference's own tests
+// (sphere.zig:43/57, triangle.zig:62), nothing shrinking.
+__device__ __forceinline__ bool prim_in_range(const float4* __restrict__ prims, int ref, const RayT& r, float t_max) {
+  float t = t_max;
+  int b = -1;
+  uint32_t c_tri = 0, c_sph = 0;
+  prim_test<false, false>(prims, ref, r, t, b, c_tri, c_sph);
+  return b >= 0;
+}
+
+// The literal traversal: reference_replay started at t_max, leaving at the first
+// hit.  Every box goes through the reference's loose test against the fixed t_max,
+// left first.  narrow: boxes the ray does not cross are culled too (the narrowed
+// test with the grazing slack and the guard; never a box holding a sphere) - they
+// hold no hit, so the answer is the same; false: the reference's
+// test alone.  Stack rows as the replay's: a.lds_rows in LDS, the rest in stack_ovf.
+template <class StackT>
+__device__ __forceinline__ bool anyhit_literal(const KArgs& a, const RayT& r, StackT* __restrict__ stk, uint32_t gl,
+                                            float t_max, bool narrow) {
+  const uint32_t rows = a.lds_rows, cap = a.ref_stack;
+  StackT* __restrict__ ovf = reinterpret_cast<StackT*>(a.stack_ovf) + gl;
+  const float slack = ray_slack(r, a.scene_extent, ray_m(r));
+  const float gw = ZRT_GUARD && r.gk > 0.0f ? guard_grow(a, r) : 0.0f;
+  stk[0] = 0;
+  uint32_t sp = 1;
+  while (sp > 0) {
+    --sp;
+    const int idx = sp < rows ? (int)stk[sp * kBlock] : (int)ovf[(size_t)(sp - rows) * a.n_lanes];
+    const float4 lo = a.nodes[2 * idx], hi = a.nodes[2 * idx + 1];
+    float e;
+    if (!box_test<true>(lo, hi, r, t_max, &e, slack, narrow && a.ref_sph[idx] == 0, gw)) continue;
+    const int left = as_int(lo.w), right = as_int(hi.w);
+    if (left < 0) {
+      if (prim_in_range(a.prims, left, r, t_max)) return true;
+      if (right != left && prim_in_range(a.prims, right, r, t_max)) return true;
+    } else if (sp + 2 <= cap) {
+      const StackT v[2] = {(StackT)right, (StackT)left};
+#pragma unroll
+      for (uint32_t j = 0; j < 2; ++j) {
+        if (sp + j < rows) stk[(sp + j) * kBlock] = v[j];
+        else ovf[(size_t)(sp + j - rows) * a.n_lanes] = v[j];
+      }
+      sp += 2;
+    } else {
+      atomicOr(a.error_flag, kErrOverflow);
+    }
+  }
+  return false;
+}
+
+// The acceptance rule: a primitive hit in (0.001, t_max) found by a traversal that
+// culls against t_max * kOpen counts only if its own reference leaf passes the
+// reference's loose test at exactly t_max.  The leaf's ancestors need no test: the
+// loose test is monotone under box containment, also with the min(t1, t_max) clamp.
+// A flat leaf fails it, as the reference never opens one.
+__device__ __forceinline__ bool leaf_accepts(const float4 lo, const float4 hi, const RayT& r, float t_max) {
+  float e;
+  return box_test<false>(lo, hi, r, t_max, &e);
+}
+
+// BINARY: near-first over the reference nodes, every box through binary_test against
+// the fixed t_max * kOpen + slack with the guard on; a leaf's candidates count when
+// the leaf accepts.  A popped node's box passed that same test when it was pushed.
+template <class StackT>
+__device__ __forceinline__ bool anyhit_binary(const KArgs& a, const RayT& r, StackT* __restrict__ stk, uint32_t gl,
+                                              float t_max) {
+  if (!ray_origin_ok(a, r)) return anyhit_literal<StackT>(a, r, stk, gl, t_max, false);
+  const float slack = ray_slack(r, a.scene_extent, ray_m(r));
+  const float gw = ZRT_GUARD && r.gk > 0.0f ? guard_grow(a, r) : 0.0f;
+  const float tb = t_max * kOpen + slack;
+  const uint32_t cap = a.stack_depth;
+  uint32_t sp = 0;
+  float e;
+  float4 lo = a.nodes[0], hi = a.nodes[1];
+  if (!binary_test(a, 0, lo, hi, r, tb, &e, slack, gw)) return false;
+  for (;;) {
+    const int left = as_int(lo.w), right = as_int(hi.w);
+    if (left < 0) {
+      if ((prim_in_range(a.prims, left, r, t_max) || (right != left && prim_in_range(a.prims, right, r, t_max))) &&
+          leaf_accepts(lo, hi, r, t_max))
+        return true;
+    } else {
+      const float4 l0 = a.nodes[2 * left], l1 = a.nodes[2 * left + 1];
+      const float4 r0 = a.nodes[2 * right], r1 = a.nodes[2 * right + 1];
+      float el, er;
+      const bool hl = binary_test(a, left, l0, l1, r, tb, &el, slack, gw);
+      const bool hr = binary_test(a, right, r0, r1, r, tb, &er, slack, gw);
+      if (hl && hr) {
+        const bool rfirst = er < el;
+        if (sp < cap) stk[(sp++) * kBlock] = (StackT)(rfirst ? left : right);
+        else atomicOr(a.error_flag, kErrOverflow);  // too deep for the stack: the subtree is dropped (flagged)
+        lo = rfirst ? r0 : l0;
+        hi = rfirst ? r1 : l1;
+        continue;
+      }
+      if (hl) { lo = l0; hi = l1; continue; }
+      if (hr) { lo = r0; hi = r1; continue; }
+    }
+    if (sp == 0) return false;
+    const int idx = stk[(--sp) * kBlock];
+    lo = a.nodes[2 * idx];
+    hi = a.nodes[2 * idx + 1];
+  }
+}
+
+// FAST, over the full 128-B wide nodes: wide_iter with the "best" held at the fixed
+// t_max - no near-tie tracking read, no order hazard, no replay of the closest hit.
+// After every node the lane looks at what the node's leaves left in (best_t, best):
+// a candidate whose reference leaf accepts is the answer.  A rejected candidate may
+// have hidden a later primitive of the same node behind its smaller t, so that ray
+// goes through the literal traversal (narrowed: it holds the same hits) - rare: the
+// near-miss spheres and the hazard scene's sphere are where it happens.  Rays whose
+// origin lies outside the bound, degenerate rays, and a t_max wide_iter's state
+// cannot carry (negative or NaN: the sign of best_t is its near-tie flag) take the
+// literal traversal alone.
+template <class StackT>
+__device__ __forceinline__ bool anyhit_wide(const KArgs& a, const RayT& r, StackT* __restrict__ stk,
+                                            const float4* __restrict__ lds_top, uint32_t gl, float t_max) {
+  const bool far = !ray_origin_ok(a, r) || ray_degenerate(r);
+  bool literal = far || !(t_max >= 0.0f);
+  if (!literal) {
+    const WideView v = wide_view(a, r, lds_top);
+    uint32_t sp = 0;
+    const float4* q = ZRT_LDS_TOP ? v.top : a.wnodes + v.base;
+    WideNode w;
+    const OctSigns os(r);
+    wide_load(q, os.sx, os.sy, os.sz, w);
+    uint32_t c_nodes = 0, c_leaves = 0, c_tri = 0, c_sph = 0;
+    Coh coh;
+    bool more = true;
+    while (more) {
+      float best_t = t_max;
+      int best = -1;
+      more = wide_iter<false, StackT, ZRT_SCALAR_NODES != 0, true, true, false>(a, r, v, stk, gl, w, q, sp, best_t, best,
+                                                                               c_nodes, c_leaves, c_tri, c_sph, coh);
+      if (best >= 0) {
+        const uint32_t leaf = a.leaf_of_slot[best];
+        if (leaf_accepts(a.nodes[2 * leaf], a.nodes[2 * leaf + 1], r, t_max)) return true;
+        literal = true;
+        break;
+      }
+    }
+  }
+  return literal ? anyhit_literal<StackT>(a, r, stk, gl, t_max, !far) : false;
+}
+
+// One ray per lane; a lane that has its answer stops traversing, the wave ends when
+// all have.  t_max: per ray, or null = +inf.  out: 1 occluded / 0 not.
+template <int MODE, class StackT>
+__global__ void __launch_bounds__(kBlock) anyhit_kernel(const KArgs a, const float* __restrict__ rays,
+                                                        const float* __restrict__ t_max_in, uint32_t n,
+                                                        uint8_t* __restrict__ out) {
+  extern __shared__ __attribute__((aligned(16))) char lds_raw[];
+  StackT* stk = reinterpret_cast<StackT*>(lds_raw) + threadIdx.x;
+  float4* lds_top = reinterpret_cast<float4*>(lds_raw + a.lds_top_off);
+  if (MODE == 3 && !layout_ok(a)) return;
+  if (MODE == 3 && ZRT_LDS_TOP) fill_lds_top(a, lds_top);
+  const uint32_t gl = blockIdx.x * kBlock + threadIdx.x;
+  if (gl >= n) return;
+  const float* q = rays + 6ull * gl;
+  const V3 d = unit(mk(q[3], q[4], q[5]));
+  const float t_max = t_max_in ? t_max_in[gl] : __builtin_inff();
+  RayT r;
+  r.ox = q[0]; r.oy = q[1]; r.oz = q[2];
+  r.dx = d.x; r.dy = d.y; r.dz = d.z;
+  r.rcp_det = a.tri_rcp_fast;
+  r.gm = a.graze_m;
+  r.gl = a.graze_leaf;
+  r.gk = a.guard;
+  inv_dir(d.x, d.y, d.z, r.ix, r.iy, r.iz);
+  bool hit = false;
+  if (MODE == 0) {
+    for (uint32_t i = 0; i < a.n_list && !hit; ++i) {  // surfaces in list order, leaving at the first hit
+      float t = t_max;
+      int b = -1;
+      if (__float_as_uint(a.shade[i].w) >> 31) tri_test<false>(a.prims, (int)i, r, t, b);
+      else sphere_test<false>(a.prims[3 * i], (int)i, r, t, b);
+      hit = b >= 0;
+    }
+  } else if (MODE == 3) {
+    hit = anyhit_wide<StackT>(a, r, stk, lds_top, gl, t_max);
+  } else if (MODE == 1) {
+    hit = anyhit_binary<StackT>(a, r, stk, gl, t_max);
+  } else {
+    hit = anyhit_literal<StackT>(a, r, stk, gl, t_max, false);
+  }
+  out[gl] = hit ? (uint8_t)1 : (uint8_t)0;
+}
+
+// An any-hit launch that set its error flag leaves 0xFF in every byte.
+__global__ void anyhit_error_kernel(uint8_t* __restrict__ out, uint32_t n,
+                                    const unsigned long long* __restrict__ error_flag) {
+  if (*error_flag == 0ull) return;
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) out[i] = (uint8_t)0xFF;
+}
+
 // First-hit feature buffers (zrt_ctx_features): one lane per pixel of the whole
 // frame, lanes in 8x8 tiles as the render loops take them.  The pixel-centre
 // primary ray (raytrace.zig:173-175 at r = 0.5: u = x / width, v = y / height;
@@ -4396,6 +4618,26 @@ hipError_t launch_debug_division(uint64_t n, unsigned long long* counts) {
 hipError_t launch_debug_rng(uint32_t prng, uint64_t key, unsigned long long* out, uint32_t n) {
   if (prng == ZRT_PRNG_XOSHIRO256) return launch(debug_rng_kernel<ZRT_PRNG_XOSHIRO256>, 1, 64, 0, key, out, n);
   return launch(debug_rng_kernel<ZRT_PRNG_XOROSHIRO128>, 1, 64, 0, key, out, n);
+}
+// The ray queries' kernels (queries.cpp), after every older one: they add to the end of the
+// code object.  anyhit_kernel by traversal mode; FAST (3) reads the full wide nodes only.
+void* anyhit_kernel_ptr(int mode, bool stk16) {
+#ifdef ZRT_ISA_KERNEL
+  (void)mode; (void)stk16;
+  return nullptr;
+#else
+#define ZRT_ANYHIT(M) (stk16 ? reinterpret_cast<void*>(&anyhit_kernel<M, uint16_t>) \
+                             : reinterpret_cast<void*>(&anyhit_kernel<M, uint32_t>))
+  return mode == 0 ? ZRT_ANYHIT(0) : mode == 1 ? ZRT_ANYHIT(1) : mode == 2 ? ZRT_ANYHIT(2) : ZRT_ANYHIT(3);
+#undef ZRT_ANYHIT
+#endif
+}
+hipError_t launch_trace_finish(hipStream_t st, float* t, int32_t* prim, uint32_t n, const uint32_t* slot_prim,
+                               const unsigned long long* error_flag) {
+  return launch(trace_finish_kernel, (n + 255) / 256, 256, st, t, prim, n, slot_prim, error_flag);
+}
+hipError_t launch_anyhit_error(hipStream_t st, uint8_t* out, uint32_t n, const unsigned long long* error_flag) {
+  return launch(anyhit_error_kernel, (n + 255) / 256, 256, st, out, n, error_flag);
 }
 
 const KernelConfig& kernel_config() {
