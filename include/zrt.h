@@ -994,6 +994,95 @@ int zrt_occluded(const zrt_scene* scene, const zrt_params* params, const float* 
 /* ms between the events around the last query launch of the context (as zrt_ctx_denoise_ms). */
 int zrt_ctx_query_ms(zrt_ctx* ctx, double* ms);
 
+/* ---- ambient occlusion: cosine rays from the first hits, exact any-hit ---------- *
+ * The reference has no lights, so ambient occlusion is the one visibility plane that
+ * is defined in its own terms: an AO ray is exactly the ray Lambertian.scatter shoots
+ * (material.zig:71-75) - origin HitRecord.location, direction normal +
+ * randomUnitVector, cosine-distributed by construction.  One fused kernel turns a
+ * feature buffer (zrt_ctx_features) into per-pixel counts of rays that got away; no ray
+ * is ever stored.  AO is a pure function of (features, camera, params, zrt_ao).
+ *
+ * All f32, nothing fused, IEEE `/`.  D is the set of pixels with x < height.  Per
+ * pixel p = (x, y), with N(p), t(p), id(p) from dev_features:
+ *   p outside D      clear = 0, ao = 0, on every call, with or without ZRT_AO_ACCUMULATE.
+ *   id(p) == 0       (a miss) no ray is shot, c = n_samples.
+ *   a lane of N(p) or t(p) is NaN   (the NaN buffer of a device error) clear =
+ *                    0xFFFFFFFF, ao = NaN; under ZRT_AO_ACCUMULATE a plane value of
+ *                    0xFFFFFFFF stays 0xFFFFFFFF (and ao NaN), on any pixel.
+ *   otherwise        the pixel-centre ray as zrt_ctx_features builds it: u = float(x) /
+ *                    float(width), v = float(y) / float(height), e = ((llc + H u) + W v)
+ *                    - o, dir = e / sqrtf((e.x e.x + e.y e.y) + e.z e.z); P = o + dir
+ *                    t(p) per component (ray.zig:14-16).  For s = first_sample ..
+ *                    first_sample + n_samples - 1: key = ((uint64(y) width + x) << 16 |
+ *                    s) + seed 0x9E3779B97F4A7C15 (the counter mode's key), rng =
+ *                    DefaultPrng.init(key) of params->prng, r = randomUnitVector(rng)
+ *                    (sample.zig:47-61, the first draws of the stream), d = N(p) + r
+ *                    (material.zig:73), the ray Ray.init(P, d), which normalises;
+ *                    "occluded" is zrt_ctx_occluded's definition for that ray at t_max
+ *                    = radius through params->traversal.  A d that normalises to NaN is
+ *                    not occluded.  c = the samples that are not occluded.
+ * Without ZRT_AO_ACCUMULATE clear(p) = c and ao(p) = float(c) / float(n_samples); with
+ * it clear(p) = clear(p) + c and ao(p) = float(clear(p)) / float(first_sample +
+ * n_samples): the caller's plane holds the counts of samples [0, first_sample).  Counts
+ * are integers, so calls over [0, 8) and [8, 16) equal one call over [0, 16).
+ *
+ * dev_features: width * height * 8 f32, 16-byte aligned; dev_clear: width * height u32
+ * in the frame's layout; dev_ao: width * height f32, or NULL.  Asynchronous on
+ * hip_stream (NULL: the context's own).  params is validated as zrt_ctx_features
+ * validates it; traversal, prng, seed, width, height, device and
+ * bounded_volume_hierarchy are read.  ZRT_E_INVALID before any device work: n_samples
+ * == 0 or > 1024, first_sample + n_samples > 65536 (the key's sample field), a radius
+ * that is NaN or <= 0.001, an unknown flag, a null dev_features / dev_clear, a
+ * misaligned pointer, height > width, params that do not fit the context.
+ *
+ * AO is a query (see "ray queries"): its rows, error flag, completion and events are
+ * the query's, zrt_ctx_query_ms times its kernel.  After a traversal stack overflow
+ * every count of D holds 0xFFFFFFFF and every ao of D NaN, and zrt_ctx_sync reports
+ * ZRT_E_UNSUPPORTED once. */
+typedef struct zrt_ao {
+  uint32_t n_samples;     /* AO rays per pixel in this call, 1 .. 1024 */
+  uint32_t first_sample;  /* index of this call's sample 0 in the pixel's AO stream */
+  float    radius;        /* t_max of every AO ray: > 0.001, +inf allowed */
+  uint32_t flags;         /* ZRT_AO_* */
+  uint32_t reserved[4];
+} zrt_ao;
+enum { ZRT_AO_ACCUMULATE = 1u };
+
+int zrt_ctx_ao(zrt_ctx* ctx, const zrt_camera* camera, const zrt_params* params, const zrt_ao* ao,
+               const float* dev_features, uint32_t* dev_clear, float* dev_ao, void* hip_stream);
+
+/* ms between the events around the last AO kernel of the context: zrt_ctx_query_ms. */
+int zrt_ctx_ao_ms(zrt_ctx* ctx, double* ms);
+
+/* One-shot, host pointers: a context, the features, the AO call, the copies out.  out_ao:
+ * width * height f32; out_clear (width * height u32) and out_features (width * height * 8
+ * f32) may be NULL.  Under ZRT_AO_ACCUMULATE out_clear is read first: its contents are the
+ * counts of samples [0, first_sample) the call adds onto (NULL: zeros). */
+int zrt_render_ao(const zrt_scene* scene, const zrt_camera* camera, const zrt_params* params, const zrt_ao* ao,
+                  float* out_ao, uint32_t* out_clear, float* out_features);
+
+/* How zrt_ctx_ao launches (no device; the launch path calls the same function): a lane
+ * is one (pixel, sample), pixels in 8x8 tile order over the whole width, a pixel's
+ * samples on adjacent lanes.  The grid is bounded by the CU count and each block loops
+ * over its groups of 256 rays, so the stack's overflow rows are sized by the resident
+ * lanes, never by the rays.  Refuses what zrt_ctx_ao refuses of params and ao. */
+enum { ZRT_AO_REDUCE_WAVE = 0, ZRT_AO_REDUCE_ATOMIC = 1 };
+typedef struct zrt_ao_plan {
+  uint64_t rays;            /* pixel slots (tiles x 64) x n_samples */
+  uint64_t groups;          /* groups of 256 rays */
+  uint64_t pixel_slots;     /* tiles over the whole width x 64 */
+  uint64_t resident_lanes;  /* grid x 256: the stride and the count of the overflow rows' lanes */
+  uint64_t ovf_row_bytes;   /* one overflow row of 32-bit entries: resident_lanes x 4 */
+  uint64_t plane_bytes;     /* the count plane of ZRT_AO_REDUCE_ATOMIC (width x height u32), else 0 */
+  uint32_t grid;            /* blocks launched: min(groups, blocks_per_cu x cu_count) */
+  uint32_t blocks_per_cu;
+  uint32_t reduction;       /* ZRT_AO_REDUCE_WAVE: n_samples divides 64, a pixel's samples lie in one wave (one
+                               ballot + popcount, the segment's first lane writes); else ZRT_AO_REDUCE_ATOMIC:
+                               vector atomic adds on a zeroed count plane, folded in by the finishing kernel */
+  uint32_t reserved;
+} zrt_ao_plan;
+int zrt_debug_ao_plan(const zrt_params* params, const zrt_ao* ao, uint32_t cu_count, zrt_ao_plan* out);
+
 /* ---- host-side scene ingestion (the caller side of the seam) ------------- *
  * Restatement of scenes.zig / obj_reader.zig / png_image.zig texture loading
  * so tests and bench can build the reference's scenes without Zig.  Assets are

@@ -20,7 +20,8 @@ from . import _ffi
 from ._ffi import (ZRT_PRNG_XOROSHIRO128, ZRT_PRNG_XOSHIRO256, ZRT_RNG_COUNTER,  # noqa: F401
                    ZRT_RNG_REFERENCE_STREAM, ZRT_TRAVERSAL_FAST, ZRT_TRAVERSAL_REFERENCE,
                    ZRT_TRAVERSAL_BINARY, ZRT_FLAG_STATS, ZRT_FLAG_NO_SCHEDULE, ZRT_FLAG_SCANLINES, ZRT_FLAG_GUARD,
-                   ZRT_DN_DEMODULATE, ZRT_TA_DEMODULATE, ZrtError, check)
+                   ZRT_DN_DEMODULATE, ZRT_TA_DEMODULATE, ZRT_AO_ACCUMULATE, ZRT_AO_REDUCE_WAVE, ZRT_AO_REDUCE_ATOMIC,
+                   ZrtError, check)
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ASSETS = os.path.join(REPO, "assets")
@@ -463,6 +464,40 @@ def occluded(scene, params: RenderParams, origins, directions, t_max=None):
     return out != 0
 
 
+def ao_settings(n_samples: int, radius: float = float("inf"), first_sample: int = 0, flags: int = 0) -> _ffi.Ao:
+    """A zrt_ao: n_samples cosine rays per pixel of length radius, the pixel's samples
+    first_sample .. ; flags: ZRT_AO_ACCUMULATE."""
+    return _ffi.Ao(n_samples=n_samples, first_sample=first_sample, radius=radius, flags=flags)
+
+
+def render_ao(scene, camera: _ffi.Camera, params: RenderParams, n_samples: int, radius: float = float("inf"),
+              first_sample: int = 0):
+    """The frame's ambient-occlusion plane (zrt_render_ao; the definition: zrt.h "ambient
+    occlusion"): n_samples cosine rays of length radius from every first hit.  Returns (ao
+    float32[H, W]: the share of rays that got away, clear uint32[H, W]: their count,
+    features float32[H, W, 8])."""
+    view = scene.view if isinstance(scene, LoadedScene) else scene
+    ao = np.zeros((params.height, params.width), dtype=np.float32)
+    clear = np.zeros((params.height, params.width), dtype=np.uint32)
+    features = np.zeros((params.height, params.width, 8), dtype=np.float32)
+    p = params.abi()
+    a = ao_settings(n_samples, radius, first_sample)
+    f = C.POINTER(C.c_float)
+    check(lib().zrt_render_ao(view, C.byref(camera), C.byref(p), C.byref(a), ao.ctypes.data_as(f),
+                              clear.ctypes.data_as(C.POINTER(C.c_uint32)), features.ctypes.data_as(f)))
+    return ao, clear, features
+
+
+def debug_ao_plan(params: RenderParams, ao: _ffi.Ao, cu_count: int = 256) -> dict:
+    """How zrt_ctx_ao launches with these params and settings on a device of cu_count CUs
+    (zrt_debug_ao_plan; no device): rays, groups, grid, resident lanes, overflow-row bytes
+    and the reduction.  Raises ZrtError for what the call would refuse."""
+    out = _ffi.AoPlan()
+    p = params.abi()
+    check(lib().zrt_debug_ao_plan(C.byref(p), C.byref(ao), cu_count, C.byref(out)))
+    return out.as_dict()
+
+
 class RenderContext:
     """Device-resident scene (zrt_ctx_*): build + upload once, render many."""
 
@@ -549,6 +584,21 @@ class RenderContext:
         p = params.abi()
         check(lib().zrt_ctx_occluded(self._h, C.byref(p), C.c_void_p(dev_rays or None), C.c_void_p(dev_t_max or None),
                                      n, C.c_void_p(dev_out or None), C.c_void_p(stream or None)))
+
+    def ao(self, camera, params: RenderParams, ao: _ffi.Ao, dev_features: int, dev_clear: int, dev_ao: int = 0,
+           stream: int = 0):
+        """Ambient occlusion from a feature buffer (zrt_ctx_ao; device pointers, asynchronous):
+        dev_clear width * height u32 receives per pixel the AO rays that got away, dev_ao
+        (0: not wanted) width * height f32 their share."""
+        p = params.abi()
+        check(lib().zrt_ctx_ao(self._h, C.byref(camera), C.byref(p), C.byref(ao), C.c_void_p(dev_features or None),
+                               C.c_void_p(dev_clear or None), C.c_void_p(dev_ao or None), C.c_void_p(stream or None)))
+
+    def ao_ms(self) -> float:
+        """Device time of the last ao() kernel in ms (zrt_ctx_ao_ms; waits for it)."""
+        ms = C.c_double()
+        check(lib().zrt_ctx_ao_ms(self._h, C.byref(ms)))
+        return ms.value
 
     def query_ms(self) -> float:
         """Device time of the last trace() / occluded() kernel in ms (zrt_ctx_query_ms; waits for it)."""

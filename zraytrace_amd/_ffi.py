@@ -36,6 +36,8 @@ ZRT_FLAG_SCANLINES = 4
 ZRT_FLAG_GUARD = 8
 ZRT_DN_DEMODULATE = 1
 ZRT_TA_DEMODULATE = 1
+ZRT_AO_ACCUMULATE = 1
+ZRT_AO_REDUCE_WAVE, ZRT_AO_REDUCE_ATOMIC = 0, 1
 
 
 class Vec3(C.Structure):
@@ -196,6 +198,21 @@ class Temporal(C.Structure):
 FRAME_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_float), C.c_uint32)
 
 
+class Ao(C.Structure):
+    _fields_ = [("n_samples", C.c_uint32), ("first_sample", C.c_uint32), ("radius", C.c_float), ("flags", C.c_uint32),
+                ("reserved", C.c_uint32 * 4)]
+
+
+class AoPlan(C.Structure):
+    _fields_ = [("rays", C.c_uint64), ("groups", C.c_uint64), ("pixel_slots", C.c_uint64),
+                ("resident_lanes", C.c_uint64), ("ovf_row_bytes", C.c_uint64), ("plane_bytes", C.c_uint64),
+                ("grid", C.c_uint32), ("blocks_per_cu", C.c_uint32), ("reduction", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_ if name != "reserved"}
+
+
 class BvhNode(C.Structure):
     _fields_ = [("min", Vec3), ("left", C.c_int32), ("max", Vec3), ("right", C.c_int32)]
 
@@ -287,6 +304,11 @@ SIGNATURES = [
     ("zrt_occluded", C.c_int, [C.POINTER(Scene), C.POINTER(Params), C.POINTER(C.c_float), C.POINTER(C.c_float),
                                C.c_uint32, C.POINTER(C.c_uint8)]),
     ("zrt_ctx_query_ms", C.c_int, [_P, C.POINTER(C.c_double)]),
+    ("zrt_ctx_ao", C.c_int, [_P, C.POINTER(Camera), C.POINTER(Params), C.POINTER(Ao), _P, _P, _P, _P]),
+    ("zrt_ctx_ao_ms", C.c_int, [_P, C.POINTER(C.c_double)]),
+    ("zrt_render_ao", C.c_int, [C.POINTER(Scene), C.POINTER(Camera), C.POINTER(Params), C.POINTER(Ao),
+                                C.POINTER(C.c_float), C.POINTER(C.c_uint32), C.POINTER(C.c_float)]),
+    ("zrt_debug_ao_plan", C.c_int, [C.POINTER(Params), C.POINTER(Ao), C.c_uint32, C.POINTER(AoPlan)]),
     ("zrt_scene_load", C.c_int, [C.c_uint32, C.c_char_p, C.POINTER(_P), C.POINTER(Camera)]),
     ("zrt_scene_view", C.POINTER(Scene), [_P]),
     ("zrt_scene_free", None, [_P]),

@@ -38,9 +38,13 @@
 // lower_left_corner are the scene's plus (float(k) * delta) * horizontal per component, in
 // f32.  One line per frame on stderr in place of the scanline lines.  It is refused with
 // every other mode above.
+// $ZRT_AO_SAMPLES=n [$ZRT_AO_RADIUS=r] $ZRT_AO_OUT=<file.png> also writes the frame's
+// ambient-occlusion plane (zrt_render_ao: n rays per pixel, radius r, default +inf) as a
+// grey PNG, beside any mode above; the frame's own output is unchanged.
 #include <unistd.h>
 
 #include <chrono>
+#include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -278,6 +282,38 @@ int main(int argc, char** argv) {
     }
   }
 
+  // $ZRT_AO_SAMPLES=n [$ZRT_AO_RADIUS=r] $ZRT_AO_OUT=file.png: also write the AO plane; the
+  // settings are checked here, before anything is rendered (zrt_debug_ao_plan: no device)
+  const char* ao_n = std::getenv("ZRT_AO_SAMPLES");
+  const char* ao_out = std::getenv("ZRT_AO_OUT");
+  zrt_ao ao;
+  std::memset(&ao, 0, sizeof(ao));
+  zrt_params ao_params = params;
+  ao_params.flags = 0;
+  ao_params.rank = 0;
+  ao_params.world_size = 1;
+  if (ao_n || ao_out || std::getenv("ZRT_AO_RADIUS")) {
+    if (!ao_n || !ao_out) {
+      std::fprintf(stderr, "error: the AO plane needs both ZRT_AO_SAMPLES=<rays per pixel> and ZRT_AO_OUT=<file.png>\n");
+      zrt_scene_free(data);
+      return 1;
+    }
+    char* end = nullptr;
+    const unsigned long n = std::strtoul(ao_n, &end, 10);
+    const char* r = std::getenv("ZRT_AO_RADIUS");
+    char* rend = nullptr;
+    ao.radius = r ? std::strtof(r, &rend) : HUGE_VALF;
+    if (r && (*rend != '\0' || rend == r)) ao.radius = NAN;  // not a number: refused below
+    ao.n_samples = (*end != '\0' || end == ao_n || n > 0xffffffffUL) ? 0u : uint32_t(n);
+    zrt_ao_plan plan;
+    if (zrt_debug_ao_plan(&ao_params, &ao, 1, &plan) != ZRT_OK) {
+      std::fprintf(stderr, "error: ZRT_AO_SAMPLES is 1 .. 1024 rays per pixel, ZRT_AO_RADIUS a length > 0.001 (%s)\n",
+                   zrt_last_error());
+      zrt_scene_free(data);
+      return 1;
+    }
+  }
+
   std::fprintf(stderr, "Raytrace start\n");
   std::fprintf(stderr, " - Surfaces:                 %u\n", scene->n_prims);
   std::fprintf(stderr, " - Pixels:                   %ux%u\n", unsigned(width), unsigned(height));
@@ -387,6 +423,15 @@ int main(int argc, char** argv) {
     for (size_t i = 0; i < sample_map.size(); ++i)
       grey[3 * i] = grey[3 * i + 1] = grey[3 * i + 2] = float(sample_map[i]) / float(samples);
     rc = zrt_image_write_png(map, grey.data(), width, height);
+  }
+  // $ZRT_AO_OUT: the frame's AO plane as a grey PNG (zrt_render_ao, a launch of its own on the
+  // first GPU); the frame above is what it was without it
+  if (ao_out && rc == ZRT_OK) {
+    std::vector<float> plane(size_t(width) * height), grey(size_t(width) * height * 3);
+    rc = zrt_render_ao(scene, &camera, &ao_params, &ao, plane.data(), nullptr, nullptr);
+    for (size_t i = 0; i < plane.size(); ++i) grey[3 * i] = grey[3 * i + 1] = grey[3 * i + 2] = plane[i];
+    if (rc == ZRT_OK) rc = zrt_image_write_png(ao_out, grey.data(), width, height);
+    if (rc == ZRT_OK) std::fprintf(stderr, "  Ambient occlusion:     %u rays per pixel -> %s\n", ao.n_samples, ao_out);
   }
   zrt_scene_free(data);
   if (rc != ZRT_OK) {

@@ -1,10 +1,12 @@
 // context.hpp - private to the host files that talk to the HIP runtime
-// (context.cpp, runs.cpp, post.cpp, queries.cpp, debug_device.cpp, multi.cpp, oneshot.cpp): the
+// (context.cpp, runs.cpp, post.cpp, queries.cpp, ao.cpp, debug_device.cpp, multi.cpp, oneshot.cpp): the
 // HIP error type, the owning handles, the context behind zrt_ctx_*, what those
 // files share of its launch path, and the catch clauses of their entry points.
 #pragma once
 #include <hip/hip_runtime_api.h>
 
+#include <algorithm>
+#include <cstdlib>
 #include <cstring>
 #include <memory>
 #include <string>
@@ -269,6 +271,7 @@ struct QueryState {
   DevBuf<unsigned long long> err;
   Completion done;
   StepTimer timer;
+  DevBuf<uint32_t> ao_plane;  // zrt_ctx_ao's count plane (the atomic reduction), zeroed per launch
 };
 }  // namespace zrt
 
@@ -341,6 +344,48 @@ TracePlan fill_trace(KArgs& a, const zrt_ctx* c, uint32_t traversal, bool full_n
 const uint32_t* slot_prim_table(zrt_ctx* c);
 void trace_rows(KArgs& a, const zrt_ctx* c, const TracePlan& t, uint64_t n_lanes, DevBuf<uint8_t>& ovf, hipStream_t st,
                 const char* launch);
+
+// ---- the query launches (queries.cpp, ao.cpp) ----
+// One lane per ray: the blocks of a query over n rays.
+inline uint32_t query_grid(uint32_t n) { return (n + kBlock - 1) / kBlock; }
+// One query launch of `grid` blocks: the trace plan (FAST any-hit: over the full nodes),
+// the query's own rows (one column per lane of the grid) and error flag, `kernel`
+// between the timer's events, `finish` (what overwrites the outputs of a launch that
+// set the flag), then the flag copied out behind `done`.
+template <class Kernel, class Finish>
+void launch_query(zrt_ctx* c, const zrt_params* p, uint32_t grid, hipStream_t st, bool anyhit, const char* name,
+                  Kernel&& kernel, Finish&& finish) {
+  QueryState& q = c->query;
+  const uint64_t n_lanes = uint64_t(grid) * kBlock;
+  q.done.create();
+  q.timer.e0.create();
+  q.timer.e1.create();
+  if (!q.err.p) q.err.alloc(1);
+  KArgs a{};
+  const TracePlan t = fill_trace(a, c, p->traversal, anyhit);
+  // tests: a stack too small for the tree (the knob of the render launches; the rows stay
+  // the uncapped plan's, so a smaller depth only flags pushes it cannot hold)
+  if (const char* cap = std::getenv("ZRT_DEBUG_STACK_CAP")) {
+    a.stack_depth = std::max<uint32_t>(4, std::min<uint32_t>(a.stack_depth, uint32_t(std::atoi(cap))));
+    a.ref_stack = std::min(a.ref_stack, a.stack_depth);
+  }
+  trace_rows(a, c, t, n_lanes, q.ovf, st, name);
+  a.error_flag = reinterpret_cast<uint32_t*>(q.err.p);
+  HIPCHK(hipMemsetAsync(q.err.p, 0, sizeof(unsigned long long), st));
+  HIPCHK(hipEventRecord(q.timer.e0, st));
+  kernel(a, t, grid, st);
+  HIPCHK(hipEventRecord(q.timer.e1, st));
+  q.timer.launched = true;
+  finish(st, q.err.p);
+  HIPCHK(hipMemcpyAsync(q.done.err.get(), q.err.p, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipEventRecord(q.done.done, st));
+  q.done.launched = true;
+  q.done.reported = false;
+}
+
+// ---- ao.cpp ----
+// zrt_ctx_ao's refusals of params and ao, and its launch (zrt_debug_ao_plan): no device.
+int plan_ao(const zrt_params* p, const zrt_ao* ao, uint32_t cu_count, zrt_ao_plan* out);
 }  // namespace zrt
 
 // The catch clauses of every C entry point: no exception crosses the ABI.

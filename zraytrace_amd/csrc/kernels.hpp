@@ -99,6 +99,18 @@ struct KArgs {
   uint64_t att_cap, ovf_cap;  // elements of `att` and of `stack_ovf` (StackT): row_ok's bounds
 };
 
+// ao_kernel / ao_finish_kernel's own arguments (zrt_ctx_ao; zrt::plan_ao fills the counts)
+struct AoArgs {
+  uint64_t n_slots;   // pixel slots: tiles over the whole width x 64
+  uint64_t n_groups;  // groups of kBlock rays (rays = n_slots x n_samples)
+  uint32_t n_samples, first_sample;
+  uint32_t accumulate;  // ZRT_AO_ACCUMULATE
+  uint32_t in_wave;     // n_samples divides 64: the reduction ends in the wave (ZRT_AO_REDUCE_WAVE)
+  uint32_t tiles_w;     // tiles over the whole width
+  uint32_t rotate;      // blocks by which the groups of a round are shifted against the round before
+  float radius;
+};
+
 // error_flag bits (zrt_ctx_sync / zrt_ctx_stats / zrt_render report them as ZRT_E_UNSUPPORTED)
 constexpr uint32_t kErrOverflow = 1u;  // a traversal stack deeper than it was sized for
 constexpr uint32_t kErrLayout = 2u;    // the wide tree's encoding is not the one this kernel decodes
@@ -183,6 +195,8 @@ void* features_kernel_ptr(int mode, bool stk16);
 // anyhit_kernel<mode, stack width> (zrt_ctx_occluded): 0 list, 1 BINARY, 2 REFERENCE, 3 FAST over the
 // full 128-B wide nodes - any-hit has no flavour over the compressed nodes
 void* anyhit_kernel_ptr(int mode, bool stk16);
+// ao_kernel<mode, prng, stack width> (zrt_ctx_ao): anyhit_kernel's modes
+void* ao_kernel_ptr(int mode, uint32_t prng, bool stk16);
 
 // One launch function per small kernel (the arguments are the kernel's, render.hip).
 hipError_t launch_finalize(hipStream_t st, const float4* partial, float* out, uint32_t n_slots, uint32_t n_chunks,
@@ -214,6 +228,10 @@ hipError_t launch_trace_finish(hipStream_t st, float* t, int32_t* prim, uint32_t
                                const unsigned long long* error_flag);
 // zrt_ctx_occluded's: 0xFF in every byte behind a launch that set *error_flag
 hipError_t launch_anyhit_error(hipStream_t st, uint8_t* out, uint32_t n, const unsigned long long* error_flag);
+// zrt_ctx_ao's: the count plane folded into the result, or 0xFFFFFFFF / NaN in D behind a launch that set *error_flag
+hipError_t launch_ao_finish(hipStream_t st, const AoArgs& g, uint32_t width, uint32_t height, uint32_t xbound,
+                            const float4* feat, uint32_t* clear, float* ao, const uint32_t* plane,
+                            const unsigned long long* error_flag);
 hipError_t launch_debug_math(int fn, const float* x, const float* y, float* out, uint32_t n);
 hipError_t launch_debug_division(uint64_t n, unsigned long long* counts);
 hipError_t launch_debug_rng(uint32_t prng, uint64_t key, unsigned long long* out, uint32_t n);

@@ -368,3 +368,42 @@ int zrt_render_temporal(const zrt_scene* scene, const zrt_camera* cameras, uint3
   }
   ZRT_CATCH_ALL
 }
+
+// The AO plane of a frame (zrt.h "ambient occlusion"): a context, the first-hit features,
+// the AO call, the copies out.  Under ZRT_AO_ACCUMULATE the counts start from out_clear's
+// contents (zero without it).
+int zrt_render_ao(const zrt_scene* scene, const zrt_camera* camera, const zrt_params* params, const zrt_ao* ao,
+                  float* out_ao, uint32_t* out_clear, float* out_features) {
+  if (!camera || !out_ao) return fail(ZRT_E_INVALID, "null argument");
+  zrt_ao_plan plan;
+  int rc = zrt::plan_ao(params, ao, 1, &plan);  // (refused before any device work)
+  if (rc) return rc;
+  try {
+    zrt::Session s;
+    rc = s.open(scene, params);
+    if (rc) return rc;
+    zrt_ctx* c = s.c();
+    const size_t px = s.px();
+    zrt::DevBuf<float> feat, plane;
+    zrt::DevBuf<uint32_t> clear;
+    feat.alloc(px * 8);
+    plane.alloc(px);
+    clear.alloc(px);
+    if ((ao->flags & ZRT_AO_ACCUMULATE) && out_clear)
+      HIPCHK(hipMemcpy(clear.p, out_clear, sizeof(uint32_t) * px, hipMemcpyHostToDevice));
+    else
+      HIPCHK(hipMemset(clear.p, 0, sizeof(uint32_t) * px));
+    rc = zrt_ctx_features(c, camera, &s.p, feat.p, nullptr);
+    if (rc) return rc;
+    rc = zrt_ctx_ao(c, camera, &s.p, ao, feat.p, clear.p, plane.p, nullptr);
+    if (rc) return rc;
+    HIPCHK(hipStreamSynchronize(c->stream));
+    rc = zrt_ctx_sync(c);  // (a device error of either launch)
+    if (rc) return rc;
+    HIPCHK(hipMemcpy(out_ao, plane.p, sizeof(float) * px, hipMemcpyDeviceToHost));
+    if (out_clear) HIPCHK(hipMemcpy(out_clear, clear.p, sizeof(uint32_t) * px, hipMemcpyDeviceToHost));
+    if (out_features) HIPCHK(hipMemcpy(out_features, feat.p, sizeof(float) * 8 * px, hipMemcpyDeviceToHost));
+    return ZRT_OK;
+  }
+  ZRT_CATCH_ALL
+}

@@ -18,41 +18,6 @@ int check_query_args(const zrt_ctx* c, const zrt_params* p) {
   return zrt::params_fit_ctx(c, p);
 }
 bool misaligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; }
-
-// One query launch: the trace plan (FAST any-hit: over the full nodes), the query's own
-// rows and error flag, `kernel` between the timer's events, `finish` (what overwrites
-// the outputs of a launch that set the flag), then the flag copied out behind `done`.
-template <class Kernel, class Finish>
-void launch_query(zrt_ctx* c, const zrt_params* p, uint32_t n, hipStream_t st, bool anyhit, const char* name,
-                  Kernel&& kernel, Finish&& finish) {
-  zrt::QueryState& q = c->query;
-  const uint32_t grid = (n + zrt::kBlock - 1) / zrt::kBlock;
-  const uint64_t n_lanes = uint64_t(grid) * zrt::kBlock;
-  q.done.create();
-  q.timer.e0.create();
-  q.timer.e1.create();
-  if (!q.err.p) q.err.alloc(1);
-  zrt::KArgs a{};
-  const zrt::TracePlan t = zrt::fill_trace(a, c, p->traversal, anyhit);
-  // tests: a stack too small for the tree (the knob of the render launches; the rows stay
-  // the uncapped plan's, so a smaller depth only flags pushes it cannot hold)
-  if (const char* cap = std::getenv("ZRT_DEBUG_STACK_CAP")) {
-    a.stack_depth = std::max<uint32_t>(4, std::min<uint32_t>(a.stack_depth, uint32_t(std::atoi(cap))));
-    a.ref_stack = std::min(a.ref_stack, a.stack_depth);
-  }
-  zrt::trace_rows(a, c, t, n_lanes, q.ovf, st, name);
-  a.error_flag = reinterpret_cast<uint32_t*>(q.err.p);
-  HIPCHK(hipMemsetAsync(q.err.p, 0, sizeof(unsigned long long), st));
-  HIPCHK(hipEventRecord(q.timer.e0, st));
-  kernel(a, t, grid, st);
-  HIPCHK(hipEventRecord(q.timer.e1, st));
-  q.timer.launched = true;
-  finish(st, q.err.p);
-  HIPCHK(hipMemcpyAsync(q.done.err.get(), q.err.p, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-  HIPCHK(hipEventRecord(q.done.done, st));
-  q.done.launched = true;
-  q.done.reported = false;
-}
 }  // namespace
 
 int zrt_ctx_trace(zrt_ctx* c, const zrt_params* p, const float* dev_rays, uint32_t n, float* dev_t, int32_t* dev_prim,
@@ -67,8 +32,8 @@ int zrt_ctx_trace(zrt_ctx* c, const zrt_params* p, const float* dev_rays, uint32
     HIPCHK(hipSetDevice(c->device));
     hipStream_t st = zrt::stream_of(c, hip_stream);
     const uint32_t* sp = zrt::slot_prim_table(c);
-    launch_query(
-        c, p, n, st, false, "trace query",
+    zrt::launch_query(
+        c, p, zrt::query_grid(n), st, false, "trace query",
         [&](zrt::KArgs& a, const zrt::TracePlan& t, uint32_t grid, hipStream_t s) {
           if (std::getenv("ZRT_DEBUG_NO_GUARD")) a.guard = 0.0f;  // as zrt_trace
           void* args[] = {&a, &dev_rays, &n, &dev_t, &dev_prim};
@@ -94,8 +59,8 @@ int zrt_ctx_occluded(zrt_ctx* c, const zrt_params* p, const float* dev_rays, con
   try {
     HIPCHK(hipSetDevice(c->device));
     hipStream_t st = zrt::stream_of(c, hip_stream);
-    launch_query(
-        c, p, n, st, true, "any-hit query",
+    zrt::launch_query(
+        c, p, zrt::query_grid(n), st, true, "any-hit query",
         [&](zrt::KArgs& a, const zrt::TracePlan& t, uint32_t grid, hipStream_t s) {
           void* args[] = {&a, &dev_rays, &dev_t_max, &n, &dev_out};
           HIPCHK(hipLaunchKernel(zrt::anyhit_kernel_ptr(t.kmode, t.stk16), dim3(grid), dim3(zrt::kBlock), args,

@@ -3928,24 +3928,14 @@ __device__ __forceinline__ bool anyhit_wide(const KArgs& a, const RayT& r, Stack
   return literal ? anyhit_literal<StackT>(a, r, stk, gl, t_max, !far) : false;
 }
 
-// One ray per lane; a lane that has its answer stops traversing, the wave ends when
-// all have.  t_max: per ray, or null = +inf.  out: 1 occluded / 0 not.
+// The any-hit of one ray whose direction Ray.init has normalised, through the
+// launch's traversal (anyhit_kernel and ao_kernel): gl is the lane's index in the
+// launch, which owns stack column gl of the overflow rows.
 template <int MODE, class StackT>
-__global__ void __launch_bounds__(kBlock) anyhit_kernel(const KArgs a, const float* __restrict__ rays,
-                                                        const float* __restrict__ t_max_in, uint32_t n,
-                                                        uint8_t* __restrict__ out) {
-  extern __shared__ __attribute__((aligned(16))) char lds_raw[];
-  StackT* stk = reinterpret_cast<StackT*>(lds_raw) + threadIdx.x;
-  float4* lds_top = reinterpret_cast<float4*>(lds_raw + a.lds_top_off);
-  if (MODE == 3 && !layout_ok(a)) return;
-  if (MODE == 3 && ZRT_LDS_TOP) fill_lds_top(a, lds_top);
-  const uint32_t gl = blockIdx.x * kBlock + threadIdx.x;
-  if (gl >= n) return;
-  const float* q = rays + 6ull * gl;
-  const V3 d = unit(mk(q[3], q[4], q[5]));
-  const float t_max = t_max_in ? t_max_in[gl] : __builtin_inff();
+__device__ __forceinline__ bool anyhit_ray(const KArgs& a, const V3 o, const V3 d, float t_max, StackT* __restrict__ stk,
+                                           const float4* __restrict__ lds_top, uint32_t gl) {
   RayT r;
-  r.ox = q[0]; r.oy = q[1]; r.oz = q[2];
+  r.ox = o.x; r.oy = o.y; r.oz = o.z;
   r.dx = d.x; r.dy = d.y; r.dz = d.z;
   r.rcp_det = a.tri_rcp_fast;
   r.gm = a.graze_m;
@@ -3968,6 +3958,26 @@ __global__ void __launch_bounds__(kBlock) anyhit_kernel(const KArgs a, const flo
   } else {
     hit = anyhit_literal<StackT>(a, r, stk, gl, t_max, false);
   }
+  return hit;
+}
+
+// One ray per lane; a lane that has its answer stops traversing, the wave ends when
+// all have.  t_max: per ray, or null = +inf.  out: 1 occluded / 0 not.
+template <int MODE, class StackT>
+__global__ void __launch_bounds__(kBlock) anyhit_kernel(const KArgs a, const float* __restrict__ rays,
+                                                        const float* __restrict__ t_max_in, uint32_t n,
+                                                        uint8_t* __restrict__ out) {
+  extern __shared__ __attribute__((aligned(16))) char lds_raw[];
+  StackT* stk = reinterpret_cast<StackT*>(lds_raw) + threadIdx.x;
+  float4* lds_top = reinterpret_cast<float4*>(lds_raw + a.lds_top_off);
+  if (MODE == 3 && !layout_ok(a)) return;
+  if (MODE == 3 && ZRT_LDS_TOP) fill_lds_top(a, lds_top);
+  const uint32_t gl = blockIdx.x * kBlock + threadIdx.x;
+  if (gl >= n) return;
+  const float* q = rays + 6ull * gl;
+  const V3 d = unit(mk(q[3], q[4], q[5]));
+  const float t_max = t_max_in ? t_max_in[gl] : __builtin_inff();
+  const bool hit = anyhit_ray<MODE, StackT>(a, mk(q[0], q[1], q[2]), d, t_max, stk, lds_top, gl);
   out[gl] = hit ? (uint8_t)1 : (uint8_t)0;
 }
 
@@ -3977,6 +3987,143 @@ __global__ void anyhit_error_kernel(uint8_t* __restrict__ out, uint32_t n,
   if (*error_flag == 0ull) return;
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) out[i] = (uint8_t)0xFF;
+}
+
+// ---------------------------------------------------------------------------
+// Ambient occlusion (zrt_ctx_ao; zrt.h "ambient occlusion"): the rays
+// Lambertian.scatter shoots from the first hits of a feature buffer, through the
+// any-hit above, counted per pixel.  No ray is stored.
+// ---------------------------------------------------------------------------
+// A pixel as the AO kernels see it.
+enum : uint32_t { kAoOff = 0, kAoOutside = 1, kAoMiss = 2, kAoPoison = 3, kAoHit = 4 };
+__device__ __forceinline__ uint32_t ao_classify(const float4* __restrict__ feat, uint64_t pix) {
+  if (__float_as_uint(reinterpret_cast<const float*>(feat)[8ull * pix + 7]) == 0u) return kAoMiss;
+  const float4 f = feat[2ull * pix];
+  return (f.x != f.x || f.y != f.y || f.z != f.z || f.w != f.w) ? kAoPoison : kAoHit;
+}
+// A pixel's result (zrt.h): c the samples of this call that got away.
+__device__ __forceinline__ void ao_store(const AoArgs& g, uint32_t kind, uint32_t c, uint64_t pix,
+                                         uint32_t* __restrict__ clear, float* __restrict__ ao) {
+  uint32_t v = 0u;
+  float f = 0.0f;
+  if (kind != kAoOutside) {
+    const uint32_t old = g.accumulate ? clear[pix] : 0u;
+    if (kind == kAoPoison || old == 0xFFFFFFFFu) {
+      v = 0xFFFFFFFFu;
+      f = __builtin_nanf("");
+    } else {
+      v = old + (kind == kAoMiss ? g.n_samples : c);
+      f = (float)v / (float)(g.accumulate ? g.first_sample + g.n_samples : g.n_samples);  // IEEE `/`
+    }
+  }
+  clear[pix] = v;
+  if (ao) ao[pix] = f;
+}
+
+// A lane is one (pixel, sample): ray i = slot * n_samples + s, slot the pixel's place in
+// the 8x8 tile order of features_kernel, so a pixel's samples sit on adjacent lanes and
+// a wave's rays share origins.  The grid is bounded (zrt::plan_ao): a block loops over
+// its groups of kBlock rays, and its lanes keep one stack column each (gl) however many
+// rays the frame has.  Rays and pixels are indexed in 64 bits.  A wave's first ray is
+// wave-uniform, so the one 64-bit division is scalar; lanes divide 32-bit offsets.
+// Lanes of misses, poisoned pixels and pixels outside D traverse nothing.
+// The reduction: one ballot of "got away" per wave; the first lane of each run of lanes
+// on one pixel takes the popcount of its run.  in_wave (n_samples divides 64): the run is
+// the whole pixel and that lane writes the result; else it adds the run's count onto the
+// zeroed plane (one vector atomic per pixel and wave) and ao_finish_kernel writes.
+// FAST is built for 4 waves per SIMD (128 VGPRs), anyhit_kernel's occupancy: left to itself the
+// compiler takes 131 and drops to 3.
+template <int MODE, int PRNG, class StackT>
+__global__ void __launch_bounds__(kBlock, MODE == 3 ? 4 : 1) ao_kernel(const KArgs a, const AoArgs g, const float4* __restrict__ feat,
+                                                    uint32_t* __restrict__ clear, float* __restrict__ ao,
+                                                    uint32_t* __restrict__ plane) {
+  extern __shared__ __attribute__((aligned(16))) char lds_raw[];
+  StackT* stk = reinterpret_cast<StackT*>(lds_raw) + threadIdx.x;
+  float4* lds_top = reinterpret_cast<float4*>(lds_raw + a.lds_top_off);
+  if (MODE == 3 && !layout_ok(a)) return;
+  if (MODE == 3 && ZRT_LDS_TOP) fill_lds_top(a, lds_top);
+  const uint32_t gl = blockIdx.x * kBlock + threadIdx.x;
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const uint32_t n = g.n_samples;
+  const V3 llc = mk(a.llc[0], a.llc[1], a.llc[2]);
+  const V3 hor = mk(a.hor[0], a.hor[1], a.hor[2]);
+  const V3 ver = mk(a.ver[0], a.ver[1], a.ver[2]);
+  const V3 o = mk(a.org[0], a.org[1], a.org[2]);
+  uint32_t round = 0;
+  for (uint64_t base = 0; base < g.n_groups; base += gridDim.x, ++round) {
+    // round k hands group base + j to block (j - k * rotate) mod grid: a block's groups wander over the
+    // frame's columns instead of lining up in one stripe of tiles (grid groups are often whole tile rows)
+    const uint64_t grp = base + (blockIdx.x + (uint64_t)round * g.rotate) % gridDim.x;
+    if (grp >= g.n_groups) continue;
+    const uint64_t i0 = grp * kBlock + wave * 64u;  // the wave's first ray
+    const uint64_t slot0 = i0 / n;
+    const uint32_t k = (uint32_t)(i0 - slot0 * n) + lane;  // < n + 64
+    const uint32_t dq = k / n;
+    const uint32_t s = k - dq * n;
+    const uint64_t slot = slot0 + dq;
+    const uint32_t tile = (uint32_t)(slot >> 6), p = (uint32_t)slot & 63u;
+    const uint32_t px = (tile % g.tiles_w) * 8u + (p & 7u), py = (tile / g.tiles_w) * 8u + (p >> 3);
+    const uint64_t pix = (uint64_t)py * a.width + px;
+    uint32_t kind = kAoOff;
+    if (slot < g.n_slots && px < a.width && py < a.height) kind = px < a.xbound ? ao_classify(feat, pix) : kAoOutside;
+    bool away = false;
+    if (kind == kAoHit) {
+      const float4 f = feat[2ull * pix];
+      const float u = (float)px / a.f_width;  // IEEE `/`, as features_kernel
+      const float v = (float)py / a.f_height;
+      const V3 dir = unit(sub(add(add(llc, scale(hor, u)), scale(ver, v)), o));
+      const V3 loc = add(o, scale(dir, f.w));  // ray.zig:14-16
+      V3 hv;
+      {  // randomUnitVector (sample.zig:47-61) on the sample's own stream: dead before the traversal
+        Rng<PRNG> rng;
+        rng.init(((pix << 16) | (uint64_t)(g.first_sample + s)) + a.seed_mix);
+        const float r1 = rand_float(rng);
+        const float r2 = rand_float(rng);
+        const float rr = dev::sqrt_rn(1.0f - r1 * r1);
+        float sn, cs;
+        dev::sincos_z(kTwoPi * r2, &sn, &cs);
+        hv = mk(cs * rr, sn * rr, r1);
+        if (!rand_bool(rng)) hv.z = hv.z * -1.0f;
+      }
+      const V3 d = unit(add(mk(f.x, f.y, f.z), hv));  // material.zig:73, Ray.init
+      away = !anyhit_ray<MODE, StackT>(a, loc, d, g.radius, stk, lds_top, gl);
+    }
+    const uint64_t bal = __ballot(away);
+    const uint32_t lo = s > lane ? 0u : lane - s;              // the run of this pixel's lanes in the wave
+    const uint32_t hi = min(63u, lane + (n - 1u - s));
+    const uint64_t run = (~0ull >> (63u - (hi - lo))) << lo;
+    const uint32_t c = (uint32_t)__popcll(bal & run);
+    if (lane == lo && kind != kAoOff) {
+      if (g.in_wave) ao_store(g, kind, c, pix, clear, ao);
+      else if (c) atomicAdd(&plane[pix], c);
+    }
+  }
+}
+
+// Behind ao_kernel, one lane per pixel of the frame.  After a launch that set its error
+// flag (a traversal stack overflow): 0xFFFFFFFF / NaN in every pixel of D.  Else, after
+// the atomic reduction: the plane's counts folded into the result, as ao_kernel's
+// in_wave lanes write it.
+__global__ void ao_finish_kernel(const AoArgs g, uint32_t width, uint32_t height, uint32_t xbound,
+                                 const float4* __restrict__ feat, uint32_t* __restrict__ clear,
+                                 float* __restrict__ ao, const uint32_t* __restrict__ plane,
+                                 const unsigned long long* __restrict__ error_flag) {
+  const bool err = *error_flag != 0ull;
+  if (!err && g.in_wave) return;
+  const uint64_t n_px = (uint64_t)width * height;
+  for (uint64_t pix = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; pix < n_px;
+       pix += (uint64_t)gridDim.x * blockDim.x) {
+    const uint32_t px = (uint32_t)(pix % width);
+    if (px >= xbound) {
+      if (!g.in_wave) ao_store(g, kAoOutside, 0u, pix, clear, ao);
+    } else if (err) {
+      clear[pix] = 0xFFFFFFFFu;
+      if (ao) ao[pix] = __builtin_nanf("");
+    } else {
+      ao_store(g, ao_classify(feat, pix), plane[pix], pix, clear, ao);
+    }
+  }
 }
 
 // First-hit feature buffers (zrt_ctx_features): one lane per pixel of the whole
@@ -4638,6 +4785,28 @@ hipError_t launch_trace_finish(hipStream_t st, float* t, int32_t* prim, uint32_t
 }
 hipError_t launch_anyhit_error(hipStream_t st, uint8_t* out, uint32_t n, const unsigned long long* error_flag) {
   return launch(anyhit_error_kernel, (n + 255) / 256, 256, st, out, n, error_flag);
+}
+// Ambient occlusion (ao.cpp), after the queries': ao_kernel by traversal mode (as anyhit_kernel), PRNG and
+// stack width.
+void* ao_kernel_ptr(int mode, uint32_t prng, bool stk16) {
+#ifdef ZRT_ISA_KERNEL
+  (void)mode; (void)prng; (void)stk16;
+  return nullptr;
+#else
+#define ZRT_AO_S(M, R) (stk16 ? reinterpret_cast<void*>(&ao_kernel<M, R, uint16_t>) \
+                              : reinterpret_cast<void*>(&ao_kernel<M, R, uint32_t>))
+#define ZRT_AO(M) (prng == ZRT_PRNG_XOSHIRO256 ? ZRT_AO_S(M, ZRT_PRNG_XOSHIRO256) : ZRT_AO_S(M, ZRT_PRNG_XOROSHIRO128))
+  return mode == 0 ? ZRT_AO(0) : mode == 1 ? ZRT_AO(1) : mode == 2 ? ZRT_AO(2) : ZRT_AO(3);
+#undef ZRT_AO
+#undef ZRT_AO_S
+#endif
+}
+hipError_t launch_ao_finish(hipStream_t st, const AoArgs& g, uint32_t width, uint32_t height, uint32_t xbound,
+                            const float4* feat, uint32_t* clear, float* ao, const uint32_t* plane,
+                            const unsigned long long* error_flag) {
+  const uint64_t n_px = uint64_t(width) * height;
+  const uint32_t grid = uint32_t(n_px + 255 < 4096ull * 256 ? (n_px + 255) / 256 : 4096);
+  return launch(ao_finish_kernel, grid, 256, st, g, width, height, xbound, feat, clear, ao, plane, error_flag);
 }
 
 const KernelConfig& kernel_config() {
