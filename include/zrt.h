@@ -1083,6 +1083,115 @@ typedef struct zrt_ao_plan {
 } zrt_ao_plan;
 int zrt_debug_ao_plan(const zrt_params* params, const zrt_ao* ao, uint32_t cu_count, zrt_ao_plan* out);
 
+/* ---- radiance queries: rayColor along caller-supplied rays -------------------- *
+ * The last member of the query family: what colour rayColor returns along a ray, so a
+ * caller can bring any camera (orthographic, fisheye, thin lens, a panorama, light
+ * probes, irradiance at surface points) as a buffer of rays.  Inputs are n rays {origin
+ * xyz, direction xyz} as zrt_ctx_trace takes them; Ray.init normalises the direction
+ * (ray.zig:11-13).  Ray i of a call has index R = first_ray + i, a 64-bit value with
+ * first_ray + n <= 2^48.  For sample s = first_sample .. first_sample + n_samples - 1 of
+ * ray R:
+ *   key = ((R << 16) | s) + seed * 0x9E3779B97F4A7C15   (the counter mode's key, R in the
+ *                                                        pixel's place)
+ *   rng = DefaultPrng.init(key) of params->prng
+ *   two floats are drawn and dropped                     (the pixel jitter of raytrace.zig:173-174)
+ *   col = rayColor(Ray.init(origin, direction), max_depth) on that stream (raytrace.zig:62-100)
+ * Dropping the two floats makes ray R the pixel with offset R of a frame whose camera
+ * maps every pixel onto that ray (horizontal = vertical = 0, origin = o,
+ * lower_left_corner = o + d): the oracle's own pixel, chunking and counters included.
+ *
+ * Traversal: params->traversal selects it; the surface list is used without a BVH; FAST
+ * walks the full 128-B nodes with the grazing-triangle guard on, as the other queries.
+ * Chunks: c is the sample chunk in use (sample_chunk, or 32 for 0).  Chunk j of the call
+ * holds samples first_sample + j c ..; its sum S_j is taken sequentially from 0 in sample
+ * order; the last chunk may be ragged.  sum = ((sum0 + S_0) + S_1) + ... per channel, in
+ * f32 with nothing fused.  Without ZRT_RQ_ACCUMULATE sum0 = 0; with it sum0 is the
+ * caller's dev_sum and first_sample % c == 0 is required, so calls over [0, 8) and
+ * [8, 16) at c = 4 or 8 equal one call over [0, 16) bit for bit.  rgb = sum * (1.0f /
+ * float(N)) per channel (raytrace.zig:157, 182), N = n_samples, or first_sample +
+ * n_samples under the flag.
+ *
+ * dev_rays: n * 6 f32; dev_sum: n float4 {r, g, b, 0}, 16-byte aligned; dev_rgb: n * 3
+ * f32, or NULL.  Asynchronous on hip_stream (NULL: the context's own).  n == 0: ZRT_OK,
+ * nothing is enqueued.  params is validated as the queries validate it; traversal, prng,
+ * seed, max_depth, sample_chunk, device and bounded_volume_hierarchy are read; width,
+ * height, samples_per_pixel and flags are not.  ZRT_E_INVALID before any device work:
+ * n_samples == 0, first_sample + n_samples > 65536 (the key's sample field), first_ray +
+ * n > 2^48, an unknown flag, ZRT_RQ_ACCUMULATE with first_sample % c != 0, a null or
+ * misaligned pointer (dev_rays, dev_rgb: 4 bytes), params that do not fit the context.
+ *
+ * It is a query (see "ray queries"): its stack and attenuation rows, counters, error
+ * flag, completion and events are the query's; it disturbs no render, run, feature
+ * launch or zrt_ctx_stats; one query is in flight per context.  After a traversal stack
+ * overflow every sum.rgb and rgb of the call is NaN, zrt_ctx_sync reports
+ * ZRT_E_UNSUPPORTED once, and the context stays usable. */
+enum { ZRT_RQ_ACCUMULATE = 1u };
+/* (A struct tag only, no typedef: the one-shot entry point below bears the same name, and a
+ * tag and a function share it in C and in C++; write `struct zrt_radiance`.) */
+struct zrt_radiance {
+  uint32_t n_samples;     /* samples per ray in this call, >= 1 */
+  uint32_t first_sample;  /* index of this call's sample 0 in the ray's stream */
+  uint64_t first_ray;     /* R of the call's ray 0 */
+  uint32_t flags;         /* ZRT_RQ_* */
+  uint32_t reserved[3];
+};
+/* The last radiance call of the context (waits for it).  rays = samples + reflections -
+ * recursion_depth_hits: every sample traces a ray unless max_depth is 0, and every
+ * scatter one more unless the depth has run out.  kernel_ms: between the events around
+ * the call's kernels (zrt_ctx_query_ms). */
+typedef struct zrt_radiance_info {
+  uint64_t samples, rays, reflections, background_hits, recursion_depth_hits;
+  double kernel_ms;
+} zrt_radiance_info;
+int zrt_ctx_radiance(zrt_ctx* ctx, const zrt_params* params, const struct zrt_radiance* rq, const float* dev_rays,
+                     uint32_t n, float* dev_sum, float* dev_rgb, void* hip_stream);
+int zrt_ctx_radiance_info(zrt_ctx* ctx, zrt_radiance_info* out);
+/* Tests: of the last radiance call of the context (waits for it) - out[0] the attenuation
+ * rows its plan kept in LDS, out[1] the most rows any of its paths pushed (more than
+ * out[0]: rows in global memory were used), out[2] the stack rows in LDS, out[3] its grid. */
+int zrt_ctx_debug_radiance(zrt_ctx* ctx, uint32_t out[4]);
+
+/* One-shot, host pointers: a context, the call, the copies out.  sum (n float4) is read
+ * first under ZRT_RQ_ACCUMULATE (NULL: zeros) and written back; it, out_rgb (n * 3 f32)
+ * and info may be NULL. */
+int zrt_radiance(const zrt_scene* scene, const zrt_params* params, const struct zrt_radiance* rq, const float* rays,
+                 uint32_t n, float* sum, float* out_rgb, zrt_radiance_info* info);
+
+/* How zrt_ctx_radiance launches (no device; the launch path calls the same function).  A
+ * work item is one (ray, chunk).  The call's chunks are served in rounds; within a round
+ * item k is ray k % n of the round's chunk k / n, so a wave holds 64 consecutive items,
+ * rays of one chunk wherever n is a multiple of 64.  The grid is bounded by the CU count
+ * and each block loops over its items with 64-bit indices, so the stack's and the
+ * attenuation's overflow rows are sized by the resident lanes, never by the rays.  The
+ * chunk sums of a round are parked in [chunk][ray]; a finishing kernel folds them into
+ * dev_sum in chunk order.  Rounds keep the parked sums under partial_cap_bytes (0: the
+ * default, 256 MiB; one chunk of every ray is parked whatever the cap).  Refuses what
+ * zrt_ctx_radiance refuses of params, rq and n.  The launch reads ZRT_RADIANCE_PARTIAL_CAP
+ * (bytes) and ZRT_RADIANCE_GRID (blocks) from the environment: test knobs, like
+ * ZRT_DEBUG_STACK_CAP. */
+typedef struct zrt_radiance_plan {
+  uint64_t items;           /* n x call_chunks */
+  uint64_t partial_bytes;   /* the parked sums of one round: n x chunks_per_round x 16 */
+  uint64_t resident_lanes;  /* grid x 256: the stride and the count of the overflow rows' lanes */
+  uint64_t key_offset;      /* (first_ray << 16) + seed * 0x9E3779B97F4A7C15: key = ((i << 16) | s) + key_offset */
+  uint32_t chunk;           /* c */
+  uint32_t call_chunks;     /* ceil(n_samples / c) */
+  uint32_t last_chunk;      /* samples of the call's last chunk, 1 .. c */
+  uint32_t chunks_per_round, rounds;
+  uint32_t grid;            /* blocks launched for a full round: min(ceil(n x chunks_per_round / 256), blocks_per_cu x cu_count) */
+  uint32_t blocks_per_cu;
+  uint32_t reserved;
+} zrt_radiance_plan;
+int zrt_debug_radiance_plan(const zrt_params* params, const struct zrt_radiance* rq, uint32_t n, uint32_t cu_count,
+                            uint64_t partial_cap_bytes, zrt_radiance_plan* out);
+
+/* Rays of an equirectangular panorama from a point (host only): width * height * 6 f32,
+ * pixel (x, y) at index y * width + x, row 0 the bottom.  phi = 2 pi (x + 0.5) / width,
+ * theta = pi (y + 0.5) / height measured from -y; d = (sin(theta) cos(phi), -cos(theta),
+ * sin(theta) sin(phi)), computed in double and rounded to f32; the origin is copied
+ * unchanged. */
+int zrt_rays_equirect(const float origin[3], uint32_t width, uint32_t height, float* out_rays);
+
 /* ---- host-side scene ingestion (the caller side of the seam) ------------- *
  * Restatement of scenes.zig / obj_reader.zig / png_image.zig texture loading
  * so tests and bench can build the reference's scenes without Zig.  Assets are

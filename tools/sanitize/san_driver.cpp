@@ -11,6 +11,8 @@
 //   planner.cpp, flatten.cpp, debug_plans.cpp  the LDS / buffer / launch / pass /
 //                  adaptive planners and the scene flattener, through the zrt_debug_*
 //                  entry points that need no device; the per-tile walk directly
+//   radiance.cpp   its part that needs no device (-DZRT_PLAN_ONLY): plan_radiance through
+//                  zrt_debug_radiance_plan, zrt_rays_equirect
 //   oracle/        oracle_render (both RNG modes), oracle_render_scanlines,
 //                  oracle_trace, oracle_bvh_build
 //
@@ -277,6 +279,70 @@ static void pass_and_adapt_plans() {
             zrt_debug_adapt_plan(&p3, &ad, nullptr, 8, &n) == ZRT_E_INVALID &&
             zrt_debug_adapt_plan(&p3, &ad, nullptr, 0, nullptr) == ZRT_E_INVALID,
         "adapt plan: null arguments accepted");
+}
+
+// plan_radiance at the edge values of tests/test_radiance_plan.py: chunking, items past 32
+// bits, rounds under a cap, the grid bound, every refusal; the equirectangular generator
+// writing exactly width * height * 6 floats (the buffer is that long: a write past it aborts)
+static void radiance_plans() {
+  struct Case { uint32_t n, samples, first_sample; uint64_t first_ray; uint32_t flags, chunk, cu; uint64_t cap; bool ok; };
+  const Case cases[] = {{100, 9, 0, 0, 0, 4, 256, 0, true},
+                        {0xffffffffu, 4096, 0, 0, 0, 2, 256, 0, true},
+                        {257, 9, 0, 0, 0, 4, 1, 257 * 16, true},
+                        {1u << 20, 64, 0, 0, 0, 4, 256, 1, true},
+                        {0, 5, 0, 0, 0, 2, 256, 0, true},
+                        {4, 1, 65535, 0, 0, 0, 256, 0, true},
+                        {3, 1, 0, (1ull << 48) - 3, 0, 0, 256, 0, true},
+                        {4, 4, 8, 0, ZRT_RQ_ACCUMULATE, 4, 256, 0, true},
+                        {4, 0, 0, 0, 0, 4, 256, 0, false},
+                        {4, 2, 65535, 0, 0, 4, 256, 0, false},
+                        {4, 1, 0, (1ull << 48) - 3, 0, 4, 256, 0, false},
+                        {4, 1, 0, ~0ull, 0, 4, 256, 0, false},
+                        {4, 1, 0, 0, 2, 4, 256, 0, false},
+                        {4, 4, 6, 0, ZRT_RQ_ACCUMULATE, 4, 256, 0, false},
+                        {4, 1, 0, 0, 0, 4, 0, 0, false}};
+  for (const Case& c : cases) {
+    zrt_params p = params(1, 1, 1, 8, ZRT_RNG_COUNTER);
+    p.sample_chunk = c.chunk;
+    struct zrt_radiance rq;
+    std::memset(&rq, 0, sizeof(rq));
+    rq.n_samples = c.samples;
+    rq.first_sample = c.first_sample;
+    rq.first_ray = c.first_ray;
+    rq.flags = c.flags;
+    zrt_radiance_plan plan;
+    const int rc = zrt_debug_radiance_plan(&p, &rq, c.n, c.cu, c.cap, &plan);
+    const bool fine = c.ok ? rc == ZRT_OK && plan.items == uint64_t(c.n) * plan.call_chunks &&
+                                 (c.n == 0 || (plan.grid >= 1 && plan.grid <= plan.blocks_per_cu * c.cu &&
+                                               uint64_t(plan.rounds) * plan.chunks_per_round >= plan.call_chunks &&
+                                               plan.partial_bytes == uint64_t(c.n) * plan.chunks_per_round * 16))
+                           : rc == ZRT_E_INVALID;
+    CHECK(fine, "radiance plan n %u samples %u first %u flags %u: rc %d", c.n, c.samples, c.first_sample, c.flags, rc);
+  }
+  zrt_params p = params(1, 1, 1, 8, ZRT_RNG_COUNTER);
+  struct zrt_radiance rq;
+  std::memset(&rq, 0, sizeof(rq));
+  rq.n_samples = 1;
+  zrt_radiance_plan plan;
+  CHECK(zrt_debug_radiance_plan(nullptr, &rq, 1, 1, 0, &plan) == ZRT_E_INVALID &&
+            zrt_debug_radiance_plan(&p, nullptr, 1, 1, 0, &plan) == ZRT_E_INVALID &&
+            zrt_debug_radiance_plan(&p, &rq, 1, 1, 0, nullptr) == ZRT_E_INVALID,
+        "radiance plan: null arguments accepted");
+  const float origin[3] = {1.5f, -2.0f, 0.25f};
+  for (uint32_t w : {1u, 4u, 7u}) {
+    const uint32_t h = w == 4 ? 2 : 3;
+    std::vector<float> rays(size_t(w) * h * 6);
+    CHECK(zrt_rays_equirect(origin, w, h, rays.data()) == ZRT_OK, "equirect %ux%u: %s", w, h, zrt_last_error());
+    bool unit = true;
+    for (size_t i = 0; i < size_t(w) * h; ++i) {
+      const float* r = &rays[6 * i];
+      const double l = double(r[3]) * r[3] + double(r[4]) * r[4] + double(r[5]) * r[5];
+      unit = unit && std::fabs(l - 1.0) < 1e-6 && r[0] == origin[0] && r[1] == origin[1] && r[2] == origin[2];
+    }
+    CHECK(unit, "equirect %ux%u: a direction is not a unit vector or an origin moved", w, h);
+  }
+  CHECK(zrt_rays_equirect(origin, 0, 2, nullptr) == ZRT_E_INVALID && zrt_rays_equirect(nullptr, 1, 1, nullptr) == ZRT_E_INVALID,
+        "equirect: bad arguments accepted");
 }
 
 // plan_reproject at the cases of tests/test_temporal_host.py: a scene's camera, the
@@ -670,6 +736,7 @@ int main(int argc, char** argv) {
   const std::string assets = argv[1], tmp = argv[2];
   for (uint32_t i : {0u, 1u, 2u, 3u, 4u}) one_scene(i, assets, tmp);
   pass_and_adapt_plans();
+  radiance_plans();
   reproject_plans(assets);
   tile_walks();
   degenerate::all();

@@ -21,7 +21,7 @@ from ._ffi import (ZRT_PRNG_XOROSHIRO128, ZRT_PRNG_XOSHIRO256, ZRT_RNG_COUNTER, 
                    ZRT_RNG_REFERENCE_STREAM, ZRT_TRAVERSAL_FAST, ZRT_TRAVERSAL_REFERENCE,
                    ZRT_TRAVERSAL_BINARY, ZRT_FLAG_STATS, ZRT_FLAG_NO_SCHEDULE, ZRT_FLAG_SCANLINES, ZRT_FLAG_GUARD,
                    ZRT_DN_DEMODULATE, ZRT_TA_DEMODULATE, ZRT_AO_ACCUMULATE, ZRT_AO_REDUCE_WAVE, ZRT_AO_REDUCE_ATOMIC,
-                   ZrtError, check)
+                   ZRT_RQ_ACCUMULATE, ZrtError, check)
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ASSETS = os.path.join(REPO, "assets")
@@ -498,6 +498,60 @@ def debug_ao_plan(params: RenderParams, ao: _ffi.Ao, cu_count: int = 256) -> dic
     return out.as_dict()
 
 
+def radiance_settings(n_samples: int, first_sample: int = 0, first_ray: int = 0, flags: int = 0) -> _ffi.Radiance:
+    """A zrt_radiance: n_samples samples per ray, the ray's samples first_sample .. ; the
+    call's ray 0 has index first_ray; flags: ZRT_RQ_ACCUMULATE."""
+    return _ffi.Radiance(n_samples=n_samples, first_sample=first_sample, first_ray=first_ray, flags=flags)
+
+
+def _rays6(origins, directions) -> np.ndarray:
+    return np.ascontiguousarray(np.concatenate([np.asarray(origins, np.float32).reshape(-1, 3),
+                                                np.asarray(directions, np.float32).reshape(-1, 3)], axis=1))
+
+
+def radiance(scene, params: RenderParams, origins, directions, n_samples: int, first_sample: int = 0,
+             first_ray: int = 0, sum=None):
+    """What rayColor returns along each ray, averaged over n_samples samples (zrt_radiance; the
+    definition: zrt.h "radiance queries").  params gives traversal, prng, seed, max_depth and
+    sample_chunk.  sum (float32[n, 4]): the sums of samples [0, first_sample) the call adds onto
+    (ZRT_RQ_ACCUMULATE); updated in place.  Returns (rgb float32[n, 3], info dict)."""
+    view = scene.view if isinstance(scene, LoadedScene) else scene
+    rays = _rays6(origins, directions)
+    n = rays.shape[0]
+    rgb = np.zeros((n, 3), np.float32)
+    rq = radiance_settings(n_samples, first_sample, first_ray, ZRT_RQ_ACCUMULATE if sum is not None else 0)
+    if sum is not None and (sum.dtype != np.float32 or sum.shape != (n, 4) or not sum.flags.c_contiguous):
+        raise ValueError("sum must be a C-contiguous float32[n, 4]")
+    info = _ffi.RadianceInfo()
+    p = params.abi()
+    f = C.POINTER(C.c_float)
+    check(lib().zrt_radiance(view, C.byref(p), C.byref(rq), rays.ctypes.data_as(f), n,
+                             sum.ctypes.data_as(f) if sum is not None else None, rgb.ctypes.data_as(f),
+                             C.byref(info)))
+    return rgb, info.as_dict()
+
+
+def debug_radiance_plan(params: RenderParams, rq: _ffi.Radiance, n: int, cu_count: int = 256,
+                        partial_cap_bytes: int = 0) -> dict:
+    """How zrt_ctx_radiance launches n rays with these params and settings on a device of
+    cu_count CUs (zrt_debug_radiance_plan; no device): chunks, items, rounds, parked bytes,
+    grid and resident lanes.  Raises ZrtError for what the call would refuse."""
+    out = _ffi.RadiancePlan()
+    p = params.abi()
+    check(lib().zrt_debug_radiance_plan(C.byref(p), C.byref(rq), n, cu_count, partial_cap_bytes, C.byref(out)))
+    return out.as_dict()
+
+
+def rays_equirect(origin, width: int, height: int) -> np.ndarray:
+    """Rays of an equirectangular panorama from a point (zrt_rays_equirect; host only):
+    float32[height, width, 6] {origin, direction}, row 0 the bottom."""
+    o = np.ascontiguousarray(np.asarray(origin, np.float32).reshape(3))
+    out = np.zeros((max(height, 0), max(width, 0), 6), np.float32)
+    f = C.POINTER(C.c_float)
+    check(lib().zrt_rays_equirect(o.ctypes.data_as(f), width, height, out.ctypes.data_as(f)))
+    return out
+
+
 class RenderContext:
     """Device-resident scene (zrt_ctx_*): build + upload once, render many."""
 
@@ -593,6 +647,29 @@ class RenderContext:
         p = params.abi()
         check(lib().zrt_ctx_ao(self._h, C.byref(camera), C.byref(p), C.byref(ao), C.c_void_p(dev_features or None),
                                C.c_void_p(dev_clear or None), C.c_void_p(dev_ao or None), C.c_void_p(stream or None)))
+
+    def radiance(self, params: RenderParams, rq: _ffi.Radiance, dev_rays: int, n: int, dev_sum: int,
+                 dev_rgb: int = 0, stream: int = 0):
+        """rayColor along n rays on the resident scene (zrt_ctx_radiance; device pointers,
+        asynchronous): rays n x {origin, direction} f32; dev_sum n float4 {r, g, b, 0} receives
+        the sample sums (read first under ZRT_RQ_ACCUMULATE), dev_rgb (0: not wanted) n x 3 f32
+        their mean."""
+        p = params.abi()
+        check(lib().zrt_ctx_radiance(self._h, C.byref(p), C.byref(rq), C.c_void_p(dev_rays or None), n,
+                                     C.c_void_p(dev_sum or None), C.c_void_p(dev_rgb or None),
+                                     C.c_void_p(stream or None)))
+
+    def radiance_info(self) -> dict:
+        """The last radiance() call's counters and kernel time (zrt_ctx_radiance_info; waits for it)."""
+        out = _ffi.RadianceInfo()
+        check(lib().zrt_ctx_radiance_info(self._h, C.byref(out)))
+        return out.as_dict()
+
+    def debug_radiance(self) -> dict:
+        """The last radiance() call's plan and deepest path (zrt_ctx_debug_radiance; waits for it)."""
+        out = (C.c_uint32 * 4)()
+        check(lib().zrt_ctx_debug_radiance(self._h, out))
+        return dict(zip(("att_lds_rows", "deepest_path_rows", "stack_lds_rows", "grid"), out))
 
     def ao_ms(self) -> float:
         """Device time of the last ao() kernel in ms (zrt_ctx_ao_ms; waits for it)."""

@@ -38,6 +38,7 @@ ZRT_DN_DEMODULATE = 1
 ZRT_TA_DEMODULATE = 1
 ZRT_AO_ACCUMULATE = 1
 ZRT_AO_REDUCE_WAVE, ZRT_AO_REDUCE_ATOMIC = 0, 1
+ZRT_RQ_ACCUMULATE = 1
 
 
 class Vec3(C.Structure):
@@ -213,6 +214,29 @@ class AoPlan(C.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_ if name != "reserved"}
 
 
+class Radiance(C.Structure):
+    _fields_ = [("n_samples", C.c_uint32), ("first_sample", C.c_uint32), ("first_ray", C.c_uint64),
+                ("flags", C.c_uint32), ("reserved", C.c_uint32 * 3)]
+
+
+class RadianceInfo(C.Structure):
+    _fields_ = [("samples", C.c_uint64), ("rays", C.c_uint64), ("reflections", C.c_uint64),
+                ("background_hits", C.c_uint64), ("recursion_depth_hits", C.c_uint64), ("kernel_ms", C.c_double)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
+class RadiancePlan(C.Structure):
+    _fields_ = [("items", C.c_uint64), ("partial_bytes", C.c_uint64), ("resident_lanes", C.c_uint64),
+                ("key_offset", C.c_uint64), ("chunk", C.c_uint32), ("call_chunks", C.c_uint32),
+                ("last_chunk", C.c_uint32), ("chunks_per_round", C.c_uint32), ("rounds", C.c_uint32),
+                ("grid", C.c_uint32), ("blocks_per_cu", C.c_uint32), ("reserved", C.c_uint32)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_ if name != "reserved"}
+
+
 class BvhNode(C.Structure):
     _fields_ = [("min", Vec3), ("left", C.c_int32), ("max", Vec3), ("right", C.c_int32)]
 
@@ -309,6 +333,14 @@ SIGNATURES = [
     ("zrt_render_ao", C.c_int, [C.POINTER(Scene), C.POINTER(Camera), C.POINTER(Params), C.POINTER(Ao),
                                 C.POINTER(C.c_float), C.POINTER(C.c_uint32), C.POINTER(C.c_float)]),
     ("zrt_debug_ao_plan", C.c_int, [C.POINTER(Params), C.POINTER(Ao), C.c_uint32, C.POINTER(AoPlan)]),
+    ("zrt_ctx_radiance", C.c_int, [_P, C.POINTER(Params), C.POINTER(Radiance), _P, C.c_uint32, _P, _P, _P]),
+    ("zrt_ctx_radiance_info", C.c_int, [_P, C.POINTER(RadianceInfo)]),
+    ("zrt_ctx_debug_radiance", C.c_int, [_P, C.POINTER(C.c_uint32)]),
+    ("zrt_radiance", C.c_int, [C.POINTER(Scene), C.POINTER(Params), C.POINTER(Radiance), C.POINTER(C.c_float),
+                               C.c_uint32, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(RadianceInfo)]),
+    ("zrt_debug_radiance_plan", C.c_int, [C.POINTER(Params), C.POINTER(Radiance), C.c_uint32, C.c_uint32, C.c_uint64,
+                                          C.POINTER(RadiancePlan)]),
+    ("zrt_rays_equirect", C.c_int, [C.POINTER(C.c_float), C.c_uint32, C.c_uint32, C.POINTER(C.c_float)]),
     ("zrt_scene_load", C.c_int, [C.c_uint32, C.c_char_p, C.POINTER(_P), C.POINTER(Camera)]),
     ("zrt_scene_view", C.POINTER(Scene), [_P]),
     ("zrt_scene_free", None, [_P]),

@@ -41,6 +41,9 @@
 // $ZRT_AO_SAMPLES=n [$ZRT_AO_RADIUS=r] $ZRT_AO_OUT=<file.png> also writes the frame's
 // ambient-occlusion plane (zrt_render_ao: n rays per pixel, radius r, default +inf) as a
 // grey PNG, beside any mode above; the frame's own output is unchanged.
+// $ZRT_PANORAMA_OUT=<file.png> [$ZRT_PANORAMA_WIDTH=w, default 512] also writes a w x w/2
+// equirectangular panorama from the scene camera's origin (zrt_rays_equirect + zrt_radiance,
+// with the run's samples, depth, seed, PRNG and traversal), beside any mode above.
 #include <unistd.h>
 
 #include <chrono>
@@ -314,6 +317,28 @@ int main(int argc, char** argv) {
     }
   }
 
+  // $ZRT_PANORAMA_OUT=file.png [$ZRT_PANORAMA_WIDTH=w]: also write a panorama; checked here,
+  // before anything is rendered (zrt_debug_radiance_plan: no device)
+  const char* pano_out = std::getenv("ZRT_PANORAMA_OUT");
+  uint32_t pano_w = 512;
+  struct zrt_radiance pano_rq;
+  std::memset(&pano_rq, 0, sizeof(pano_rq));
+  pano_rq.n_samples = samples;
+  if (pano_out || std::getenv("ZRT_PANORAMA_WIDTH")) {
+    const char* w = std::getenv("ZRT_PANORAMA_WIDTH");
+    char* end = nullptr;
+    const unsigned long v = w ? std::strtoul(w, &end, 10) : pano_w;
+    zrt_radiance_plan plan;
+    if (!pano_out || (w && (*end != '\0' || end == w)) || v < 2 || v > 16384 || v % 2 != 0 ||
+        zrt_debug_radiance_plan(&ao_params, &pano_rq, uint32_t(v * (v / 2)), 1, 0, &plan) != ZRT_OK) {
+      std::fprintf(stderr, "error: the panorama needs ZRT_PANORAMA_OUT=<file.png>, an even ZRT_PANORAMA_WIDTH of 2 .. 16384 "
+                           "and one sample or more\n");
+      zrt_scene_free(data);
+      return 1;
+    }
+    pano_w = uint32_t(v);
+  }
+
   std::fprintf(stderr, "Raytrace start\n");
   std::fprintf(stderr, " - Surfaces:                 %u\n", scene->n_prims);
   std::fprintf(stderr, " - Pixels:                   %ux%u\n", unsigned(width), unsigned(height));
@@ -432,6 +457,20 @@ int main(int argc, char** argv) {
     for (size_t i = 0; i < plane.size(); ++i) grey[3 * i] = grey[3 * i + 1] = grey[3 * i + 2] = plane[i];
     if (rc == ZRT_OK) rc = zrt_image_write_png(ao_out, grey.data(), width, height);
     if (rc == ZRT_OK) std::fprintf(stderr, "  Ambient occlusion:     %u rays per pixel -> %s\n", ao.n_samples, ao_out);
+  }
+  // $ZRT_PANORAMA_OUT: what the scene camera's origin sees in every direction (zrt_radiance, a
+  // launch of its own on the first GPU); the frame above is what it was without it
+  if (pano_out && rc == ZRT_OK) {
+    const uint32_t pano_h = pano_w / 2, n = pano_w * pano_h;
+    std::vector<float> rays(size_t(n) * 6), pano(size_t(n) * 3);
+    const float origin[3] = {camera.origin.x, camera.origin.y, camera.origin.z};
+    rc = zrt_rays_equirect(origin, pano_w, pano_h, rays.data());
+    zrt_radiance_info info;
+    if (rc == ZRT_OK) rc = zrt_radiance(scene, &ao_params, &pano_rq, rays.data(), n, nullptr, pano.data(), &info);
+    if (rc == ZRT_OK) rc = zrt_image_write_png(pano_out, pano.data(), pano_w, pano_h);
+    if (rc == ZRT_OK)
+      std::fprintf(stderr, "  Panorama:              %ux%u, %u samples per ray, %llu rays -> %s\n", pano_w, pano_h,
+                   pano_rq.n_samples, (unsigned long long)info.rays, pano_out);
   }
   zrt_scene_free(data);
   if (rc != ZRT_OK) {

@@ -141,8 +141,9 @@ static void fill_lds(KArgs& a, const LdsPlan& lp) {
 
 // The launch of zrt_trace and zrt_ctx_features: one lane per ray over the loop's own
 // traversal (FAST: over the compressed nodes where the context built them, MODE 8),
-// with the grazing-triangle guard, any ray origin and no attenuation rows.
-TracePlan fill_trace(KArgs& a, const zrt_ctx* c, uint32_t traversal, bool full_nodes) {
+// with the grazing-triangle guard, any ray origin and no attenuation rows (max_depth 0;
+// the radiance query plans rows for its paths).
+TracePlan fill_trace(KArgs& a, const zrt_ctx* c, uint32_t traversal, bool full_nodes, uint32_t max_depth) {
   const Scene& s = c->scene;
   const int mode = !s.shape.use_bvh ? 0 : traversal == ZRT_TRAVERSAL_REFERENCE ? 2 : traversal == ZRT_TRAVERSAL_BINARY ? 1 : 3;
   const uint32_t stack_depth = mode == 3 ? std::max(s.shape.wide_stack, s.shape.stack_depth) : s.shape.stack_depth;
@@ -150,7 +151,7 @@ TracePlan fill_trace(KArgs& a, const zrt_ctx* c, uint32_t traversal, bool full_n
   TracePlan t;
   t.kmode = qn ? 8 : mode;
   t.stk16 = mode == 3 ? fast_stk16(s.shape.n_wide, s.shape.n_nodes) : s.shape.n_nodes < 65536;
-  t.lp = plan_lds(qn ? s.shape.q_top : s.shape.n_top, s.shape.n_mats, mode, t.stk16, stack_depth, 0, false, false,
+  t.lp = plan_lds(qn ? s.shape.q_top : s.shape.n_top, s.shape.n_mats, mode, t.stk16, stack_depth, max_depth, false, false,
                   ZRT_PRNG_XOROSHIRO128, qn ? kQuantNodeF4 : 8u);
   fill_scene(a, c, qn, stack_depth);
   fill_lds(a, t.lp);

@@ -1,5 +1,5 @@
 // context.hpp - private to the host files that talk to the HIP runtime
-// (context.cpp, runs.cpp, post.cpp, queries.cpp, ao.cpp, debug_device.cpp, multi.cpp, oneshot.cpp): the
+// (context.cpp, runs.cpp, post.cpp, queries.cpp, ao.cpp, radiance.cpp, debug_device.cpp, multi.cpp, oneshot.cpp): the
 // HIP error type, the owning handles, the context behind zrt_ctx_*, what those
 // files share of its launch path, and the catch clauses of their entry points.
 #pragma once
@@ -272,6 +272,16 @@ struct QueryState {
   Completion done;
   StepTimer timer;
   DevBuf<uint32_t> ao_plane;  // zrt_ctx_ao's count plane (the atomic reduction), zeroed per launch
+  // zrt_ctx_radiance's: attenuation rows past the LDS ones ([row][lane of the grid]), a round's parked
+  // chunk sums ([chunk][ray]), the launch's progress counters (kScratchSlots, zeroed per call) and what
+  // zrt_ctx_radiance_info reports of the last call: its counters behind `done`, its samples
+  DevBuf<uint32_t> att;
+  DevBuf<float4> partial;
+  DevBuf<unsigned long long> counters;
+  Pinned<unsigned long long> counters_host;
+  uint64_t rq_samples = 0;
+  uint32_t rq_att_lds_rows = 0, rq_stack_lds_rows = 0, rq_grid = 0;  // the last call's plan (zrt_ctx_debug_radiance)
+  bool rq_launched = false;
 };
 }  // namespace zrt
 
@@ -339,7 +349,8 @@ struct TracePlan {
   LdsPlan lp;
 };
 // full_nodes: FAST over the full wide nodes even where the context holds compressed ones (any-hit)
-TracePlan fill_trace(KArgs& a, const zrt_ctx* c, uint32_t traversal, bool full_nodes = false);
+// max_depth: the plan's attenuation rows are sized for paths of that depth (0: none, a closest hit alone)
+TracePlan fill_trace(KArgs& a, const zrt_ctx* c, uint32_t traversal, bool full_nodes = false, uint32_t max_depth = 0);
 // The device copy of Scene::slot_to_prim, uploaded on first use (features, queries).
 const uint32_t* slot_prim_table(zrt_ctx* c);
 void trace_rows(KArgs& a, const zrt_ctx* c, const TracePlan& t, uint64_t n_lanes, DevBuf<uint8_t>& ovf, hipStream_t st,
@@ -351,10 +362,10 @@ inline uint32_t query_grid(uint32_t n) { return (n + kBlock - 1) / kBlock; }
 // One query launch of `grid` blocks: the trace plan (FAST any-hit: over the full nodes),
 // the query's own rows (one column per lane of the grid) and error flag, `kernel`
 // between the timer's events, `finish` (what overwrites the outputs of a launch that
-// set the flag), then the flag copied out behind `done`.
+// set the flag), then the flag copied out behind `done`.  max_depth: fill_trace's.
 template <class Kernel, class Finish>
 void launch_query(zrt_ctx* c, const zrt_params* p, uint32_t grid, hipStream_t st, bool anyhit, const char* name,
-                  Kernel&& kernel, Finish&& finish) {
+                  Kernel&& kernel, Finish&& finish, uint32_t max_depth = 0) {
   QueryState& q = c->query;
   const uint64_t n_lanes = uint64_t(grid) * kBlock;
   q.done.create();
@@ -362,7 +373,7 @@ void launch_query(zrt_ctx* c, const zrt_params* p, uint32_t grid, hipStream_t st
   q.timer.e1.create();
   if (!q.err.p) q.err.alloc(1);
   KArgs a{};
-  const TracePlan t = fill_trace(a, c, p->traversal, anyhit);
+  const TracePlan t = fill_trace(a, c, p->traversal, anyhit, max_depth);
   // tests: a stack too small for the tree (the knob of the render launches; the rows stay
   // the uncapped plan's, so a smaller depth only flags pushes it cannot hold)
   if (const char* cap = std::getenv("ZRT_DEBUG_STACK_CAP")) {

@@ -138,6 +138,11 @@ int plan_denoise(const zrt_params* p, const zrt_denoise* dn, DenoiseLaunch* out)
 int plan_reproject(const zrt_camera* prev, const zrt_params* p, zrt_reproject_plan* out);
 int plan_temporal(const zrt_params* p, const zrt_temporal* tp, TemporalLaunch* out);
 
+// ---- radiance.cpp (its part that needs no device) ----
+// zrt_ctx_radiance's refusals of params, rq and n, and its launch (zrt_debug_radiance_plan).
+int plan_radiance(const zrt_params* p, const struct zrt_radiance* rq, uint32_t n, uint32_t cu_count, uint64_t partial_cap,
+                  zrt_radiance_plan* out);
+
 // ---- tile_class.cpp: the all-sky tiles of a frame (DESIGN.md §3 "All-sky tiles") ----
 // A tile's class word: bit 31 (kTileFrozen's bit, so compact_kernel drops such tiles
 // from a tile order) marks a tile no primary ray of which can hit anything; the low

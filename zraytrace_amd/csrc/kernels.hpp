@@ -111,6 +111,16 @@ struct AoArgs {
   float radius;
 };
 
+// radiance_kernel's own arguments for one round (zrt_ctx_radiance; zrt::plan_radiance fills the counts)
+struct RadianceArgs {
+  uint64_t n_items;     // the round's items: n x its chunks; item k is ray k % n of the round's chunk k / n
+  uint64_t key_offset;  // (first_ray << 16) + seed * 0x9E3779B97F4A7C15: key = ((ray << 16) | sample) + key_offset
+  uint32_t n;           // rays
+  uint32_t chunk;       // samples per chunk
+  uint32_t sample0;     // the first sample of the round's chunk 0
+  uint32_t sample_end;  // first_sample + n_samples of the call (the last chunk may be ragged)
+};
+
 // error_flag bits (zrt_ctx_sync / zrt_ctx_stats / zrt_render report them as ZRT_E_UNSUPPORTED)
 constexpr uint32_t kErrOverflow = 1u;  // a traversal stack deeper than it was sized for
 constexpr uint32_t kErrLayout = 2u;    // the wide tree's encoding is not the one this kernel decodes
@@ -159,6 +169,8 @@ constexpr int kVNodeTrips = 32, kVNodeLines = 33, kSNodeTrips = 34, kRbTrips = 3
 
 // zrt_ctx_debug_counters: the tiles the last launch rendered in sky_kernel (filled in on the host)
 constexpr int kSkyTilesSlot = 47;
+// radiance_kernel (the query's own counters): the most attenuation rows any path of the call pushed
+constexpr int kRqDeepestSlot = 44;
 
 constexpr int kBlock = 256;
 // accumulate_kernel / resolve_kernel's metrics: kMetricShards shards, kMetricStride words apart (render.hip)
@@ -197,6 +209,8 @@ void* features_kernel_ptr(int mode, bool stk16);
 void* anyhit_kernel_ptr(int mode, bool stk16);
 // ao_kernel<mode, prng, stack width> (zrt_ctx_ao): anyhit_kernel's modes
 void* ao_kernel_ptr(int mode, uint32_t prng, bool stk16);
+// radiance_kernel<mode, prng, stack width> (zrt_ctx_radiance): anyhit_kernel's modes
+void* radiance_kernel_ptr(int mode, uint32_t prng, bool stk16);
 
 // One launch function per small kernel (the arguments are the kernel's, render.hip).
 hipError_t launch_finalize(hipStream_t st, const float4* partial, float* out, uint32_t n_slots, uint32_t n_chunks,
@@ -232,6 +246,11 @@ hipError_t launch_anyhit_error(hipStream_t st, uint8_t* out, uint32_t n, const u
 hipError_t launch_ao_finish(hipStream_t st, const AoArgs& g, uint32_t width, uint32_t height, uint32_t xbound,
                             const float4* feat, uint32_t* clear, float* ao, const uint32_t* plane,
                             const unsigned long long* error_flag);
+// zrt_ctx_radiance's: n_chunks parked chunk sums ([chunk][ray]) folded into sum in chunk order (from 0 where
+// zero_first); final: rgb = sum * scale, or NaN in sum.rgb and rgb behind a launch that set *error_flag
+hipError_t launch_radiance_finish(hipStream_t st, const float4* partial, uint32_t n, uint32_t n_chunks,
+                                  uint32_t zero_first, float4* sum, float* rgb, float scale, uint32_t final,
+                                  const unsigned long long* error_flag);
 hipError_t launch_debug_math(int fn, const float* x, const float* y, float* out, uint32_t n);
 hipError_t launch_debug_division(uint64_t n, unsigned long long* counts);
 hipError_t launch_debug_rng(uint32_t prng, uint64_t key, unsigned long long* out, uint32_t n);

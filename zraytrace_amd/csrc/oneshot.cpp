@@ -407,3 +407,44 @@ int zrt_render_ao(const zrt_scene* scene, const zrt_camera* camera, const zrt_pa
   }
   ZRT_CATCH_ALL
 }
+
+int zrt_radiance(const zrt_scene* scene, const zrt_params* params, const struct zrt_radiance* rq, const float* rays,
+                 uint32_t n, float* sum, float* out_rgb, zrt_radiance_info* info) {
+  zrt_radiance_plan plan;
+  int rc = zrt::plan_radiance(params, rq, n, 1, 0, &plan);  // (refused before any device work)
+  if (rc) return rc;
+  if (n && !rays) return fail(ZRT_E_INVALID, "null argument");
+  rc = zrt::validate_scene(scene);
+  if (rc) return rc;
+  rc = zrt::check_device(int(params->device));
+  if (rc) return rc;
+  if (n == 0) {
+    if (info) *info = zrt_radiance_info{};
+    return ZRT_OK;
+  }
+  try {
+    const bool use_bvh = params->bounded_volume_hierarchy != 0 && scene->n_prims > 10;
+    zrt::HostScene h;
+    zrt::flatten_for_device(&h, scene, use_bvh, int(params->device));
+    std::unique_ptr<zrt_ctx> c = zrt::ctx_on_device(h, int(params->device));
+    zrt::DevBuf<float> d_rays, d_rgb;
+    zrt::DevBuf<float4> d_sum;
+    d_rays.alloc(6ull * n);
+    d_sum.alloc(n);
+    d_rgb.alloc(3ull * n);
+    HIPCHK(hipMemcpy(d_rays.p, rays, sizeof(float) * 6ull * n, hipMemcpyHostToDevice));
+    if ((rq->flags & ZRT_RQ_ACCUMULATE) && sum)
+      HIPCHK(hipMemcpy(d_sum.p, sum, sizeof(float4) * n, hipMemcpyHostToDevice));
+    else
+      HIPCHK(hipMemset(d_sum.p, 0, sizeof(float4) * n));
+    rc = zrt_ctx_radiance(c.get(), params, rq, d_rays.p, n, reinterpret_cast<float*>(d_sum.p), d_rgb.p, nullptr);
+    if (rc) return rc;
+    rc = zrt_ctx_sync(c.get());  // (a device error of the launch)
+    if (rc) return rc;
+    if (sum) HIPCHK(hipMemcpy(sum, d_sum.p, sizeof(float4) * n, hipMemcpyDeviceToHost));
+    if (out_rgb) HIPCHK(hipMemcpy(out_rgb, d_rgb.p, sizeof(float) * 3ull * n, hipMemcpyDeviceToHost));
+    if (info) return zrt_ctx_radiance_info(c.get(), info);
+    return ZRT_OK;
+  }
+  ZRT_CATCH_ALL
+}

@@ -4616,6 +4616,133 @@ __global__ void debug_rng_kernel(uint64_t key, unsigned long long* out, uint32_t
 }
 
 // ---------------------------------------------------------------------------
+// Radiance queries (zrt_ctx_radiance; zrt.h "radiance queries"): rayColor
+// along caller-supplied rays.  render_loop's sampling loop with its primary ray read from
+// a buffer instead of built by Camera.getRay: the sample's stream is keyed by (ray index,
+// sample), the two jitter floats are drawn and dropped, and each loop trip is one rayColor
+// step - trace_kernel's closest hit (so any origin and any direction are served as there),
+// then shade_step; a path that ends in the sky takes att_product over its rows.
+// A work item is one (ray, chunk) and a lane runs its item's samples on its own, the
+// chunk's sequential sum in registers.  Within a round item k is ray k % n of chunk k / n.
+// The grid is bounded (zrt::plan_radiance): a block loops over its items, block b taking
+// items b * 256 + 256 * grid * t, and its lanes keep one stack column and one column of
+// attenuation rows each (gl) however many rays the call has.  A wave's first item is
+// wave-uniform, so the one 64-bit division is scalar.  The chunk sums are parked in
+// [chunk][ray]; radiance_finish_kernel folds them.  No lane state is parked in LDS across
+// the traversal: the wave is not in lockstep, and closest_hit takes the ray by value.
+// FAST is built for 4 waves per SIMD (128 VGPRs), ao_kernel's occupancy: left to itself the
+// compiler takes 122 (xoroshiro) / 130 (xoshiro) and the latter drops to 3.
+// ---------------------------------------------------------------------------
+template <int MODE, int PRNG, class StackT>
+__global__ void __launch_bounds__(kBlock, MODE == 3 ? 4 : 1) radiance_kernel(const KArgs a, const RadianceArgs g,
+                                                                             const float* __restrict__ rays) {
+  extern __shared__ __attribute__((aligned(16))) char lds_raw[];
+  StackT* stk = reinterpret_cast<StackT*>(lds_raw) + threadIdx.x;
+  float4* lds_top = reinterpret_cast<float4*>(lds_raw + a.lds_top_off);
+  lds_u32* att_l = (lds_u32*)(lds_raw + a.lds_att_off) + threadIdx.x;  // [row][lane] att codes
+  if (MODE == 3 && !layout_ok(a)) return;
+  if (MODE == 3 && ZRT_LDS_TOP) fill_lds_top(a, lds_top);
+  const DevMaterial* mats = a.mats;
+  if (a.mats_in_lds) {  // block-uniform
+    float4* m = reinterpret_cast<float4*>(lds_raw + a.lds_mat_off);
+    fill_lds_mats(a, m);
+    mats = reinterpret_cast<const DevMaterial*>(m);
+  }
+  const uint32_t gl = blockIdx.x * kBlock + threadIdx.x;  // n_lanes < 2^32
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const AttRows ar{att_l, kBlock, gl, a.n_lanes};
+  uint32_t c_refl = 0, c_bg = 0, c_depth = 0, c_shade = 0, c_tex = 0;
+  uint32_t deepest = 0;  // the most attenuation rows a path of this lane pushed (kRqDeepestSlot)
+  Coh coh;
+  for (uint64_t base = (uint64_t)blockIdx.x * kBlock; base < g.n_items; base += (uint64_t)gridDim.x * kBlock) {
+    const uint64_t i0 = base + wave * 64u;  // the wave's first item
+    const uint64_t c0 = i0 / g.n;
+    const uint64_t k = (i0 - c0 * g.n) + lane;  // < n + 64
+    const uint32_t dq = g.n >= 64u ? (k >= g.n ? 1u : 0u) : (uint32_t)k / g.n;
+    const uint32_t ray = (uint32_t)(k - (uint64_t)dq * g.n);
+    const uint64_t cj = c0 + dq;  // the item's chunk within the round
+    if (cj * g.n + ray >= g.n_items) continue;  // past the round's end
+    const uint32_t s_end = min(g.sample0 + ((uint32_t)cj + 1u) * g.chunk, g.sample_end);
+    uint32_t sample = g.sample0 + (uint32_t)cj * g.chunk;
+    const float* q = rays + 6ull * ray;
+    float acc_r = 0.0f, acc_g = 0.0f, acc_b = 0.0f;
+    V3 o = mk(0.0f, 0.0f, 0.0f), d = mk(0.0f, 0.0f, 1.0f);
+    uint32_t depth_left = 0;
+    bool in_sample = false;
+    Rng<PRNG> rng;
+    rng.init(0);
+    for (;;) {
+      if (!in_sample) {  // a new sample: its stream, the dropped jitter, Ray.init (ray.zig:11-13)
+        rng.init((((uint64_t)ray << 16) | (uint64_t)sample) + g.key_offset);
+        (void)rand_float(rng);
+        (void)rand_float(rng);
+        o = mk(q[0], q[1], q[2]);
+        d = unit(mk(q[3], q[4], q[5]));
+        depth_left = a.max_depth;
+        in_sample = true;
+      }
+      // ---- one rayColor step (raytrace.zig:62-100)
+      bool path_end = false, sky = false;
+      V3 L = mk(0.0f, 0.0f, 0.0f);
+      if (depth_left == 0) {
+        ++c_depth;
+        path_end = true;
+      } else {
+        float best_t;
+        int best;
+        closest_hit<MODE, StackT>(a, o, d, stk, lds_top, gl, best_t, best);
+        shade_step<false, Rng<PRNG>>(a, mats, ar, rng, best, best_t, o, d, depth_left, path_end, sky, L, c_bg, c_refl,
+                                     c_shade, c_tex, coh);
+      }
+      if (path_end) {
+        const V3 col = sky ? att_product<false>(a, mats, ar, a.max_depth - depth_left, L, coh) : L;
+        acc_r += col.x;
+        acc_g += col.y;
+        acc_b += col.z;
+        // (shade_step pushes a scatter's row while depth_left > 1: the one at depth 1 is never read)
+        deepest = max(deepest, a.max_depth - depth_left - (depth_left == 0 && a.max_depth != 0 ? 1u : 0u));
+        in_sample = false;
+        if (++sample == s_end) break;  // the chunk's sequential sum is complete
+      }
+    }
+    a.partial[cj * g.n + ray] = make_float4(acc_r, acc_g, acc_b, 0.0f);
+  }
+  wave_add_u64(&a.counters[kDepthHits], c_depth);
+  wave_add_u64(&a.counters[kReflections], c_refl);
+  wave_add_u64(&a.counters[kBackground], c_bg);
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) deepest = max(deepest, (uint32_t)__shfl_xor((int)deepest, off));
+  if (lane == 0 && deepest) atomicMax(&a.counters[kRqDeepestSlot], (unsigned long long)deepest);
+}
+
+// Behind radiance_kernel, one lane per ray: the round's n_chunks parked sums added onto
+// the ray's sum in chunk order (started from 0 where zero_first), each add rounded once.
+// final (after the call's last round): rgb = sum * scale (raytrace.zig:157, 182), or, after
+// a launch that set its error flag (a traversal stack overflow), NaN in sum.rgb and rgb.
+__global__ void radiance_finish_kernel(const float4* __restrict__ partial, uint32_t n, uint32_t n_chunks,
+                                       uint32_t zero_first, float4* __restrict__ sum, float* __restrict__ rgb,
+                                       float scale, uint32_t final,
+                                       const unsigned long long* __restrict__ error_flag) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  float4 s = zero_first ? make_float4(0.0f, 0.0f, 0.0f, 0.0f) : sum[i];
+  for (uint32_t j = 0; j < n_chunks; ++j) {
+    const float4 p = partial[(uint64_t)j * n + i];
+    s.x += p.x;
+    s.y += p.y;
+    s.z += p.z;
+  }
+  if (final && *error_flag != 0ull) s.x = s.y = s.z = __builtin_nanf("");
+  sum[i] = make_float4(s.x, s.y, s.z, 0.0f);
+  if (final && rgb) {
+    rgb[3ull * i + 0] = s.x * scale;
+    rgb[3ull * i + 1] = s.y * scale;
+    rgb[3ull * i + 2] = s.z * scale;
+  }
+}
+
+// ---------------------------------------------------------------------------
 // host side (kernels.hpp): what must see a kernel symbol or a device template
 // ---------------------------------------------------------------------------
 namespace {
@@ -4807,6 +4934,27 @@ hipError_t launch_ao_finish(hipStream_t st, const AoArgs& g, uint32_t width, uin
   const uint64_t n_px = uint64_t(width) * height;
   const uint32_t grid = uint32_t(n_px + 255 < 4096ull * 256 ? (n_px + 255) / 256 : 4096);
   return launch(ao_finish_kernel, grid, 256, st, g, width, height, xbound, feat, clear, ao, plane, error_flag);
+}
+// Radiance queries (radiance.cpp), after AO's: radiance_kernel by traversal mode (as anyhit_kernel), PRNG and
+// stack width.
+void* radiance_kernel_ptr(int mode, uint32_t prng, bool stk16) {
+#ifdef ZRT_ISA_KERNEL
+  (void)mode; (void)prng; (void)stk16;
+  return nullptr;
+#else
+#define ZRT_RQ_S(M, R) (stk16 ? reinterpret_cast<void*>(&radiance_kernel<M, R, uint16_t>) \
+                              : reinterpret_cast<void*>(&radiance_kernel<M, R, uint32_t>))
+#define ZRT_RQ(M) (prng == ZRT_PRNG_XOSHIRO256 ? ZRT_RQ_S(M, ZRT_PRNG_XOSHIRO256) : ZRT_RQ_S(M, ZRT_PRNG_XOROSHIRO128))
+  return mode == 0 ? ZRT_RQ(0) : mode == 1 ? ZRT_RQ(1) : mode == 2 ? ZRT_RQ(2) : ZRT_RQ(3);
+#undef ZRT_RQ
+#undef ZRT_RQ_S
+#endif
+}
+hipError_t launch_radiance_finish(hipStream_t st, const float4* partial, uint32_t n, uint32_t n_chunks,
+                                  uint32_t zero_first, float4* sum, float* rgb, float scale, uint32_t final,
+                                  const unsigned long long* error_flag) {
+  return launch(radiance_finish_kernel, uint32_t((uint64_t(n) + 255) / 256), 256, st, partial, n, n_chunks, zero_first,
+                sum, rgb, scale, final, error_flag);
 }
 
 const KernelConfig& kernel_config() {
