@@ -1192,6 +1192,135 @@ int zrt_debug_radiance_plan(const zrt_params* params, const struct zrt_radiance*
  * unchanged. */
 int zrt_rays_equirect(const float origin[3], uint32_t width, uint32_t height, float* out_rays);
 
+/* ---- camera queries: frames through device-generated lens rays ------------------ *
+ * A radiance query shoots the same ray for every sample of ray R.  A camera query
+ * generates the primary ray of every sample on the device, from a lens model, and uses
+ * the two jitter floats: antialiased frames of any of the models below, depth of field,
+ * and any window of a frame, with the radiance query's chunked sums, accumulation and
+ * counters.
+ *
+ * A call renders the pixel rectangle {x0, y0, w, h} of a width x height frame (width and
+ * height from params, each 1 .. 65535; the whole width is addressable: raytrace.zig:168's
+ * square is not applied).  Pixel (x, y) has index R = y * width + x.  Sample s = first_sample
+ * .. first_sample + n_samples - 1 of it draws
+ *   key  = ((R << 16) | s) + seed * 0x9E3779B97F4A7C15    (the counter mode's key of that
+ *                                                          pixel: the render's own)
+ *   rng  = DefaultPrng.init(key) of params->prng
+ *   r1, r2 = two floats from rng                           (used, not dropped)
+ *   u = ((float(x) + r1) - 0.5f) / float(width)            (IEEE /, raytrace.zig:173-174)
+ *   v = ((float(y) + r2) - 0.5f) / float(height)
+ *   (o, tgt) = model(u, v);  dir = tgt - o per component
+ *   col = rayColor(Ray.init(o, dir), max_depth), continuing on rng
+ * A model that needs lens samples draws them from a second stream,
+ * DefaultPrng.init(key ^ 0xD1B54A32D192ED03), before rng is initialised.
+ * All model arithmetic is f32, nothing fused, in the order written;
+ * P(u, v) = (lower_left_corner + horizontal * u) + vertical * v (Camera.getRay,
+ * camera.zig:47-49).
+ *   ZRT_LENS_PINHOLE   o = origin, tgt = P(u, v): raytrace.zig:173-175, so on the square the
+ *                      render covers the frame is oracle_render's bit for bit.
+ *   ZRT_LENS_THIN      pairs a = 2 f - 1, b = 2 f' - 1 from the lens stream until
+ *                      a a + b b < 1; o = (origin + axis_u * a) + axis_v * b (the lens axes
+ *                      scaled by the lens radius); tgt = P(u, v): the plane is the focal plane.
+ *   ZRT_LENS_ORTHO     o = P(u, v), tgt = o + axis_w.
+ *   ZRT_LENS_EQUIRECT  phi = 6.2831855f * u, theta = 3.1415927f * v; sin and cos as the
+ *                      reference's std.math.sin / cos; d = (sin(theta) cos(phi), -cos(theta),
+ *                      sin(theta) sin(phi)) (zrt_rays_equirect's axes); o = origin, tgt = o + d.
+ *   ZRT_LENS_FISHEYE   equidistant, no masking outside the image circle: px = 2 u - 1,
+ *                      py = 2 v - 1, r = sqrtf(px px + py py), th = r * half_fov; r == 0:
+ *                      d = axis_w, else k = sin(th) / r, d = ((axis_u * (px * k)) + axis_v *
+ *                      (py * k)) + axis_w * cos(th); o = origin, tgt = o + d.
+ *
+ * Traversal, chunks, sums, means, ZRT_CQ_ACCUMULATE and the counters are zrt_ctx_radiance's
+ * word for word, with the pixel in the ray's place: rgb = sum * (1.0f / float(N)).
+ * dev_sum (width * height float4, 16-byte aligned) and dev_rgb (width * height * 3 f32, or
+ * NULL) are whole-frame buffers indexed by R, row 0 at the bottom: dev_rgb is a frame as
+ * zrt_image_write_png and zrt_ctx_denoise take it.  Pixels outside the rectangle are not
+ * touched.  Asynchronous on hip_stream (NULL: the context's own); it is a query: one is in
+ * flight per context, and after a traversal stack overflow the rectangle's pixels are NaN,
+ * zrt_ctx_sync reports ZRT_E_UNSUPPORTED once, and the context stays usable.
+ * params: width, height, traversal, prng, seed, max_depth, sample_chunk, device and
+ * bounded_volume_hierarchy are read.  ZRT_E_INVALID before any device work: an empty
+ * rectangle or one that leaves the frame, an unknown kind or flag, a non-finite descriptor
+ * float, half_fov <= 0 (read by the fisheye alone, checked for every kind), n_samples == 0,
+ * first_sample + n_samples > 65536, ZRT_CQ_ACCUMULATE with first_sample % c != 0, a null or
+ * misaligned pointer, a slot count (8 x 8 tiles over the rectangle x 64) of 2^32 or more,
+ * params that do not fit the context. */
+enum { ZRT_LENS_PINHOLE = 0, ZRT_LENS_THIN = 1, ZRT_LENS_ORTHO = 2, ZRT_LENS_EQUIRECT = 3, ZRT_LENS_FISHEYE = 4 };
+enum { ZRT_CQ_ACCUMULATE = 1u };
+typedef struct zrt_lens {
+  uint32_t kind;                                            /* ZRT_LENS_* */
+  zrt_vec3 origin, lower_left_corner, horizontal, vertical; /* the view (or focal) plane, as zrt_camera */
+  zrt_vec3 axis_u, axis_v, axis_w;                          /* thin: lens axes x radius; ortho, fisheye: the frame */
+  float half_fov;                                           /* fisheye: radians from the axis at |p| = 1; > 0 */
+  uint32_t reserved[2];
+} zrt_lens;
+typedef struct zrt_camera_query {
+  uint32_t x0, y0, w, h;   /* the rectangle, inside the frame, not empty */
+  uint32_t n_samples;      /* samples per pixel in this call, >= 1 */
+  uint32_t first_sample;   /* index of this call's sample 0 in the pixel's stream */
+  uint32_t flags;          /* ZRT_CQ_* */
+  uint32_t reserved[5];
+} zrt_camera_query;
+int zrt_ctx_camera(zrt_ctx* ctx, const zrt_params* params, const zrt_lens* lens, const zrt_camera_query* query,
+                   float* dev_sum, float* dev_rgb, void* hip_stream);
+/* zrt_ctx_radiance_info's fields of the last camera call (waits for it).  The camera query and
+ * the radiance query share one state on a context - rows, parked sums, counters, events - so
+ * each info call, and zrt_ctx_debug_radiance, reports the last call of *either* kind:
+ * zrt_ctx_camera_info after a later zrt_ctx_radiance answers for that radiance call, and
+ * zrt_ctx_radiance_info after a zrt_ctx_camera for the camera call (samples = pixels of the
+ * rectangle x n_samples).  ZRT_E_INVALID before the context's first camera call. */
+int zrt_ctx_camera_info(zrt_ctx* ctx, zrt_radiance_info* out);
+/* One-shot, host pointers: a context, the call, the copies out.  sum (width * height
+ * float4) is read first (NULL: zeros; so pixels outside the rectangle come back as they
+ * went in) and written back; it, out_rgb (width * height * 3 f32, read first likewise) and
+ * info may be NULL. */
+int zrt_render_lens(const zrt_scene* scene, const zrt_params* params, const zrt_lens* lens,
+                    const zrt_camera_query* query, float* sum, float* out_rgb, zrt_radiance_info* info);
+
+/* How zrt_ctx_camera launches (no device; the launch path calls the same function).  Slots
+ * enumerate the rectangle in 8 x 8 tiles anchored at (x0, y0), row-major over the tiles, 64
+ * consecutive slots per tile: slot t * 64 + l is pixel (x0 + 8 (t % tiles_w) + (l & 7),
+ * y0 + 8 (t / tiles_w) + (l >> 3)), so a wave's primary rays are a tile, as in the render;
+ * slots outside the rectangle do no work.  radiance is zrt_debug_radiance_plan's over the
+ * slots (n = slots; its key_offset is seed * 0x9E3779B97F4A7C15).  Refuses what
+ * zrt_ctx_camera refuses of params and query; zrt_lens_check refuses what it refuses of the
+ * lens.  The launch reads ZRT_RADIANCE_PARTIAL_CAP and ZRT_RADIANCE_GRID as the radiance
+ * query does. */
+typedef struct zrt_camera_plan {
+  uint64_t slots;              /* tiles_w x tiles_h x 64 */
+  uint64_t pixels;             /* w x h */
+  uint32_t tiles_w, tiles_h;
+  zrt_radiance_plan radiance;
+} zrt_camera_plan;
+int zrt_debug_camera_plan(const zrt_params* params, const zrt_camera_query* query, uint32_t cu_count,
+                          uint64_t partial_cap_bytes, zrt_camera_plan* out);
+int zrt_lens_check(const zrt_lens* lens);
+
+/* A lens of `kind` at a pose (host only), from the very u, v, w and h that zrt_camera_init
+ * computes (camera.zig:17-35; viewport_width = aspect * 2 h), in f32, in this order:
+ *   horizontal = u * (focus_dist * viewport_width), vertical = v * (focus_dist * viewport_height)
+ *   lower_left_corner = ((look_from - horizontal * 0.5f) - vertical * 0.5f) - w * focus_dist
+ *   axis_u = u * (aperture * 0.5f), axis_v = v * (aperture * 0.5f)   (pinhole, thin, equirect)
+ *   axis_u = u, axis_v = v                                             (ortho, fisheye)
+ *   axis_w = -w                                                        (the viewing direction)
+ *   half_fov = fisheye_fov_deg * (pi / 360) in f32
+ * With focus_dist = 1 the plane equals zrt_camera_init's bit for bit, whatever the aperture.
+ * ZRT_E_INVALID: an unknown kind, or a result zrt_lens_check refuses. */
+int zrt_lens_init(uint32_t kind, const float look_from[3], const float look_at[3], const float vup[3],
+                  float vfov_deg, float aspect, float aperture, float focus_dist, float fisheye_fov_deg,
+                  zrt_lens* out);
+/* The lens of `kind` at the pose of a zrt_camera (host only; what the command line's
+ * ZRT_LENS uses), in f32 in this order: c = ((lower_left_corner + horizontal * 0.5f) +
+ * vertical * 0.5f) - origin, D = |c| = sqrtf((c.x c.x + c.y c.y) + c.z c.z), the viewing
+ * direction f = c * (1.0f / D), u = horizontal * (1.0f / |horizontal|), v = vertical *
+ * (1.0f / |vertical|).
+ * focus_dist <= 0: the camera's own plane, unchanged (a pinhole is then the camera bit for
+ * bit); else horizontal and vertical scaled by focus_dist / D and lower_left_corner =
+ * ((origin - horizontal * 0.5f) - vertical * 0.5f) + f * focus_dist.  axis_u, axis_v and
+ * half_fov as zrt_lens_init; axis_w = f. */
+int zrt_lens_from_camera(uint32_t kind, const zrt_camera* camera, float aperture, float focus_dist,
+                         float fisheye_fov_deg, zrt_lens* out);
+
 /* ---- host-side scene ingestion (the caller side of the seam) ------------- *
  * Restatement of scenes.zig / obj_reader.zig / png_image.zig texture loading
  * so tests and bench can build the reference's scenes without Zig.  Assets are

@@ -13,6 +13,8 @@
 //                  entry points that need no device; the per-tile walk directly
 //   radiance.cpp   its part that needs no device (-DZRT_PLAN_ONLY): plan_radiance through
 //                  zrt_debug_radiance_plan, zrt_rays_equirect
+//   camera_query.cpp its part that needs no device: plan_camera through zrt_debug_camera_plan,
+//                  zrt_lens_check, zrt_lens_init, zrt_lens_from_camera
 //   oracle/        oracle_render (both RNG modes), oracle_render_scanlines,
 //                  oracle_trace, oracle_bvh_build
 //
@@ -343,6 +345,87 @@ static void radiance_plans() {
   }
   CHECK(zrt_rays_equirect(origin, 0, 2, nullptr) == ZRT_E_INVALID && zrt_rays_equirect(nullptr, 1, 1, nullptr) == ZRT_E_INVALID,
         "equirect: bad arguments accepted");
+}
+
+// plan_camera at the edge values of tests/test_camera_plan.py: rectangles that are and are not
+// multiples of 8, the largest frame, every refusal of the query; zrt_lens_init, zrt_lens_check
+// and zrt_lens_from_camera over every kind, degenerate poses and non-finite floats
+static void camera_plans() {
+  struct Case { uint32_t width, height, x0, y0, w, h, samples, first_sample, flags, chunk, cu; uint64_t cap; bool ok; };
+  const Case cases[] = {{24, 16, 0, 0, 24, 16, 9, 0, 0, 4, 256, 0, true},
+                        {24, 16, 3, 5, 13, 9, 9, 0, 0, 4, 256, 0, true},
+                        {24, 16, 23, 15, 1, 1, 1, 65535, 0, 0, 1, 0, true},
+                        {40, 24, 0, 0, 40, 24, 9, 0, 0, 4, 256, 960 * 16, true},
+                        {65535, 65535, 0, 0, 65535, 65527, 64, 0, 0, 4, 4, 1, true},
+                        {24, 16, 0, 0, 24, 16, 8, 8, ZRT_CQ_ACCUMULATE, 4, 256, 0, true},
+                        {65535, 65535, 0, 0, 65535, 65535, 1, 0, 0, 4, 256, 0, false},
+                        {24, 16, 0, 0, 0, 16, 1, 0, 0, 4, 256, 0, false},
+                        {24, 16, 1, 0, 24, 16, 1, 0, 0, 4, 256, 0, false},
+                        {24, 16, 0xffffffffu, 0, 2, 1, 1, 0, 0, 4, 256, 0, false},
+                        {24, 16, 0, 16, 1, 1, 1, 0, 0, 4, 256, 0, false},
+                        {24, 16, 0, 0, 24, 16, 0, 0, 0, 4, 256, 0, false},
+                        {24, 16, 0, 0, 24, 16, 2, 65535, 0, 4, 256, 0, false},
+                        {24, 16, 0, 0, 24, 16, 1, 0, 2, 4, 256, 0, false},
+                        {24, 16, 0, 0, 24, 16, 4, 6, ZRT_CQ_ACCUMULATE, 4, 256, 0, false},
+                        {24, 16, 0, 0, 24, 16, 1, 0, 0, 4, 0, 0, false},
+                        {0, 16, 0, 0, 1, 1, 1, 0, 0, 4, 256, 0, false},
+                        {65536, 1, 0, 0, 1, 1, 1, 0, 0, 4, 256, 0, false}};
+  for (const Case& c : cases) {
+    zrt_params p = params(c.width, c.height, 1, 8, ZRT_RNG_COUNTER);
+    p.sample_chunk = c.chunk;
+    zrt_camera_query q;
+    std::memset(&q, 0, sizeof(q));
+    q.x0 = c.x0; q.y0 = c.y0; q.w = c.w; q.h = c.h;
+    q.n_samples = c.samples;
+    q.first_sample = c.first_sample;
+    q.flags = c.flags;
+    zrt_camera_plan plan;
+    const int rc = zrt_debug_camera_plan(&p, &q, c.cu, c.cap, &plan);
+    const bool fine = c.ok ? rc == ZRT_OK && plan.slots == uint64_t(plan.tiles_w) * plan.tiles_h * 64 && plan.slots < (1ull << 32) &&
+                                 plan.pixels == uint64_t(c.w) * c.h && plan.slots >= plan.pixels &&
+                                 plan.radiance.items == plan.slots * plan.radiance.call_chunks &&
+                                 plan.radiance.grid >= 1 && plan.radiance.grid <= plan.radiance.blocks_per_cu * c.cu
+                           : rc == ZRT_E_INVALID;
+    CHECK(fine, "camera plan %ux%u rect %u %u %u %u samples %u: rc %d", c.width, c.height, c.x0, c.y0, c.w, c.h, c.samples, rc);
+  }
+  zrt_params p = params(8, 8, 1, 8, ZRT_RNG_COUNTER);
+  zrt_camera_query q;
+  std::memset(&q, 0, sizeof(q));
+  q.w = q.h = q.n_samples = 1;
+  zrt_camera_plan plan;
+  CHECK(zrt_debug_camera_plan(nullptr, &q, 1, 0, &plan) == ZRT_E_INVALID && zrt_debug_camera_plan(&p, nullptr, 1, 0, &plan) == ZRT_E_INVALID &&
+            zrt_debug_camera_plan(&p, &q, 1, 0, nullptr) == ZRT_E_INVALID,
+        "camera plan: null arguments accepted");
+  const float from[3] = {0.4f, 1.7f, -3.6f}, at[3] = {0.1f, 0.2f, 0.0f}, up[3] = {0.0f, 1.0f, 0.0f};
+  zrt_camera cam;
+  CHECK(zrt_camera_init(from, at, up, 40.0f, 1.5f, &cam) == ZRT_OK, "camera_init: %s", zrt_last_error());
+  for (uint32_t kind = 0; kind <= ZRT_LENS_FISHEYE; ++kind) {
+    zrt_lens l, m;
+    CHECK(zrt_lens_init(kind, from, at, up, 40.0f, 1.5f, 0.3f, 1.0f, 180.0f, &l) == ZRT_OK && zrt_lens_check(&l) == ZRT_OK,
+          "lens_init kind %u: %s", kind, zrt_last_error());
+    CHECK(std::memcmp(&l.lower_left_corner, &cam.lower_left_corner, sizeof(zrt_vec3) * 3) == 0 &&
+              std::memcmp(&l.origin, &cam.origin, sizeof(zrt_vec3)) == 0,
+          "lens_init kind %u: the plane at focus_dist 1 is not zrt_camera_init's", kind);
+    CHECK(zrt_lens_from_camera(kind, &cam, 0.3f, 0.0f, 180.0f, &m) == ZRT_OK &&
+              std::memcmp(&m.lower_left_corner, &cam.lower_left_corner, sizeof(zrt_vec3) * 3) == 0,
+          "lens_from_camera kind %u: %s", kind, zrt_last_error());
+    CHECK(zrt_lens_from_camera(kind, &cam, 0.3f, 2.5f, 120.0f, &m) == ZRT_OK && zrt_lens_check(&m) == ZRT_OK,
+          "lens_from_camera kind %u at a focal distance: %s", kind, zrt_last_error());
+    CHECK(zrt_lens_init(kind, from, from, up, 40.0f, 1.5f, 0.0f, 1.0f, 180.0f, &l) == ZRT_E_INVALID &&
+              zrt_lens_init(kind, from, at, up, 40.0f, 1.5f, 0.0f, 1.0f, 0.0f, &l) == ZRT_E_INVALID &&
+              (kind == ZRT_LENS_ORTHO || kind == ZRT_LENS_FISHEYE ||  // (their axes are the frame's: no aperture)
+               zrt_lens_init(kind, from, at, up, 40.0f, 1.5f, INFINITY, 1.0f, 180.0f, &l) == ZRT_E_INVALID) &&
+              zrt_lens_init(kind, from, at, up, 40.0f, 1.5f, 0.0f, NAN, 180.0f, &l) == ZRT_E_INVALID &&
+              zrt_lens_init(kind, nullptr, at, up, 40.0f, 1.5f, 0.0f, 1.0f, 180.0f, &l) == ZRT_E_INVALID,
+          "lens_init kind %u: a degenerate pose, field of view or aperture accepted", kind);
+    zrt_camera flat = cam;
+    flat.horizontal = zrt_vec3{0.0f, 0.0f, 0.0f};
+    CHECK(zrt_lens_from_camera(kind, &flat, 0.0f, 0.0f, 180.0f, &m) == ZRT_E_INVALID, "lens_from_camera kind %u: a flat plane accepted", kind);
+  }
+  zrt_lens l;
+  CHECK(zrt_lens_init(5, from, at, up, 40.0f, 1.5f, 0.0f, 1.0f, 180.0f, &l) == ZRT_E_INVALID && zrt_lens_check(nullptr) == ZRT_E_INVALID &&
+            zrt_lens_from_camera(5, &cam, 0.0f, 0.0f, 180.0f, &l) == ZRT_E_INVALID,
+        "lens: an unknown kind or a null lens accepted");
 }
 
 // plan_reproject at the cases of tests/test_temporal_host.py: a scene's camera, the
@@ -737,6 +820,7 @@ int main(int argc, char** argv) {
   for (uint32_t i : {0u, 1u, 2u, 3u, 4u}) one_scene(i, assets, tmp);
   pass_and_adapt_plans();
   radiance_plans();
+  camera_plans();
   reproject_plans(assets);
   tile_walks();
   degenerate::all();

@@ -21,7 +21,8 @@ from ._ffi import (ZRT_PRNG_XOROSHIRO128, ZRT_PRNG_XOSHIRO256, ZRT_RNG_COUNTER, 
                    ZRT_RNG_REFERENCE_STREAM, ZRT_TRAVERSAL_FAST, ZRT_TRAVERSAL_REFERENCE,
                    ZRT_TRAVERSAL_BINARY, ZRT_FLAG_STATS, ZRT_FLAG_NO_SCHEDULE, ZRT_FLAG_SCANLINES, ZRT_FLAG_GUARD,
                    ZRT_DN_DEMODULATE, ZRT_TA_DEMODULATE, ZRT_AO_ACCUMULATE, ZRT_AO_REDUCE_WAVE, ZRT_AO_REDUCE_ATOMIC,
-                   ZRT_RQ_ACCUMULATE, ZrtError, check)
+                   ZRT_RQ_ACCUMULATE, ZRT_CQ_ACCUMULATE, ZRT_LENS_PINHOLE, ZRT_LENS_THIN, ZRT_LENS_ORTHO,
+                   ZRT_LENS_EQUIRECT, ZRT_LENS_FISHEYE, ZrtError, check)
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ASSETS = os.path.join(REPO, "assets")
@@ -552,6 +553,75 @@ def rays_equirect(origin, width: int, height: int) -> np.ndarray:
     return out
 
 
+def lens_init(kind: int, look_from, look_at, vup, vfov: float, aspect: float, aperture: float = 0.0,
+              focus_dist: float = 1.0, fisheye_fov: float = 180.0) -> _ffi.Lens:
+    """The lens of `kind` (ZRT_LENS_*) at a pose (zrt_lens_init; host only): camera_init's
+    plane scaled to the focal distance, the lens axes, the fisheye's field of view in degrees."""
+    f3 = C.c_float * 3
+    out = _ffi.Lens()
+    check(lib().zrt_lens_init(kind, f3(*look_from), f3(*look_at), f3(*vup), vfov, aspect, aperture, focus_dist,
+                              fisheye_fov, C.byref(out)))
+    return out
+
+
+def lens_from_camera(kind: int, camera: _ffi.Camera, aperture: float = 0.0, focus_dist: float = 0.0,
+                     fisheye_fov: float = 180.0) -> _ffi.Lens:
+    """The lens of `kind` at the pose of a camera (zrt_lens_from_camera; host only);
+    focus_dist 0 keeps the camera's own plane."""
+    out = _ffi.Lens()
+    check(lib().zrt_lens_from_camera(kind, C.byref(camera), aperture, focus_dist, fisheye_fov, C.byref(out)))
+    return out
+
+
+def camera_query(x0: int, y0: int, w: int, h: int, n_samples: int, first_sample: int = 0,
+                 flags: int = 0) -> _ffi.CameraQuery:
+    """A zrt_camera_query: the pixel rectangle, n_samples samples per pixel from the pixel's
+    sample first_sample; flags: ZRT_CQ_ACCUMULATE."""
+    return _ffi.CameraQuery(x0=x0, y0=y0, w=w, h=h, n_samples=n_samples, first_sample=first_sample, flags=flags)
+
+
+def render_lens(scene, params: RenderParams, lens: _ffi.Lens, n_samples: int, rect=None, first_sample: int = 0,
+                sum=None, rgb=None):
+    """A frame (or the rectangle rect = (x0, y0, w, h) of it) through a lens (zrt_render_lens;
+    the definition: zrt.h "camera queries").  params gives width, height, traversal, prng, seed,
+    max_depth and sample_chunk.  sum (float32[height, width, 4]): updated in place; with
+    first_sample > 0 the call adds onto it (ZRT_CQ_ACCUMULATE).  rgb (float32[height, width, 3]):
+    written inside the rectangle, kept outside it.  Returns (rgb, info dict)."""
+    view = scene.view if isinstance(scene, LoadedScene) else scene
+    w, h = params.width, params.height
+    x0, y0, rw, rh = rect if rect is not None else (0, 0, w, h)
+    q = camera_query(x0, y0, rw, rh, n_samples, first_sample, ZRT_CQ_ACCUMULATE if first_sample else 0)
+    if rgb is None:
+        rgb = np.zeros((h, w, 3), np.float32)
+    for a, c in ((sum, 4), (rgb, 3)):
+        if a is not None and (a.dtype != np.float32 or a.shape != (h, w, c) or not a.flags.c_contiguous):
+            raise ValueError(f"sum and rgb must be C-contiguous float32[height, width, {c}]")
+    if first_sample and sum is None:
+        raise ValueError("first_sample > 0 needs the sums of the samples before it")
+    info = _ffi.RadianceInfo()
+    p = params.abi()
+    f = C.POINTER(C.c_float)
+    check(lib().zrt_render_lens(view, C.byref(p), C.byref(lens), C.byref(q),
+                                sum.ctypes.data_as(f) if sum is not None else None, rgb.ctypes.data_as(f),
+                                C.byref(info)))
+    return rgb, info.as_dict()
+
+
+def debug_camera_plan(params: RenderParams, q: _ffi.CameraQuery, cu_count: int = 256,
+                      partial_cap_bytes: int = 0) -> dict:
+    """How zrt_ctx_camera launches this query (zrt_debug_camera_plan; no device): slots, tiles
+    and the radiance plan over the slots.  Raises ZrtError for what the call would refuse."""
+    out = _ffi.CameraPlan()
+    p = params.abi()
+    check(lib().zrt_debug_camera_plan(C.byref(p), C.byref(q), cu_count, partial_cap_bytes, C.byref(out)))
+    return out.as_dict()
+
+
+def lens_check(lens: _ffi.Lens) -> None:
+    """Raises ZrtError for a lens zrt_ctx_camera would refuse (zrt_lens_check; no device)."""
+    check(lib().zrt_lens_check(C.byref(lens)))
+
+
 class RenderContext:
     """Device-resident scene (zrt_ctx_*): build + upload once, render many."""
 
@@ -658,6 +728,21 @@ class RenderContext:
         check(lib().zrt_ctx_radiance(self._h, C.byref(p), C.byref(rq), C.c_void_p(dev_rays or None), n,
                                      C.c_void_p(dev_sum or None), C.c_void_p(dev_rgb or None),
                                      C.c_void_p(stream or None)))
+
+    def camera(self, params: RenderParams, lens: _ffi.Lens, q: _ffi.CameraQuery, dev_sum: int, dev_rgb: int = 0,
+               stream: int = 0):
+        """A pixel rectangle of a frame through a lens on the resident scene (zrt_ctx_camera;
+        device pointers, asynchronous): dev_sum width * height float4 and dev_rgb (0: not wanted)
+        width * height * 3 f32 are whole-frame buffers; only the rectangle's pixels are written."""
+        p = params.abi()
+        check(lib().zrt_ctx_camera(self._h, C.byref(p), C.byref(lens), C.byref(q), C.c_void_p(dev_sum or None),
+                                   C.c_void_p(dev_rgb or None), C.c_void_p(stream or None)))
+
+    def camera_info(self) -> dict:
+        """The last camera() call's counters and kernel time (zrt_ctx_camera_info; waits for it)."""
+        out = _ffi.RadianceInfo()
+        check(lib().zrt_ctx_camera_info(self._h, C.byref(out)))
+        return out.as_dict()
 
     def radiance_info(self) -> dict:
         """The last radiance() call's counters and kernel time (zrt_ctx_radiance_info; waits for it)."""

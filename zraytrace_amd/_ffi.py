@@ -39,6 +39,8 @@ ZRT_TA_DEMODULATE = 1
 ZRT_AO_ACCUMULATE = 1
 ZRT_AO_REDUCE_WAVE, ZRT_AO_REDUCE_ATOMIC = 0, 1
 ZRT_RQ_ACCUMULATE = 1
+ZRT_CQ_ACCUMULATE = 1
+ZRT_LENS_PINHOLE, ZRT_LENS_THIN, ZRT_LENS_ORTHO, ZRT_LENS_EQUIRECT, ZRT_LENS_FISHEYE = range(5)
 
 
 class Vec3(C.Structure):
@@ -237,6 +239,27 @@ class RadiancePlan(C.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_ if name != "reserved"}
 
 
+class Lens(C.Structure):
+    _fields_ = [("kind", C.c_uint32), ("origin", Vec3), ("lower_left_corner", Vec3), ("horizontal", Vec3),
+                ("vertical", Vec3), ("axis_u", Vec3), ("axis_v", Vec3), ("axis_w", Vec3), ("half_fov", C.c_float),
+                ("reserved", C.c_uint32 * 2)]
+
+
+class CameraQuery(C.Structure):
+    _fields_ = [("x0", C.c_uint32), ("y0", C.c_uint32), ("w", C.c_uint32), ("h", C.c_uint32),
+                ("n_samples", C.c_uint32), ("first_sample", C.c_uint32), ("flags", C.c_uint32),
+                ("reserved", C.c_uint32 * 5)]
+
+
+class CameraPlan(C.Structure):
+    _fields_ = [("slots", C.c_uint64), ("pixels", C.c_uint64), ("tiles_w", C.c_uint32), ("tiles_h", C.c_uint32),
+                ("radiance", RadiancePlan)]
+
+    def as_dict(self):
+        return {"slots": self.slots, "pixels": self.pixels, "tiles_w": self.tiles_w, "tiles_h": self.tiles_h,
+                "radiance": self.radiance.as_dict()}
+
+
 class BvhNode(C.Structure):
     _fields_ = [("min", Vec3), ("left", C.c_int32), ("max", Vec3), ("right", C.c_int32)]
 
@@ -341,6 +364,17 @@ SIGNATURES = [
     ("zrt_debug_radiance_plan", C.c_int, [C.POINTER(Params), C.POINTER(Radiance), C.c_uint32, C.c_uint32, C.c_uint64,
                                           C.POINTER(RadiancePlan)]),
     ("zrt_rays_equirect", C.c_int, [C.POINTER(C.c_float), C.c_uint32, C.c_uint32, C.POINTER(C.c_float)]),
+    ("zrt_ctx_camera", C.c_int, [_P, C.POINTER(Params), C.POINTER(Lens), C.POINTER(CameraQuery), _P, _P, _P]),
+    ("zrt_ctx_camera_info", C.c_int, [_P, C.POINTER(RadianceInfo)]),
+    ("zrt_render_lens", C.c_int, [C.POINTER(Scene), C.POINTER(Params), C.POINTER(Lens), C.POINTER(CameraQuery),
+                                  C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(RadianceInfo)]),
+    ("zrt_debug_camera_plan", C.c_int, [C.POINTER(Params), C.POINTER(CameraQuery), C.c_uint32, C.c_uint64,
+                                        C.POINTER(CameraPlan)]),
+    ("zrt_lens_check", C.c_int, [C.POINTER(Lens)]),
+    ("zrt_lens_init", C.c_int, [C.c_uint32, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.POINTER(Lens)]),
+    ("zrt_lens_from_camera", C.c_int, [C.c_uint32, C.POINTER(Camera), C.c_float, C.c_float, C.c_float,
+                                       C.POINTER(Lens)]),
     ("zrt_scene_load", C.c_int, [C.c_uint32, C.c_char_p, C.POINTER(_P), C.POINTER(Camera)]),
     ("zrt_scene_view", C.POINTER(Scene), [_P]),
     ("zrt_scene_free", None, [_P]),

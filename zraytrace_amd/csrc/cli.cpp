@@ -44,6 +44,13 @@
 // $ZRT_PANORAMA_OUT=<file.png> [$ZRT_PANORAMA_WIDTH=w, default 512] also writes a w x w/2
 // equirectangular panorama from the scene camera's origin (zrt_rays_equirect + zrt_radiance,
 // with the run's samples, depth, seed, PRNG and traversal), beside any mode above.
+// $ZRT_LENS=pinhole|thin|ortho|equirect|fisheye $ZRT_LENS_OUT=<file.png> [$ZRT_APERTURE=a, default 0]
+// [$ZRT_FOCUS_DIST=d, default: the camera's own plane] [$ZRT_FISHEYE_FOV=degrees, default 180]
+// also writes the frame through that lens at the scene camera's pose (zrt_lens_from_camera +
+// zrt_render_lens over the whole width x height, with the run's samples, depth, seed, PRNG and
+// traversal), beside any mode above.  pinhole is the scene camera itself over the whole width.
+// The two go together, and the three options only with them: a run that sets any of the five
+// without both ZRT_LENS and ZRT_LENS_OUT is refused before anything is rendered.
 #include <unistd.h>
 
 #include <chrono>
@@ -339,6 +346,40 @@ int main(int argc, char** argv) {
     pano_w = uint32_t(v);
   }
 
+  // $ZRT_LENS=<model> $ZRT_LENS_OUT=file.png [$ZRT_APERTURE, $ZRT_FOCUS_DIST, $ZRT_FISHEYE_FOV]: also
+  // write the frame through a lens; checked here, before anything is rendered (no device)
+  const char* lens_name = std::getenv("ZRT_LENS");
+  const char* lens_out = std::getenv("ZRT_LENS_OUT");
+  zrt_lens lens;
+  zrt_camera_query lens_q;
+  std::memset(&lens_q, 0, sizeof(lens_q));
+  lens_q.w = width;
+  lens_q.h = height;
+  lens_q.n_samples = samples;
+  if (lens_name || lens_out || std::getenv("ZRT_APERTURE") || std::getenv("ZRT_FOCUS_DIST") || std::getenv("ZRT_FISHEYE_FOV")) {
+    const char* names[] = {"pinhole", "thin", "ortho", "equirect", "fisheye"};
+    uint32_t kind = 5;
+    for (uint32_t k = 0; k < 5 && lens_name; ++k)
+      if (std::strcmp(lens_name, names[k]) == 0) kind = k;
+    bool ok = lens_name && lens_out && kind < 5;
+    float opt[3] = {0.0f, 0.0f, 180.0f};  // aperture, focus distance (0: the camera's plane), fisheye field of view
+    const char* opt_names[3] = {"ZRT_APERTURE", "ZRT_FOCUS_DIST", "ZRT_FISHEYE_FOV"};
+    for (int k = 0; k < 3; ++k)
+      if (const char* e = std::getenv(opt_names[k])) {
+        char* end = nullptr;
+        opt[k] = std::strtof(e, &end);
+        if (end == e || *end != '\0' || !(opt[k] >= 0.0f)) ok = false;
+      }
+    zrt_camera_plan plan;
+    if (!ok || zrt_lens_from_camera(kind, &camera, opt[0], opt[1], opt[2], &lens) != ZRT_OK ||
+        zrt_debug_camera_plan(&ao_params, &lens_q, 1, 0, &plan) != ZRT_OK) {
+      std::fprintf(stderr, "error: the lens frame needs ZRT_LENS=pinhole|thin|ortho|equirect|fisheye and ZRT_LENS_OUT=<file.png>; "
+                           "ZRT_APERTURE and ZRT_FOCUS_DIST are lengths >= 0, ZRT_FISHEYE_FOV degrees > 0\n");
+      zrt_scene_free(data);
+      return 1;
+    }
+  }
+
   std::fprintf(stderr, "Raytrace start\n");
   std::fprintf(stderr, " - Surfaces:                 %u\n", scene->n_prims);
   std::fprintf(stderr, " - Pixels:                   %ux%u\n", unsigned(width), unsigned(height));
@@ -471,6 +512,17 @@ int main(int argc, char** argv) {
     if (rc == ZRT_OK)
       std::fprintf(stderr, "  Panorama:              %ux%u, %u samples per ray, %llu rays -> %s\n", pano_w, pano_h,
                    pano_rq.n_samples, (unsigned long long)info.rays, pano_out);
+  }
+  // $ZRT_LENS_OUT: the frame through the lens at the scene camera's pose (zrt_render_lens, a launch
+  // of its own on the first GPU); the frame above is what it was without it
+  if (lens_out && rc == ZRT_OK) {
+    std::vector<float> frame(size_t(width) * height * 3);
+    zrt_radiance_info info;
+    rc = zrt_render_lens(scene, &ao_params, &lens, &lens_q, nullptr, frame.data(), &info);
+    if (rc == ZRT_OK) rc = zrt_image_write_png(lens_out, frame.data(), width, height);
+    if (rc == ZRT_OK)
+      std::fprintf(stderr, "  Lens frame:            %s, %ux%u, %u samples per pixel, %llu rays -> %s\n", lens_name,
+                   unsigned(width), unsigned(height), lens_q.n_samples, (unsigned long long)info.rays, lens_out);
   }
   zrt_scene_free(data);
   if (rc != ZRT_OK) {

@@ -1,5 +1,5 @@
 // context.hpp - private to the host files that talk to the HIP runtime
-// (context.cpp, runs.cpp, post.cpp, queries.cpp, ao.cpp, radiance.cpp, debug_device.cpp, multi.cpp, oneshot.cpp): the
+// (context.cpp, runs.cpp, post.cpp, queries.cpp, ao.cpp, radiance.cpp, camera_query.cpp, debug_device.cpp, multi.cpp, oneshot.cpp): the
 // HIP error type, the owning handles, the context behind zrt_ctx_*, what those
 // files share of its launch path, and the catch clauses of their entry points.
 #pragma once
@@ -282,6 +282,9 @@ struct QueryState {
   uint64_t rq_samples = 0;
   uint32_t rq_att_lds_rows = 0, rq_stack_lds_rows = 0, rq_grid = 0;  // the last call's plan (zrt_ctx_debug_radiance)
   bool rq_launched = false;
+  // zrt_ctx_camera (camera_query.cpp) shares all of the above with the radiance query, rq_samples included:
+  // either info call reports the last call of the two kinds
+  bool cq_launched = false;
 };
 }  // namespace zrt
 
@@ -393,6 +396,37 @@ void launch_query(zrt_ctx* c, const zrt_params* p, uint32_t grid, hipStream_t st
   q.done.launched = true;
   q.done.reported = false;
 }
+
+// ---- radiance.cpp: what the radiance query and the camera query (camera_query.cpp) share ----
+inline bool ptr_misaligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; }
+// a test knob's value (ZRT_RADIANCE_PARTIAL_CAP, ZRT_RADIANCE_GRID), or 0 when it is not set
+uint64_t query_env_u64(const char* name);
+// Before launch_query: the plan's grid under ZRT_RADIANCE_GRID; the query's attenuation rows for that
+// grid, a round's parked sums and the counters, grown once `st` has drained (an earlier query may
+// still use the old ones - one query is in flight per context, so it ran on `st` or has been waited
+// for: the pattern of trace_rows); the counters zeroed on `st`.  Returns the grid.
+uint32_t prepare_radiance(zrt_ctx* c, const zrt_params* p, const zrt_radiance_plan& plan, hipStream_t st);
+// Inside launch_query's kernel step: the checked rows, what zrt_ctx_debug_radiance reports, and the
+// query's buffers in the kernel arguments.
+void fill_radiance(zrt_ctx* c, const zrt_params* p, KArgs& a, const TracePlan& t, uint32_t launch_grid, const char* name);
+// The plan's rounds over n rays or slots: round(r, chunks, n_items, sample0, round_grid) per round.
+// chunk: the kernel's (plan.chunk bounded by the key's sample field, so its 32-bit sample arithmetic
+// stays far from wrapping; chunk0 > 0 only where plan.chunk < 65536).
+template <class Round>
+void radiance_rounds(const zrt_radiance_plan& plan, uint32_t n, uint32_t first_sample, uint32_t chunk,
+                     uint32_t launch_grid, Round&& round) {
+  for (uint32_t r = 0; r < plan.rounds; ++r) {
+    const uint32_t chunk0 = r * plan.chunks_per_round;
+    const uint32_t chunks = std::min(plan.chunks_per_round, plan.call_chunks - chunk0);
+    const uint64_t n_items = uint64_t(n) * chunks;
+    round(r, chunks, n_items, first_sample + chunk0 * chunk,
+          uint32_t(std::min<uint64_t>(launch_grid, (n_items + kBlock - 1) / kBlock)));
+  }
+}
+// After launch_query's finish step: the counters copied out behind `done`.
+void copy_radiance_counters(zrt_ctx* c, hipStream_t s);
+// zrt_ctx_radiance_info / zrt_ctx_camera_info: the last call of either kind (waits for it).
+int radiance_info(zrt_ctx* c, zrt_radiance_info* out);
 
 // ---- ao.cpp ----
 // zrt_ctx_ao's refusals of params and ao, and its launch (zrt_debug_ao_plan): no device.

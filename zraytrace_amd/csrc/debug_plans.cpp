@@ -39,6 +39,11 @@ int zrt_debug_reproject_plan(const zrt_camera* prev, const zrt_params* params, z
   return zrt::plan_reproject(prev, params, out);
 }
 
+int zrt_debug_camera_plan(const zrt_params* params, const zrt_camera_query* query, uint32_t cu_count,
+                          uint64_t partial_cap_bytes, zrt_camera_plan* out) {
+  return zrt::plan_camera(params, query, cu_count, partial_cap_bytes, out);
+}
+
 int zrt_debug_octant_offsets(uint32_t stride_f4, uint32_t n_top, uint32_t node_f4) {
   try {
     zrt::check_octant_offsets(stride_f4, n_top, node_f4);

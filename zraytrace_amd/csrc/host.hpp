@@ -143,6 +143,13 @@ int plan_temporal(const zrt_params* p, const zrt_temporal* tp, TemporalLaunch* o
 int plan_radiance(const zrt_params* p, const struct zrt_radiance* rq, uint32_t n, uint32_t cu_count, uint64_t partial_cap,
                   zrt_radiance_plan* out);
 
+// ---- camera_query.cpp (its part that needs no device) ----
+// zrt_ctx_camera's refusals of params and the query, and its launch: the slots of the
+// rectangle and plan_radiance over them (zrt_debug_camera_plan); its refusals of the lens.
+int plan_camera(const zrt_params* p, const zrt_camera_query* cq, uint32_t cu_count, uint64_t partial_cap,
+                zrt_camera_plan* out);
+int check_lens(const zrt_lens* lens);
+
 // ---- tile_class.cpp: the all-sky tiles of a frame (DESIGN.md §3 "All-sky tiles") ----
 // A tile's class word: bit 31 (kTileFrozen's bit, so compact_kernel drops such tiles
 // from a tile order) marks a tile no primary ray of which can hit anything; the low

@@ -121,6 +121,23 @@ struct RadianceArgs {
   uint32_t sample_end;  // first_sample + n_samples of the call (the last chunk may be ragged)
 };
 
+// camera_kernel / camera_finish_kernel's own arguments for one round (zrt_ctx_camera; zrt::plan_camera fills the
+// counts).  Passed by value: every field is a kernel argument, so the lens model reads scalars.
+struct CameraArgs {
+  uint64_t n_items;     // the round's items: n x its chunks; item k is slot k % n of the round's chunk k / n
+  uint64_t key_offset;  // seed * 0x9E3779B97F4A7C15: key = ((R << 16) | sample) + key_offset, R = y * width + x
+  uint32_t n;           // slots: tiles_w x tiles_h x 64 (a multiple of 64: a wave's items are one tile of one chunk)
+  uint32_t chunk;       // samples per chunk
+  uint32_t sample0;     // the first sample of the round's chunk 0
+  uint32_t sample_end;  // first_sample + n_samples of the call (the last chunk may be ragged)
+  uint32_t x0, y0, w, h;  // the rectangle; slot t * 64 + l is pixel (x0 + 8 (t % tiles_w) + (l & 7), y0 + 8 (t / tiles_w) + (l >> 3))
+  uint32_t tiles_w;
+  uint32_t width;       // of the frame
+  uint32_t kind;        // ZRT_LENS_*
+  float f_width, f_height, half_fov;
+  float org[3], llc[3], hor[3], ver[3], au[3], av[3], aw[3];  // zrt_lens
+};
+
 // error_flag bits (zrt_ctx_sync / zrt_ctx_stats / zrt_render report them as ZRT_E_UNSUPPORTED)
 constexpr uint32_t kErrOverflow = 1u;  // a traversal stack deeper than it was sized for
 constexpr uint32_t kErrLayout = 2u;    // the wide tree's encoding is not the one this kernel decodes
@@ -211,6 +228,8 @@ void* anyhit_kernel_ptr(int mode, bool stk16);
 void* ao_kernel_ptr(int mode, uint32_t prng, bool stk16);
 // radiance_kernel<mode, prng, stack width> (zrt_ctx_radiance): anyhit_kernel's modes
 void* radiance_kernel_ptr(int mode, uint32_t prng, bool stk16);
+// camera_kernel<mode, prng, stack width> (zrt_ctx_camera): radiance_kernel's modes
+void* camera_kernel_ptr(int mode, uint32_t prng, bool stk16);
 
 // One launch function per small kernel (the arguments are the kernel's, render.hip).
 hipError_t launch_finalize(hipStream_t st, const float4* partial, float* out, uint32_t n_slots, uint32_t n_chunks,
@@ -251,6 +270,11 @@ hipError_t launch_ao_finish(hipStream_t st, const AoArgs& g, uint32_t width, uin
 hipError_t launch_radiance_finish(hipStream_t st, const float4* partial, uint32_t n, uint32_t n_chunks,
                                   uint32_t zero_first, float4* sum, float* rgb, float scale, uint32_t final,
                                   const unsigned long long* error_flag);
+// zrt_ctx_camera's: launch_radiance_finish over the slots of g (n_items is not read), slot -> pixel; only the
+// rectangle's pixels of sum and rgb (whole-frame buffers indexed by R) are read or written
+hipError_t launch_camera_finish(hipStream_t st, const float4* partial, const CameraArgs& g, uint32_t n_chunks,
+                                uint32_t zero_first, float4* sum, float* rgb, float scale, uint32_t final,
+                                const unsigned long long* error_flag);
 hipError_t launch_debug_math(int fn, const float* x, const float* y, float* out, uint32_t n);
 hipError_t launch_debug_division(uint64_t n, unsigned long long* counts);
 hipError_t launch_debug_rng(uint32_t prng, uint64_t key, unsigned long long* out, uint32_t n);

@@ -448,3 +448,43 @@ int zrt_radiance(const zrt_scene* scene, const zrt_params* params, const struct 
   }
   ZRT_CATCH_ALL
 }
+
+int zrt_render_lens(const zrt_scene* scene, const zrt_params* params, const zrt_lens* lens, const zrt_camera_query* query,
+                    float* sum, float* out_rgb, zrt_radiance_info* info) {
+  zrt_camera_plan plan;
+  int rc = zrt::plan_camera(params, query, 1, 0, &plan);  // (refused before any device work)
+  if (rc) return rc;
+  rc = zrt::check_lens(lens);
+  if (rc) return rc;
+  rc = zrt::validate_scene(scene);
+  if (rc) return rc;
+  rc = zrt::check_device(int(params->device));
+  if (rc) return rc;
+  try {
+    const bool use_bvh = params->bounded_volume_hierarchy != 0 && scene->n_prims > 10;
+    zrt::HostScene h;
+    zrt::flatten_for_device(&h, scene, use_bvh, int(params->device));
+    std::unique_ptr<zrt_ctx> c = zrt::ctx_on_device(h, int(params->device));
+    const uint64_t n = uint64_t(params->width) * params->height;  // whole-frame buffers
+    zrt::DevBuf<float> d_rgb;
+    zrt::DevBuf<float4> d_sum;
+    d_sum.alloc(n);
+    d_rgb.alloc(3ull * n);
+    // what the caller holds outside the rectangle (and, accumulating, inside) goes in first
+    if (sum)
+      HIPCHK(hipMemcpy(d_sum.p, sum, sizeof(float4) * n, hipMemcpyHostToDevice));
+    else
+      HIPCHK(hipMemset(d_sum.p, 0, sizeof(float4) * n));
+    if (out_rgb)
+      HIPCHK(hipMemcpy(d_rgb.p, out_rgb, sizeof(float) * 3ull * n, hipMemcpyHostToDevice));
+    rc = zrt_ctx_camera(c.get(), params, lens, query, reinterpret_cast<float*>(d_sum.p), d_rgb.p, nullptr);
+    if (rc) return rc;
+    rc = zrt_ctx_sync(c.get());  // (a device error of the launch)
+    if (rc) return rc;
+    if (sum) HIPCHK(hipMemcpy(sum, d_sum.p, sizeof(float4) * n, hipMemcpyDeviceToHost));
+    if (out_rgb) HIPCHK(hipMemcpy(out_rgb, d_rgb.p, sizeof(float) * 3ull * n, hipMemcpyDeviceToHost));
+    if (info) return zrt_ctx_camera_info(c.get(), info);
+    return ZRT_OK;
+  }
+  ZRT_CATCH_ALL
+}

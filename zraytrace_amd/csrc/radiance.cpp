@@ -89,50 +89,90 @@ int zrt_rays_equirect(const float origin[3], uint32_t width, uint32_t height, fl
 }
 
 #ifndef ZRT_PLAN_ONLY
-namespace {
-bool misaligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; }
-// a test knob's value, or 0 when it is not set
-uint64_t env_u64(const char* name) {
+namespace zrt {
+uint64_t query_env_u64(const char* name) {
   const char* e = std::getenv(name);
   return e ? std::strtoull(e, nullptr, 10) : 0;
 }
-}  // namespace
+
+uint32_t prepare_radiance(zrt_ctx* c, const zrt_params* p, const zrt_radiance_plan& plan, hipStream_t st) {
+  QueryState& q = c->query;
+  uint32_t grid = plan.grid;
+  if (const uint64_t g = query_env_u64("ZRT_RADIANCE_GRID")) grid = uint32_t(std::min<uint64_t>(grid, g));
+  const uint64_t n_lanes = uint64_t(grid) * kBlock;
+  KArgs probe{};
+  const TracePlan t0 = fill_trace(probe, c, p->traversal, true, p->max_depth);
+  const BufNeed need{uint64_t(att_rows_per_path(t0.lp, p->max_depth)) * n_lanes, 0};
+  const uint64_t partial_elems = plan.partial_bytes / sizeof(float4);
+  if (q.att.n < need.att_elems || q.partial.n < partial_elems || !q.counters.p) {
+    HIPCHK(hipStreamSynchronize(st));
+    q.att.grow(need.att_elems);
+    q.partial.grow(partial_elems);
+    if (!q.counters.p) q.counters.alloc(kScratchSlots);
+  }
+  q.counters_host.alloc(kScratchSlots);
+  HIPCHK(hipMemsetAsync(q.counters.p, 0, sizeof(unsigned long long) * kScratchSlots, st));
+  return grid;
+}
+
+void fill_radiance(zrt_ctx* c, const zrt_params* p, KArgs& a, const TracePlan& t, uint32_t launch_grid, const char* name) {
+  QueryState& q = c->query;
+  check_buffers(name, BufNeed{uint64_t(att_rows_per_path(t.lp, p->max_depth)) * a.n_lanes, 0}, q.att.n, 0);
+  q.rq_att_lds_rows = t.lp.att_rows;
+  q.rq_stack_lds_rows = t.lp.stack_rows;
+  q.rq_grid = launch_grid;
+  a.max_depth = p->max_depth;
+  a.att = q.att.p;
+  a.att_cap = q.att.n;
+  a.partial = q.partial.p;
+  a.counters = q.counters.p;
+}
+
+void copy_radiance_counters(zrt_ctx* c, hipStream_t s) {
+  QueryState& q = c->query;
+  HIPCHK(hipMemcpyAsync(q.counters_host.get(), q.counters.p, sizeof(unsigned long long) * kScratchSlots,
+                        hipMemcpyDeviceToHost, s));
+}
+
+int radiance_info(zrt_ctx* c, zrt_radiance_info* out) {
+  try {
+    HIPCHK(hipSetDevice(c->device));
+    const QueryState& q = c->query;
+    HIPCHK(hipEventSynchronize(q.done.done));
+    *out = zrt_radiance_info{};
+    out->samples = q.rq_samples;
+    out->reflections = q.counters_host[kReflections];
+    out->background_hits = q.counters_host[kBackground];
+    out->recursion_depth_hits = q.counters_host[kDepthHits];
+    out->rays = out->samples + out->reflections - out->recursion_depth_hits;
+    float f = 0.0f;
+    HIPCHK(hipEventElapsedTime(&f, q.timer.e0, q.timer.e1));
+    out->kernel_ms = f;
+    return ZRT_OK;
+  }
+  ZRT_CATCH_ALL
+}
+}  // namespace zrt
 
 int zrt_ctx_radiance(zrt_ctx* c, const zrt_params* p, const struct zrt_radiance* rq, const float* dev_rays, uint32_t n,
                      float* dev_sum, float* dev_rgb, void* hip_stream) {
   if (!c) return fail(ZRT_E_INVALID, "null argument");
   zrt_radiance_plan plan;
-  int rc = zrt::plan_radiance(p, rq, n, uint32_t(std::max(1, c->cu_count)), env_u64("ZRT_RADIANCE_PARTIAL_CAP"), &plan);
+  int rc = zrt::plan_radiance(p, rq, n, uint32_t(std::max(1, c->cu_count)), zrt::query_env_u64("ZRT_RADIANCE_PARTIAL_CAP"),
+                              &plan);
   if (rc) return rc;
   rc = zrt::params_fit_ctx(c, p);
   if (rc) return rc;
   if (n == 0) return ZRT_OK;
   if (!dev_rays || !dev_sum) return fail(ZRT_E_INVALID, "null argument");
-  if (misaligned(dev_rays, 4) || misaligned(dev_rgb, 4))
+  if (zrt::ptr_misaligned(dev_rays, 4) || zrt::ptr_misaligned(dev_rgb, 4))
     return fail(ZRT_E_INVALID, "radiance: dev_rays and dev_rgb must be 4-byte aligned");
-  if (misaligned(dev_sum, 16)) return fail(ZRT_E_INVALID, "radiance: dev_sum must be 16-byte aligned");
+  if (zrt::ptr_misaligned(dev_sum, 16)) return fail(ZRT_E_INVALID, "radiance: dev_sum must be 16-byte aligned");
   try {
     HIPCHK(hipSetDevice(c->device));
     hipStream_t st = zrt::stream_of(c, hip_stream);
     zrt::QueryState& q = c->query;
-    uint32_t grid = plan.grid;
-    if (const uint64_t g = env_u64("ZRT_RADIANCE_GRID")) grid = uint32_t(std::min<uint64_t>(grid, g));
-    const uint64_t n_lanes = uint64_t(grid) * zrt::kBlock;
-    // the query's buffers, grown before the launch's events: an earlier query may still use the
-    // old ones - one query is in flight per context, so it ran on `st` or has been waited for
-    // (the pattern of trace_rows)
-    zrt::KArgs probe{};
-    const zrt::TracePlan t0 = zrt::fill_trace(probe, c, p->traversal, true, p->max_depth);
-    const zrt::BufNeed need{uint64_t(zrt::att_rows_per_path(t0.lp, p->max_depth)) * n_lanes, 0};
-    const uint64_t partial_elems = plan.partial_bytes / sizeof(float4);
-    if (q.att.n < need.att_elems || q.partial.n < partial_elems || !q.counters.p) {
-      HIPCHK(hipStreamSynchronize(st));
-      q.att.grow(need.att_elems);
-      q.partial.grow(partial_elems);
-      if (!q.counters.p) q.counters.alloc(zrt::kScratchSlots);
-    }
-    q.counters_host.alloc(zrt::kScratchSlots);
-    HIPCHK(hipMemsetAsync(q.counters.p, 0, sizeof(unsigned long long) * zrt::kScratchSlots, st));
+    const uint32_t grid = zrt::prepare_radiance(c, p, plan, st);
     const bool accumulate = (rq->flags & ZRT_RQ_ACCUMULATE) != 0;
     const uint32_t total = accumulate ? rq->first_sample + rq->n_samples : rq->n_samples;
     const float scale = 1.0f / float(total);  // raytrace.zig:157
@@ -140,41 +180,26 @@ int zrt_ctx_radiance(zrt_ctx* c, const zrt_params* p, const struct zrt_radiance*
     zrt::launch_query(
         c, p, grid, st, true, "radiance query",
         [&](zrt::KArgs& a, const zrt::TracePlan& t, uint32_t launch_grid, hipStream_t s) {
-          zrt::check_buffers("radiance query",
-                             zrt::BufNeed{uint64_t(zrt::att_rows_per_path(t.lp, p->max_depth)) * a.n_lanes, 0}, q.att.n, 0);
-          q.rq_att_lds_rows = t.lp.att_rows;
-          q.rq_stack_lds_rows = t.lp.stack_rows;
-          q.rq_grid = launch_grid;
-          a.max_depth = p->max_depth;
-          a.att = q.att.p;
-          a.att_cap = q.att.n;
-          a.partial = q.partial.p;
-          a.counters = q.counters.p;
+          zrt::fill_radiance(c, p, a, t, launch_grid, "radiance query");
           zrt::RadianceArgs g{};
           g.key_offset = plan.key_offset;
           g.n = n;
-          // (a chunk past the key's sample field is one chunk of any call: the kernel's 32-bit
-          // sample arithmetic then stays far from wrapping)
           g.chunk = std::min<uint32_t>(plan.chunk, 65536u);
           g.sample_end = rq->first_sample + rq->n_samples;
           void* kernel = zrt::radiance_kernel_ptr(t.kmode, p->prng, t.stk16);
-          for (uint32_t r = 0; r < plan.rounds; ++r) {
-            const uint32_t chunk0 = r * plan.chunks_per_round;
-            const uint32_t chunks = std::min(plan.chunks_per_round, plan.call_chunks - chunk0);
-            g.n_items = uint64_t(n) * chunks;
-            g.sample0 = rq->first_sample + chunk0 * g.chunk;  // (chunk0 > 0 only where plan.chunk < 65536)
-            const uint32_t round_grid =
-                uint32_t(std::min<uint64_t>(launch_grid, (g.n_items + zrt::kBlock - 1) / zrt::kBlock));
-            void* args[] = {&a, &g, &dev_rays};
-            HIPCHK(hipLaunchKernel(kernel, dim3(round_grid), dim3(zrt::kBlock), args, t.lp.bytes, s));
-            HIPCHK(zrt::launch_radiance_finish(s, q.partial.p, n, chunks, r == 0 && !accumulate ? 1u : 0u, sum, nullptr,
-                                               0.0f, 0u, q.err.p));
-          }
+          zrt::radiance_rounds(plan, n, rq->first_sample, g.chunk, launch_grid,
+                               [&](uint32_t r, uint32_t chunks, uint64_t n_items, uint32_t sample0, uint32_t round_grid) {
+                                 g.n_items = n_items;
+                                 g.sample0 = sample0;
+                                 void* args[] = {&a, &g, &dev_rays};
+                                 HIPCHK(hipLaunchKernel(kernel, dim3(round_grid), dim3(zrt::kBlock), args, t.lp.bytes, s));
+                                 HIPCHK(zrt::launch_radiance_finish(s, q.partial.p, n, chunks, r == 0 && !accumulate ? 1u : 0u,
+                                                                    sum, nullptr, 0.0f, 0u, q.err.p));
+                               });
         },
         [&](hipStream_t s, const unsigned long long* err) {
           HIPCHK(zrt::launch_radiance_finish(s, q.partial.p, n, 0u, 0u, sum, dev_rgb, scale, 1u, err));
-          HIPCHK(hipMemcpyAsync(q.counters_host.get(), q.counters.p, sizeof(unsigned long long) * zrt::kScratchSlots,
-                                hipMemcpyDeviceToHost, s));
+          zrt::copy_radiance_counters(c, s);
         },
         p->max_depth);
     q.rq_samples = uint64_t(n) * rq->n_samples;
@@ -187,22 +212,7 @@ int zrt_ctx_radiance(zrt_ctx* c, const zrt_params* p, const struct zrt_radiance*
 int zrt_ctx_radiance_info(zrt_ctx* c, zrt_radiance_info* out) {
   if (!c || !out) return fail(ZRT_E_INVALID, "null argument");
   if (!c->query.rq_launched) return fail(ZRT_E_INVALID, "no radiance query launched on this context yet");
-  try {
-    HIPCHK(hipSetDevice(c->device));
-    const zrt::QueryState& q = c->query;
-    HIPCHK(hipEventSynchronize(q.done.done));
-    *out = zrt_radiance_info{};
-    out->samples = q.rq_samples;
-    out->reflections = q.counters_host[zrt::kReflections];
-    out->background_hits = q.counters_host[zrt::kBackground];
-    out->recursion_depth_hits = q.counters_host[zrt::kDepthHits];
-    out->rays = out->samples + out->reflections - out->recursion_depth_hits;
-    float f = 0.0f;
-    HIPCHK(hipEventElapsedTime(&f, q.timer.e0, q.timer.e1));
-    out->kernel_ms = f;
-    return ZRT_OK;
-  }
-  ZRT_CATCH_ALL
+  return zrt::radiance_info(c, out);
 }
 
 int zrt_ctx_debug_radiance(zrt_ctx* c, uint32_t out[4]) {

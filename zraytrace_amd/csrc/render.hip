@@ -4743,6 +4743,185 @@ __global__ void radiance_finish_kernel(const float4* __restrict__ partial, uint3
 }
 
 // ---------------------------------------------------------------------------
+// Camera queries (zrt_ctx_camera; zrt.h "camera queries"): frames through
+// device-generated lens rays.  radiance_kernel's item loop with the primary ray generated
+// at each sample start instead of read from a buffer: the sample's stream is the render's
+// own (keyed by the pixel's frame offset and the sample), its two jitter floats are used,
+// and a lens model (g.kind: a kernel argument, so the switch is a scalar branch and the
+// descriptor stays in SGPRs) maps (u, v) to an origin and a target; dir = tgt - o.  A model
+// that samples its lens draws from the stream of key ^ kLensStream through the same
+// generator object before the sample's stream is started.
+// A work item is one (slot, chunk).  Slots enumerate the rectangle in 8 x 8 tiles anchored
+// at (x0, y0), 64 slots per tile, so g.n is a multiple of 64: a wave's 64 items are one tile
+// of one chunk (the render's primary-ray coherence) and the one 64-bit division is scalar.
+// Slots outside the rectangle do no work and park nothing; camera_finish_kernel reads only
+// the slots inside.  Everything else - the bounded grid, the rows per lane of the grid,
+// [chunk][slot] parked sums, the counters, FAST's 4 waves per SIMD - is radiance_kernel's.
+// ---------------------------------------------------------------------------
+constexpr uint64_t kLensStream = 0xD1B54A32D192ED03ULL;
+
+template <int MODE, int PRNG, class StackT>
+__global__ void __launch_bounds__(kBlock, MODE == 3 ? 4 : 1) camera_kernel(const KArgs a, const CameraArgs g) {
+  extern __shared__ __attribute__((aligned(16))) char lds_raw[];
+  StackT* stk = reinterpret_cast<StackT*>(lds_raw) + threadIdx.x;
+  float4* lds_top = reinterpret_cast<float4*>(lds_raw + a.lds_top_off);
+  lds_u32* att_l = (lds_u32*)(lds_raw + a.lds_att_off) + threadIdx.x;  // [row][lane] att codes
+  if (MODE == 3 && !layout_ok(a)) return;
+  if (MODE == 3 && ZRT_LDS_TOP) fill_lds_top(a, lds_top);
+  const DevMaterial* mats = a.mats;
+  if (a.mats_in_lds) {  // block-uniform
+    float4* m = reinterpret_cast<float4*>(lds_raw + a.lds_mat_off);
+    fill_lds_mats(a, m);
+    mats = reinterpret_cast<const DevMaterial*>(m);
+  }
+  const uint32_t gl = blockIdx.x * kBlock + threadIdx.x;  // n_lanes < 2^32
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const AttRows ar{att_l, kBlock, gl, a.n_lanes};
+  uint32_t c_refl = 0, c_bg = 0, c_depth = 0, c_shade = 0, c_tex = 0;
+  uint32_t deepest = 0;  // the most attenuation rows a path of this lane pushed (kRqDeepestSlot)
+  Coh coh;
+  for (uint64_t base = (uint64_t)blockIdx.x * kBlock; base < g.n_items; base += (uint64_t)gridDim.x * kBlock) {
+    const uint64_t i0 = base + wave * 64u;  // the wave's first item: slot 0 of a tile
+    if (i0 >= g.n_items) continue;          // past the round's end (n_items is a multiple of 64)
+    const uint64_t cj = i0 / g.n;           // the wave's chunk within the round
+    const uint32_t slot0 = (uint32_t)(i0 - cj * g.n);
+    const uint32_t tile = slot0 >> 6;
+    const uint32_t ty = tile / g.tiles_w, tx = tile - ty * g.tiles_w;
+    const uint32_t lx = tx * 8u + (lane & 7u), ly = ty * 8u + (lane >> 3);
+    if (lx >= g.w || ly >= g.h) continue;  // a slot outside the rectangle
+    const uint32_t px = g.x0 + lx, py = g.y0 + ly;
+    const uint64_t pixel_key = (((uint64_t)py * g.width + px) << 16) + g.key_offset;  // (the sample field is free)
+    const float fx = (float)px, fy = (float)py;
+    const uint32_t s_end = min(g.sample0 + ((uint32_t)cj + 1u) * g.chunk, g.sample_end);
+    uint32_t sample = g.sample0 + (uint32_t)cj * g.chunk;
+    float acc_r = 0.0f, acc_g = 0.0f, acc_b = 0.0f;
+    V3 o = mk(0.0f, 0.0f, 0.0f), d = mk(0.0f, 0.0f, 1.0f);
+    uint32_t depth_left = 0;
+    bool in_sample = false;
+    Rng<PRNG> rng;
+    rng.init(0);
+    for (;;) {
+      if (!in_sample) {  // a new sample: lens floats, its stream, jitter, the model, Ray.init (ray.zig:11-13)
+        // (R << 16 has its low 16 bits clear and sample < 65536: the sum is the `|` of the definition)
+        const uint64_t key = pixel_key + (uint64_t)sample;
+        float la = 0.0f, lb = 0.0f;
+        if (g.kind == ZRT_LENS_THIN) {  // a point of the unit disc by rejection, on the lens stream
+          rng.init(key ^ kLensStream);
+          do {
+            la = 2.0f * rand_float(rng) - 1.0f;
+            lb = 2.0f * rand_float(rng) - 1.0f;
+          } while (!(la * la + lb * lb < 1.0f));
+        }
+        rng.init(key);
+        const float r1 = rand_float(rng);
+        const float r2 = rand_float(rng);
+        const float u = dev::div_rn((fx + r1) - 0.5f, g.f_width);  // raytrace.zig:173-174
+        const float v = dev::div_rn((fy + r2) - 0.5f, g.f_height);
+        const V3 org = mk(g.org[0], g.org[1], g.org[2]);
+        const V3 au = mk(g.au[0], g.au[1], g.au[2]);
+        const V3 av = mk(g.av[0], g.av[1], g.av[2]);
+        const V3 aw = mk(g.aw[0], g.aw[1], g.aw[2]);
+        V3 tgt;
+        if (g.kind == ZRT_LENS_EQUIRECT) {
+          float sp, cp, st, ct;
+          dev::sincos_z(kTwoPi * u, &sp, &cp);
+          dev::sincos_z(3.1415927f * v, &st, &ct);
+          o = org;
+          tgt = add(o, mk(st * cp, -ct, st * sp));
+        } else if (g.kind == ZRT_LENS_FISHEYE) {
+          const float qx = 2.0f * u - 1.0f, qy = 2.0f * v - 1.0f;
+          const float r = dev::sqrt_rn(qx * qx + qy * qy);
+          V3 dd = aw;
+          if (r != 0.0f) {
+            float sn, cs;
+            dev::sincos_z(r * g.half_fov, &sn, &cs);
+            const float k = dev::div_rn(sn, r);
+            dd = add(add(scale(au, qx * k), scale(av, qy * k)), scale(aw, cs));
+          }
+          o = org;
+          tgt = add(o, dd);
+        } else {  // the view plane: Camera.getRay's point (camera.zig:47-49)
+          const V3 llc = mk(g.llc[0], g.llc[1], g.llc[2]);
+          const V3 hor = mk(g.hor[0], g.hor[1], g.hor[2]);
+          const V3 ver = mk(g.ver[0], g.ver[1], g.ver[2]);
+          const V3 P = add(add(llc, scale(hor, u)), scale(ver, v));
+          if (g.kind == ZRT_LENS_ORTHO) {
+            o = P;
+            tgt = add(o, aw);
+          } else {  // pinhole; the thin lens: an origin on the lens, the plane is the focal plane
+            o = g.kind == ZRT_LENS_THIN ? add(add(org, scale(au, la)), scale(av, lb)) : org;
+            tgt = P;
+          }
+        }
+        d = unit(sub(tgt, o));
+        depth_left = a.max_depth;
+        in_sample = true;
+      }
+      // ---- one rayColor step (raytrace.zig:62-100)
+      bool path_end = false, sky = false;
+      V3 L = mk(0.0f, 0.0f, 0.0f);
+      if (depth_left == 0) {
+        ++c_depth;
+        path_end = true;
+      } else {
+        float best_t;
+        int best;
+        closest_hit<MODE, StackT>(a, o, d, stk, lds_top, gl, best_t, best);
+        shade_step<false, Rng<PRNG>>(a, mats, ar, rng, best, best_t, o, d, depth_left, path_end, sky, L, c_bg, c_refl,
+                                     c_shade, c_tex, coh);
+      }
+      if (path_end) {
+        const V3 col = sky ? att_product<false>(a, mats, ar, a.max_depth - depth_left, L, coh) : L;
+        acc_r += col.x;
+        acc_g += col.y;
+        acc_b += col.z;
+        // (shade_step pushes a scatter's row while depth_left > 1: the one at depth 1 is never read)
+        deepest = max(deepest, a.max_depth - depth_left - (depth_left == 0 && a.max_depth != 0 ? 1u : 0u));
+        in_sample = false;
+        if (++sample == s_end) break;  // the chunk's sequential sum is complete
+      }
+    }
+    a.partial[cj * g.n + slot0 + lane] = make_float4(acc_r, acc_g, acc_b, 0.0f);
+  }
+  wave_add_u64(&a.counters[kDepthHits], c_depth);
+  wave_add_u64(&a.counters[kReflections], c_refl);
+  wave_add_u64(&a.counters[kBackground], c_bg);
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) deepest = max(deepest, (uint32_t)__shfl_xor((int)deepest, off));
+  if (lane == 0 && deepest) atomicMax(&a.counters[kRqDeepestSlot], (unsigned long long)deepest);
+}
+
+// Behind camera_kernel, one lane per slot: radiance_finish_kernel with the slot mapped to
+// its pixel.  sum and rgb are whole-frame buffers indexed by R = y * width + x; a slot
+// outside the rectangle reads and writes nothing, so the frame's other pixels stay.
+__global__ void camera_finish_kernel(const float4* __restrict__ partial, const CameraArgs g, uint32_t n_chunks,
+                                     uint32_t zero_first, float4* __restrict__ sum, float* __restrict__ rgb,
+                                     float scale, uint32_t final, const unsigned long long* __restrict__ error_flag) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= g.n) return;
+  const uint32_t tile = i >> 6, l = i & 63u;
+  const uint32_t ty = tile / g.tiles_w, tx = tile - ty * g.tiles_w;
+  const uint32_t lx = tx * 8u + (l & 7u), ly = ty * 8u + (l >> 3);
+  if (lx >= g.w || ly >= g.h) return;
+  const uint64_t R = (uint64_t)(g.y0 + ly) * g.width + (g.x0 + lx);
+  float4 s = zero_first ? make_float4(0.0f, 0.0f, 0.0f, 0.0f) : sum[R];
+  for (uint32_t j = 0; j < n_chunks; ++j) {
+    const float4 p = partial[(uint64_t)j * g.n + i];
+    s.x += p.x;
+    s.y += p.y;
+    s.z += p.z;
+  }
+  if (final && *error_flag != 0ull) s.x = s.y = s.z = __builtin_nanf("");
+  sum[R] = make_float4(s.x, s.y, s.z, 0.0f);
+  if (final && rgb) {
+    rgb[3ull * R + 0] = s.x * scale;
+    rgb[3ull * R + 1] = s.y * scale;
+    rgb[3ull * R + 2] = s.z * scale;
+  }
+}
+
+// ---------------------------------------------------------------------------
 // host side (kernels.hpp): what must see a kernel symbol or a device template
 // ---------------------------------------------------------------------------
 namespace {
@@ -4954,6 +5133,26 @@ hipError_t launch_radiance_finish(hipStream_t st, const float4* partial, uint32_
                                   uint32_t zero_first, float4* sum, float* rgb, float scale, uint32_t final,
                                   const unsigned long long* error_flag) {
   return launch(radiance_finish_kernel, uint32_t((uint64_t(n) + 255) / 256), 256, st, partial, n, n_chunks, zero_first,
+                sum, rgb, scale, final, error_flag);
+}
+// Camera queries (camera_query.cpp): camera_kernel by radiance_kernel's modes, PRNG and stack width.
+void* camera_kernel_ptr(int mode, uint32_t prng, bool stk16) {
+#ifdef ZRT_ISA_KERNEL
+  (void)mode; (void)prng; (void)stk16;
+  return nullptr;
+#else
+#define ZRT_CQ_S(M, R) (stk16 ? reinterpret_cast<void*>(&camera_kernel<M, R, uint16_t>) \
+                              : reinterpret_cast<void*>(&camera_kernel<M, R, uint32_t>))
+#define ZRT_CQ(M) (prng == ZRT_PRNG_XOSHIRO256 ? ZRT_CQ_S(M, ZRT_PRNG_XOSHIRO256) : ZRT_CQ_S(M, ZRT_PRNG_XOROSHIRO128))
+  return mode == 0 ? ZRT_CQ(0) : mode == 1 ? ZRT_CQ(1) : mode == 2 ? ZRT_CQ(2) : ZRT_CQ(3);
+#undef ZRT_CQ
+#undef ZRT_CQ_S
+#endif
+}
+hipError_t launch_camera_finish(hipStream_t st, const float4* partial, const CameraArgs& g, uint32_t n_chunks,
+                                uint32_t zero_first, float4* sum, float* rgb, float scale, uint32_t final,
+                                const unsigned long long* error_flag) {
+  return launch(camera_finish_kernel, uint32_t((uint64_t(g.n) + 255) / 256), 256, st, partial, g, n_chunks, zero_first,
                 sum, rgb, scale, final, error_flag);
 }
 
