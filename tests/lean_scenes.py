@@ -1,6 +1,6 @@
 """Four tiny BVH scenes around the lean lockstep kernel's conditions.
 
-The lean kernel (render.hip ZRT_LEAN_*) is launched only for a scene of
+The lean kernel (render.hip struct Lean) is launched only for a scene of
 solid-colour Lambertian and metal materials, rendered from inside the scene's
 ray-origin bound.  Each scene here is a dozen triangles (a faceted mound) over a
 ground sphere, built through ctypes as tests/many_materials.py builds its grid:

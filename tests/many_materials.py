@@ -1,7 +1,7 @@
 """A scene with one material per sphere: a material table of any size.
 
 The lockstep and list-lane loops read the material table from LDS only
-(render.hip ZRT_MATS_LDS_ONLY); n_side chooses whether the table fits their
+(render.hip render_loop / render_loop_list); n_side chooses whether the table fits their
 share of the block's LDS (48 B per material on the device, ~26 KiB share) or
 the launch has to fall back to a loop that reads it from global memory.
 """

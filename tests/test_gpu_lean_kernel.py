@@ -1,7 +1,7 @@
 """The lean lockstep kernel against the general one and the oracle.
 
 render.hip compiles the timed lockstep FAST kernel a second time for scenes of
-solid-colour Lambertian and metal materials (ZRT_LEAN_*); the host launches it
+solid-colour Lambertian and metal materials (render.hip struct Lean); the host launches it
 where plan_launch and the camera allow it, and ZRT_LEAN=0 keeps the general
 kernel.  Every case here renders with ZRT_LEAN=1 and with ZRT_LEAN=0, the timed
 flavour and the STATS flavour (always the general kernel) of each, and asks of

@@ -462,7 +462,7 @@ def _mm_cases():
 @pytest.mark.parametrize("bvh,max_depth,pool,prng", _mm_cases())
 def test_material_table_past_lds_share(bvh, max_depth, pool, prng, monkeypatch):
     """The lockstep and list-lane loops read the material table from LDS only
-    (ZRT_MATS_LDS_ONLY); a table past their LDS share renders on the loop that reads
+    (through LDS-typed pointers); a table past their LDS share renders on the loop that reads
     it from global memory (FAST: the wavefront loop; list: the wave-unit loop), with
     no tile schedule (its probe is the lockstep loop) - the oracle's frame either way.
     At max_depth 0 no loop shades and the wavefront loop (written for max_depth >= 1:

@@ -1,7 +1,7 @@
 """Material.scatter and the texture lookup at their edges, in every sampling loop.
 
-render.hip writes the scatter out four times (shade_step in its general and
-its lean form, shade_hit_a in its two ZRT_LIST_CONVERGE forms) and the texture lookup once (image_texel_code); the
+render.hip writes the scatter out three times (shade_step in its general and
+its lean form, shade_hit_a with the materials' shared operations issued once per wave) and the texture lookup once (image_texel_code); the
 reference scenes reach few of their branches.  The scenes of
 tests/shading_scenes.py reach the others - tests/test_shading_scenes.py proves it
 on the CPU, ray by ray:

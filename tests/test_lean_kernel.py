@@ -1,8 +1,8 @@
 """The host's choice of the lean lockstep kernel (no device).
 
 render.hip compiles the timed lockstep FAST kernel a second time without image
-textures, dielectrics, the ray-origin check, the IEEE 1/det fallback and the
-scanline rows (ZRT_LEAN_*).  zrt_ctx_render_tiles launches it only where the
+textures, dielectrics, the ray-origin check and the
+scanline rows (render.hip struct Lean).  zrt_ctx_render_tiles launches it only where the
 scene, the params and the camera allow it (plan_launch's `lean`, lean_launch);
 zrt_debug_lean_kernel reports that decision through the same functions.
 
@@ -23,7 +23,7 @@ from zraytrace_amd import _ffi
 import lean_scenes as LS
 
 PRNGS = (z.ZRT_PRNG_XOROSHIRO128, z.ZRT_PRNG_XOSHIRO256)
-DEFAULT_ON = True  # render.hip ZRT_LEAN_DEFAULT: an eligible launch is lean with ZRT_LEAN unset
+DEFAULT_ON = True  # planner.cpp lean_wanted: an eligible launch is lean with ZRT_LEAN unset
 REFERENCE_SCENES = [0, 1, 2, 3, 4, 6]
 # the mesh scenes of solid Lambertian and metal materials only (scenes.zig): lean by default
 SOLID_MESH_SCENES = [0, 2, 3]

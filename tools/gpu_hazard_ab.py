@@ -1,6 +1,8 @@
 """GPU box: FAST on tests/hazard_rays.py's adversarial rays with the library
 in ZRT_LIB (e.g. the round-1 opening margin, abvar/open16) against the
-oracle: how many hazard / band / order-effect rays it gets wrong."""
+oracle: how many hazard / band / order-effect rays it gets wrong.
+(abvar/open16 was a variant of a build knob since retired: it needs a checkout
+from before the knobs were folded, DESIGN.md §3 "Retired build knobs".)"""
 import json
 import os
 import sys

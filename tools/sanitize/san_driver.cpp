@@ -55,7 +55,6 @@ const KernelConfig& kernel_config() {
     c.block_paths = 128 * 4;                           // kPoolPaths per wave x 4 waves
     c.layout = kLayoutVersion | kLayoutSphereSlots | kLayoutSphereFirst;
     c.paxis_m = 1024.0f;
-    c.lds_top = c.lane_lds = c.mats_lds_only = c.lean_default = c.grow = c.sphere_slots = true;
     return c;
   }();
   return k;

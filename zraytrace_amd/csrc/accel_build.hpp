@@ -45,8 +45,8 @@ constexpr int32_t kSphereSlotBias = int32_t(1) << 30;
 // the reference leaf's box bit for bit.
 // sphere_grow: inner children whose subtree holds a sphere are grown by this
 // much more (absolute): the rounded sphere test's reach beyond the sphere.
-// mark_spheres: leaf slots holding a sphere carry ref a - kSphereSlotBias (the
-// kernel must then be built to decode them: render.hip ZRT_SPHERE_SLOTS).
+// mark_spheres: leaf slots holding a sphere carry ref a - kSphereSlotBias (as
+// render.hip's kernels decode them: kKernelLayout).
 WideBvh build_wide_bvh(const std::vector<RefLeaf>& leaves, uint32_t top_levels = 2, float inflate = 0.0f,
                        float sphere_grow = 0.0f, bool mark_spheres = false);
 

@@ -197,7 +197,7 @@ static bool schedule_tiles(zrt_ctx* c, KArgs& a, uint32_t prng, bool stk16, uint
   const LdsPlan pp = plan_lds(sh.n_top, sh.n_mats, 3, stk16, a.stack_depth, a.max_depth, false, false, prng);
   // (it reads the material table from LDS only: no schedule for a table past its LDS
   // share - the render then takes the tiles in order)
-  if (K.mats_lds_only && !pp.mats_in_lds) return false;
+  if (!pp.mats_in_lds) return false;
   pr.partial.grow(uint64_t(my_tiles) * 64u);
   pr.scratch.grow(kScratchSlots);
   if (pr.tile_cost.n < my_tiles) {
@@ -549,7 +549,7 @@ KArgs fill_args(const zrt_ctx* c, const Frame& f, const FrameSize& z, const Laun
   a.n_paths = uint32_t(z.n_paths);
   // (a loop that reads the table from LDS only and has none there - the lockstep loop
   // at max_depth 0, which shades nothing - copies none: its plan holds no region for it)
-  if (K.mats_lds_only && P.kmode == 3 && !P.lp.mats_in_lds) a.n_mats = 0u;
+  if (P.kmode == 3 && !P.lp.mats_in_lds) a.n_mats = 0u;
   a.seed_mix = f.p->seed * 0x9E3779B97F4A7C15ULL + f.pass.key_offset;
   a.chunk = f.pass.chunk;
   a.n_chunks = f.pass.pass_chunks;

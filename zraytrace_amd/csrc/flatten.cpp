@@ -47,10 +47,6 @@ float guard_model(double max_p12) {
   const double k = 2.6 * 0x1p-24 * max_p12 / 1e-6;
   return float(std::min(k, double(0x1p-10)));
 }
-float graze_leaf_margin() {  // ZRT_GRAZE_LEAF: leaf slots' coefficient (A/B of a leaf-only guard)
-  if (const char* e = std::getenv("ZRT_GRAZE_LEAF")) return std::max(0x1p-18f, float(std::atof(e)));
-  return 0x1p-18f;
-}
 }  // namespace
 
 // Flatten the scene for the device: BVH (pre-order), slots in DFS leaf order.
@@ -172,7 +168,7 @@ void flatten_scene(HostScene* c, const zrt_scene* s, bool use_bvh, int device, i
     const float sphere_grow = any_sphere ? float(std::ldexp(std::sqrt(2.0), -9) * (3.0 * std::sqrt(3.0) + 1.0) * double(H)) : 0.0f;
     const double tw = now_ms();
     c->graze_m = graze_margin();
-    c->graze_leaf = std::max(c->graze_m, graze_leaf_margin());
+    c->graze_leaf = std::max(c->graze_m, 0x1p-18f);  // (KArgs::graze_leaf: no kernel reads it)
     c->guard = 0.0f;  // (set below, once the triangles are known)
     // the top levels stored first (LDS): two for the full 128-B nodes; a tree that
     // also gets compressed nodes stores qtop_levels() (their 64-B nodes leave room
@@ -180,14 +176,12 @@ void flatten_scene(HostScene* c, const zrt_scene* s, bool use_bvh, int device, i
     const uint32_t n_leaf_est = uint32_t(leaves.size());
     const bool want_q = qnodes >= 0 ? qnodes != 0 : want_qnodes((n_leaf_est + 2) / 3);  // (about leaves / 3 nodes)
     const uint32_t top_levels = want_q ? qtop_levels() : 2u;
-    const WideBvh wide = build_wide_bvh(leaves, top_levels, K.grow ? 0.5f * c->graze_m : 0.0f,
-                                        K.sphere_slots ? sphere_grow : 0.0f, K.sphere_slots);
+    const WideBvh wide = build_wide_bvh(leaves, top_levels, 0.5f * c->graze_m, sphere_grow, true);
     if (std::getenv("ZRT_DEBUG_LAUNCH"))
       std::fprintf(stderr, "zrt preprocess: wide tree %u nodes in %.1f ms\n", wide.n_nodes, now_ms() - tw);
     const size_t nw = wide.nodes.size();
     // one copy per ray octant o (bit k set: direction k negative) with axis k's
     // min / max planes swapped, so float4 0-2 are the near planes, 3-5 the far
-    // (a one-copy A/B build, ZRT_OCT_COPIES = 0: octant 0's alone, planes selected per ray)
     std::vector<float4> wn(K.oct_copies * nw);
     for (uint32_t o = 0; o < K.oct_copies; ++o) {
       float4* dst = wn.data() + o * nw;
@@ -199,8 +193,8 @@ void flatten_scene(HostScene* c, const zrt_scene* s, bool use_bvh, int device, i
     c->wide_stack = wide.max_stack + 3;  // + the dead entries of a branch-free push
     // compressed nodes for trees past the caches (want_qnodes): the same tree, 64-B nodes
     // (quantize_wide stores octant copies with pre-swapped planes, which wide_iter_q
-    // reads as such: never built for a one-copy A/B build, ZRT_OCT_COPIES = 0)
-    if (want_q && K.oct_copies == 8) {
+    // reads as such)
+    if (want_q) {
       const double tq = now_ms();
       QuantWide qw = quantize_wide(wide);
       if (qw.ok) {

@@ -96,7 +96,7 @@ struct LaunchPlan {
   int mode = 0;   // 0 list, 1 binary, 2 reference, 3 FAST
   int kmode = 0;  // the kernel: mode, or 4 wavefront, 5 / 7 / 8 / 9 path pool, 6 list with per-lane items
   bool stk16 = false, wf = false, pool = false, qn = false, guard_on = false;
-  // the timed launch may take the lean kernel (ZRT_LEAN_*): the scene and the params
+  // the timed launch may take the lean kernel (render.hip struct Lean): the scene and the params
   // allow it; the launch itself adds that its camera lies inside the origin bound
   // and that it is not the STATS flavour (lean_launch)
   bool lean = false;

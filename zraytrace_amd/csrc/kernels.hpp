@@ -94,7 +94,7 @@ struct KArgs {
                            // on the host, and scattered rays start at hits), so ray_origin_ok is skipped
   uint32_t layout;         // the wide tree's encoding (accel_build.hpp kLayout*): must equal kKernelLayout
   float graze_m;           // the grazing margins' coefficient (RayT::gm; DESIGN.md §3 "Grazing rays")
-  float graze_leaf;        // ... of leaf slots' relative margin (RayT::gl, >= graze_m)
+  float graze_leaf;        // (no kernel reads it: leaf slots share graze_m; the host still fills it)
   float guard;             // the grazing-triangle guard (RayT::gk, wide_iter; 0: off)
   uint64_t att_cap, ovf_cap;  // elements of `att` and of `stack_ovf` (StackT): row_ok's bounds
 };
@@ -195,22 +195,21 @@ constexpr uint32_t kMetricShards = 64, kMetricStride = 16, kMetricWords = kMetri
 constexpr uint32_t kTileFrozen = 0x80000000u;  // tile_done[lt]: bit 31 set once the tile is frozen (resolve_kernel)
 
 // The values render.hip's kernels were compiled with, which the host plans
-// against (planner.cpp, flatten.cpp): the ZRT_* build knobs of render.hip and the
-// sizes that follow from them.  Host files read this struct and no build macro,
+// against (planner.cpp, flatten.cpp): the numeric ZRT_* build knobs of render.hip
+// (launch sizes), the sizes that follow from them, and whether this is a profiling
+// build.  Host files read this struct and no build macro,
 // so a variant build (tools/variants.sh: -D flags on render.hip alone) plans for
 // the kernels it really holds.
 struct KernelConfig {
   uint32_t waves_wide, waves_wf, waves_pool, waves_list, waves_per_simd;  // ZRT_WAVES_*: blocks per CU of each loop
   uint32_t att_rows_lock, att_rows_wf, att_rows_pool, att_rows_list;      // ZRT_ATT_ROWS_*
   uint32_t stack_rows_lock, sync_samples, probe_spp;  // ZRT_STACK_ROWS_LOCK, ZRT_SYNC_SAMPLES, ZRT_PROBE_SPP
-  uint32_t oct_copies;                                // kOctCopies: 8, or 1 (ZRT_OCT_COPIES = 0)
+  uint32_t oct_copies;                                // kOctCopies: 8, the wide tree once per ray octant
   uint32_t lane_words[2];                             // LaneState<prng>::kWords
   uint32_t block_paths;                               // kBlockPaths: the path pool's paths per block
   uint32_t layout;                                    // kKernelLayout
   float paxis_m;                                      // kPaxisM
-  // ZRT_LDS_TOP, ZRT_LANE_LDS, ZRT_MATS_LDS_ONLY, ZRT_LOCK_QN, ZRT_PROFILE, ZRT_LEAN_DEFAULT, ZRT_GROW, ZRT_SPHERE_SLOTS
-  bool lds_top, lane_lds, mats_lds_only, lock_qn, profile, lean_default, grow, sphere_slots;
-  bool oct_mul24;  // ZRT_OCT_MUL24 (with octant copies): zrt::check_octant_offsets bounds the trees
+  bool profile;                                       // ZRT_PROFILE
 };
 const KernelConfig& kernel_config();
 

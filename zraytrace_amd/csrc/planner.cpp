@@ -113,12 +113,11 @@ float paxis_threshold() {
   return kernel_config().paxis_m;
 }
 // A ray's octant copy starts oct * stride_f4 float4s into the nodes and oct * n_top *
-// node_f4 into the LDS top levels (render.hip wide_view).  Kernels built with
-// ZRT_OCT_MUL24 form both by a 24-bit multiply, which reads the low 24 bits of each
+// node_f4 into the LDS top levels (render.hip wide_view).  The kernels form both by
+// a 24-bit multiply (oct_times), which reads the low 24 bits of each
 // factor only: a tree whose stride or top levels reach 2^24 float4s (2 M full nodes
 // per copy; the C5 mesh has 3.7 M float4s) is refused before anything is uploaded.
 void check_octant_offsets(uint32_t stride_f4, uint32_t n_top, uint32_t node_f4) {
-  if (!kernel_config().oct_mul24) return;
   constexpr uint64_t lim = 1ull << 24;
   const uint64_t top = uint64_t(n_top) * node_f4;
   if (stride_f4 >= lim || top >= lim)
@@ -143,7 +142,7 @@ static bool use_pool(bool stk16) {
 bool want_qnodes(uint32_t n_wide) {
   if (const char* e = std::getenv("ZRT_QNODES")) return std::atoi(e) != 0;
   (void)n_wide;
-  return kernel_config().lock_qn;  // (the A/B build's lockstep loop reads nothing else)
+  return false;
 }
 // Top levels of a compressed tree served from LDS (ZRT_QTOP overrides): every ray
 // reads the root and a level-1 node, most a level-2 node - with 64-B nodes the
@@ -202,7 +201,7 @@ bool fast_stk16(uint32_t n_wide, uint32_t n_nodes) {
 // pool: the path-pool loop (MODE 5): its attenuation rows are per path
 // (kBlockPaths per block), and its rays / hits / queues follow them.
 // The lockstep FAST loop (mode 3, neither wf nor pool) also holds its lane state
-// (ZRT_LANE_LDS) and keeps at most ZRT_STACK_ROWS_LOCK stack rows in LDS.
+// (LaneState) and keeps at most ZRT_STACK_ROWS_LOCK stack rows in LDS.
 LdsPlan plan_lds(uint32_t n_top, uint32_t n_mats, int mode, bool stk16, uint32_t stack_depth, uint32_t max_depth,
                  bool wf, bool pool, uint32_t prng, uint32_t node_f4, uint32_t rows_cap) {
   const uint32_t waves = mode == 3 ? (pool ? K.waves_pool : wf ? K.waves_wf : K.waves_wide)
@@ -212,10 +211,10 @@ LdsPlan plan_lds(uint32_t n_top, uint32_t n_mats, int mode, bool stk16, uint32_t
   const size_t budget = (160u << 10) / waves - (1u << 10);
   const size_t entry = stk16 ? sizeof(uint16_t) : sizeof(uint32_t);
   const size_t row_att = sizeof(uint32_t) * (pool ? K.block_paths : kBlock);  // one att code per lane / path
-  const size_t top = mode == 3 && K.lds_top ? size_t(n_top) * node_f4 * sizeof(float4) * K.oct_copies : 0;
+  const size_t top = mode == 3 ? size_t(n_top) * node_f4 * sizeof(float4) * K.oct_copies : 0;
   const size_t pool_b = pool ? pool_lds_bytes() : 0;
   const bool lock = mode == 3 && !wf && !pool;
-  const size_t state = lock && K.lane_lds ? size_t(K.lane_words[prng == ZRT_PRNG_XOSHIRO256]) * 4u * kBlock : 0;
+  const size_t state = lock ? size_t(K.lane_words[prng == ZRT_PRNG_XOSHIRO256]) * 4u * kBlock : 0;
   // attenuation rows wanted: rows 0 .. max_depth-2 are ever pushed (raytrace.zig:99 at depth > 1).
   // A row is one 4-B att code per lane (att_code; round 3: three floats, 12 B), so
   // the same LDS holds three times the rows: the lockstep loop 6 (round 3, 2 rows
@@ -248,10 +247,10 @@ LdsPlan plan_lds(uint32_t n_top, uint32_t n_mats, int mode, bool stk16, uint32_t
     L.stack_rows = std::max<uint32_t>(1, std::min<uint32_t>(L.stack_rows, rows_cap));
   const size_t stack = (size_t(L.stack_rows) * kBlock * entry + 15) & ~size_t(15);
   const size_t used = stack + top + pool_b + state;
-  // loops that read the material table from LDS only (ZRT_MATS_LDS_ONLY): the table
+  // loops that read the material table from LDS only (the lockstep and list loops): the table
   // before the attenuation rows, which live in global memory when LDS runs out
   const size_t mats = size_t(n_mats) * sizeof(DevMaterial);
-  const bool mats_first = K.mats_lds_only && (lock || mode == 0);
+  const bool mats_first = lock || mode == 0;
   const size_t mats_res = mats_first && used + mats <= budget ? mats : 0;
   L.att_rows = std::min<uint32_t>(want, used + mats_res < budget ? uint32_t((budget - used - mats_res) / row_att) : 0u);
   L.top_off = uint32_t(stack);
@@ -308,7 +307,7 @@ uint64_t ovf_cap_elems(uint64_t ovf_bytes, bool stk16) { return ovf_bytes / (stk
 // ZRT_LEAN=0 forces the general kernel; an ineligible launch never takes the lean one
 static bool lean_wanted() {
   if (const char* e = std::getenv("ZRT_LEAN")) return std::atoi(e) != 0;
-  return kernel_config().lean_default;
+  return true;
 }
 // KArgs::check_origins of a render launch is 0: its camera lies inside the scene's origin bound
 bool camera_inside(const zrt_camera* cam, const float root_c[3], float origin_bound) {
@@ -342,16 +341,13 @@ LaunchPlan plan_launch(const SceneShape& s, const zrt_params* p) {
   // must fit beside its rays and queues in the block's LDS share, else the 32-bit
   // stack with overflow rows
   P.pool = mode == 3 && shades && (use_pool(P.stk16) || P.guard_on);
-  // the path pool over compressed nodes (MODE 8 / 9) where the context built them (and
-  // the lockstep loop in the ZRT_LOCK_QN A/B build, which has no other traversal)
-  const bool lock_qn = K.lock_qn && mode == 3 && !P.pool && !P.wf;
-  if (lock_qn && !s.q_ok) throw Error(ZRT_E_UNSUPPORTED, "ZRT_LOCK_QN build: no compressed nodes for this tree");
-  P.qn = (P.pool || lock_qn) && s.q_ok;
+  // the path pool over compressed nodes (MODE 8 / 9) where the context built them
+  P.qn = P.pool && s.q_ok;
   P.node_f4 = P.qn ? kQuantNodeF4 : 8u;
   const uint32_t n_top = P.qn ? s.q_top : s.n_top;
   if (P.pool && P.stk16) {
     const size_t budget = (160u << 10) / K.waves_pool - (1u << 10);
-    const size_t top = K.lds_top ? size_t(n_top) * P.node_f4 * sizeof(float4) * K.oct_copies : 0;
+    const size_t top = size_t(n_top) * P.node_f4 * sizeof(float4) * K.oct_copies;
     // (rows the tests' cap keeps out of LDS need not fit it)
     const uint32_t rows = std::min(P.stack_depth, stack_rows_cap());
     if (size_t(rows) * kBlock * sizeof(uint16_t) + top + pool_lds_bytes() > budget) P.stk16 = false;
@@ -364,7 +360,7 @@ LaunchPlan plan_launch(const SceneShape& s, const zrt_params* p) {
   // touched) so the LDS never caps the occupancy the registers allow; the
   // other traversals keep the whole stack in LDS (plan_lds)
   P.lp = plan_lds(n_top, s.n_mats, mode, P.stk16, P.stack_depth, p->max_depth, P.wf, P.pool, p->prng, P.node_f4);
-  if (K.mats_lds_only && (P.kmode == 3 || P.kmode == 6) && !P.lp.mats_in_lds) {
+  if ((P.kmode == 3 || P.kmode == 6) && !P.lp.mats_in_lds) {
     // a material table past the loop's LDS share: the loop that reads it from global
     // memory (the wavefront loop for FAST, the wave-unit list loop; same images).
     // At max_depth 0 the lockstep loop stays (the wavefront loop would trace, and its
@@ -380,7 +376,7 @@ LaunchPlan plan_launch(const SceneShape& s, const zrt_params* p) {
   }
   // the lean kernel: the lockstep FAST loop over full nodes, shading (it reads the
   // material table from LDS only), in a scene that has none of what it leaves out
-  P.lean = P.kmode == 3 && !K.lock_qn && shades && P.lp.mats_in_lds != 0 && s.tri_rcp_fast && !s.has_dielectric &&
+  P.lean = P.kmode == 3 && shades && P.lp.mats_in_lds != 0 && s.tri_rcp_fast && !s.has_dielectric &&
            !s.has_image_texture && (p->flags & ZRT_FLAG_SCANLINES) == 0 && lean_wanted();
   return P;
 }

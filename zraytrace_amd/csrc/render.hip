@@ -39,27 +39,23 @@ namespace zrt {
 // allocations): past it, kErrBounds is raised and the access skipped, so a
 // sizing mistake the host check (zrt::check_buffers) missed reports instead of
 // faulting.  The timed flavour compiles it away.
-#ifndef ZRT_DEBUG_BOUNDS
-#define ZRT_DEBUG_BOUNDS 1
-#endif
 template <bool STATS>
 __device__ __forceinline__ bool row_ok(const KArgs& a, uint64_t idx, uint64_t cap) {
-  if (!STATS || !ZRT_DEBUG_BOUNDS || idx < cap) return true;
+  if (!STATS || idx < cap) return true;
   atomicOr(a.error_flag, kErrBounds);
   return false;
 }
 
-#ifndef ZRT_RARE_ARGS
-#define ZRT_RARE_ARGS 1  // kernel arguments that only rare branches of the FAST loop read (the error flag, the
-                         // stack's overflow rows, the replay's reference tree) are loaded from the argument
-                         // block inside those branches, through a pointer the compiler cannot trace: they no
-                         // longer sit in (spilled) SGPRs across the sampling loop
-#endif
+// Kernel arguments that only rare branches of the FAST loop read (the error flag, the
+// stack's overflow rows, the replay's reference tree) are loaded from the argument
+// block inside those branches, through a pointer the compiler cannot trace: they do
+// not sit in (spilled) SGPRs across the sampling loop.
 // The kernel's arguments as a rare branch reads them.  Every kernel that reaches these
 // paths takes its KArgs by value as its first parameter, so the argument block starts
 // with it; the empty asm hides where the pointer came from, which keeps each load - a
 // scalar load from the constant address space - inside the branch that asked for it.
-#if ZRT_RARE_ARGS && defined(__HIP_DEVICE_COMPILE__)
+// (The host pass only needs the code to compile.)
+#if defined(__HIP_DEVICE_COMPILE__)
 typedef const __attribute__((address_space(4))) KArgs* RareArgs;
 __device__ __forceinline__ RareArgs rare_args(const KArgs& a) {
   (void)a;
@@ -97,31 +93,6 @@ __device__ __forceinline__ uint64_t prof_stamp() {
 #ifndef ZRT_PROBE_SPP
 #define ZRT_PROBE_SPP 1  // samples per pixel of the scheduling probe; A/B at N=8: 1, 2, 4, 8 give the same render launch
 #endif
-#ifndef ZRT_LIST_SCALAR
-#define ZRT_LIST_SCALAR 1  // list mode reads its (wave-uniform) surfaces with scalar loads
-#endif
-#ifndef ZRT_OCT_COPIES
-#define ZRT_OCT_COPIES 1  // the wide tree stored once per ray octant (0: one copy, planes selected per ray)
-#endif
-#ifndef ZRT_ORDER_EXACT
-#define ZRT_ORDER_EXACT 1  // FAST / BINARY: re-trace order-hazard rays the reference's way (0: A/B only, not exact)
-#endif
-#ifndef ZRT_LEAF_LOOP
-#define ZRT_LEAF_LOOP 1  // 16-bit stack too: opened leaves walked in one loop (one copy of the primitive tests)
-#endif
-#ifndef ZRT_HAZARD_ENTRY
-#define ZRT_HAZARD_ENTRY 1  // also replay rays whose best hit lies below its own leaf's loose entry
-#endif
-#ifndef ZRT_LDS_TOP
-#define ZRT_LDS_TOP 1  // FAST: the wide tree's top levels read from LDS (0: A/B, every node from global memory)
-#endif
-#ifndef ZRT_LANE_LDS
-#define ZRT_LANE_LDS 1  // lockstep FAST loop: RNG state, chunk sums, sample and depth kept in LDS across the traversal
-#endif
-#ifndef ZRT_LANE_OD
-#define ZRT_LANE_OD 0  // lockstep FAST loop: the ray's origin and direction parked with the lane state too
-                       // (25 spills instead of 26; C4 53.6 vs 53.9 Gray/s, profiles/r06/r06c)
-#endif
 #ifndef ZRT_STACK_ROWS_LOCK
 #define ZRT_STACK_ROWS_LOCK 16  // lockstep FAST loop: traversal stack rows in LDS (deeper rows in global memory)
 #endif
@@ -133,45 +104,17 @@ __device__ __forceinline__ uint64_t prof_stamp() {
 // solid-colour Lambertian and metal materials only, whose triangles all pass the
 // tri_rcp_fast bound, rendered from a camera inside the origin bound, without
 // scanline rows (zrt::plan_launch's `lean` and the launch's own check_origins
-// decide on the host; ZRT_LEAN=0 forces the general kernel).  One switch per
-// feature it leaves out, so each can be measured on its own (0: the lean kernel
-// keeps that feature's code, as the general kernel has it):
-#ifndef ZRT_LEAN_TEX
-#define ZRT_LEAN_TEX 1  // no image textures: no (u, v), no texel codes, no texel stores in att_value
-#endif
-#ifndef ZRT_LEAN_DIEL
-#define ZRT_LEAN_DIEL 1  // no dielectric: no refraction branch, no (1, 1, 1) attenuation code
-#endif
-#ifndef ZRT_LEAN_ORIGIN
-#define ZRT_LEAN_ORIGIN 1  // every ray origin inside the bound: ray_origin_ok is true
-#endif
-#ifndef ZRT_LEAN_DET
-#define ZRT_LEAN_DET 0  // 1: no IEEE 1/det behind dev::rcp_core (every triangle is under the tri_rcp_fast
-                        // bound).  Exact, but off: alone it spills 30 VGPRs for 26, and the other four
-                        // without it ran C4 0.4 % faster than all five in every A/B round
-#endif
-#ifndef ZRT_LEAN_EPI
-#define ZRT_LEAN_EPI 1  // no scanline rows and no probe cost at the end of a unit
-#endif
-#ifndef ZRT_LEAN_DEFAULT
-#define ZRT_LEAN_DEFAULT 1  // an eligible launch takes the lean kernel unless ZRT_LEAN=0 (0: only with ZRT_LEAN=1)
-#endif
-// Per-ray scalar overhead of the FAST traversal's prologue (every kernel that
-// traverses the wide tree; exact by construction, one switch each for A/B):
-#ifndef ZRT_OCT_MASKS_LOCAL
-#define ZRT_OCT_MASKS_LOCAL 1  // the three sign masks of 1/d are formed where a rare path reads them (the
-                               // order-hazard replay's box test), behind a value the compiler cannot trace
-                               // back to the ray's start: it no longer parks them in six spill lanes per ray
-#endif
-#ifndef ZRT_OCT_MUL24
-#define ZRT_OCT_MUL24 1  // the octant copy's offsets by a full-rate 24-bit multiply (v_mul_u32_u24) instead of
-                         // the quarter-rate v_mul_lo_u32: wide_stride and n_top * node_f4 are below 2^24
-                         // (flatten_scene refuses larger trees: zrt::check_octant_offsets)
-#endif
+// decide on the host; ZRT_LEAN=0 forces the general kernel).  The features it
+// leaves out:
+//   tex     no image textures: no (u, v), no texel codes, no texel stores in att_value
+//   diel    no dielectric: no refraction branch, no (1, 1, 1) attenuation code
+//   origin  every ray origin inside the bound: ray_origin_ok is true
+//   epi     no scanline rows and no probe cost at the end of a unit
+// (It keeps the IEEE 1/det behind dev::rcp_core: dropping that alone spilt 30 VGPRs
+// for 26, and the other four without it ran C4 0.4 % faster than all five.)
 template <bool LEAN>
 struct Lean {
-  static constexpr bool tex = LEAN && ZRT_LEAN_TEX, diel = LEAN && ZRT_LEAN_DIEL, origin = LEAN && ZRT_LEAN_ORIGIN,
-                        det = LEAN && ZRT_LEAN_DET, epi = LEAN && ZRT_LEAN_EPI;
+  static constexpr bool tex = LEAN, diel = LEAN, origin = LEAN, epi = LEAN;
 };
 
 // ---------------------------------------------------------------------------
@@ -267,15 +210,6 @@ __device__ __forceinline__ V3 add(V3 a, V3 b) { return mk(a.x + b.x, a.y + b.y, 
 __device__ __forceinline__ V3 sub(V3 a, V3 b) { return mk(a.x - b.x, a.y - b.y, a.z - b.z); }
 __device__ __forceinline__ V3 scale(V3 a, float s) { return mk(a.x * s, a.y * s, a.z * s); }
 __device__ __forceinline__ V3 neg(V3 a) { return mk(-a.x, -a.y, -a.z); }
-#ifndef ZRT_FD_UNIT  // per-site switches of the short divisions (A/B and register-pressure probes)
-#define ZRT_FD_UNIT ZRT_FAST_DIV
-#endif
-#ifndef ZRT_FD_INV
-#define ZRT_FD_INV ZRT_FAST_DIV
-#endif
-#ifndef ZRT_FD_TRI
-#define ZRT_FD_TRI ZRT_FAST_DIV
-#endif
 __device__ __forceinline__ V3 unit(V3 v) {  // vector.zig:88-92
   const float l = dev::sqrt_rn(v.x * v.x + v.y * v.y + v.z * v.z);
   // v.k / l as dev::div_core over one reciprocal of l (12 VALU instead of 30):
@@ -285,7 +219,7 @@ __device__ __forceinline__ V3 unit(V3 v) {  // vector.zig:88-92
   // (the range is checked on the operands, |v.k| >= l * 2^-50, before any quotient
   // exists, so each component's three steps need two registers at a time)
   const float vmin = __builtin_fminf(__builtin_fminf(__builtin_fabsf(v.x), __builtin_fabsf(v.y)), __builtin_fabsf(v.z));
-  if (__builtin_expect(ZRT_FD_UNIT && l >= 0x1p-50f && l <= 0x1p50f && vmin >= l * 0x1p-50f, 1)) {
+  if (__builtin_expect(ZRT_FAST_DIV && l >= 0x1p-50f && l <= 0x1p50f && vmin >= l * 0x1p-50f, 1)) {
     const float y = dev::rcp_core(l);
     return mk(dev::div_core(v.x, l, y), dev::div_core(v.y, l, y), dev::div_core(v.z, l, y));
   }
@@ -296,7 +230,7 @@ __device__ __forceinline__ V3 unit(V3 v) {  // vector.zig:88-92
 __device__ __forceinline__ void inv_dir(float dx, float dy, float dz, float& ix, float& iy, float& iz) {
   const float lo = __builtin_fminf(__builtin_fminf(__builtin_fabsf(dx), __builtin_fabsf(dy)), __builtin_fabsf(dz));
   const float hi = __builtin_fmaxf(__builtin_fmaxf(__builtin_fabsf(dx), __builtin_fabsf(dy)), __builtin_fabsf(dz));
-  if (__builtin_expect(ZRT_FD_INV && lo >= 0x1p-126f && hi < 0x1p126f, 1)) {
+  if (__builtin_expect(ZRT_FAST_DIV && lo >= 0x1p-126f && hi < 0x1p126f, 1)) {
     ix = dev::rcp_core(dx);
     iy = dev::rcp_core(dy);
     iz = dev::rcp_core(dz);
@@ -311,7 +245,7 @@ __device__ __forceinline__ void inv_dir(float dx, float dy, float dz, float& ix,
 // 2^126, so dev::rcp_core needs no per-lane guard (a per-lane branch here, in the
 // leaf loop, cost the FAST kernel 4 spilled VGPRs)
 __device__ __forceinline__ float inv_det_rn(float det, uint32_t fast) {
-  if (ZRT_FD_TRI && fast) return dev::rcp_core(det);
+  if (ZRT_FAST_DIV && fast) return dev::rcp_core(det);
   return 1.0f / det;
 }
 __device__ __forceinline__ V3 reflect(V3 v, V3 n) { return sub(v, scale(n, 2.0f * dot(v, n))); }
@@ -333,9 +267,12 @@ struct RayT {
   // triangle.zig:61 that passes det >= 1e-6 lies in dev::rcp_core's range; a
   // wave-uniform value (from KArgs), so the choice below is a scalar branch
   uint32_t rcp_det;
-  // the scene's grazing-margin coefficients (KArgs::graze_m / graze_leaf, 2^-18 by
-  // default): inner slots / leaf slots; wave-uniform, so they stay in SGPRs
-  float gm, gl;
+  // the scene's grazing-margin coefficient (KArgs::graze_m, 2^-18 by default);
+  // wave-uniform, so it stays in SGPRs
+  float gm;
+  // KArgs::graze_leaf.  Nothing reads it (leaf slots share gm); it stays, filled, until
+  // KArgs::graze_leaf goes: without it the register allocation of every kernel changes
+  float gl;
   float gk;  // the grazing-triangle guard's coefficient (KArgs::guard; 0: off), wave-uniform
 };
 
@@ -359,28 +296,16 @@ struct RayT {
 //   coordinates.
 // On the grazing rays no hit lies outside its box's t interval by more than 0.72
 // of half these margins (tools/grazing_excess.py).
-#ifndef ZRT_GRAZE_SLACK
-#define ZRT_GRAZE_SLACK 1  // 0: A/B only (round-2 margins, not exact on grazing rays)
-#endif
-#ifndef ZRT_GROW
-#define ZRT_GROW ZRT_GRAZE_SLACK  // A/B only: 0 stores inner boxes ungrown (not exact)
-#endif
-#ifndef ZRT_REL_M
-#define ZRT_REL_M ZRT_GRAZE_SLACK  // A/B only: 0 keeps the constant relative margin (not exact)
-#endif
-#ifndef ZRT_LEAF_SLACK
-#define ZRT_LEAF_SLACK ZRT_GRAZE_SLACK  // A/B only: 0 drops the leaf slots' slack (not exact)
-#endif
 // (recomputed where used from 1/d, 1 VALU each, rather than kept in VGPRs across
 // the traversal: two more live registers cost the deep-tree loop spills)
 __device__ __forceinline__ float ray_m(const RayT& r) {  // max_k |1/d_k|
   return __builtin_fmaxf(__builtin_fmaxf(__builtin_fabsf(r.ix), __builtin_fabsf(r.iy)), __builtin_fabsf(r.iz));
 }
 // relative margin of every narrowed cull: 1 + 2^-16 + 2^-18 m
-__device__ __forceinline__ float ray_rel(const RayT& r, float m) { return ZRT_REL_M ? 1.0000153f + r.gm * m : 1.0000153f; }
+__device__ __forceinline__ float ray_rel(const RayT& r, float m) { return 1.0000153f + r.gm * m; }
 // the reference boxes' slack: 2^-18 x the triangles' largest |coordinate| x m
 __device__ __forceinline__ float ray_slack(const RayT& r, float extent, float m) {
-  return ZRT_LEAF_SLACK ? __builtin_fmaxf(extent, 0x1p-100f) * r.gm * m : 0.0f;
+  return __builtin_fmaxf(extent, 0x1p-100f) * r.gm * m;
 }
 
 // Nearly axis-parallel rays (DESIGN.md §3 "Per-axis margins").  The margins
@@ -395,16 +320,10 @@ __device__ __forceinline__ float ray_slack(const RayT& r, float extent, float m)
 // the triangles' largest |coordinate|, ray_slack's spatial term) - 6 more adds
 // per slot, for waves with such a lane only; the other waves keep ray_rel with
 // m <= kPaxisM.
-#ifndef ZRT_GRAZE_LEAF
-#define ZRT_GRAZE_LEAF 0  // leaf slots' relative margin from its own coefficient (KArgs::graze_leaf; A/B of a
-                          // leaf-only guard: fixed none of the grazing-triangle misses, C4 -4 %, profiles/r04/r04c)
-#endif
-#ifndef ZRT_PAXIS
-#define ZRT_PAXIS 1  // 0: A/B only (every wave on the t-space margins of ray_rel / ray_slack)
-#endif
-#ifndef ZRT_PAXIS_LOCK
-#define ZRT_PAXIS_LOCK 0  // the lockstep loop too (its 96-VGPR budget spills 7 -> 28 registers with the branch: C4 -2.8 %)
-#endif
+// (The lockstep loop keeps the t-space margins: its 96-VGPR budget spills 7 -> 28
+// registers with the branch, C4 -2.8 %.  A leaf-only margin from a coefficient of
+// its own, KArgs::graze_leaf, fixed none of the grazing-triangle misses at C4 -4 %,
+// profiles/r04/r04c: leaf slots share ray_rel.)
 #ifndef ZRT_PAXIS_LOG2M
 #define ZRT_PAXIS_LOG2M 10
 #endif
@@ -422,9 +341,6 @@ __device__ __forceinline__ float paxis_t(float g, float inv) {
 // The grazing-triangle guard's spatial widening for this ray: gk (T + extent)
 // (T as in paxis_grow bounds |o - a| for every triangle vertex a): the reach of
 // an accepted hit beyond its triangle, k |ao| + k_c (DESIGN.md §3 "Triangles").
-#ifndef ZRT_GUARD
-#define ZRT_GUARD 1
-#endif
 __device__ __forceinline__ float guard_grow(const KArgs& a, const RayT& r) {
   const float T = (__builtin_fabsf(r.ox - a.tri_c[0]) + a.tri_h[0]) + (__builtin_fabsf(r.oy - a.tri_c[1]) + a.tri_h[1]) +
                   (__builtin_fabsf(r.oz - a.tri_c[2]) + a.tri_h[2]);
@@ -486,10 +402,7 @@ constexpr float kNearTie = 1.00006104f;  // 1 + 2^-14
 // ("Exactness"; the REFERENCE traversal's STATS flavour
 // measures m: zrt_stats.box_excess_max_*).  Round 1 used 1 + 2^-16 here, which
 // left the verdict's band (1 + 2^-15, 1 + 2^-14] unguarded.
-#ifndef ZRT_OPEN_MARGIN
-#define ZRT_OPEN_MARGIN 1.000244140625f  // A/B only: 1.0000153f reproduces round 1
-#endif
-constexpr float kOpen = ZRT_OPEN_MARGIN;
+constexpr float kOpen = 1.000244140625f;
 
 template <bool TIE, bool TRACK>
 __device__ __forceinline__ void accept_hit(float t, int slot, float& best_t, int& best, const RayT& r,
@@ -575,41 +488,6 @@ __device__ __forceinline__ void prim_test(const float4* __restrict__ prims, int 
   }
 }
 
-#ifndef ZRT_SORT_SKIP
-#define ZRT_SORT_SKIP 1  // FAST: skip the inner-child sort when no lane of the wave has two children to order
-#endif
-#ifndef ZRT_Q_GLOBAL
-#define ZRT_Q_GLOBAL 0  // lockstep FAST loop: the current node's pointer always its global copy (A/B: exact,
-                        // C4 -0.5 %, C3 +-0, profiles/r06/r06q2)
-#endif
-#ifndef ZRT_MATS_LDS_ONLY
-// the lockstep and list-lane loops read the material table from their LDS copy only,
-// through LDS-typed pointers (ds_read), not a generic pointer chosen at run time (flat
-// loads); the host plans the table into LDS first and falls back to the wavefront /
-// wave-unit list loop when it does not fit (C4 +1.5 %, C2 +0.5 %: profiles/r06/r06l)
-#define ZRT_MATS_LDS_ONLY 1
-#endif
-#ifndef ZRT_STACK_LDS_FAST
-#define ZRT_STACK_LDS_FAST 2  // FAST, while every lane's stack is in its LDS rows: 2 the pops as ds_reads in the
-                              // usual branches (C3 +1.6-2.4 %, C4 +0.3 %: profiles/r06/r06w), 1 push / pop as
-                              // LDS selects (A/B: C3 +1.3 %, C4 ±0.3 %), 0 the generic pop only
-#endif
-#ifndef ZRT_SCALAR_NODES
-#define ZRT_SCALAR_NODES 1  // FAST: a wide node every active lane reads next comes through the scalar cache
-#endif
-#ifndef ZRT_POOL_SCALAR
-#define ZRT_POOL_SCALAR 0  // path-pool loop: a node every traversing lane reads next comes through the scalar cache
-#endif
-#ifndef ZRT_SCALAR_RB
-#define ZRT_SCALAR_RB 0  // FAST: a wave-uniform node's second refs through the scalar cache (exact; C4 -2.4 %,
-                         // C3 -1.9 %, profiles/r06/r06o: less data-return work, more issue)
-#endif
-#ifndef ZRT_LOCK_QN
-#define ZRT_LOCK_QN 0  // A/B: the lockstep FAST loop over the compressed 64-B nodes (wide_iter_q)
-#endif
-#ifndef ZRT_SCALAR_PRIMS
-#define ZRT_SCALAR_PRIMS 1  // FAST: a primitive every active lane tests is read through the scalar cache
-#endif
 // prim_test for a WAVE-UNIFORM ref: the record is read with scalar loads
 // (s_load through the constant address space), so the 48 bytes do not cross
 // the vector data return (TD), which is what the FAST loop saturates (DESIGN.md
@@ -658,14 +536,9 @@ __device__ __forceinline__ bool order_hazard(const KArgs& a, const RayT& r, floa
   best_t = __builtin_fabsf(best_t);
   if (best < 0) return false;
   if (near || !ENTRY) return near;  // FAST folds the entry test into the flag (accept_hit)
-#if ZRT_HAZARD_ENTRY
   const uint32_t leaf = a.leaf_of_slot[best];  // the reference BVH node holding slot `best`
   const float e = loose_entry(a.nodes[2 * leaf], a.nodes[2 * leaf + 1], r);
   return e > best_t * kNearTie;
-#else
-  (void)a; (void)r;
-  return false;
-#endif
 }
 
 // The geometry of a primitive hit alone (t_max = inf): its t, or +inf.  Used by
@@ -712,26 +585,12 @@ struct ExcessAcc {
   }
 };
 
-#ifndef ZRT_REPLAY_NARROW
-#define ZRT_REPLAY_NARROW 1  // the replay also culls boxes the ray does not cross (0: the reference's test alone)
-#endif
-#ifndef ZRT_REPLAY_INLINE
-#define ZRT_REPLAY_INLINE 1
-#endif
-#if ZRT_REPLAY_INLINE
-#define ZRT_REPLAY_ATTR __forceinline__
-#else
-#define ZRT_REPLAY_ATTR __noinline__
-#endif
 // A ray whose origin lies where the wide tree's sphere growth was sized for
 // (KArgs::origin_bound, DESIGN.md §3 "Spheres"); other rays (none in a render of
 // the reference's scenes: their cameras lie inside that region) are traced the
 // reference's way alone.
-#ifndef ZRT_ORIGIN_CHECK
-#define ZRT_ORIGIN_CHECK 1  // A/B only: 0 drops the check (not exact for origins outside the bound)
-#endif
 __device__ __forceinline__ bool ray_origin_ok(const KArgs& a, const RayT& r) {
-  if (!ZRT_ORIGIN_CHECK || !a.check_origins) return true;  // (wave-uniform: a scalar branch)
+  if (!a.check_origins) return true;  // (wave-uniform: a scalar branch)
   const float m = __builtin_fmaxf(__builtin_fmaxf(__builtin_fabsf(r.ox - a.root_c[0]), __builtin_fabsf(r.oy - a.root_c[1])),
                                   __builtin_fabsf(r.oz - a.root_c[2]));
   return m <= a.origin_bound;
@@ -744,13 +603,13 @@ __device__ __forceinline__ bool ray_origin_ok(const KArgs& a, const RayT& r) {
 // grazing slack) - except boxes holding a sphere, whose rounded
 // test reaches beyond the sphere (KArgs::ref_sph); false: the reference's test alone.
 template <class StackT>
-__device__ ZRT_REPLAY_ATTR void reference_replay(const KArgs& a, const RayT& ray, StackT* __restrict__ stk, uint32_t gl,
-                                              float& best_t, int& best, bool narrow = true) {
-#if ZRT_OCT_MASKS_LOCAL && defined(__HIP_DEVICE_COMPILE__)
+__device__ __forceinline__ void reference_replay(const KArgs& a, const RayT& ray, StackT* __restrict__ stk, uint32_t gl,
+                                                 float& best_t, int& best, bool narrow = true) {
+#if defined(__HIP_DEVICE_COMPILE__)
   // box_test swaps each axis' planes by the sign of 1/d: the same comparisons as the
   // octant's (wide_view), which the compiler would make once per ray and keep - spilled
-  // to lanes - for this branch almost no ray takes.  The copies below hold the same
-  // values, but their comparisons are made here.
+  // to six lanes per ray - for this branch almost no ray takes.  The copies below hold
+  // the same values, but their comparisons are made here.
   RayT r = ray;
   asm volatile("" : "+v"(r.ix), "+v"(r.iy), "+v"(r.iz));
 #else
@@ -763,7 +622,7 @@ __device__ ZRT_REPLAY_ATTR void reference_replay(const KArgs& a, const RayT& ray
   const float4* __restrict__ nodes = ra->nodes;
   const uint8_t* __restrict__ ref_sph = ra->ref_sph;
   const float slack = ray_slack(r, a.scene_extent, ray_m(r));
-  const float gw = ZRT_GUARD && r.gk > 0.0f ? guard_grow(a, r) : 0.0f;  // the grazing-triangle guard
+  const float gw = r.gk > 0.0f ?guard_grow(a, r) : 0.0f;  // the grazing-triangle guard
   best_t = __builtin_inff();
   best = -1;
   uint32_t c_tri = 0, c_sph = 0;
@@ -778,7 +637,7 @@ __device__ ZRT_REPLAY_ATTR void reference_replay(const KArgs& a, const RayT& ray
     // emptiness test (a box the ray does not cross holds no hit):
     // left-first with the reference's t_max, so every leaf is accepted or
     // rejected exactly as the reference does it, in ~1 % of its node visits
-    if (!box_test<ZRT_REPLAY_NARROW>(lo, hi, r, best_t, &e, slack, narrow && ref_sph[idx] == 0, gw)) continue;
+    if (!box_test<true>(lo, hi, r, best_t, &e, slack, narrow && ref_sph[idx] == 0, gw)) continue;
     const int left = as_int(lo.w), right = as_int(hi.w);
     if (left < 0) {
       prim_test<false, false>(a.prims, left, r, best_t, best, c_tri, c_sph);
@@ -819,7 +678,7 @@ __device__ __forceinline__ void traverse_bvh(const KArgs& a, const RayT& r, Stac
   const uint32_t cap = a.stack_depth;
   if (FAST) {
     const float slack = ray_slack(r, a.scene_extent, ray_m(r));
-    const float gw = ZRT_GUARD && r.gk > 0.0f ? guard_grow(a, r) : 0.0f;  // the grazing-triangle guard
+    const float gw = r.gk > 0.0f ?guard_grow(a, r) : 0.0f;  // the grazing-triangle guard
     float e;
     float4 lo = a.nodes[0], hi = a.nodes[1];
     if (STATS) ++c_nodes;
@@ -830,8 +689,8 @@ __device__ __forceinline__ void traverse_bvh(const KArgs& a, const RayT& r, Stac
     int left = as_int(lo.w), right = as_int(hi.w);
     for (;;) {
       if (left < 0) {
-        prim_test<true, STATS, ZRT_ORDER_EXACT>(a.prims, left, r, best_t, best, c_tri, c_sph);
-        if (right != left) prim_test<true, STATS, ZRT_ORDER_EXACT>(a.prims, right, r, best_t, best, c_tri, c_sph);
+        prim_test<true, STATS, true>(a.prims, left, r, best_t, best, c_tri, c_sph);
+        if (right != left) prim_test<true, STATS, true>(a.prims, right, r, best_t, best, c_tri, c_sph);
       } else {
         const float4 l0 = a.nodes[2 * left], l1 = a.nodes[2 * left + 1];
         const float4 r0 = a.nodes[2 * right], r1 = a.nodes[2 * right + 1];
@@ -869,7 +728,7 @@ __device__ __forceinline__ void traverse_bvh(const KArgs& a, const RayT& r, Stac
       if (!found) break;
     }
     // the order hazard of DESIGN.md §3, as in traverse_wide (the stack is all in LDS here)
-    if (__builtin_expect(ZRT_ORDER_EXACT && order_hazard<true>(a, r, best_t, best), 0))
+    if (__builtin_expect(order_hazard<true>(a, r, best_t, best), 0))
       reference_replay<StackT>(a, r, stk, 0u, best_t, best);
     if (__builtin_expect(!ray_origin_ok(a, r), 0)) reference_replay<StackT>(a, r, stk, 0u, best_t, best, false);
   } else {
@@ -939,16 +798,13 @@ __device__ __forceinline__ void cswap(float& ka, int& ra, float& kb, int& rb) {
   ra = tr;
 }
 
-// Two slots' slab distances (bound - o) * inv.  (Written as packed f32,
-// v_pk_add_f32 / v_pk_mul_f32 with the same roundings, this traversal ran
-// 1.2-1.8x slower: packed f32 issues at half the rate of single f32 here.)
+// Two slots' slab distances.  (Written as packed f32, v_pk_add_f32 /
+// v_pk_mul_f32 with the same roundings, this traversal ran 1.2-1.8x slower:
+// packed f32 issues at half the rate of single f32 here.)
 typedef float f2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ f2 slab2(float b0, float b1, float o, float inv) {
-  return (f2){(b0 - o) * inv, (b1 - o) * inv};
-}
 
-// The same distances as fma(plane, 1/d, -o/d) (ZRT_FMA_SLABS): one rounding
-// after an exact product instead of (plane - o) * (1/d)'s two, 24 VALU fewer
+// The reference's (plane - o) * (1/d) as fma(plane, 1/d, -o/d): one rounding
+// after an exact product instead of two, 24 VALU fewer
 // per wide node.  With p = RN(o_k / d_k) such a distance lies within
 // 1.0002 u |p| + 3.0001 u |s| of the reference's RN(RN(plane - o) * (1/d))
 // (u = 2^-24); wide_iter's culls carry kFmaE2 * max_k |p_k| more slack for it
@@ -960,16 +816,12 @@ __device__ __forceinline__ f2 slab2(float b0, float b1, float o, float inv) {
 // A ray with |1/d_k| >= 2^100 or |p_k| >= 2^120 (a direction component ~0) is
 // "degenerate": it culls everything here and is traced the reference's way
 // (wide_finish, ray_degenerate).
-#ifndef ZRT_FMA_SLABS
-#define ZRT_FMA_SLABS 1  // 0: the reference's (plane - o) * (1/d) for every slot (A/B)
-#endif
 constexpr float kFmaE2 = 0x1.04p-23f;   // >= 2 x 1.0002 u (+ the rounding of this product)
 constexpr float kFmaSure = 1.0000019f;  // 1 + 2^-19 > 1 + 6.0002 u: relative error of both ends
 __device__ __forceinline__ f2 slab2f(float b0, float b1, float p, float inv) {
   return (f2){__builtin_fmaf(b0, inv, -p), __builtin_fmaf(b1, inv, -p)};
 }
 __device__ __forceinline__ bool ray_degenerate(const RayT& r) {
-  if (!ZRT_FMA_SLABS) return false;
   const float pm = __builtin_fmaxf(__builtin_fmaxf(__builtin_fabsf(r.ox * r.ix), __builtin_fabsf(r.oy * r.iy)),
                                    __builtin_fabsf(r.oz * r.iz));
   return !(ray_m(r) < 0x1p100f) || !(pm < 0x1p120f);
@@ -986,16 +838,10 @@ __device__ __forceinline__ SlotT slot_interval(float nx, float ny, float nz, flo
   s.ex = __builtin_fminf(__builtin_fminf(fx, fy), __builtin_fminf(fz, tb));
   return s;
 }
-#ifndef ZRT_SPHERE_FIRST
-#define ZRT_SPHERE_FIRST 1  // A/B: 0 looks for sphere slots in all four slots of every node
-#endif
-#ifndef ZRT_SPHERE_SLOTS
-#define ZRT_SPHERE_SLOTS 1  // A/B only: 0 culls sphere leaves like triangle leaves (not exact, DESIGN.md §3 "Spheres")
-#endif
 // The wide-tree encoding these kernels decode (accel_build.hpp kLayout*); the
 // host refuses any other before launching, and a kernel handed one anyway sets
 // kErrLayout and returns without reading the tree.
-constexpr uint32_t kKernelLayout = kLayoutVersion | (ZRT_SPHERE_SLOTS ? kLayoutSphereSlots | kLayoutSphereFirst : 0u);
+constexpr uint32_t kKernelLayout = kLayoutVersion | kLayoutSphereSlots | kLayoutSphereFirst;
 __device__ __forceinline__ bool layout_ok(const KArgs& a) {
   if (a.layout == kKernelLayout) return true;  // (block-uniform: every thread returns together)
   if (threadIdx.x == 0) atomicOr(a.error_flag, kErrLayout);
@@ -1028,10 +874,6 @@ __device__ __forceinline__ bool loose_planes(float bx, float by, float bz, float
   const float nz = (bz - r.oz) * r.iz, fz = (cz - r.oz) * r.iz;
   // the exact loose entry (the order-hazard test's E; wide_iter's en when its slabs are not widened)
   entry = __builtin_fmaxf(__builtin_fmaxf(nx, ny), __builtin_fmaxf(nz, t_min));
-  if (!ZRT_GRAZE_SLACK)
-    return (__builtin_fminf(fx, tb) > __builtin_fmaxf(nx, t_min)) &&
-           (__builtin_fminf(fy, tb) > __builtin_fmaxf(ny, t_min)) &&
-           (__builtin_fminf(fz, tb) > __builtin_fmaxf(nz, t_min));
   // the leaf's own coordinate slack (ray_slack): g = 2 x 2^-19 x its largest |coordinate|,
   // g |1/d_k| on axis k; a hit below the leaf's entry by that still counts against tb
   const float cl = __builtin_fmaxf(
@@ -1047,50 +889,35 @@ __device__ __forceinline__ bool loose_planes(float bx, float by, float bz, float
   // the narrowed test of the box grown by g (NaN bounds constrain nothing)
   const float en = __builtin_fmaxf(__builtin_fmaxf(nx - gx, ny - gy), __builtin_fmaxf(nz - gz, t_min));
   const float ex = __builtin_fminf(__builtin_fminf(fx + gx, fy + gy), __builtin_fminf(fz + gz, tl));
-  return loose && !(en > ex * (ZRT_GRAZE_LEAF ? 1.0000153f + r.gl * ray_m(r) : ray_rel(r, ray_m(r))));
+  return loose && !(en > ex * ray_rel(r, ray_m(r)));
 }
 __device__ __forceinline__ bool loose_slot(const float4* __restrict__ q, int k, const RayT& r, float tb,
-                                           bool sx, bool sy, bool sz, float& entry, float gg = 0.0f) {
+                                           float& entry, float gg = 0.0f) {
   const float* f = reinterpret_cast<const float*>(q) + k;
-#if ZRT_OCT_COPIES
-  (void)sx; (void)sy; (void)sz;
-  const int px = 0, py = 4, pz = 8, qx = 12, qy = 16, qz = 20;
-#else
-  const int px = sx ? 12 : 0, py = sy ? 16 : 4, pz = sz ? 20 : 8;
-  const int qx = sx ? 0 : 12, qy = sy ? 4 : 16, qz = sz ? 8 : 20;
-#endif
-  return loose_planes(f[px], f[py], f[pz], f[qx], f[qy], f[qz], r, tb, entry, gg);
+  return loose_planes(f[0], f[4], f[8], f[12], f[16], f[20], r, tb, entry, gg);
 }
 
 // static_ok of leaf slot k, its slab distances recomputed from the node in memory
 // (the same two roundings as wide_iter's) so that none stays live across the node
 template <class FP>
-__device__ __forceinline__ bool static_ok_at(FP f, const RayT& r, bool sx, bool sy, bool sz, float& entry) {
-#if ZRT_OCT_COPIES
-  (void)sx; (void)sy; (void)sz;
-  const int px = 0, py = 4, pz = 8, qx = 12, qy = 16, qz = 20;
-#else
-  const int px = sx ? 12 : 0, py = sy ? 16 : 4, pz = sz ? 20 : 8;
-  const int qx = sx ? 0 : 12, qy = sy ? 4 : 16, qz = sz ? 8 : 20;
-#endif
-  const float nx = (f[px] - r.ox) * r.ix, ny = (f[py] - r.oy) * r.iy, nz = (f[pz] - r.oz) * r.iz;
+__device__ __forceinline__ bool static_ok_at(FP f, const RayT& r, float& entry) {
+  const float nx = (f[0] - r.ox) * r.ix, ny = (f[4] - r.oy) * r.iy, nz = (f[8] - r.oz) * r.iz;
   entry = __builtin_fmaxf(__builtin_fmaxf(nx, ny), __builtin_fmaxf(nz, 0.001f));  // the exact loose entry
-  return static_ok(nx, ny, nz, (f[qx] - r.ox) * r.ix, (f[qy] - r.oy) * r.iy, (f[qz] - r.oz) * r.iz);
+  return static_ok(nx, ny, nz, (f[12] - r.ox) * r.ix, (f[16] - r.oy) * r.iy, (f[20] - r.oz) * r.iz);
 }
 // (q is a generic pointer: a node of the top levels lives in LDS - the root,
 // which holds the ground sphere's leaf in every reference scene - and is read
 // with ds_read, not a flat load through the vector memory path)
-__device__ __forceinline__ bool static_ok_slot(const float4* __restrict__ q, int k, const RayT& r, bool sx, bool sy,
-                                               bool sz, float& entry) {
+__device__ __forceinline__ bool static_ok_slot(const float4* __restrict__ q, int k, const RayT& r, float& entry) {
 #if defined(__HIP_DEVICE_COMPILE__)
   if (__builtin_amdgcn_is_shared(reinterpret_cast<const void*>(q)))
     return static_ok_at((const __attribute__((address_space(3))) float*)(reinterpret_cast<const float*>(q)) + k, r,
-                        sx, sy, sz, entry);
+                        entry);
 #endif
-  return static_ok_at(reinterpret_cast<const float*>(q) + k, r, sx, sy, sz, entry);
+  return static_ok_at(reinterpret_cast<const float*>(q) + k, r, entry);
 }
 
-constexpr uint32_t kOctCopies = ZRT_OCT_COPIES ? 8u : 1u;
+constexpr uint32_t kOctCopies = 8u;  // the wide tree is stored once per ray octant
 
 // The wide tree's top levels (accel_build.cpp stores them first: nodes 0 ..
 // n_top-1), every octant copy, copied into the block's LDS once at kernel
@@ -1156,17 +983,11 @@ struct WideNode {
   float4 nx, ny, nz, fx, fy, fz, ra;
 };
 
+// (the octant's signs: unused - the planes come pre-swapped in the ray's octant copy -
+// but dropping the arguments, dead as they are, changes how the lockstep kernel is scheduled)
 __device__ __forceinline__ void wide_load(const float4* __restrict__ q, bool sx, bool sy, bool sz, WideNode& w) {
-#if ZRT_OCT_COPIES
   (void)sx; (void)sy; (void)sz;
   w.nx = q[0]; w.ny = q[1]; w.nz = q[2]; w.fx = q[3]; w.fy = q[4]; w.fz = q[5]; w.ra = q[6];
-#else
-  const float4 m0 = q[0], m1 = q[1], m2 = q[2], m3 = q[3], m4 = q[4], m5 = q[5];
-  w.nx = sx ? m3 : m0; w.fx = sx ? m0 : m3;
-  w.ny = sy ? m4 : m1; w.fy = sy ? m1 : m4;
-  w.nz = sz ? m5 : m2; w.fz = sz ? m2 : m5;
-  w.ra = q[6];
-#endif
 }
 
 // Where a ray reads the wide tree: its octant's copy (global memory) and that
@@ -1176,17 +997,18 @@ struct WideView {
   uint32_t base;                   // float4 offset of this octant's copy (< 2^32)
   uint32_t n_top;
 };
-// (the octant's three sign masks are no part of it: with octant copies only rare
-// paths read them, and form them there - OctSigns - instead of carrying them)
+// (the octant's three sign masks are no part of it: only the compressed nodes'
+// leaf records read them, and form them there - OctSigns - instead of carrying them)
 struct OctSigns {
   bool sx, sy, sz;
   __device__ __forceinline__ explicit OctSigns(const RayT& r) : sx(r.ix < 0.0f), sy(r.iy < 0.0f), sz(r.iz < 0.0f) {}
 };
 
 // oct * n for an octant (< 8) and a float4 count the host keeps below 2^24
-// (zrt::check_octant_offsets): the product is below 2^27, exact in either form
+// (zrt::check_octant_offsets): the product is below 2^27, exact in either form.
+// A full-rate 24-bit multiply (v_mul_u32_u24) instead of the quarter-rate v_mul_lo_u32.
 __device__ __forceinline__ uint32_t oct_times(uint32_t oct, uint32_t n) {
-#if ZRT_OCT_MUL24 && defined(__HIP_DEVICE_COMPILE__)
+#if defined(__HIP_DEVICE_COMPILE__)
   return __umul24(oct, n);
 #else
   return oct * n;
@@ -1195,16 +1017,11 @@ __device__ __forceinline__ uint32_t oct_times(uint32_t oct, uint32_t n) {
 
 __device__ __forceinline__ WideView wide_view(const KArgs& a, const RayT& r, const float4* __restrict__ lds_top) {
   WideView v;
-#if ZRT_OCT_COPIES
   const OctSigns s(r);
   const uint32_t oct = (s.sx ? 1u : 0u) | (s.sy ? 2u : 0u) | (s.sz ? 4u : 0u);
   v.base = oct_times(oct, a.wide_stride);
-#else
-  const uint32_t oct = 0;
-  v.base = 0;
-#endif
   v.top = lds_top + oct_times(oct, a.n_top * a.node_f4);
-  v.n_top = ZRT_LDS_TOP ? a.n_top : 0u;
+  v.n_top = a.n_top;
   return v;
 }
 
@@ -1231,8 +1048,9 @@ __device__ __forceinline__ const float4* wide_node_ptr(const KArgs& a, const Wid
 // the order-hazard test of wide_finish follows).  Its state between calls is
 // (w, q, sp, best_t, best) and the lane's stack column, so a traversal can be
 // suspended between nodes (the wavefront loop, render_loop_wf).
-template <bool STATS, class StackT, bool SCALAR_NODES = ZRT_SCALAR_NODES, bool PAXIS = ZRT_PAXIS_LOCK, bool GUARD = true,
-          bool QG = false>
+// SCALAR_NODES: a node every active lane reads next comes through the scalar cache
+// (false in the wavefront and path-pool loops, whose lanes traverse unrelated nodes).
+template <bool STATS, class StackT, bool SCALAR_NODES = true, bool PAXIS = false, bool GUARD = true>
 __device__ __forceinline__ bool wide_iter(const KArgs& a, const RayT& r, const WideView& v,
                                           StackT* __restrict__ stk, uint32_t gl, WideNode& w,
                                           const float4*& q, uint32_t& sp, float& best_t, int& best,
@@ -1244,12 +1062,11 @@ __device__ __forceinline__ bool wide_iter(const KArgs& a, const RayT& r, const W
   constexpr bool kOvf = true;
   const uint32_t rows = a.lds_rows;
   const float inf = __builtin_inff();
-  const OctSigns os(r);  // (read by rare paths only: wide_load ignores them with octant copies)
+  const OctSigns os(r);  // (wide_load)
   const bool sx = os.sx, sy = os.sy, sz = os.sz;
   int r0 = as_int(w.ra.x), r1 = as_int(w.ra.y), r2 = as_int(w.ra.z), r3 = as_int(w.ra.w);
   const float tb = __builtin_fabsf(best_t) * kOpen;
   const float m = ray_m(r), rel = ray_rel(r, m), slk = ray_slack(r, a.scene_extent, m);
-#if ZRT_FMA_SLABS
   // slab distances fma(plane, 1/d, -p), p = o / d (see slab2f): E2 covers their error
   const float px = r.ox * r.ix, py = r.oy * r.iy, pz = r.oz * r.iz;
   const float pm = __builtin_fmaxf(__builtin_fmaxf(__builtin_fabsf(px), __builtin_fabsf(py)), __builtin_fabsf(pz));
@@ -1273,7 +1090,7 @@ __device__ __forceinline__ bool wide_iter(const KArgs& a, const RayT& r, const W
   fz01 = slab2f(w.fz.x, w.fz.y, PFZ, r.iz); fz23 = slab2f(w.fz.z, w.fz.w, PFZ, r.iz);
   // (the wavefront, path-pool and trace loops only: in the lockstep kernel the branch
   // alone cost 4 more spilled VGPRs, C4 -4 %, profiles/r04/r04d)
-  if (ZRT_GUARD && GUARD && PAXIS && __builtin_expect(r.gk > 0.0f, 0)) {  // scene-uniform: a scalar branch
+  if (GUARD && PAXIS && __builtin_expect(r.gk > 0.0f, 0)) {  // scene-uniform: a scalar branch
     const float g = guard_grow(a, r);
     gg = g;
     const float wx = paxis_t(g, r.ix), wy = paxis_t(g, r.iy), wz = paxis_t(g, r.iz);
@@ -1285,27 +1102,11 @@ __device__ __forceinline__ bool wide_iter(const KArgs& a, const RayT& r, const W
     ZRT_SLABS(px, py, pz, px, py, pz)
   }
 #undef ZRT_SLABS
-#else
-  constexpr bool deg = false;
-  constexpr float E2 = 0.0f, Eg = 0.0f, gg = 0.0f;
-#define ZRT_SLAB_X(V, A, B) slab2(V.A, V.B, r.ox, r.ix)
-#define ZRT_SLAB_Y(V, A, B) slab2(V.A, V.B, r.oy, r.iy)
-#define ZRT_SLAB_Z(V, A, B) slab2(V.A, V.B, r.oz, r.iz)
-  f2 nx01 = ZRT_SLAB_X(w.nx, x, y), nx23 = ZRT_SLAB_X(w.nx, z, w);
-  f2 ny01 = ZRT_SLAB_Y(w.ny, x, y), ny23 = ZRT_SLAB_Y(w.ny, z, w);
-  f2 nz01 = ZRT_SLAB_Z(w.nz, x, y), nz23 = ZRT_SLAB_Z(w.nz, z, w);
-  f2 fx01 = ZRT_SLAB_X(w.fx, x, y), fx23 = ZRT_SLAB_X(w.fx, z, w);
-  f2 fy01 = ZRT_SLAB_Y(w.fy, x, y), fy23 = ZRT_SLAB_Y(w.fy, z, w);
-  f2 fz01 = ZRT_SLAB_Z(w.fz, x, y), fz23 = ZRT_SLAB_Z(w.fz, z, w);
-#undef ZRT_SLAB_X
-#undef ZRT_SLAB_Y
-#undef ZRT_SLAB_Z
-#endif
   // a lane of the wave runs nearly parallel to an axis (paxis_grow): every slab
   // widened in place by its axis's own term; the leaf slots' exact intervals (the
   // reference's loose test, the hazard entry) are then recomputed by loose_slot
   bool pw = false;
-  if (ZRT_PAXIS && PAXIS && __builtin_expect(__ballot(m > a.paxis_m) != 0ull, 0)) {
+  if (PAXIS && __builtin_expect(__ballot(m > a.paxis_m) != 0ull, 0)) {
     pw = true;
     const float g = paxis_grow(a, r);
     const float gx = paxis_t(g, r.ix), gy = paxis_t(g, r.iy), gz = paxis_t(g, r.iz);
@@ -1324,35 +1125,29 @@ __device__ __forceinline__ bool wide_iter(const KArgs& a, const RayT& r, const W
   // inner slots' boxes are stored grown, leaf slots' are the reference leaves');
   // widened slabs carry their margins already (rounding: 2^-16)
   const float rl = pw ? 1.0000153f : rel, sl = (pw ? 0.0f : slk) + E2;
-#if ZRT_GRAZE_LEAF
-  const float rll = pw ? 1.0000153f : 1.0000153f + r.gl * m;  // leaf slots (KArgs::graze_leaf)
-#else
-  const float rll = rl;
-#endif
-  const bool h0 = !deg && !(s0.en > __builtin_fmaf(s0.ex, r0 < 0 ? rll : rl, r0 < 0 ? sl : E2));
-  const bool h1 = !deg && !(s1.en > __builtin_fmaf(s1.ex, r1 < 0 ? rll : rl, r1 < 0 ? sl : E2));
-  const bool h2 = !deg && !(s2.en > __builtin_fmaf(s2.ex, r2 < 0 ? rll : rl, r2 < 0 ? sl : E2));
-  const bool h3 = !deg && !(s3.en > __builtin_fmaf(s3.ex, r3 < 0 ? rll : rl, r3 < 0 ? sl : E2));
+  const bool h0 = !deg && !(s0.en > __builtin_fmaf(s0.ex, rl, r0 < 0 ? sl : E2));
+  const bool h1 = !deg && !(s1.en > __builtin_fmaf(s1.ex, rl, r1 < 0 ? sl : E2));
+  const bool h2 = !deg && !(s2.en > __builtin_fmaf(s2.ex, rl, r2 < 0 ? sl : E2));
+  const bool h3 = !deg && !(s3.en > __builtin_fmaf(s3.ex, rl, r3 < 0 ? sl : E2));
   if (STATS) {
     ++c_nodes;
     c_leaves += (r0 < 0) + (r1 < 0) + (r2 < 0) + (r3 < 0);
   }
   // leaf slots that pass both tests: their primitive refs (a in r_k, b in the node's last float4)
   bool o0 = r0 < 0 && h0, o1 = r1 < 0 && h1, o2 = r2 < 0 && h2, o3 = r3 < 0 && h3;
-  // (certain: en < ex by the FMA distances' error; ZRT_FMA_SLABS = 0: kFmaSure is exact enough)
-#define ZRT_SURE(S) (__builtin_fmaf(S.en, ZRT_FMA_SLABS ? kFmaSure : 1.0f, Eg) < S.ex)
+  // (certain: en < ex by the FMA distances' error)
+#define ZRT_SURE(S) (__builtin_fmaf(S.en, kFmaSure, Eg) < S.ex)
   // (guarded: the slabs are widened, so every opened leaf takes its exact loose entry - the
   // hazard test's E - and its widened per-axis tests from memory)
   const bool pg = pw || gg > 0.0f;
   const bool w0 = o0 && (pg || !ZRT_SURE(s0)), w1 = o1 && (pg || !ZRT_SURE(s1));
   const bool w2 = o2 && (pg || !ZRT_SURE(s2)), w3 = o3 && (pg || !ZRT_SURE(s3));
   if (w0 || w1 || w2 || w3) {  // rare: an interval within the margin, decide per axis
-    if (w0) o0 = loose_slot(q, 0, r, tb, sx, sy, sz, s0.en, gg);
-    if (w1) o1 = loose_slot(q, 1, r, tb, sx, sy, sz, s1.en, gg);
-    if (w2) o2 = loose_slot(q, 2, r, tb, sx, sy, sz, s2.en, gg);
-    if (w3) o3 = loose_slot(q, 3, r, tb, sx, sy, sz, s3.en, gg);
+    if (w0) o0 = loose_slot(q, 0, r, tb, s0.en, gg);
+    if (w1) o1 = loose_slot(q, 1, r, tb, s1.en, gg);
+    if (w2) o2 = loose_slot(q, 2, r, tb, s2.en, gg);
+    if (w3) o3 = loose_slot(q, 3, r, tb, s3.en, gg);
   }
-#if ZRT_SPHERE_SLOTS
   // leaf slots holding a sphere (ref a - 2^30, accel_build.hpp): opened when the
   // reference's loose test passes against t_max = +inf.  The rounded sphere test
   // accepts rays that pass outside the sphere - and its box - by up to ~sqrt(u)|oc|
@@ -1364,16 +1159,13 @@ __device__ __forceinline__ bool wide_iter(const KArgs& a, const RayT& r, const W
   // is not empty: every axis passes) opens it, ex <= t_min (an axis's far plane
   // at or behind t_min: that axis fails; tb > t_min) keeps it shut; the rest, and
   // every slot of a widened wave (pw), take the per-axis test from memory.
-#if ZRT_SPHERE_FIRST  // accel_build puts a node's sphere leaves in its first slots
+  // (accel_build puts a node's sphere leaves in its first slots)
   if (__builtin_expect(__ballot(r0 < -kSphereSlotBias) != 0ull, 0)) {
-#else
-  if (__builtin_expect(__ballot(min(min(r0, r1), min(r2, r3)) < -kSphereSlotBias) != 0ull, 0)) {
-#endif
 #define ZRT_SPHERE_SLOT(K)                                                                                   \
   if (r##K < -kSphereSlotBias) {                                                                             \
     o##K = !pw && !deg && ZRT_SURE(s##K);                                                                    \
     if (!o##K && !deg && s##K.ex + __builtin_fmaf(__builtin_fabsf(s##K.ex), 0x1p-19f, Eg) > 0.001f)          \
-      o##K = static_ok_slot(q, K, r, sx, sy, sz, s##K.en);                                                   \
+      o##K = static_ok_slot(q, K, r, s##K.en);                                                               \
     r##K += kSphereSlotBias;                                                                                 \
   }
     ZRT_SPHERE_SLOT(0)
@@ -1382,7 +1174,6 @@ __device__ __forceinline__ bool wide_iter(const KArgs& a, const RayT& r, const W
     ZRT_SPHERE_SLOT(3)
 #undef ZRT_SPHERE_SLOT
   }
-#endif
 #undef ZRT_SURE
   const int l0 = o0 ? r0 : 0, l1 = o1 ? r1 : 0, l2 = o2 ? r2 : 0, l3 = o3 ? r3 : 0;
   const float4* leaf_q = q;  // (the leaves are intersected after the next node is chosen)
@@ -1391,15 +1182,13 @@ __device__ __forceinline__ bool wide_iter(const KArgs& a, const RayT& r, const W
   float k0 = r0 >= 0 && h0 ? s0.en : inf, k1 = r1 >= 0 && h1 ? s1.en : inf;
   float k2 = r2 >= 0 && h2 ? s2.en : inf, k3 = r3 >= 0 && h3 ? s3.en : inf;
   const uint32_t n = (k0 != inf) + (k1 != inf) + (k2 != inf) + (k3 != inf);
-#if ZRT_STACK_LDS_FAST
   // every active lane's stack top and its next three pushes inside the LDS rows (a
   // wave-uniform test, true throughout for trees whose stack fits the LDS plan): the
-  // pop is a ds_read of the lane's LDS column - not a generic load that could also
-  // reach the global rows - and push, pop and the choice between them are selects,
-  // not exec-mask regions (the same stack contents and the same next node)
-  if (ZRT_STACK_LDS_FAST == 2 && __ballot(sp + 3u > rows) == 0ull) {
-    // (A/B form 2: the same branches as below, the pop a ds_read of the LDS column)
-    if (ZRT_SORT_SKIP && __ballot(n > 1u) == 0ull) {
+  // same branches as the generic form below, the pop a ds_read of the lane's LDS
+  // column - not a generic load that could also reach the global rows (C3 +1.6-2.4 %,
+  // C4 +0.3 %: profiles/r06/r06w; push / pop as LDS selects instead: C3 +1.3 %, C4 ±0.3 %)
+  if (__ballot(sp + 3u > rows) == 0ull) {
+    if (__ballot(n > 1u) == 0ull) {
       if (n != 0) {
         next = k0 != inf ? r0 : k1 != inf ? r1 : k2 != inf ? r2 : r3;
       } else if (sp != 0) {
@@ -1425,33 +1214,7 @@ __device__ __forceinline__ bool wide_iter(const KArgs& a, const RayT& r, const W
         next = (int32_t)stk[sp * stride];
       }
     }
-  } else if (ZRT_STACK_LDS_FAST == 1 && __ballot(sp + 3u > rows) == 0ull) {
-    const uint32_t psp = sp != 0 ? sp - 1u : 0u;
-    const int32_t top = (int32_t)stk[psp * stride];
-    if (ZRT_SORT_SKIP && __ballot(n > 1u) == 0ull) {
-      next = n != 0 ? (k0 != inf ? r0 : k1 != inf ? r1 : k2 != inf ? r2 : r3) : sp != 0 ? top : -1;
-      sp = n != 0 ? sp : psp;
-    } else {
-      cswap(k0, r0, k1, r1);
-      cswap(k2, r2, k3, r3);
-      cswap(k0, r0, k2, r2);
-      cswap(k1, r1, k3, r3);
-      cswap(k1, r1, k2, r2);
-      // (a lane with no inner child writes above its top: dead entries)
-      stk[sp * stride] = (StackT)(n == 4 ? r3 : n == 3 ? r2 : r1);
-      stk[(sp + 1) * stride] = (StackT)(n == 4 ? r2 : r1);
-      stk[(sp + 2) * stride] = (StackT)r1;
-      const uint32_t nsp = sp + n - 1;
-      if (__builtin_expect(__ballot(n != 0 && nsp > cap - 3) != 0ull, 0)) {
-        if (n != 0 && nsp > cap - 3) raise_error(a, kErrOverflow);
-      }
-      next = n != 0 ? r0 : sp != 0 ? top : -1;
-      sp = n != 0 ? min(nsp, cap - 3) : psp;
-    }
-  } else {
-#endif
-#if ZRT_SORT_SKIP
-  if (__ballot(n > 1u) == 0ull) {
+  } else if (__ballot(n > 1u) == 0ull) {
     // every active lane follows at most one inner child: no sort, nothing to push
     // (a wave-uniform branch around the 5 compare-exchanges and the 3 stores)
     if (n != 0) {
@@ -1462,130 +1225,91 @@ __device__ __forceinline__ bool wide_iter(const KArgs& a, const RayT& r, const W
                                   : (int32_t)stk[sp * stride];
     }
   } else {
-#endif
-  // sort (entry, ref) ascending: 5 compare-exchanges
-  cswap(k0, r0, k1, r1);
-  cswap(k2, r2, k3, r3);
-  cswap(k0, r0, k2, r2);
-  cswap(k1, r1, k3, r3);
-  cswap(k1, r1, k2, r2);
-  if (n != 0) {
-    // push r_{n-1} .. r_1 (farthest first) and continue with the nearest; the
-    // three stores are unconditional (entries above the new top are dead)
-    const StackT e0 = (StackT)(n == 4 ? r3 : n == 3 ? r2 : r1), e1 = (StackT)(n == 4 ? r2 : r1);
-    const StackT e2 = (StackT)r1;
-    // sp <= cap - 3 always holds (the clamp below), so the three stores stay in the rows
-    if (sp + 3 <= rows) {
-      stk[sp * stride] = e0;
-      stk[(sp + 1) * stride] = e1;
-      stk[(sp + 2) * stride] = e2;
-    } else if (kOvf) {  // deep trees: rows past the LDS part live in global memory
-      const StackT e[3] = {e0, e1, e2};
+    // sort (entry, ref) ascending: 5 compare-exchanges
+    cswap(k0, r0, k1, r1);
+    cswap(k2, r2, k3, r3);
+    cswap(k0, r0, k2, r2);
+    cswap(k1, r1, k3, r3);
+    cswap(k1, r1, k2, r2);
+    if (n != 0) {
+      // push r_{n-1} .. r_1 (farthest first) and continue with the nearest; the
+      // three stores are unconditional (entries above the new top are dead)
+      const StackT e0 = (StackT)(n == 4 ? r3 : n == 3 ? r2 : r1), e1 = (StackT)(n == 4 ? r2 : r1);
+      const StackT e2 = (StackT)r1;
+      // sp <= cap - 3 always holds (the clamp below), so the three stores stay in the rows
+      if (sp + 3 <= rows) {
+        stk[sp * stride] = e0;
+        stk[(sp + 1) * stride] = e1;
+        stk[(sp + 2) * stride] = e2;
+      } else if (kOvf) {  // deep trees: rows past the LDS part live in global memory
+        const StackT e[3] = {e0, e1, e2};
 #pragma unroll
-      for (uint32_t j = 0; j < 3; ++j) {
-        if (sp + j < rows) {
-          stk[(sp + j) * stride] = e[j];
-        } else {
-          if (row_ok<STATS>(a, (uint64_t)(sp + j - rows) * a.n_lanes + gl, a.ovf_cap))
-            ovf_column<StackT>(a, gl)[(size_t)(sp + j - rows) * a.n_lanes] = e[j];
-          if (STATS) ++coh.ovfw;
+        for (uint32_t j = 0; j < 3; ++j) {
+          if (sp + j < rows) {
+            stk[(sp + j) * stride] = e[j];
+          } else {
+            if (row_ok<STATS>(a, (uint64_t)(sp + j - rows) * a.n_lanes + gl, a.ovf_cap))
+              ovf_column<StackT>(a, gl)[(size_t)(sp + j - rows) * a.n_lanes] = e[j];
+            if (STATS) ++coh.ovfw;
+          }
         }
       }
+      const uint32_t nsp = sp + n - 1;
+      // the host sizes cap = the tree's deepest stack + 3, so this never fires
+      // unless the stack was sized too small: then entries would be lost
+      if (__builtin_expect(nsp > cap - 3, 0)) raise_error(a, kErrOverflow);
+      sp = min(nsp, cap - 3);
+      next = r0;
+    } else if (sp != 0) {
+      --sp;
+      next = kOvf && sp >= rows ? (row_ok<STATS>(a, (uint64_t)(sp - rows) * a.n_lanes + gl, a.ovf_cap) ? (int32_t)ovf_column<StackT>(a, gl)[(size_t)(sp - rows) * a.n_lanes] : -1)
+                                    : (int32_t)stk[sp * stride];
     }
-    const uint32_t nsp = sp + n - 1;
-    // the host sizes cap = the tree's deepest stack + 3, so this never fires
-    // unless the stack was sized too small: then entries would be lost
-    if (__builtin_expect(nsp > cap - 3, 0)) raise_error(a, kErrOverflow);
-    sp = min(nsp, cap - 3);
-    next = r0;
-  } else if (sp != 0) {
-    --sp;
-    next = kOvf && sp >= rows ? (row_ok<STATS>(a, (uint64_t)(sp - rows) * a.n_lanes + gl, a.ovf_cap) ? (int32_t)ovf_column<StackT>(a, gl)[(size_t)(sp - rows) * a.n_lanes] : -1)
-                                  : (int32_t)stk[sp * stride];
   }
-#if ZRT_SORT_SKIP
-  }
-#endif
-#if ZRT_STACK_LDS_FAST
-  }
-#endif
   // each lane walks ITS opened leaves in slot order, so lanes that opened
   // different slots share loop trips (the result is the closest t, ties to
   // the lower slot, order hazards flagged).  A/B against four unrolled slot
   // blocks: C5 +2.9 %, C3 +3.2 %, C4 -0.2 % (and one copy of the tests).
-  if constexpr (sizeof(StackT) == 4 || ZRT_LEAF_LOOP) {
-    uint32_t open = (l0 != 0 ? 1u : 0u) | (l1 != 0 ? 2u : 0u) | (l2 != 0 ? 4u : 0u) | (l3 != 0 ? 8u : 0u);
-    if (open != 0) {
-      float4 rb;
-#if ZRT_SCALAR_RB && defined(__HIP_DEVICE_COMPILE__)
-      // a node every active lane reads (loaded through the scalar cache, or wave-uniform
-      // anyway): its second refs through the scalar cache too - a vector dwordx4 costs
-      // the data-return path 16 cycles however few lanes or addresses it has
-      // (tools/ubench_shapes.hip)
-      const uint64_t qa = reinterpret_cast<uint64_t>(leaf_q);
-      const uint64_t fq = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(qa >> 32)) << 32) |
-                          (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)qa);
-      if (__ballot(qa != fq) == 0ull && !__builtin_amdgcn_is_shared((const void*)fq)) {
-        typedef const __attribute__((address_space(4))) float4 cfloat4;
-        rb = ((cfloat4*)fq)[7];
-      } else {
-        rb = leaf_q[7];
-        if (STATS) coh.rb_trips += wave_once();
+  uint32_t open = (l0 != 0 ? 1u : 0u) | (l1 != 0 ? 2u : 0u) | (l2 != 0 ? 4u : 0u) | (l3 != 0 ? 8u : 0u);
+  if (open != 0) {
+    // the second refs: a vector load even for a wave-uniform node (through the scalar
+    // cache: exact, C4 -2.4 %, C3 -1.9 %, profiles/r06/r06o: less data-return work,
+    // more issue)
+    const float4 rb = leaf_q[7];
+    if (STATS) coh.rb_trips += wave_once();
+    do {
+      const uint32_t k = (uint32_t)__builtin_ctz(open);
+      open &= open - 1u;
+      const int L = k == 0 ? l0 : k == 1 ? l1 : k == 2 ? l2 : l3;
+      const int pb = as_int(k == 0 ? rb.x : k == 1 ? rb.y : k == 2 ? rb.z : rb.w);
+      // the leaf's loose entry, or (FMA distances) an upper bound of it: flags a superset
+      // (a guarded leaf's entry is exact: it went through loose_slot)
+      const float lp = __builtin_fmaf(k == 0 ? s0.en : k == 1 ? s1.en : k == 2 ? s2.en : s3.en, kFmaSure, E2);
+      if (STATS) {
+        const int f = __builtin_amdgcn_readfirstlane(L);
+        coh.ptests += 1u;
+        coh.uprims += __ballot(L != f) == 0ull ? 1u : 0u;
       }
-#else
-      rb = leaf_q[7];
-      if (STATS) coh.rb_trips += wave_once();
-#endif
-      do {
-        const uint32_t k = (uint32_t)__builtin_ctz(open);
-        open &= open - 1u;
-        const int L = k == 0 ? l0 : k == 1 ? l1 : k == 2 ? l2 : l3;
-        const int pb = as_int(k == 0 ? rb.x : k == 1 ? rb.y : k == 2 ? rb.z : rb.w);
-        // the leaf's loose entry, or (FMA distances) an upper bound of it: flags a superset
-        // (a guarded leaf's entry is exact: it went through loose_slot)
-        const float lp = ZRT_HAZARD_ENTRY ? (ZRT_FMA_SLABS ? __builtin_fmaf(k == 0 ? s0.en : k == 1 ? s1.en : k == 2 ? s2.en : s3.en, kFmaSure, E2)
-                                                           : (k == 0 ? s0.en : k == 1 ? s1.en : k == 2 ? s2.en : s3.en))
-                                        : -1.0f;
+      const int fl = __builtin_amdgcn_readfirstlane(L), fb = __builtin_amdgcn_readfirstlane(pb);
+      if (__ballot(L != fl || pb != fb) == 0ull) {  // one leaf in every active lane: scalar loads
+        if (STATS) coh.sp_trips += wave_once() * (fb != fl ? 2u : 1u);
+        prim_test_uniform<true, STATS, true>(a.prims, fl, r, best_t, best, c_tri, c_sph, lp);
+        if (fb != fl) prim_test_uniform<true, STATS, true>(a.prims, fb, r, best_t, best, c_tri, c_sph, lp);
+      } else {
         if (STATS) {
-          const int f = __builtin_amdgcn_readfirstlane(L);
-          coh.ptests += 1u;
-          coh.uprims += __ballot(L != f) == 0ull ? 1u : 0u;
+          const uint32_t dl = wave_distinct((uint32_t)L);
+          if (wave_once()) { ++coh.vp_trips; coh.vp_lines += dl; coh.vp_cost += max(16u, dl); }
         }
-        const int fl = __builtin_amdgcn_readfirstlane(L), fb = __builtin_amdgcn_readfirstlane(pb);
-        if (ZRT_SCALAR_PRIMS && __ballot(L != fl || pb != fb) == 0ull) {  // one leaf in every active lane
-          if (STATS) coh.sp_trips += wave_once() * (fb != fl ? 2u : 1u);
-          prim_test_uniform<true, STATS, ZRT_ORDER_EXACT>(a.prims, fl, r, best_t, best, c_tri, c_sph, lp);
-          if (fb != fl) prim_test_uniform<true, STATS, ZRT_ORDER_EXACT>(a.prims, fb, r, best_t, best, c_tri, c_sph, lp);
-        } else {
+        prim_test<true, STATS, true>(a.prims, L, r, best_t, best, c_tri, c_sph, lp);
+        if (pb != L) {
           if (STATS) {
-            const uint32_t dl = wave_distinct((uint32_t)L);
-            if (wave_once()) { ++coh.vp_trips; coh.vp_lines += dl; coh.vp_cost += max(16u, dl); }
+            const uint32_t db = wave_distinct((uint32_t)pb);
+            if (wave_once()) { ++coh.vp_trips; coh.vp_lines += db; coh.vp_cost += max(16u, db); }
           }
-          prim_test<true, STATS, ZRT_ORDER_EXACT>(a.prims, L, r, best_t, best, c_tri, c_sph, lp);
-          if (pb != L) {
-            if (STATS) {
-              const uint32_t db = wave_distinct((uint32_t)pb);
-              if (wave_once()) { ++coh.vp_trips; coh.vp_lines += db; coh.vp_cost += max(16u, db); }
-            }
-            prim_test<true, STATS, ZRT_ORDER_EXACT>(a.prims, pb, r, best_t, best, c_tri, c_sph, lp);
-          }
+          prim_test<true, STATS, true>(a.prims, pb, r, best_t, best, c_tri, c_sph, lp);
         }
-      } while (open != 0);
-    }
-  } else if ((l0 | l1 | l2 | l3) != 0) {
-    const float4 rb = leaf_q[7];  // (loaded with the node instead: 3.6 % slower, 2 spills)
-#define ZRT_WIDE_LEAF(L, RB, K)                                                                     \
-  if (L != 0) {                                                                                     \
-    const int pb = as_int(RB);                                                                      \
-    const float lp = ZRT_HAZARD_ENTRY ? (ZRT_FMA_SLABS ? __builtin_fmaf(s##K.en, kFmaSure, E2) : s##K.en) : -1.0f; \
-    prim_test<true, STATS, ZRT_ORDER_EXACT>(a.prims, L, r, best_t, best, c_tri, c_sph, lp);              \
-    if (pb != L) prim_test<true, STATS, ZRT_ORDER_EXACT>(a.prims, pb, r, best_t, best, c_tri, c_sph, lp); \
-  }
-    ZRT_WIDE_LEAF(l0, rb.x, 0)
-    ZRT_WIDE_LEAF(l1, rb.y, 1)
-    ZRT_WIDE_LEAF(l2, rb.z, 2)
-    ZRT_WIDE_LEAF(l3, rb.w, 3)
-#undef ZRT_WIDE_LEAF
+      }
+    } while (open != 0);
   }
   if (STATS && next >= 0 && (uint32_t)next >= v.n_top) {
     const int32_t f = __builtin_amdgcn_readfirstlane(next);
@@ -1596,9 +1320,9 @@ __device__ __forceinline__ bool wide_iter(const KArgs& a, const RayT& r, const W
   if (next < 0) return false;
   if ((uint32_t)next < v.n_top) {  // a top-level node: from LDS (ds_read)
     const float4* __restrict__ t = v.top + 8u * (uint32_t)next;
-    // QG: q names the node's global copy even here (the leaf refs and the rare plane
-    // re-reads then load from global memory, never through a generic pointer)
-    q = QG ? a.wnodes + (v.base + 8u * (uint32_t)next) : t;
+    // (q naming the node's global copy even here, so that the leaf refs and the rare plane
+    // re-reads never go through a generic pointer: exact, C4 -0.5 %, C3 +-0, profiles/r06/r06q2)
+    q = t;
     wide_load(t, sx, sy, sz, w);
   } else {
     const uint32_t at = v.base + 8u * (uint32_t)next;  // this ray's octant copy
@@ -1634,7 +1358,7 @@ __device__ __forceinline__ void wide_finish(const KArgs& a, const RayT& r, Stack
   // inlined, and a second copy cost the lockstep loop 2.8 % on C4 (registers).
   // (the lean kernel is launched only where the host found check_origins 0)
   const bool far = __builtin_expect((!Lean<LEAN>::origin && !ray_origin_ok(a, r)) || ray_degenerate(r), 0);
-  if (__builtin_expect((ZRT_ORDER_EXACT && order_hazard<false>(a, r, best_t, best)) || far, 0)) {
+  if (__builtin_expect(order_hazard<false>(a, r, best_t, best) || far, 0)) {
     if (STATS) ++c_replays;
     reference_replay<StackT>(a, r, stk, gl, best_t, best, !far);
   }
@@ -1678,7 +1402,7 @@ __device__ __forceinline__ bool static_ok_planes(float bx, float by, float bz, f
   return static_ok(nx, ny, nz, (cx - r.ox) * r.ix, (cy - r.oy) * r.iy, (cz - r.oz) * r.iz);
 }
 
-template <bool STATS, class StackT, bool PAXIS = true, bool GUARD = true, bool SCALAR = false>
+template <bool STATS, class StackT, bool PAXIS = true, bool GUARD = true>
 __device__ __forceinline__ bool wide_iter_q(const KArgs& a, const RayT& r, const WideView& v,
                                             StackT* __restrict__ stk, uint32_t gl, WideNodeQ& w,
                                             const float4*& q, uint32_t& sp, float& best_t, int& best,
@@ -1707,7 +1431,7 @@ __device__ __forceinline__ bool wide_iter_q(const KArgs& a, const RayT& r, const
   float Eg = E2, gg = 0.0f;
   // the slab offsets of the near / far planes (wide_iter: p -+ the guard's w)
   float onx = px, ony = py, onz = pz, ofx = px, ofy = py, ofz = pz;
-  if (ZRT_GUARD && GUARD && PAXIS && __builtin_expect(r.gk > 0.0f, 0)) {  // scene-uniform: a scalar branch
+  if (GUARD && PAXIS && __builtin_expect(r.gk > 0.0f, 0)) {  // scene-uniform: a scalar branch
     const float g = guard_grow(a, r);
     gg = g;
     const float wx = paxis_t(g, r.ix), wy = paxis_t(g, r.iy), wz = paxis_t(g, r.iz);
@@ -1734,7 +1458,7 @@ __device__ __forceinline__ bool wide_iter_q(const KArgs& a, const RayT& r, const
   // per-axis widening (wide_iter, paxis_grow): the same terms, kept for the leaf records
   bool pw = false;
   float gx = 0.0f, gy = 0.0f, gz = 0.0f;
-  if (ZRT_PAXIS && PAXIS && __builtin_expect(__ballot(m > a.paxis_m) != 0ull, 0)) {
+  if (PAXIS && __builtin_expect(__ballot(m > a.paxis_m) != 0ull, 0)) {
     pw = true;
     const float g = paxis_grow(a, r);
     gx = paxis_t(g, r.ix); gy = paxis_t(g, r.iy); gz = paxis_t(g, r.iz);
@@ -1750,16 +1474,11 @@ __device__ __forceinline__ bool wide_iter_q(const KArgs& a, const RayT& r, const
   const SlotT s2 = slot_interval(nx23.x, ny23.x, nz23.x, fx23.x, fy23.x, fz23.x, tb);
   const SlotT s3 = slot_interval(nx23.y, ny23.y, nz23.y, fx23.y, fy23.y, fz23.y, tb);
   const float rl = pw ? 1.0000153f : rel, sl = (pw ? 0.0f : slk) + E2;
-#if ZRT_GRAZE_LEAF
-  const float rll = pw ? 1.0000153f : 1.0000153f + r.gl * m;
-#else
-  const float rll = rl;
-#endif
   // the quantized boxes' narrowed test (a superset of the full node's, with its margins)
-  const bool h0 = !deg && !(s0.en > __builtin_fmaf(s0.ex, r0 < 0 ? rll : rl, r0 < 0 ? sl : E2));
-  const bool h1 = !deg && !(s1.en > __builtin_fmaf(s1.ex, r1 < 0 ? rll : rl, r1 < 0 ? sl : E2));
-  const bool h2 = !deg && !(s2.en > __builtin_fmaf(s2.ex, r2 < 0 ? rll : rl, r2 < 0 ? sl : E2));
-  const bool h3 = !deg && !(s3.en > __builtin_fmaf(s3.ex, r3 < 0 ? rll : rl, r3 < 0 ? sl : E2));
+  const bool h0 = !deg && !(s0.en > __builtin_fmaf(s0.ex, rl, r0 < 0 ? sl : E2));
+  const bool h1 = !deg && !(s1.en > __builtin_fmaf(s1.ex, rl, r1 < 0 ? sl : E2));
+  const bool h2 = !deg && !(s2.en > __builtin_fmaf(s2.ex, rl, r2 < 0 ? sl : E2));
+  const bool h3 = !deg && !(s3.en > __builtin_fmaf(s3.ex, rl, r3 < 0 ? sl : E2));
   if (STATS) {
     ++c_nodes;
     c_leaves += (r0 < 0) + (r1 < 0) + (r2 < 0) + (r3 < 0);
@@ -1843,10 +1562,10 @@ __device__ __forceinline__ bool wide_iter_q(const KArgs& a, const RayT& r, const
     SlotT s = slot_interval(__builtin_fmaf(bx, r.ix, -onx) - gx, __builtin_fmaf(by, r.iy, -ony) - gy,
                             __builtin_fmaf(bz, r.iz, -onz) - gz, __builtin_fmaf(cx, r.ix, -ofx) + gx,
                             __builtin_fmaf(cy, r.iy, -ofy) + gy, __builtin_fmaf(cz, r.iz, -ofz) + gz, tb);
-#define ZRT_SURE(S) (__builtin_fmaf(S.en, ZRT_FMA_SLABS ? kFmaSure : 1.0f, Eg) < S.ex)
+#define ZRT_SURE(S) (__builtin_fmaf(S.en, kFmaSure, Eg) < S.ex)
     // (in wide_iter's order: the narrowed test, the per-axis test within the margin,
     // then a sphere slot's static test, which decides it)
-    bool o = !deg && !(s.en > __builtin_fmaf(s.ex, rll, sl));
+    bool o = !deg && !(s.en > __builtin_fmaf(s.ex, rl, sl));
     if (o && (pw || gg > 0.0f || !ZRT_SURE(s))) o = loose_planes(bx, by, bz, cx, cy, cz, r, tb, s.en, gg);
     if (sph) {
       o = !pw && !deg && ZRT_SURE(s);
@@ -1856,14 +1575,14 @@ __device__ __forceinline__ bool wide_iter_q(const KArgs& a, const RayT& r, const
 #undef ZRT_SURE
     if (!o) continue;
     const int La = as_int(mn.w), pb = as_int(mx.w);
-    const float lp = ZRT_HAZARD_ENTRY ? (ZRT_FMA_SLABS ? __builtin_fmaf(s.en, kFmaSure, E2) : s.en) : -1.0f;
+    const float lp = __builtin_fmaf(s.en, kFmaSure, E2);
     if (STATS) {
       const int f = __builtin_amdgcn_readfirstlane(La);
       coh.ptests += 1u;
       coh.uprims += __ballot(La != f) == 0ull ? 1u : 0u;
     }
-    prim_test<true, STATS, ZRT_ORDER_EXACT>(a.prims, La, r, best_t, best, c_tri, c_sph, lp);
-    if (pb != La) prim_test<true, STATS, ZRT_ORDER_EXACT>(a.prims, pb, r, best_t, best, c_tri, c_sph, lp);
+    prim_test<true, STATS, true>(a.prims, La, r, best_t, best, c_tri, c_sph, lp);
+    if (pb != La) prim_test<true, STATS, true>(a.prims, pb, r, best_t, best, c_tri, c_sph, lp);
   }
   if (STATS && next >= 0 && (uint32_t)next >= v.n_top) {
     const int32_t f = __builtin_amdgcn_readfirstlane(next);
@@ -1884,16 +1603,6 @@ __device__ __forceinline__ bool wide_iter_q(const KArgs& a, const RayT& r, const
     const uint32_t at = v.base + kQuantNodeF4 * (uint32_t)next;
     const float4* __restrict__ g = a.wnodes + at;
     q = g;
-#if defined(__HIP_DEVICE_COMPILE__)
-    if constexpr (SCALAR) {  // one node in every active lane (the lockstep loop): scalar loads
-      const uint32_t fa = __builtin_amdgcn_readfirstlane(at);
-      if (__ballot(at != fa) == 0ull) {
-        typedef const __attribute__((address_space(4))) float4 cfloat4;
-        qnode_load((cfloat4*)a.wnodes + fa, w);
-        return true;
-      }
-    }
-#endif
     qnode_load(g, w);
   }
   return true;
@@ -1910,37 +1619,36 @@ __device__ __forceinline__ void node_load(const float4* q, const RayT& r, W& w) 
   }
 }
 
-// zrt_trace over compressed nodes (MODE 8): traverse_wide with wide_iter_q; LOCK: the
-// lockstep loop's A/B build (ZRT_LOCK_QN: its margins, wave-uniform nodes from the scalar cache)
-template <bool STATS, class StackT, bool LOCK = false>
+// zrt_trace over compressed nodes (MODE 8): traverse_wide with wide_iter_q
+template <bool STATS, class StackT>
 __device__ __forceinline__ void traverse_wide_q(const KArgs& a, const RayT& r, StackT* __restrict__ stk,
                                                 const float4* __restrict__ lds_top, uint32_t gl, float& best_t,
                                                 int& best, uint32_t& c_nodes, uint32_t& c_leaves, uint32_t& c_tri,
                                                 uint32_t& c_sph, uint32_t& c_replays, Coh& coh) {
   const WideView v = wide_view(a, r, lds_top);
   uint32_t sp = 0;
-  const float4* q = ZRT_LDS_TOP ? v.top : a.wnodes + v.base;
+  const float4* q = v.top;
   WideNodeQ w;
   qnode_load(q, w);
-  while (wide_iter_q<STATS, StackT, LOCK ? ZRT_PAXIS_LOCK != 0 : true, true, LOCK>(
+  while (wide_iter_q<STATS, StackT>(
       a, r, v, stk, gl, w, q, sp, best_t, best, c_nodes, c_leaves, c_tri, c_sph, coh)) {
   }
   wide_finish<STATS, StackT>(a, r, stk, gl, best_t, best, c_replays);
 }
 
-template <bool STATS, class StackT, bool PAXIS = ZRT_PAXIS_LOCK, bool LEAN = false>
+template <bool STATS, class StackT, bool PAXIS = false, bool LEAN = false>
 __device__ __forceinline__ void traverse_wide(const KArgs& a, const RayT& r, StackT* __restrict__ stk,
                                               const float4* __restrict__ lds_top, uint32_t gl, float& best_t,
                                               int& best, uint32_t& c_nodes, uint32_t& c_leaves, uint32_t& c_tri,
                                               uint32_t& c_sph, uint32_t& c_replays, Coh& coh) {
   const WideView v = wide_view(a, r, lds_top);
   uint32_t sp = 0;
-  // the root is node 0 of this octant's copy (in LDS when the top levels are)
-  const float4* q = ZRT_LDS_TOP && !ZRT_Q_GLOBAL ? v.top : a.wnodes + v.base;
+  // the root is node 0 of this octant's copy, in LDS with the other top levels
+  const float4* q = v.top;
   WideNode w;
   const OctSigns os(r);
-  wide_load(ZRT_LDS_TOP ? v.top : a.wnodes + v.base, os.sx, os.sy, os.sz, w);
-  while (wide_iter<STATS, StackT, ZRT_SCALAR_NODES, PAXIS, true, ZRT_Q_GLOBAL != 0>(
+  wide_load(q, os.sx, os.sy, os.sz, w);
+  while (wide_iter<STATS, StackT, true, PAXIS>(
       a, r, v, stk, gl, w, q, sp, best_t, best, c_nodes, c_leaves, c_tri, c_sph, coh)) {
   }
   wide_finish<STATS, StackT, LEAN>(a, r, stk, gl, best_t, best, c_replays);
@@ -2165,9 +1873,6 @@ __device__ __forceinline__ uint32_t att_row(const KArgs& a, const AttRows& ar, u
   const uint64_t k = (uint64_t)(i - a.att_lds_rows) * ar.g_stride + ar.g_index;
   return row_ok<STATS>(a, k, a.att_cap) ? a.att[k] : kAttOne;
 }
-#ifndef ZRT_ATT_PAIRS
-#define ZRT_ATT_PAIRS 1  // att_product decodes two rows at a time (their texel loads in flight together)
-#endif
 template <bool STATS, bool LEAN = false>
 __device__ __forceinline__ V3 att_product(const KArgs& a, const DevMaterial* __restrict__ mats, const AttRows& ar,
                                           uint32_t n, V3 col, Coh& coh) {
@@ -2175,13 +1880,11 @@ __device__ __forceinline__ V3 att_product(const KArgs& a, const DevMaterial* __r
   // two rows per trip: both texel loads are issued before either product, so a
   // textured path's chain of dependent fetches is half as long (the values and
   // the order of the multiplications are the recursion's, as below)
-  if (ZRT_ATT_PAIRS) {
-    for (; i >= 2; i -= 2) {
-      const V3 hi = att_value<LEAN>(a, mats, att_row<STATS>(a, ar, i - 1, coh));
-      const V3 lo = att_value<LEAN>(a, mats, att_row<STATS>(a, ar, i - 2, coh));
-      col = mk(hi.x * col.x, hi.y * col.y, hi.z * col.z);
-      col = mk(lo.x * col.x, lo.y * col.y, lo.z * col.z);
-    }
+  for (; i >= 2; i -= 2) {
+    const V3 hi = att_value<LEAN>(a, mats, att_row<STATS>(a, ar, i - 1, coh));
+    const V3 lo = att_value<LEAN>(a, mats, att_row<STATS>(a, ar, i - 2, coh));
+    col = mk(hi.x * col.x, hi.y * col.y, hi.z * col.z);
+    col = mk(lo.x * col.x, lo.y * col.y, lo.z * col.z);
   }
   for (; i-- > 0;) {
     const V3 at = att_value<LEAN>(a, mats, att_row<STATS>(a, ar, i, coh));
@@ -2207,7 +1910,7 @@ __device__ __forceinline__ void hit_record(const KArgs& a, const DevMaterial* __
                                            uint32_t& c_tex, Coh& coh, HitRec& h) {
   float4 sh;
   const int fb = __builtin_amdgcn_readfirstlane(best);
-  if (ZRT_SCALAR_PRIMS && __ballot(best != fb) == 0ull) {  // one hit surface in every lane here
+  if (__ballot(best != fb) == 0ull) {  // one hit surface in every lane here: scalar loads
 #if defined(__HIP_DEVICE_COMPILE__)
     typedef const __attribute__((address_space(4))) float4 cfloat4;
     sh = ((cfloat4*)a.shade)[fb];
@@ -2358,21 +2061,8 @@ __device__ __forceinline__ void shade_step(const KArgs& a, const DevMaterial* __
 template <int PRNG>
 struct LaneState {
   static constexpr uint32_t kRngWords = sizeof(Rng<PRNG>) / 4;
-  static constexpr uint32_t kOdWords = ZRT_LANE_OD ? 6 : 0;  // the ray's origin and direction (park_od)
-  static constexpr uint32_t kWords = kRngWords + 5 + kOdWords;
-  __device__ __forceinline__ static void park_od(lds_u32* p, V3 o, V3 d) {
-    const float v[6] = {o.x, o.y, o.z, d.x, d.y, d.z};
-#pragma unroll
-    for (uint32_t k = 0; k < kOdWords; ++k) p[(kRngWords + 5 + k) * kBlock] = __float_as_uint(v[k]);
-  }
-  __device__ __forceinline__ static void unpark_od(const lds_u32* p, V3& o, V3& d) {
-    if (!kOdWords) return;
-    float v[6];
-#pragma unroll
-    for (uint32_t k = 0; k < 6; ++k) v[k] = __uint_as_float(p[(kRngWords + 5 + k) * kBlock]);
-    o = mk(v[0], v[1], v[2]);
-    d = mk(v[3], v[4], v[5]);
-  }
+  // (parking the ray's origin and direction too: 25 spills for 26, C4 -0.5 %, profiles/r06/r06c)
+  static constexpr uint32_t kWords = kRngWords + 5;
   __device__ __forceinline__ static void park(lds_u32* p, const Rng<PRNG>& rng, float r, float g, float b,
                                               uint32_t sample, uint32_t depth) {
     uint32_t w[kRngWords];
@@ -2424,12 +2114,9 @@ __device__ __forceinline__ uint32_t auto_sync(const KArgs& a) {
 // PROBE: the scheduling probe's instance (schedule_probe_kernel): its one-sample
 // units - one per tile, 65 536 on C4 - are dealt to the waves round-robin instead of
 // through the global counter, whose one atomic per unit serialised the probe
-// (ZRT_PROBE_STATIC; the render launch's units are 32 samples and keep the counter)
-#ifndef ZRT_PROBE_STATIC
-#define ZRT_PROBE_STATIC 1
-#endif
+// (the render launch's units are 32 samples and keep the counter)
 template <int MODE /*0 list, 1 BVH binary, 2 BVH reference, 3 wide (FAST)*/, int PRNG, bool STATS, class StackT,
-          bool PROBE = false, bool LEAN = false /* MODE 3, timed flavour: the lean kernel (ZRT_LEAN_*) */>
+          bool PROBE = false, bool LEAN = false /* MODE 3, timed flavour: the lean kernel (struct Lean) */>
 __device__ __forceinline__ void render_loop(const KArgs& a) {
   static_assert(!LEAN || (MODE == 3 && !STATS && !PROBE), "the lean kernel is the timed lockstep FAST loop's");
   extern __shared__ __attribute__((aligned(16))) char lds_raw[];
@@ -2437,13 +2124,13 @@ __device__ __forceinline__ void render_loop(const KArgs& a) {
   float4* lds_top = reinterpret_cast<float4*>(lds_raw + a.lds_top_off);
   lds_u32* att_l = (lds_u32*)(lds_raw + a.lds_att_off) + threadIdx.x;  // [row][lane] att codes
   if (MODE == 3 && !layout_ok(a)) return;
-  if (MODE == 3 && ZRT_LDS_TOP) fill_lds_top(a, lds_top);
+  if (MODE == 3) fill_lds_top(a, lds_top);
   const DevMaterial* mats = a.mats;
-  if (ZRT_MATS_LDS_ONLY && MODE == 3) {  // the host planned the table into LDS: LDS-typed reads
-    float4* m = reinterpret_cast<float4*>(lds_raw + a.lds_mat_off);
-    fill_lds_mats(a, m);
-    mats = reinterpret_cast<const DevMaterial*>(m);
-  } else if (a.mats_in_lds) {  // block-uniform
+  // The lockstep loop reads the material table from its LDS copy only, through
+  // LDS-typed pointers (ds_read), not a generic pointer chosen at run time (flat
+  // loads); the host plans the table into LDS first and falls back to the wavefront
+  // loop when it does not fit (C4 +1.5 %, C2 +0.5 %: profiles/r06/r06l).
+  if (MODE == 3 || a.mats_in_lds) {  // (a.mats_in_lds: block-uniform)
     float4* m = reinterpret_cast<float4*>(lds_raw + a.lds_mat_off);
     fill_lds_mats(a, m);
     mats = reinterpret_cast<const DevMaterial*>(m);
@@ -2454,7 +2141,7 @@ __device__ __forceinline__ void render_loop(const KArgs& a) {
   // depth - is parked in LDS ([word][lane], LaneState) while it traverses: the
   // traversal needs every VGPR of the 6-wave budget, and these values otherwise
   // went to scratch (9 stores + 9 loads per step through the vector-memory path)
-  constexpr bool kLaneLds = MODE == 3 && ZRT_LANE_LDS;
+  constexpr bool kLaneLds = MODE == 3;
   lds_u32* st_l = (lds_u32*)(lds_raw + a.lds_state_off) + threadIdx.x;
 
   bool active = false, in_sample = false;  // active: this lane still has samples in the wave's unit
@@ -2512,7 +2199,7 @@ __device__ __forceinline__ void render_loop(const KArgs& a) {
           c_depth = c_refl = c_bg = 0;  // (so the launch totals are the rows' sums)
         }
         uint32_t u = 0;
-        if (PROBE && ZRT_PROBE_STATIC) {
+        if (PROBE) {
           u = probe_u;
           probe_u += gridDim.x * (kBlock / 64);
         } else {
@@ -2574,15 +2261,15 @@ __device__ __forceinline__ void render_loop(const KArgs& a) {
       RayT r;
       r.ox = o.x; r.oy = o.y; r.oz = o.z;
       r.dx = d.x; r.dy = d.y; r.dz = d.z;
-      r.rcp_det = Lean<LEAN>::det ? 1u : a.tri_rcp_fast;
+      r.rcp_det = a.tri_rcp_fast;
       r.gm = a.graze_m;
       r.gl = a.graze_leaf;
       r.gk = a.guard;
       inv_dir(d.x, d.y, d.z, r.ix, r.iy, r.iz);
-            float best_t = __builtin_inff();
+      float best_t = __builtin_inff();
       int best = -1;
       if (MODE == 0) {
-#if ZRT_LIST_SCALAR && defined(__HIP_DEVICE_COMPILE__)
+#if defined(__HIP_DEVICE_COMPILE__)
         // the list is wave-uniform: read it through the scalar cache (s_load)
         typedef const __attribute__((address_space(4))) float4 cfloat4;
         cfloat4* cprims = (cfloat4*)a.prims;
@@ -2604,17 +2291,11 @@ __device__ __forceinline__ void render_loop(const KArgs& a) {
       } else if (MODE == 3) {
         if (kLaneLds) {
           LaneState<PRNG>::park(st_l, rng, acc_r, acc_g, acc_b, sample, depth_left);
-          if (ZRT_LANE_OD) LaneState<PRNG>::park_od(st_l, o, d);
         }
-        if constexpr (ZRT_LOCK_QN && !PROBE)
-          traverse_wide_q<STATS, StackT, true>(a, r, stk, lds_top, gl, best_t, best, c_nodes, c_leaves, c_tri, c_sph,
-                                               c_replays, coh);
-        else
-          traverse_wide<STATS, StackT, ZRT_PAXIS_LOCK != 0, LEAN>(a, r, stk, lds_top, gl, best_t, best, c_nodes, c_leaves,
-                                                                  c_tri, c_sph, c_replays, coh);
+        traverse_wide<STATS, StackT, false, LEAN>(a, r, stk, lds_top, gl, best_t, best, c_nodes, c_leaves, c_tri, c_sph,
+                                                  c_replays, coh);
         if (kLaneLds) {
           LaneState<PRNG>::unpark(st_l, rng, acc_r, acc_g, acc_b, sample, depth_left);
-          if (ZRT_LANE_OD) LaneState<PRNG>::unpark_od(st_l, o, d);
         }
       } else {
         traverse_bvh<MODE == 1, STATS>(a, r, stk, best_t, best, c_nodes, c_tri, c_sph, &excess);
@@ -2707,7 +2388,7 @@ __device__ __forceinline__ void render_loop_wf(const KArgs& a) {
   float4* lds_top = reinterpret_cast<float4*>(lds_raw + a.lds_top_off);
   lds_u32* att_l = (lds_u32*)(lds_raw + a.lds_att_off) + threadIdx.x;  // [row][lane] att codes
   if (!layout_ok(a)) return;
-  if (ZRT_LDS_TOP) fill_lds_top(a, lds_top);
+  fill_lds_top(a, lds_top);
   const DevMaterial* mats = a.mats;
   if (a.mats_in_lds) {  // block-uniform
     float4* m = reinterpret_cast<float4*>(lds_raw + a.lds_mat_off);
@@ -2848,7 +2529,7 @@ __device__ __forceinline__ void render_loop_wf(const KArgs& a) {
     sp = 0;
     {
       const WideView v = wide_view(a, r, lds_top);
-      q = ZRT_LDS_TOP ? v.top : a.wnodes + v.base;
+      q = v.top;
     }
     trav = true;
   }
@@ -2931,18 +2612,15 @@ struct PoolLds {
 
 // Where a path's attenuation rows past LDS go: [path][row] keeps one path's rows in
 // one or two 32-B sectors, so its pushes of one sample (and the next samples') merge
-// in L2 before they are written back; [row][path] (0) spreads them, every 4-B code a
+// in L2 before they are written back; [row][path] would spread them, every 4-B code a
 // sector of its own (the pool's lanes shade paths at unrelated depths).
-#ifndef ZRT_POOL_ATT_PATH
-#define ZRT_POOL_ATT_PATH 1
-#endif
 template <int PRNG, bool STATS, class StackT, bool GUARD, bool QN = false>
 __device__ __forceinline__ void render_loop_pool(const KArgs& a) {
   extern __shared__ __attribute__((aligned(16))) char lds_raw[];
   StackT* stk = reinterpret_cast<StackT*>(lds_raw) + threadIdx.x;  // LDS: the lane's traversal stack column
   float4* lds_top = reinterpret_cast<float4*>(lds_raw + a.lds_top_off);
   if (!layout_ok(a)) return;
-  if (ZRT_LDS_TOP) fill_lds_top(a, lds_top);
+  fill_lds_top(a, lds_top);
   const DevMaterial* mats = a.mats;
   if (a.mats_in_lds) {  // block-uniform
     float4* m = reinterpret_cast<float4*>(lds_raw + a.lds_mat_off);
@@ -2962,7 +2640,7 @@ __device__ __forceinline__ void render_loop_pool(const KArgs& a) {
     pl.queue = (__attribute__((address_space(3))) uint8_t*)(base + 8 * kBlockPaths) + wave_paths;
   }
   lds_u32* att_base = (lds_u32*)(lds_raw + a.lds_att_off);  // [row][path of the block] att codes
-  // global rows past the LDS ones: [path][row] (ZRT_POOL_ATT_PATH), g_rows per path
+  // global rows past the LDS ones: [path][row], g_rows per path
   const uint32_t g_rows = a.max_depth > a.att_lds_rows ? a.max_depth - a.att_lds_rows : 1u;
 
   // unit slots (wave-uniform): tile, chunk, the samples [.., unit_end) of the chunk
@@ -3024,7 +2702,7 @@ __device__ __forceinline__ void render_loop_pool(const KArgs& a) {
             best = -1;
             sp = 0;
             v = wide_view(a, r, lds_top);
-            q = ZRT_LDS_TOP ? v.top : a.wnodes + v.base;
+            q = v.top;
             node_load<QN>(q, r, w);
             trav = true;
           }
@@ -3037,8 +2715,8 @@ __device__ __forceinline__ void render_loop_pool(const KArgs& a) {
             more = wide_iter_q<STATS, StackT, true, GUARD>(a, r, v, stk, gl, w, q, sp, best_t, best, c_nodes, c_leaves,
                                                           c_tri, c_sph, coh);
           else
-            more = wide_iter<STATS, StackT, ZRT_POOL_SCALAR != 0, true, GUARD>(a, r, v, stk, gl, w, q, sp, best_t, best,
-                                                                               c_nodes, c_leaves, c_tri, c_sph, coh);
+            more = wide_iter<STATS, StackT, false, true, GUARD>(a, r, v, stk, gl, w, q, sp, best_t, best, c_nodes, c_leaves,
+                                                                c_tri, c_sph, coh);
           if (!more) {
             wide_finish<STATS, StackT>(a, r, stk, gl, best_t, best, c_replays);
             const uint32_t P = wave_paths + cp;
@@ -3058,8 +2736,7 @@ __device__ __forceinline__ void render_loop_pool(const KArgs& a) {
 #pragma unroll 1
     for (uint32_t s = 0; s < 2; ++s) {
       const uint32_t p = s * 64u + (uint32_t)lane, P = wave_paths + p;
-      const AttRows ar = ZRT_POOL_ATT_PATH ? AttRows{att_base + P, kBlockPaths, (g_paths + P) * g_rows, 1u}
-                                           : AttRows{att_base + P, kBlockPaths, g_paths + P, a.n_paths};
+      const AttRows ar{att_base + P, kBlockPaths, (g_paths + P) * g_rows, 1u};
       const uint32_t unit_end = s ? s_end[1] : s_end[0];
       const uint32_t x0 = s ? s_x0[1] : s_x0[0], y0 = s ? s_y0[1] : s_y0[0];
       bool push = false;
@@ -3206,13 +2883,7 @@ __device__ __forceinline__ void render_loop_pool(const KArgs& a) {
   }
 }
 
-#ifndef ZRT_LIST_MERGE
-#define ZRT_LIST_MERGE 1  // list loop: one unit() per step for every new direction (scatters and camera rays)
-#endif
-#ifndef ZRT_LIST_CONVERGE
-#define ZRT_LIST_CONVERGE 1  // list loop: the operations materials share in Material.scatter issued once per wave (C2 +2.9 %, profiles/r06/r06i)
-#endif
-// shade_step's first half for the list loop (ZRT_LIST_MERGE): a hit's scatter up
+// shade_step's first half for the list loop: a hit's scatter up
 // to the direction it normalises.  Every material's new direction - and a new
 // sample's camera ray - is normalised once per step for all lanes together
 // (unit(), vector.zig:88-92, ~20 VALU: where the materials ran it in their own
@@ -3235,7 +2906,7 @@ __device__ __forceinline__ void shade_hit_a(const KArgs& a, const DevMaterial* _
   }
   float4 sh;
   const int fb = __builtin_amdgcn_readfirstlane(best);
-  if (ZRT_SCALAR_PRIMS && __ballot(best != fb) == 0ull) {
+  if (__ballot(best != fb) == 0ull) {
 #if defined(__HIP_DEVICE_COMPILE__)
     typedef const __attribute__((address_space(4))) float4 cfloat4;
     sh = ((cfloat4*)a.shade)[fb];
@@ -3289,7 +2960,6 @@ __device__ __forceinline__ void shade_hit_a(const KArgs& a, const DevMaterial* _
   // metal and dielectric both start from unit(d): one normalisation for the lanes of either
   V3 ud = d;
   if (mkind != ZRT_MAT_LAMBERTIAN) ud = unit(d);
-#if ZRT_LIST_CONVERGE
   // Material.scatter (material.zig:43-129) with the operations the materials share
   // issued once for the lanes of all of them (a wave whose lanes hit two or three
   // materials otherwise runs each shared piece once per material): the correctly
@@ -3298,75 +2968,43 @@ __device__ __forceinline__ void shade_hit_a(const KArgs& a, const DevMaterial* _
   // each lane's draws still in its own order (r1, r2, bool / one draw after its
   // Schlick term) -, reflect() for metal and reflected dielectric rays, and the
   // albedo lookup for Lambertian and metal.  The same operations on the same values
-  // per lane as the branches below: bit-identical (test_list_loops_bit_exact).
-  {
-    const bool lamb = mkind == ZRT_MAT_LAMBERTIAN, metal = mkind == ZRT_MAT_METAL;
-    const bool diel = !lamb && !metal;
-    float r1 = 0.0f;
-    if (lamb) r1 = rand_float(rng);
-    float ratio = 1.0f, cos_theta = 0.0f;
-    if (diel) {
-      ratio = front ? dev::rcp_rn(mat.ior()) : mat.ior();
-      cos_theta = dev::fmin_z(dot(neg(ud), normal), 1.0f);
-    }
-    const float qv = lamb ? r1 : cos_theta;
-    const float root = dev::sqrt_rn(1.0f - qv * qv);  // Lambertian rr, dielectric sin_theta
-    bool refl = diel && ratio * root > 1.0f;
-    float reflectance = 0.0f;
-    const bool schlick = diel && !refl;
-    if (schlick) {
-      const float r0 = dev::div_rn(1.0f - ratio, 1.0f + ratio);
-      reflectance = r0 + (1.0f - r0) * dev::pow5_z(1.0f - cos_theta);
-    }
-    float r2 = 0.0f;
-    if (lamb || schlick) r2 = rand_float(rng);
-    if (schlick) refl = reflectance > r2;
-    if (lamb) {
-      float sn, cs;
-      dev::sincos_z(kTwoPi * r2, &sn, &cs);
-      V3 hv = mk(cs * root, sn * root, r1);
-      if (!rand_bool(rng)) hv.z = hv.z * -1.0f;
-      x = add(normal, hv);
-    } else if (metal || refl) {
-      x = reflect(ud, normal);
-    } else {
-      x = refract(ud, normal, ratio);
-    }
-    att = kAttOne;
-    if (!diel) att = albedo_code(mat, tag & 0x7fffffffu, tu, tv);  // (metal: used only when not absorbed)
-    pend = metal ? 2u : 1u;
-    return;
+  // per lane as shade_step's per-material branches: bit-identical
+  // (test_list_loops_bit_exact; C2 +2.9 %, profiles/r06/r06i).
+  const bool lamb = mkind == ZRT_MAT_LAMBERTIAN, metal = mkind == ZRT_MAT_METAL;
+  const bool diel = !lamb && !metal;
+  float r1 = 0.0f;
+  if (lamb) r1 = rand_float(rng);
+  float ratio = 1.0f, cos_theta = 0.0f;
+  if (diel) {
+    ratio = front ? dev::rcp_rn(mat.ior()) : mat.ior();
+    cos_theta = dev::fmin_z(dot(neg(ud), normal), 1.0f);
   }
-#endif
-  if (mkind == ZRT_MAT_LAMBERTIAN) {
-    const float r1 = rand_float(rng);
-    const float r2 = rand_float(rng);
-    const float rr = dev::sqrt_rn(1.0f - r1 * r1);
+  const float qv = lamb ? r1 : cos_theta;
+  const float root = dev::sqrt_rn(1.0f - qv * qv);  // Lambertian rr, dielectric sin_theta
+  bool refl = diel && ratio * root > 1.0f;
+  float reflectance = 0.0f;
+  const bool schlick = diel && !refl;
+  if (schlick) {
+    const float r0 = dev::div_rn(1.0f - ratio, 1.0f + ratio);
+    reflectance = r0 + (1.0f - r0) * dev::pow5_z(1.0f - cos_theta);
+  }
+  float r2 = 0.0f;
+  if (lamb || schlick) r2 = rand_float(rng);
+  if (schlick) refl = reflectance > r2;
+  if (lamb) {
     float sn, cs;
     dev::sincos_z(kTwoPi * r2, &sn, &cs);
-    V3 hv = mk(cs * rr, sn * rr, r1);
+    V3 hv = mk(cs * root, sn * root, r1);
     if (!rand_bool(rng)) hv.z = hv.z * -1.0f;
     x = add(normal, hv);
-    att = albedo_code(mat, tag & 0x7fffffffu, tu, tv);
-    pend = 1;
-  } else if (mkind == ZRT_MAT_METAL) {
+  } else if (metal || refl) {
     x = reflect(ud, normal);
-    att = albedo_code(mat, tag & 0x7fffffffu, tu, tv);  // (used only when the scatter is not absorbed)
-    pend = 2;
   } else {
-    const float ratio = front ? dev::rcp_rn(mat.ior()) : mat.ior();
-    const float cos_theta = dev::fmin_z(dot(neg(ud), normal), 1.0f);
-    const float sin_theta = dev::sqrt_rn(1.0f - cos_theta * cos_theta);
-    bool refl = ratio * sin_theta > 1.0f;
-    if (!refl) {
-      const float r0 = dev::div_rn(1.0f - ratio, 1.0f + ratio);
-      const float reflectance = r0 + (1.0f - r0) * dev::pow5_z(1.0f - cos_theta);
-      refl = reflectance > rand_float(rng);
-    }
-    x = refl ? reflect(ud, normal) : refract(ud, normal, ratio);
-    att = kAttOne;
-    pend = 1;
+    x = refract(ud, normal, ratio);
   }
+  att = kAttOne;
+  if (!diel) att = albedo_code(mat, tag & 0x7fffffffu, tu, tv);  // (metal: used only when not absorbed)
+  pend = metal ? 2u : 1u;
 }
 
 // ---------------------------------------------------------------------------
@@ -3388,16 +3026,10 @@ template <int PRNG, bool STATS>
 __device__ __forceinline__ void render_loop_list(const KArgs& a) {
   extern __shared__ __attribute__((aligned(16))) char lds_raw[];
   lds_u32* att_l = (lds_u32*)(lds_raw + a.lds_att_off) + threadIdx.x;  // [row][lane] att codes
-  const DevMaterial* mats = a.mats;
-  if (ZRT_MATS_LDS_ONLY) {  // the host planned the table into LDS: LDS-typed reads
-    float4* m = reinterpret_cast<float4*>(lds_raw + a.lds_mat_off);
-    fill_lds_mats(a, m);
-    mats = reinterpret_cast<const DevMaterial*>(m);
-  } else if (a.mats_in_lds) {  // block-uniform
-    float4* m = reinterpret_cast<float4*>(lds_raw + a.lds_mat_off);
-    fill_lds_mats(a, m);
-    mats = reinterpret_cast<const DevMaterial*>(m);
-  }
+  // (the host planned the material table into LDS, as for the lockstep loop: LDS-typed reads)
+  float4* mats_l = reinterpret_cast<float4*>(lds_raw + a.lds_mat_off);
+  fill_lds_mats(a, mats_l);
+  const DevMaterial* mats = reinterpret_cast<const DevMaterial*>(mats_l);
 #if defined(__HIP_DEVICE_COMPILE__)
   typedef const __attribute__((address_space(4))) float4 cfloat4;  // the list is wave-uniform: scalar loads
   cfloat4* cprims = (cfloat4*)a.prims;
@@ -3497,7 +3129,7 @@ __device__ __forceinline__ void render_loop_list(const KArgs& a) {
     V3 L = mk(0.0f, 0.0f, 0.0f);
     const uint32_t dh0 = c_depth, rf0 = c_refl, bg0 = c_bg;
     const AttRows ar{att_l, kBlock, gl, a.n_lanes};
-    V3 x = mk(0.0f, 0.0f, 0.0f), loc = x, nrm = x;  // ZRT_LIST_MERGE: the direction to normalise, hit, normal
+    V3 x = mk(0.0f, 0.0f, 0.0f), loc = x, nrm = x;  // the direction to normalise, hit, normal
     uint32_t att = 0, pend = 0;
     if (depth_left == 0) {
       ++c_depth;
@@ -3524,14 +3156,11 @@ __device__ __forceinline__ void render_loop_list(const KArgs& a) {
           sphere_test<false>(cprims[3 * i], (int)i, r, best_t, best);
         }
       }
-      if (ZRT_LIST_MERGE)
-        shade_hit_a<STATS>(a, mats, rng, best, best_t, o, d, path_end, sky, L, c_bg, c_shade, c_tex, x, loc, nrm, att,
-                           pend);
-      else
-        shade_step<STATS>(a, mats, ar, rng, best, best_t, o, d, depth_left, path_end, sky, L, c_bg, c_refl, c_shade,
-                          c_tex, coh);
+      // one unit() per step for every new direction (scatters and camera rays): shade_hit_a
+      shade_hit_a<STATS>(a, mats, rng, best, best_t, o, d, path_end, sky, L, c_bg, c_shade, c_tex, x, loc, nrm, att,
+                         pend);
     }
-    bool cam = false;  // ZRT_LIST_MERGE: the item's next sample starts in this step
+    bool cam = false;  // the item's next sample starts in this step
     if (path_end) {
       const V3 col = sky ? att_product<STATS>(a, mats, ar, a.max_depth - depth_left, L, coh) : L;
       acc_r += col.x;
@@ -3541,7 +3170,7 @@ __device__ __forceinline__ void render_loop_list(const KArgs& a) {
       if (++sample == s_end) {  // the chunk's sequential sum, in its [chunk][pixel slot] place
         a.partial[slot] = make_float4(acc_r, acc_g, acc_b, 0.0f);
         has = false;
-      } else if (ZRT_LIST_MERGE) {  // the next sample's jitter + Camera.getRay (raytrace.zig:173-175)
+      } else {  // the next sample's jitter + Camera.getRay (raytrace.zig:173-175)
         const uint64_t offset = (uint64_t)py * a.width + px;
         rng.init(((offset << 16) | (uint64_t)sample) + a.seed_mix);
         const float u = dev::div_known((float)px + rand_float(rng) - 0.5f, a.f_width, a.inv_width);
@@ -3553,7 +3182,7 @@ __device__ __forceinline__ void render_loop_list(const KArgs& a) {
         in_sample = true;
       }
     }
-    if (ZRT_LIST_MERGE && (pend != 0u || cam)) {  // every new direction of the step, normalised together
+    if (pend != 0u || cam) {  // every new direction of the step, normalised together
       const V3 nd = unit(x);
       if (cam) {
         o = mk(a.org[0], a.org[1], a.org[2]);
@@ -3745,7 +3374,7 @@ __global__ void __launch_bounds__(kBlock) trace_kernel(const KArgs a, const floa
   StackT* stk = reinterpret_cast<StackT*>(lds_raw) + threadIdx.x;
   float4* lds_top = reinterpret_cast<float4*>(lds_raw + a.lds_top_off);
   if ((MODE == 3 || MODE == 8) && !layout_ok(a)) return;
-  if ((MODE == 3 || MODE == 8) && ZRT_LDS_TOP) fill_lds_top(a, lds_top);
+  if ((MODE == 3 || MODE == 8)) fill_lds_top(a, lds_top);
   const uint32_t gl = blockIdx.x * kBlock + threadIdx.x;
   if (gl >= n) return;
   const float* q = rays + 6ull * gl;
@@ -3804,7 +3433,7 @@ __device__ __forceinline__ bool anyhit_literal(const KArgs& a, const RayT& r, St
   const uint32_t rows = a.lds_rows, cap = a.ref_stack;
   StackT* __restrict__ ovf = reinterpret_cast<StackT*>(a.stack_ovf) + gl;
   const float slack = ray_slack(r, a.scene_extent, ray_m(r));
-  const float gw = ZRT_GUARD && r.gk > 0.0f ? guard_grow(a, r) : 0.0f;
+  const float gw = r.gk > 0.0f ?guard_grow(a, r) : 0.0f;
   stk[0] = 0;
   uint32_t sp = 1;
   while (sp > 0) {
@@ -3850,7 +3479,7 @@ __device__ __forceinline__ bool anyhit_binary(const KArgs& a, const RayT& r, Sta
                                               float t_max) {
   if (!ray_origin_ok(a, r)) return anyhit_literal<StackT>(a, r, stk, gl, t_max, false);
   const float slack = ray_slack(r, a.scene_extent, ray_m(r));
-  const float gw = ZRT_GUARD && r.gk > 0.0f ? guard_grow(a, r) : 0.0f;
+  const float gw = r.gk > 0.0f ?guard_grow(a, r) : 0.0f;
   const float tb = t_max * kOpen + slack;
   const uint32_t cap = a.stack_depth;
   uint32_t sp = 0;
@@ -3905,7 +3534,7 @@ __device__ __forceinline__ bool anyhit_wide(const KArgs& a, const RayT& r, Stack
   if (!literal) {
     const WideView v = wide_view(a, r, lds_top);
     uint32_t sp = 0;
-    const float4* q = ZRT_LDS_TOP ? v.top : a.wnodes + v.base;
+    const float4* q = v.top;
     WideNode w;
     const OctSigns os(r);
     wide_load(q, os.sx, os.sy, os.sz, w);
@@ -3915,8 +3544,8 @@ __device__ __forceinline__ bool anyhit_wide(const KArgs& a, const RayT& r, Stack
     while (more) {
       float best_t = t_max;
       int best = -1;
-      more = wide_iter<false, StackT, ZRT_SCALAR_NODES != 0, true, true, false>(a, r, v, stk, gl, w, q, sp, best_t, best,
-                                                                               c_nodes, c_leaves, c_tri, c_sph, coh);
+      more = wide_iter<false, StackT, true, true, true>(a, r, v, stk, gl, w, q, sp, best_t, best, c_nodes, c_leaves,
+                                                        c_tri, c_sph, coh);
       if (best >= 0) {
         const uint32_t leaf = a.leaf_of_slot[best];
         if (leaf_accepts(a.nodes[2 * leaf], a.nodes[2 * leaf + 1], r, t_max)) return true;
@@ -3971,7 +3600,7 @@ __global__ void __launch_bounds__(kBlock) anyhit_kernel(const KArgs a, const flo
   StackT* stk = reinterpret_cast<StackT*>(lds_raw) + threadIdx.x;
   float4* lds_top = reinterpret_cast<float4*>(lds_raw + a.lds_top_off);
   if (MODE == 3 && !layout_ok(a)) return;
-  if (MODE == 3 && ZRT_LDS_TOP) fill_lds_top(a, lds_top);
+  if (MODE == 3) fill_lds_top(a, lds_top);
   const uint32_t gl = blockIdx.x * kBlock + threadIdx.x;
   if (gl >= n) return;
   const float* q = rays + 6ull * gl;
@@ -4041,7 +3670,7 @@ __global__ void __launch_bounds__(kBlock, MODE == 3 ? 4 : 1) ao_kernel(const KAr
   StackT* stk = reinterpret_cast<StackT*>(lds_raw) + threadIdx.x;
   float4* lds_top = reinterpret_cast<float4*>(lds_raw + a.lds_top_off);
   if (MODE == 3 && !layout_ok(a)) return;
-  if (MODE == 3 && ZRT_LDS_TOP) fill_lds_top(a, lds_top);
+  if (MODE == 3) fill_lds_top(a, lds_top);
   const uint32_t gl = blockIdx.x * kBlock + threadIdx.x;
   const uint32_t lane = threadIdx.x & 63u;
   const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -4139,7 +3768,7 @@ __global__ void __launch_bounds__(kBlock) features_kernel(const KArgs a, const u
   StackT* stk = reinterpret_cast<StackT*>(lds_raw) + threadIdx.x;
   float4* lds_top = reinterpret_cast<float4*>(lds_raw + a.lds_top_off);
   if ((MODE == 3 || MODE == 8) && !layout_ok(a)) return;
-  if ((MODE == 3 || MODE == 8) && ZRT_LDS_TOP) fill_lds_top(a, lds_top);
+  if ((MODE == 3 || MODE == 8)) fill_lds_top(a, lds_top);
   const uint32_t gl = blockIdx.x * kBlock + threadIdx.x;
   const uint32_t tiles_w = (a.width + 7u) / 8u;  // (tiles over the whole width here, not tiles_x)
   const uint32_t tile = gl >> 6, p = gl & 63u;
@@ -4641,7 +4270,7 @@ __global__ void __launch_bounds__(kBlock, MODE == 3 ? 4 : 1) radiance_kernel(con
   float4* lds_top = reinterpret_cast<float4*>(lds_raw + a.lds_top_off);
   lds_u32* att_l = (lds_u32*)(lds_raw + a.lds_att_off) + threadIdx.x;  // [row][lane] att codes
   if (MODE == 3 && !layout_ok(a)) return;
-  if (MODE == 3 && ZRT_LDS_TOP) fill_lds_top(a, lds_top);
+  if (MODE == 3) fill_lds_top(a, lds_top);
   const DevMaterial* mats = a.mats;
   if (a.mats_in_lds) {  // block-uniform
     float4* m = reinterpret_cast<float4*>(lds_raw + a.lds_mat_off);
@@ -4767,7 +4396,7 @@ __global__ void __launch_bounds__(kBlock, MODE == 3 ? 4 : 1) camera_kernel(const
   float4* lds_top = reinterpret_cast<float4*>(lds_raw + a.lds_top_off);
   lds_u32* att_l = (lds_u32*)(lds_raw + a.lds_att_off) + threadIdx.x;  // [row][lane] att codes
   if (MODE == 3 && !layout_ok(a)) return;
-  if (MODE == 3 && ZRT_LDS_TOP) fill_lds_top(a, lds_top);
+  if (MODE == 3) fill_lds_top(a, lds_top);
   const DevMaterial* mats = a.mats;
   if (a.mats_in_lds) {  // block-uniform
     float4* m = reinterpret_cast<float4*>(lds_raw + a.lds_mat_off);
@@ -5166,9 +4795,7 @@ const KernelConfig& kernel_config() {
       kBlockPaths,
       kKernelLayout,
       kPaxisM,
-      ZRT_LDS_TOP != 0, ZRT_LANE_LDS != 0, ZRT_MATS_LDS_ONLY != 0, ZRT_LOCK_QN != 0, ZRT_PROFILE != 0,
-      ZRT_LEAN_DEFAULT != 0, ZRT_GROW != 0, ZRT_SPHERE_SLOTS != 0,
-      ZRT_OCT_MUL24 != 0 && ZRT_OCT_COPIES != 0,
+      ZRT_PROFILE != 0,
   };
   return k;
 }
