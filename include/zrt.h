@@ -1321,6 +1321,89 @@ int zrt_lens_init(uint32_t kind, const float look_from[3], const float look_at[3
 int zrt_lens_from_camera(uint32_t kind, const zrt_camera* camera, float aperture, float focus_dist,
                          float fisheye_fov_deg, zrt_lens* out);
 
+/* ---- denoising lens frames: lens features, moments, filters on a rectangle ------- *
+ * What makes a low-sample camera-query frame usable: first-hit features along the lens
+ * model's centre rays, the second moment of the query's chunk sums (and the variance
+ * plane it gives), and both filters over a pixel rectangle instead of raytrace.zig:168's
+ * square.  All arithmetic is f32, nothing fused, IEEE `/` and sqrtf, in the order written.
+ * A zrt_rect is a camera query's rectangle: inside the width x height frame, not empty. */
+typedef struct zrt_rect { uint32_t x0, y0, w, h; } zrt_rect;
+
+/* Host only; every launch path below calls it.  ZRT_E_INVALID: a null pointer, an empty
+ * rectangle, one that leaves the frame, params the camera query would refuse (width or
+ * height outside 1 .. 65535, and what every entry point refuses of params). */
+int zrt_rect_check(const zrt_params* params, const zrt_rect* rect);
+
+/* zrt_ctx_features along lens rays: the feature buffer (width*height*8 f32, 16-byte aligned,
+ * two float4 per pixel, the whole width addressable) of the pixels of rect; pixels outside
+ * are not touched.  The centre ray of pixel (x, y): u = float(x) / float(width), v =
+ * float(y) / float(height) - the camera query's jitter formula at r1 = r2 = 0.5, exactly -
+ * (o, tgt) = model(u, v) as the camera query defines the five models, the thin lens taken at
+ * its centre (o = origin, no lens stream drawn), dir = tgt - o, Ray.init.  The hit and the
+ * eight floats are zrt_ctx_features': the closest hit in (0.001, inf) through
+ * params->traversal with the grazing-triangle guard on; {N, t}, {A, id}; a miss gives N = 0,
+ * t = 0, A = backgroundColor(d), id = 0.  With zrt_lens_from_camera(PINHOLE, cam) and rect =
+ * {0, 0, height, height} the rectangle equals zrt_ctx_features' bit for bit.
+ * It is a query (see "ray queries"): the query's rows, error flag, completion and events, one
+ * query in flight per context; after a traversal stack overflow the rectangle's floats are
+ * NaN and zrt_ctx_sync reports ZRT_E_UNSUPPORTED once.  Lanes take the rectangle in 8 x 8
+ * tiles anchored at (x0, y0), as the camera query's slots.  ZRT_E_INVALID: what
+ * zrt_rect_check and zrt_lens_check refuse, a null or misaligned pointer, params that do not
+ * fit the context. */
+int zrt_ctx_camera_features(zrt_ctx* ctx, const zrt_params* params, const zrt_lens* lens, const zrt_rect* rect,
+                            float* dev_features, void* hip_stream);
+
+/* zrt_ctx_camera whose sum.w holds Q, zrt_ctx_accum_variance's second moment: per chunk of
+ * the call, in chunk order, l_j = (S_j.r + S_j.g) + S_j.b, Q = Q + l_j * l_j; a ragged last
+ * chunk goes into the sums but not into Q.  Q starts at 0, or at the caller's sum.w under
+ * ZRT_CQ_ACCUMULATE, so calls over [0, 8) and [8, 16) equal one over [0, 16), Q included,
+ * whatever the rounds.  After a device error Q is NaN, as the sums are.  Everything else -
+ * sums, means, counters, rounds, refusals, zrt_ctx_camera_info - is zrt_ctx_camera's, which
+ * itself keeps writing 0 into sum.w. */
+int zrt_ctx_camera_moments(zrt_ctx* ctx, const zrt_params* params, const zrt_lens* lens,
+                           const zrt_camera_query* query, float* dev_sum, float* dev_rgb, void* hip_stream);
+
+/* The variance plane of such sums over rect: dev_sum as zrt_ctx_camera_moments left it after
+ * n_total samples per pixel, dev_variance width*height f32 in the frame's layout (the plane
+ * zrt_ctx_denoise_guided takes).  (k, ik, sc) = zrt_debug_variance_plan(params, n_total),
+ * with its refusals (n_total % c != 0, k < 2).  Per pixel of rect: M = (sum.r + sum.g) +
+ * sum.b, mean = M * ik, v = Q * ik - mean * mean, v = v > 0 ? v : 0 (a NaN stays NaN), var =
+ * v * sc.  Pixels outside rect are not touched.  Elementwise and stateless: not a query;
+ * asynchronous on hip_stream (NULL: the context's own). */
+int zrt_ctx_camera_variance(zrt_ctx* ctx, const zrt_params* params, const zrt_rect* rect, uint32_t n_total,
+                            const float* dev_sum, float* dev_variance, void* hip_stream);
+
+/* Both filters with D = rect.  dev_variance == NULL: the definition of "denoising" (flags
+ * must be 0 and dev_out_variance NULL); otherwise that of "variance-guided denoising", with
+ * ZRT_DN_DEMODULATE allowed.  Each holds word for word with D = the pixels of rect: a tap
+ * outside rect is skipped even though the frame holds valid pixels there, the guided 3 x 3
+ * smoothing takes V(p) for a neighbour outside rect, and pixels outside rect are copied,
+ * frame and variance, over the whole width x height frame.  height > width is not refused.
+ * With rect = {0, 0, height, height} the outputs are zrt_ctx_denoise's and
+ * zrt_ctx_denoise_guided's bit for bit.  Buffers as theirs; the context's ping-pong planes
+ * and zrt_ctx_denoise_ms serve it as they serve them.  ZRT_E_INVALID: what zrt_rect_check
+ * refuses, what they refuse of dn, flags and pointers. */
+int zrt_ctx_denoise_rect(zrt_ctx* ctx, const zrt_params* params, const zrt_denoise* dn, uint32_t flags,
+                         const zrt_rect* rect, const float* dev_frame, const float* dev_features,
+                         const float* dev_variance, float* dev_out, float* dev_out_variance, void* hip_stream);
+
+/* One-shot on one GPU (params->device): a context, zrt_ctx_camera_moments (guided != 0) or
+ * zrt_ctx_camera (guided == 0) over the query, zrt_ctx_camera_features,
+ * zrt_ctx_camera_variance at n_total = n_samples (guided) and zrt_ctx_denoise_rect over
+ * the query's rectangle, then the copies out.  Every device buffer starts zeroed: pixels
+ * outside the rectangle come back 0.  dn NULL: zrt_denoise_guided_defaults' filter (guided)
+ * or zrt_denoise_defaults'; flags are the caller's and must be 0 when guided == 0.  out_rgb
+ * (width*height*3 f32): the filtered frame; out_noisy (may be NULL): the unfiltered frame,
+ * bit for bit zrt_render_lens'; out_features (may be NULL): width*height*8 f32; out_variance
+ * (may be NULL; guided): width*height f32; info, denoise_ms may be NULL.  ZRT_E_INVALID before
+ * any device work: what the calls above refuse of their arguments, and, guided, what the
+ * variance plan refuses of n_samples (the sums start zeroed, so they hold the call's samples
+ * whatever first_sample and ZRT_CQ_ACCUMULATE say). */
+int zrt_render_lens_denoised(const zrt_scene* scene, const zrt_params* params, const zrt_lens* lens,
+                             const zrt_camera_query* query, const zrt_denoise* dn, uint32_t guided, uint32_t flags,
+                             float* out_rgb, float* out_noisy, float* out_features, float* out_variance,
+                             zrt_radiance_info* info, double* denoise_ms);
+
 /* ---- host-side scene ingestion (the caller side of the seam) ------------- *
  * Restatement of scenes.zig / obj_reader.zig / png_image.zig texture loading
  * so tests and bench can build the reference's scenes without Zig.  Assets are

@@ -425,6 +425,22 @@ static void camera_plans() {
   CHECK(zrt_lens_init(5, from, at, up, 40.0f, 1.5f, 0.0f, 1.0f, 180.0f, &l) == ZRT_E_INVALID && zrt_lens_check(nullptr) == ZRT_E_INVALID &&
             zrt_lens_from_camera(5, &cam, 0.0f, 0.0f, 180.0f, &l) == ZRT_E_INVALID,
         "lens: an unknown kind or a null lens accepted");
+  // zrt_rect_check (planner.cpp): rectangles at the frame's edges, the largest frame, a frame
+  // taller than wide, every refusal
+  zrt_params rp = p;
+  rp.width = 33;
+  rp.height = 40;
+  const zrt_rect in[] = {{0, 0, 33, 40}, {32, 39, 1, 1}, {5, 3, 28, 37}}, out[] = {{0, 0, 0, 1}, {0, 0, 1, 0}, {33, 0, 1, 1},
+                        {0, 40, 1, 1}, {5, 3, 29, 1}, {5, 3, 1, 38}, {0xFFFFFFFFu, 0, 2, 1}, {1, 1, 0xFFFFFFFFu, 0xFFFFFFFFu}};
+  for (const zrt_rect& r : in) CHECK(zrt_rect_check(&rp, &r) == ZRT_OK, "rect_check: %s", zrt_last_error());
+  for (const zrt_rect& r : out) CHECK(zrt_rect_check(&rp, &r) == ZRT_E_INVALID, "rect_check: {%u, %u, %u, %u} accepted", r.x0, r.y0, r.w, r.h);
+  rp.width = rp.height = 65535;
+  const zrt_rect last{65534, 65534, 1, 1};
+  CHECK(zrt_rect_check(&rp, &last) == ZRT_OK, "rect_check at 65535: %s", zrt_last_error());
+  rp.height = 65536;
+  CHECK(zrt_rect_check(&rp, &last) == ZRT_E_INVALID && zrt_rect_check(nullptr, &last) == ZRT_E_INVALID &&
+            zrt_rect_check(&p, nullptr) == ZRT_E_INVALID,
+        "rect_check: a 65536-row frame or a null argument accepted");
 }
 
 // plan_reproject at the cases of tests/test_temporal_host.py: a scene's camera, the

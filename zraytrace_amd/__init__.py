@@ -622,6 +622,48 @@ def lens_check(lens: _ffi.Lens) -> None:
     check(lib().zrt_lens_check(C.byref(lens)))
 
 
+def rect(x0: int, y0: int, w: int, h: int) -> _ffi.Rect:
+    """A zrt_rect: a pixel rectangle of the frame."""
+    return _ffi.Rect(x0=x0, y0=y0, w=w, h=h)
+
+
+def rect_check(params: RenderParams, r: _ffi.Rect) -> None:
+    """Raises ZrtError for a rectangle (or a frame) the lens post calls would refuse
+    (zrt_rect_check; no device)."""
+    p = params.abi()
+    check(lib().zrt_rect_check(C.byref(p), C.byref(r)))
+
+
+def render_lens_denoised(scene, params: RenderParams, lens: _ffi.Lens, n_samples: int, rect=None,
+                         denoise: _ffi.Denoise = None, guided: bool = True, flags: int = None):
+    """A lens frame (or its rectangle rect = (x0, y0, w, h)) rendered and filtered
+    (zrt_render_lens_denoised; the definition: zrt.h "denoising lens frames"): the camera query
+    with moments, lens features, the variance plane and the guided filter over the rectangle;
+    guided False: the plain a-trous filter.  denoise None: the matching defaults; flags None:
+    the guided defaults' flags (0 for the plain filter).  Returns (rgb, dict) with noisy,
+    features, variance (guided), info and denoise_ms in the dict."""
+    view = scene.view if isinstance(scene, LoadedScene) else scene
+    w, h = params.width, params.height
+    x0, y0, rw, rh = rect if rect is not None else (0, 0, w, h)
+    q = camera_query(x0, y0, rw, rh, n_samples)
+    if flags is None:
+        flags = denoise_guided_defaults()[1] if guided else 0
+    rgb = np.zeros((h, w, 3), np.float32)
+    noisy = np.zeros((h, w, 3), np.float32)
+    features = np.zeros((h, w, 8), np.float32)
+    variance = np.zeros((h, w), np.float32) if guided else None
+    info = _ffi.RadianceInfo()
+    ms = C.c_double()
+    p = params.abi()
+    f = C.POINTER(C.c_float)
+    check(lib().zrt_render_lens_denoised(view, C.byref(p), C.byref(lens), C.byref(q),
+                                         C.byref(denoise) if denoise is not None else None, 1 if guided else 0, flags,
+                                         rgb.ctypes.data_as(f), noisy.ctypes.data_as(f), features.ctypes.data_as(f),
+                                         variance.ctypes.data_as(f) if guided else None, C.byref(info), C.byref(ms)))
+    return rgb, {"noisy": noisy, "features": features, "variance": variance, "info": info.as_dict(),
+                 "denoise_ms": ms.value}
+
+
 class RenderContext:
     """Device-resident scene (zrt_ctx_*): build + upload once, render many."""
 
@@ -737,6 +779,41 @@ class RenderContext:
         p = params.abi()
         check(lib().zrt_ctx_camera(self._h, C.byref(p), C.byref(lens), C.byref(q), C.c_void_p(dev_sum or None),
                                    C.c_void_p(dev_rgb or None), C.c_void_p(stream or None)))
+
+    def camera_moments(self, params: RenderParams, lens: _ffi.Lens, q: _ffi.CameraQuery, dev_sum: int,
+                       dev_rgb: int = 0, stream: int = 0):
+        """camera() whose sums' fourth lane carries Q, the second moment of the chunk sums
+        (zrt_ctx_camera_moments): what camera_variance() reads."""
+        p = params.abi()
+        check(lib().zrt_ctx_camera_moments(self._h, C.byref(p), C.byref(lens), C.byref(q),
+                                           C.c_void_p(dev_sum or None), C.c_void_p(dev_rgb or None),
+                                           C.c_void_p(stream or None)))
+
+    def camera_features(self, params: RenderParams, lens: _ffi.Lens, r: _ffi.Rect, dev_features: int,
+                        stream: int = 0):
+        """The first-hit features of the rectangle's pixels along the lens' centre rays
+        (zrt_ctx_camera_features; a query): features()' buffer, written inside the rectangle only."""
+        p = params.abi()
+        check(lib().zrt_ctx_camera_features(self._h, C.byref(p), C.byref(lens), C.byref(r),
+                                            C.c_void_p(dev_features or None), C.c_void_p(stream or None)))
+
+    def camera_variance(self, params: RenderParams, r: _ffi.Rect, n_total: int, dev_sum: int, dev_variance: int,
+                        stream: int = 0):
+        """The variance plane (width * height f32, the frame's layout) of camera_moments()' sums
+        after n_total samples per pixel, over the rectangle (zrt_ctx_camera_variance)."""
+        p = params.abi()
+        check(lib().zrt_ctx_camera_variance(self._h, C.byref(p), C.byref(r), n_total, C.c_void_p(dev_sum or None),
+                                            C.c_void_p(dev_variance or None), C.c_void_p(stream or None)))
+
+    def denoise_rect(self, params: RenderParams, dn: _ffi.Denoise, flags: int, r: _ffi.Rect, dev_frame: int,
+                     dev_features: int, dev_variance: int, dev_out: int, dev_out_variance: int = 0, stream: int = 0):
+        """denoise() (dev_variance 0) or denoise_guided() with the rectangle as the filter's
+        domain (zrt_ctx_denoise_rect): taps outside it are skipped, pixels outside it copied."""
+        p = params.abi()
+        check(lib().zrt_ctx_denoise_rect(self._h, C.byref(p), C.byref(dn), flags, C.byref(r),
+                                         C.c_void_p(dev_frame or None), C.c_void_p(dev_features or None),
+                                         C.c_void_p(dev_variance or None), C.c_void_p(dev_out or None),
+                                         C.c_void_p(dev_out_variance or None), C.c_void_p(stream or None)))
 
     def camera_info(self) -> dict:
         """The last camera() call's counters and kernel time (zrt_ctx_camera_info; waits for it)."""

@@ -251,6 +251,10 @@ class CameraQuery(C.Structure):
                 ("reserved", C.c_uint32 * 5)]
 
 
+class Rect(C.Structure):
+    _fields_ = [("x0", C.c_uint32), ("y0", C.c_uint32), ("w", C.c_uint32), ("h", C.c_uint32)]
+
+
 class CameraPlan(C.Structure):
     _fields_ = [("slots", C.c_uint64), ("pixels", C.c_uint64), ("tiles_w", C.c_uint32), ("tiles_h", C.c_uint32),
                 ("radiance", RadiancePlan)]
@@ -371,6 +375,17 @@ SIGNATURES = [
     ("zrt_debug_camera_plan", C.c_int, [C.POINTER(Params), C.POINTER(CameraQuery), C.c_uint32, C.c_uint64,
                                         C.POINTER(CameraPlan)]),
     ("zrt_lens_check", C.c_int, [C.POINTER(Lens)]),
+    ("zrt_rect_check", C.c_int, [C.POINTER(Params), C.POINTER(Rect)]),
+    ("zrt_ctx_camera_features", C.c_int, [_P, C.POINTER(Params), C.POINTER(Lens), C.POINTER(Rect), _P, _P]),
+    ("zrt_ctx_camera_moments", C.c_int, [_P, C.POINTER(Params), C.POINTER(Lens), C.POINTER(CameraQuery), _P, _P,
+                                         _P]),
+    ("zrt_ctx_camera_variance", C.c_int, [_P, C.POINTER(Params), C.POINTER(Rect), C.c_uint32, _P, _P, _P]),
+    ("zrt_ctx_denoise_rect", C.c_int, [_P, C.POINTER(Params), C.POINTER(Denoise), C.c_uint32, C.POINTER(Rect), _P, _P,
+                                       _P, _P, _P, _P]),
+    ("zrt_render_lens_denoised", C.c_int, [C.POINTER(Scene), C.POINTER(Params), C.POINTER(Lens),
+                                           C.POINTER(CameraQuery), C.POINTER(Denoise), C.c_uint32, C.c_uint32,
+                                           C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                           C.POINTER(C.c_float), C.POINTER(RadianceInfo), C.POINTER(C.c_double)]),
     ("zrt_lens_init", C.c_int, [C.c_uint32, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float),
                                 C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.POINTER(Lens)]),
     ("zrt_lens_from_camera", C.c_int, [C.c_uint32, C.POINTER(Camera), C.c_float, C.c_float, C.c_float,

@@ -5,6 +5,9 @@
 // grid, then camera_finish_kernel folding the round's parked chunk sums into the frame's
 // sums.  A camera query is a query (queries.cpp) and shares the radiance query's state
 // (radiance.cpp): rows, parked sums, counters.
+// zrt_ctx_camera_moments is the same launch with Q, the second moment of the chunk sums, kept
+// in sum.w by the finishing kernel; zrt_ctx_camera_features is a query of one lane per slot
+// (lens_features_kernel): the first-hit features along the lens model's centre rays.
 // ZRT_PLAN_ONLY (the host sanitizer build, tools/sanitize): the part that needs no device.
 #include <algorithm>
 #include <cmath>
@@ -134,8 +137,33 @@ int zrt_lens_from_camera(uint32_t kind, const zrt_camera* cam, float aperture, f
 }
 
 #ifndef ZRT_PLAN_ONLY
-int zrt_ctx_camera(zrt_ctx* c, const zrt_params* p, const zrt_lens* lens, const zrt_camera_query* cq, float* dev_sum,
-                   float* dev_rgb, void* hip_stream) {
+namespace {
+// The lens and the rectangle's slots in the kernels' arguments (the sample fields stay the caller's).
+void fill_lens_args(zrt::CameraArgs& g, const zrt_params* p, const zrt_lens* lens, uint32_t x0, uint32_t y0, uint32_t w,
+                    uint32_t h) {
+  g.x0 = x0;
+  g.y0 = y0;
+  g.w = w;
+  g.h = h;
+  g.tiles_w = (w + 7u) / 8u;
+  g.n = g.tiles_w * ((h + 7u) / 8u) * 64u;
+  g.width = p->width;
+  g.kind = lens->kind;
+  g.f_width = float(p->width);
+  g.f_height = float(p->height);
+  g.half_fov = lens->half_fov;
+  zrt::copy3(g.org, lens->origin);
+  zrt::copy3(g.llc, lens->lower_left_corner);
+  zrt::copy3(g.hor, lens->horizontal);
+  zrt::copy3(g.ver, lens->vertical);
+  zrt::copy3(g.au, lens->axis_u);
+  zrt::copy3(g.av, lens->axis_v);
+  zrt::copy3(g.aw, lens->axis_w);
+}
+
+// zrt_ctx_camera, and with moments zrt_ctx_camera_moments: sum.w carries Q.
+int camera_launch(zrt_ctx* c, const zrt_params* p, const zrt_lens* lens, const zrt_camera_query* cq, float* dev_sum,
+                  float* dev_rgb, void* hip_stream, bool with_moments) {
   if (!c) return fail(ZRT_E_INVALID, "null argument");
   zrt_camera_plan cplan;
   int rc = zrt::plan_camera(p, cq, uint32_t(std::max(1, c->cu_count)), zrt::query_env_u64("ZRT_RADIANCE_PARTIAL_CAP"),
@@ -161,26 +189,11 @@ int zrt_ctx_camera(zrt_ctx* c, const zrt_params* p, const zrt_lens* lens, const 
     float4* sum = reinterpret_cast<float4*>(dev_sum);
     zrt::CameraArgs g{};
     g.key_offset = plan.key_offset;
-    g.n = n;
     g.chunk = std::min<uint32_t>(plan.chunk, 65536u);
     g.sample_end = cq->first_sample + cq->n_samples;
-    g.x0 = cq->x0;
-    g.y0 = cq->y0;
-    g.w = cq->w;
-    g.h = cq->h;
-    g.tiles_w = cplan.tiles_w;
-    g.width = p->width;
-    g.kind = lens->kind;
-    g.f_width = float(p->width);
-    g.f_height = float(p->height);
-    g.half_fov = lens->half_fov;
-    zrt::copy3(g.org, lens->origin);
-    zrt::copy3(g.llc, lens->lower_left_corner);
-    zrt::copy3(g.hor, lens->horizontal);
-    zrt::copy3(g.ver, lens->vertical);
-    zrt::copy3(g.au, lens->axis_u);
-    zrt::copy3(g.av, lens->axis_v);
-    zrt::copy3(g.aw, lens->axis_w);
+    fill_lens_args(g, p, lens, cq->x0, cq->y0, cq->w, cq->h);
+    // the call's whole chunks, which go into Q: all of them but a ragged last one
+    const uint32_t moments = with_moments ? 1u : 0u, whole_chunks = cq->n_samples / plan.chunk;
     zrt::launch_query(
         c, p, grid, st, true, "camera query",
         [&](zrt::KArgs& a, const zrt::TracePlan& t, uint32_t launch_grid, hipStream_t s) {
@@ -192,17 +205,63 @@ int zrt_ctx_camera(zrt_ctx* c, const zrt_params* p, const zrt_lens* lens, const 
                                  g.sample0 = sample0;
                                  void* args[] = {&a, &g};
                                  HIPCHK(hipLaunchKernel(kernel, dim3(round_grid), dim3(zrt::kBlock), args, t.lp.bytes, s));
+                                 const uint32_t chunk0 = r * plan.chunks_per_round;
+                                 const uint32_t q_chunks = whole_chunks > chunk0 ? std::min(chunks, whole_chunks - chunk0) : 0u;
                                  HIPCHK(zrt::launch_camera_finish(s, q.partial.p, g, chunks, r == 0 && !accumulate ? 1u : 0u,
-                                                                  sum, nullptr, 0.0f, 0u, q.err.p));
+                                                                  sum, nullptr, 0.0f, 0u, q.err.p, moments, q_chunks));
                                });
         },
         [&](hipStream_t s, const unsigned long long* err) {
-          HIPCHK(zrt::launch_camera_finish(s, q.partial.p, g, 0u, 0u, sum, dev_rgb, scale, 1u, err));
+          HIPCHK(zrt::launch_camera_finish(s, q.partial.p, g, 0u, 0u, sum, dev_rgb, scale, 1u, err, moments, 0u));
           zrt::copy_radiance_counters(c, s);
         },
         p->max_depth);
     q.rq_samples = cplan.pixels * cq->n_samples;
     q.cq_launched = q.rq_launched = true;  // (the two queries share their state: see zrt.h)
+    return ZRT_OK;
+  }
+  ZRT_CATCH_ALL
+}
+}  // namespace
+
+int zrt_ctx_camera(zrt_ctx* c, const zrt_params* p, const zrt_lens* lens, const zrt_camera_query* cq, float* dev_sum,
+                   float* dev_rgb, void* hip_stream) {
+  return camera_launch(c, p, lens, cq, dev_sum, dev_rgb, hip_stream, false);
+}
+
+int zrt_ctx_camera_moments(zrt_ctx* c, const zrt_params* p, const zrt_lens* lens, const zrt_camera_query* cq,
+                           float* dev_sum, float* dev_rgb, void* hip_stream) {
+  return camera_launch(c, p, lens, cq, dev_sum, dev_rgb, hip_stream, true);
+}
+
+// ---- lens features (zrt.h "denoising lens frames"): a query, one lane per slot of the rectangle ----
+int zrt_ctx_camera_features(zrt_ctx* c, const zrt_params* p, const zrt_lens* lens, const zrt_rect* rect,
+                            float* dev_features, void* hip_stream) {
+  if (!c) return fail(ZRT_E_INVALID, "null argument");
+  int rc = zrt::check_rect(p, rect);
+  if (rc) return rc;
+  rc = zrt::check_lens(lens);
+  if (rc) return rc;
+  rc = zrt::params_fit_ctx(c, p);
+  if (rc) return rc;
+  if (!dev_features) return fail(ZRT_E_INVALID, "null argument");
+  if (zrt::ptr_misaligned(dev_features, 16))
+    return fail(ZRT_E_INVALID, "camera features: dev_features must be 16-byte aligned");
+  try {
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t st = zrt::stream_of(c, hip_stream);
+    const uint32_t* sp = zrt::slot_prim_table(c);
+    zrt::CameraArgs g{};
+    fill_lens_args(g, p, lens, rect->x0, rect->y0, rect->w, rect->h);  // (16-bit extents: the slots fit 32 bits)
+    float4* out = reinterpret_cast<float4*>(dev_features);
+    zrt::launch_query(
+        c, p, zrt::query_grid(g.n), st, true, "lens feature query",
+        [&](zrt::KArgs& a, const zrt::TracePlan& t, uint32_t grid, hipStream_t s) {
+          void* args[] = {&a, &g, &sp, &out};
+          HIPCHK(hipLaunchKernel(zrt::lens_features_kernel_ptr(t.kmode, t.stk16), dim3(grid), dim3(zrt::kBlock), args,
+                                 t.lp.bytes, s));
+        },
+        [&](hipStream_t s, const unsigned long long* err) { HIPCHK(zrt::launch_lens_features_error(s, out, g, err)); });
     return ZRT_OK;
   }
   ZRT_CATCH_ALL

@@ -51,6 +51,10 @@
 // traversal), beside any mode above.  pinhole is the scene camera itself over the whole width.
 // The two go together, and the three options only with them: a run that sets any of the five
 // without both ZRT_LENS and ZRT_LENS_OUT is refused before anything is rendered.
+// $ZRT_LENS_DENOISE=plain|guided|demod (with ZRT_LENS and ZRT_LENS_OUT, refused without them):
+// ZRT_LENS_OUT receives the lens frame filtered (zrt_render_lens_denoised over the whole frame) by
+// the default a-trous filter, the default variance-guided filter without, or with, albedo
+// demodulation.  The guided ones need the samples to be two or more whole sample chunks.
 #include <unistd.h>
 
 #include <chrono>
@@ -356,7 +360,10 @@ int main(int argc, char** argv) {
   lens_q.w = width;
   lens_q.h = height;
   lens_q.n_samples = samples;
-  if (lens_name || lens_out || std::getenv("ZRT_APERTURE") || std::getenv("ZRT_FOCUS_DIST") || std::getenv("ZRT_FISHEYE_FOV")) {
+  const char* lens_dn = std::getenv("ZRT_LENS_DENOISE");
+  uint32_t lens_dn_mode = 3;  // 0 plain, 1 guided, 2 guided with demodulation
+  if (lens_name || lens_out || lens_dn || std::getenv("ZRT_APERTURE") || std::getenv("ZRT_FOCUS_DIST") ||
+      std::getenv("ZRT_FISHEYE_FOV")) {
     const char* names[] = {"pinhole", "thin", "ortho", "equirect", "fisheye"};
     uint32_t kind = 5;
     for (uint32_t k = 0; k < 5 && lens_name; ++k)
@@ -370,11 +377,19 @@ int main(int argc, char** argv) {
         opt[k] = std::strtof(e, &end);
         if (end == e || *end != '\0' || !(opt[k] >= 0.0f)) ok = false;
       }
+    if (lens_dn) {
+      const char* modes[] = {"plain", "guided", "demod"};
+      for (uint32_t k = 0; k < 3; ++k)
+        if (std::strcmp(lens_dn, modes[k]) == 0) lens_dn_mode = k;
+      zrt_variance_plan vp;
+      if (lens_dn_mode > 2 || (lens_dn_mode > 0 && zrt_debug_variance_plan(&ao_params, samples, &vp) != ZRT_OK)) ok = false;
+    }
     zrt_camera_plan plan;
     if (!ok || zrt_lens_from_camera(kind, &camera, opt[0], opt[1], opt[2], &lens) != ZRT_OK ||
         zrt_debug_camera_plan(&ao_params, &lens_q, 1, 0, &plan) != ZRT_OK) {
       std::fprintf(stderr, "error: the lens frame needs ZRT_LENS=pinhole|thin|ortho|equirect|fisheye and ZRT_LENS_OUT=<file.png>; "
-                           "ZRT_APERTURE and ZRT_FOCUS_DIST are lengths >= 0, ZRT_FISHEYE_FOV degrees > 0\n");
+                           "ZRT_APERTURE and ZRT_FOCUS_DIST are lengths >= 0, ZRT_FISHEYE_FOV degrees > 0; ZRT_LENS_DENOISE=plain|guided|demod "
+                           "(guided, demod: the samples must be two or more whole sample chunks)\n");
       zrt_scene_free(data);
       return 1;
     }
@@ -518,11 +533,17 @@ int main(int argc, char** argv) {
   if (lens_out && rc == ZRT_OK) {
     std::vector<float> frame(size_t(width) * height * 3);
     zrt_radiance_info info;
-    rc = zrt_render_lens(scene, &ao_params, &lens, &lens_q, nullptr, frame.data(), &info);
+    if (lens_dn)
+      rc = zrt_render_lens_denoised(scene, &ao_params, &lens, &lens_q, nullptr, lens_dn_mode > 0 ? 1u : 0u,
+                                    lens_dn_mode == 2 ? uint32_t(ZRT_DN_DEMODULATE) : 0u, frame.data(), nullptr, nullptr,
+                                    nullptr, &info, nullptr);
+    else
+      rc = zrt_render_lens(scene, &ao_params, &lens, &lens_q, nullptr, frame.data(), &info);
     if (rc == ZRT_OK) rc = zrt_image_write_png(lens_out, frame.data(), width, height);
     if (rc == ZRT_OK)
       std::fprintf(stderr, "  Lens frame:            %s, %ux%u, %u samples per pixel, %llu rays -> %s\n", lens_name,
                    unsigned(width), unsigned(height), lens_q.n_samples, (unsigned long long)info.rays, lens_out);
+    if (rc == ZRT_OK && lens_dn) std::fprintf(stderr, "  Lens frame filter:     %s\n", lens_dn);
   }
   zrt_scene_free(data);
   if (rc != ZRT_OK) {

@@ -14,6 +14,9 @@
 // of the region is read by up to 25 lanes of the block); from step 4 on the
 // taps of one block no longer share pixels with each other's, and are read
 // straight from memory.
+// zrt_ctx_denoise_rect (zrt.h "denoising lens frames") runs the same kernels with a pixel
+// rectangle of the frame as D: the RECT instantiations, whose planes are the rectangle's.
+// The variance plane of a camera query's sums (camera_variance_kernel) lives here too.
 #include "denoise.hpp"
 
 namespace zrt {
@@ -67,24 +70,29 @@ __device__ __forceinline__ void dn_tap(const DnCentre& p, const float4 cq, const
 
 // S = 1, 2: the step, staged through LDS; S = 0: any step, taps from memory.
 // LAST: the iteration writes RGB triples into the output frame.
-template <int S, bool LAST>
+// RECT: D is the rectangle n x ny at (ox, oy) of the frame (zrt_ctx_denoise_rect) and the
+// planes are n x ny; without it D is the square [0, n)^2 and ny, ox, oy are not read - the
+// kernels of zrt_ctx_denoise / zrt_ctx_denoise_guided stay as they were compiled.
+template <int S, bool LAST, bool RECT>
 __global__ void __launch_bounds__(kDnBX* kDnBY)
     atrous_kernel(const float4* __restrict__ cin, const float4* __restrict__ feat, float4* __restrict__ cout,
                   float* __restrict__ out, uint32_t n, uint32_t width, int step, uint32_t terms, float kc,
-                  float inv_n, float inv_a, float inv_z) {
+                  float inv_n, float inv_a, float inv_z, uint32_t ny, uint32_t ox, uint32_t oy) {
   constexpr int RW = kDnBX + 4 * S, RH = kDnBY + 4 * S;
   __shared__ float4 s_c[S ? RW * RH : 1], s_f0[S ? RW * RH : 1], s_f1[S ? RW * RH : 1];
   const int x0 = int(blockIdx.x) * kDnBX, y0 = int(blockIdx.y) * kDnBY;
   const int px = x0 + int(threadIdx.x), py = y0 + int(threadIdx.y);
-  const int ni = int(n);
+  // D = [0, ni) x [0, nj) in the planes' own coordinates; fo: the frame offset of D's origin
+  const int ni = int(n), nj = RECT ? int(ny) : ni;
+  const size_t fo = RECT ? size_t(oy) * width + ox : 0;
   if (S) {
     const int tid = int(threadIdx.y) * kDnBX + int(threadIdx.x);
     for (int i = tid; i < RW * RH; i += kDnBX * kDnBY) {
       const int gx = x0 - 2 * S + i % RW, gy = y0 - 2 * S + i / RW;
       float4 c = make_float4(0.0f, 0.0f, 0.0f, 0.0f), f0 = c, f1 = c;
-      if (gx >= 0 && gx < ni && gy >= 0 && gy < ni) {
+      if (gx >= 0 && gx < ni && gy >= 0 && gy < nj) {
         c = cin[size_t(gy) * n + size_t(gx)];
-        const size_t f = (size_t(gy) * width + size_t(gx)) * 2;
+        const size_t f = (fo + size_t(gy) * width + size_t(gx)) * 2;
         f0 = feat[f];
         f1 = feat[f + 1];
       }
@@ -94,7 +102,7 @@ __global__ void __launch_bounds__(kDnBX* kDnBY)
     }
     __syncthreads();
   }
-  if (px >= ni || py >= ni) return;
+  if (px >= ni || py >= nj) return;
   const int s = S ? S : step;
   DnCentre p;
   if (S) {
@@ -104,7 +112,7 @@ __global__ void __launch_bounds__(kDnBX* kDnBY)
     p.f1 = s_f1[l];
   } else {
     p.c = cin[size_t(py) * n + size_t(px)];
-    const size_t f = (size_t(py) * width + size_t(px)) * 2;
+    const size_t f = (fo + size_t(py) * width + size_t(px)) * 2;
     p.f0 = feat[f];
     p.f1 = feat[f + 1];
   }
@@ -126,7 +134,7 @@ __global__ void __launch_bounds__(kDnBX* kDnBY)
       }
       // (step <= 128 and n <= 65535: no overflow)
       const int qx = px + s * dx, qy = py + s * dy;
-      if (qx < 0 || qx >= ni || qy < 0 || qy >= ni) continue;
+      if (qx < 0 || qx >= ni || qy < 0 || qy >= nj) continue;
       float4 cq, f0q, f1q;
       if (S) {
         const int l = (int(threadIdx.y) + 2 * S + S * dy) * RW + int(threadIdx.x) + 2 * S + S * dx;
@@ -135,7 +143,7 @@ __global__ void __launch_bounds__(kDnBX* kDnBY)
         f1q = s_f1[l];
       } else {
         cq = cin[size_t(qy) * n + size_t(qx)];
-        const size_t f = (size_t(qy) * width + size_t(qx)) * 2;
+        const size_t f = (fo + size_t(qy) * width + size_t(qx)) * 2;
         f0q = feat[f];
         f1q = feat[f + 1];
       }
@@ -144,7 +152,7 @@ __global__ void __launch_bounds__(kDnBX* kDnBY)
   }
   const float r = ar / wsum, g = ag / wsum, b = ab / wsum;
   if (LAST) {
-    float* o = out + (size_t(py) * width + size_t(px)) * 3;
+    float* o = out + (fo + size_t(py) * width + size_t(px)) * 3;
     o[0] = r;
     o[1] = g;
     o[2] = b;
@@ -169,16 +177,17 @@ __global__ void dn_pack_kernel(const float* __restrict__ frame, float4* __restri
   }
 }
 
-template <int S>
+template <int S, bool RECT>
 hipError_t launch_iter(bool last, dim3 grid, hipStream_t st, const float4* cin, const float4* feat, float4* cout,
-                       float* out, const DenoiseLaunch& l, int step, float kc) {
+                       float* out, const DenoiseLaunch& l, int step, float kc, const DenoiseRect& r) {
   const dim3 block(kDnBX, kDnBY);
+  const uint32_t n = RECT ? r.w : l.n;
   if (last)
-    hipLaunchKernelGGL((atrous_kernel<S, true>), grid, block, 0, st, cin, feat, cout, out, l.n, l.width, step, l.terms,
-                       kc, l.inv_n, l.inv_a, l.inv_z);
+    hipLaunchKernelGGL((atrous_kernel<S, true, RECT>), grid, block, 0, st, cin, feat, cout, out, n, l.width, step,
+                       l.terms, kc, l.inv_n, l.inv_a, l.inv_z, r.h, r.x0, r.y0);
   else
-    hipLaunchKernelGGL((atrous_kernel<S, false>), grid, block, 0, st, cin, feat, cout, out, l.n, l.width, step,
-                       l.terms, kc, l.inv_n, l.inv_a, l.inv_z);
+    hipLaunchKernelGGL((atrous_kernel<S, false, RECT>), grid, block, 0, st, cin, feat, cout, out, n, l.width, step,
+                       l.terms, kc, l.inv_n, l.inv_a, l.inv_z, r.h, r.x0, r.y0);
   return hipGetLastError();
 }
 
@@ -228,24 +237,27 @@ __device__ __forceinline__ void dg_tap(const DnCentre& p, float lum_p, float kl,
 
 // S, LAST as atrous_kernel's.  LAST also multiplies the albedo back (demod) and
 // writes the variance to out_var when it is given.
-template <int S, bool LAST>
+template <int S, bool LAST, bool RECT>
 __global__ void __launch_bounds__(kDnBX* kDnBY)
     guided_kernel(const float4* __restrict__ cin, const float4* __restrict__ feat, float4* __restrict__ cout,
                   float* __restrict__ out, float* __restrict__ out_var, uint32_t n, uint32_t width, int step,
-                  uint32_t terms, float sigma_c, float inv_n, float inv_a, float inv_z, uint32_t demod) {
+                  uint32_t terms, float sigma_c, float inv_n, float inv_a, float inv_z, uint32_t demod, uint32_t ny,
+                  uint32_t ox, uint32_t oy) {
   constexpr int RW = kDnBX + 4 * S, RH = kDnBY + 4 * S;
   __shared__ float4 s_c[S ? RW * RH : 1], s_f0[S ? RW * RH : 1], s_f1[S ? RW * RH : 1];
   const int x0 = int(blockIdx.x) * kDnBX, y0 = int(blockIdx.y) * kDnBY;
   const int px = x0 + int(threadIdx.x), py = y0 + int(threadIdx.y);
-  const int ni = int(n);
+  // D = [0, ni) x [0, nj) in the planes' own coordinates; fo: the frame offset of D's origin
+  const int ni = int(n), nj = RECT ? int(ny) : ni;
+  const size_t fo = RECT ? size_t(oy) * width + ox : 0;
   if (S) {
     const int tid = int(threadIdx.y) * kDnBX + int(threadIdx.x);
     for (int i = tid; i < RW * RH; i += kDnBX * kDnBY) {
       const int gx = x0 - 2 * S + i % RW, gy = y0 - 2 * S + i / RW;
       float4 c = make_float4(0.0f, 0.0f, 0.0f, 0.0f), f0 = c, f1 = c;
-      if (gx >= 0 && gx < ni && gy >= 0 && gy < ni) {
+      if (gx >= 0 && gx < ni && gy >= 0 && gy < nj) {
         c = cin[size_t(gy) * n + size_t(gx)];
-        const size_t f = (size_t(gy) * width + size_t(gx)) * 2;
+        const size_t f = (fo + size_t(gy) * width + size_t(gx)) * 2;
         f0 = feat[f];
         f1 = feat[f + 1];
       }
@@ -255,7 +267,7 @@ __global__ void __launch_bounds__(kDnBX* kDnBY)
     }
     __syncthreads();
   }
-  if (px >= ni || py >= ni) return;
+  if (px >= ni || py >= nj) return;
   const int s = S ? S : step;
   const int lc = (int(threadIdx.y) + 2 * S) * RW + int(threadIdx.x) + 2 * S;  // the centre's LDS slot
   DnCentre p;
@@ -265,7 +277,7 @@ __global__ void __launch_bounds__(kDnBX* kDnBY)
     p.f1 = s_f1[lc];
   } else {
     p.c = cin[size_t(py) * n + size_t(px)];
-    const size_t f = (size_t(py) * width + size_t(px)) * 2;
+    const size_t f = (fo + size_t(py) * width + size_t(px)) * 2;
     p.f0 = feat[f];
     p.f1 = feat[f + 1];
   }
@@ -281,7 +293,7 @@ __global__ void __launch_bounds__(kDnBX* kDnBY)
       const float wt = (dx == 0 && dy == 0) ? 0.25f : (dx == 0 || dy == 0) ? 0.125f : 0.0625f;
       const int qx = px + dx, qy = py + dy;
       float v = p.c.w;
-      if ((dx != 0 || dy != 0) && qx >= 0 && qx < ni && qy >= 0 && qy < ni)
+      if ((dx != 0 || dy != 0) && qx >= 0 && qx < ni && qy >= 0 && qy < nj)
         v = S ? s_c[lc + dy * RW + dx].w : reinterpret_cast<const float*>(cin)[(size_t(qy) * n + size_t(qx)) * 4 + 3];
       g = g + v * wt;
     }
@@ -303,7 +315,7 @@ __global__ void __launch_bounds__(kDnBX* kDnBY)
         continue;
       }
       const int qx = px + s * dx, qy = py + s * dy;
-      if (qx < 0 || qx >= ni || qy < 0 || qy >= ni) continue;
+      if (qx < 0 || qx >= ni || qy < 0 || qy >= nj) continue;
       float4 cq, f0q, f1q;
       if (S) {
         const int l = lc + S * dy * RW + S * dx;
@@ -312,7 +324,7 @@ __global__ void __launch_bounds__(kDnBX* kDnBY)
         f1q = s_f1[l];
       } else {
         cq = cin[size_t(qy) * n + size_t(qx)];
-        const size_t f = (size_t(qy) * width + size_t(qx)) * 2;
+        const size_t f = (fo + size_t(qy) * width + size_t(qx)) * 2;
         f0q = feat[f];
         f1q = feat[f + 1];
       }
@@ -328,11 +340,11 @@ __global__ void __launch_bounds__(kDnBX* kDnBY)
       const float am = ((p.f1.x + p.f1.y) + p.f1.z) * (1.0f / 3.0f);
       if (am > kDnAlbedoMin) v = v * (am * am);
     }
-    float* o = out + (size_t(py) * width + size_t(px)) * 3;
+    float* o = out + (fo + size_t(py) * width + size_t(px)) * 3;
     o[0] = r;
     o[1] = gg;
     o[2] = b;
-    if (out_var) out_var[size_t(py) * width + size_t(px)] = v;
+    if (out_var) out_var[fo + size_t(py) * width + size_t(px)] = v;
   } else {
     cout[size_t(py) * n + size_t(px)] = make_float4(r, gg, b, v);
   }
@@ -366,19 +378,67 @@ __global__ void dg_pack_kernel(const float* __restrict__ frame, const float4* __
   }
 }
 
-template <int S>
+template <int S, bool RECT>
 hipError_t launch_guided(bool last, dim3 grid, hipStream_t st, const float4* cin, const float4* feat, float4* cout,
-                         float* out, float* out_var, const DenoiseLaunch& l, int step, float sigma_c, uint32_t demod) {
+                         float* out, float* out_var, const DenoiseLaunch& l, int step, float sigma_c, uint32_t demod,
+                         const DenoiseRect& r) {
   const dim3 block(kDnBX, kDnBY);
+  const uint32_t n = RECT ? r.w : l.n;
   if (last)
-    hipLaunchKernelGGL((guided_kernel<S, true>), grid, block, 0, st, cin, feat, cout, out, out_var, l.n, l.width, step,
-                       l.terms, sigma_c, l.inv_n, l.inv_a, l.inv_z, demod);
+    hipLaunchKernelGGL((guided_kernel<S, true, RECT>), grid, block, 0, st, cin, feat, cout, out, out_var, n, l.width,
+                       step, l.terms, sigma_c, l.inv_n, l.inv_a, l.inv_z, demod, r.h, r.x0, r.y0);
   else
-    hipLaunchKernelGGL((guided_kernel<S, false>), grid, block, 0, st, cin, feat, cout, out, out_var, l.n, l.width,
-                       step, l.terms, sigma_c, l.inv_n, l.inv_a, l.inv_z, demod);
+    hipLaunchKernelGGL((guided_kernel<S, false, RECT>), grid, block, 0, st, cin, feat, cout, out, out_var, n, l.width,
+                       step, l.terms, sigma_c, l.inv_n, l.inv_a, l.inv_z, demod, r.h, r.x0, r.y0);
   return hipGetLastError();
 }
 
+// {C_0, V_0} of a rectangle: dn_pack_kernel / dg_pack_kernel over the whole width x height frame, the
+// pixels of r into the r.w x r.h plane, every other pixel (and its variance) copied to the output.
+// var == nullptr: the plain filter's packing (no variance, no demodulation).
+__global__ void dn_pack_rect_kernel(const float* __restrict__ frame, const float4* __restrict__ feat,
+                                    const float* __restrict__ var, float4* __restrict__ c0, float* __restrict__ out,
+                                    float* __restrict__ out_var, uint32_t width, uint32_t height, DenoiseRect r,
+                                    uint32_t demod) {
+  const size_t i = size_t(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (i >= size_t(width) * height) return;
+  const uint32_t x = uint32_t(i % width), y = uint32_t(i / width);
+  float rr = frame[3 * i], g = frame[3 * i + 1], b = frame[3 * i + 2], v = var ? var[i] : 0.0f;
+  if (x >= r.x0 && x - r.x0 < r.w && y >= r.y0 && y - r.y0 < r.h) {
+    if (demod) {
+      const float4 a = feat[2 * i + 1];
+      if (__float_as_uint(a.w) != 0u) {
+        if (a.x > kDnAlbedoMin) rr = rr / a.x;
+        if (a.y > kDnAlbedoMin) g = g / a.y;
+        if (a.z > kDnAlbedoMin) b = b / a.z;
+        const float am = ((a.x + a.y) + a.z) * (1.0f / 3.0f);
+        if (am > kDnAlbedoMin) v = v / (am * am);
+      }
+    }
+    c0[size_t(y - r.y0) * r.w + (x - r.x0)] = make_float4(rr, g, b, v);
+  } else {
+    out[3 * i] = rr;
+    out[3 * i + 1] = g;
+    out[3 * i + 2] = b;
+    if (out_var) out_var[i] = v;
+  }
+}
+
+// The variance plane of a camera query's sums (zrt_ctx_camera_variance): one lane per pixel of r.
+__global__ void camera_variance_kernel(const float4* __restrict__ sum, float* __restrict__ var, uint32_t width,
+                                       DenoiseRect r, float ik, float sc) {
+  const size_t i = size_t(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (i >= size_t(r.w) * r.h) return;
+  const size_t R = size_t(r.y0 + uint32_t(i / r.w)) * width + (r.x0 + uint32_t(i % r.w));
+  const float4 s = sum[R];
+  const float m = (s.x + s.y) + s.z;
+  const float mean = m * ik;
+  float v = s.w * ik - mean * mean;
+  v = (v > 0.0f || v != v) ? v : 0.0f;  // (as variance_kernel: a NaN stays NaN)
+  var[R] = v * sc;
+}
+
+constexpr DenoiseRect kNoRect{0, 0, 0, 0};
 }  // namespace
 
 hipError_t denoise_guided_enqueue(const DenoiseLaunch& l, float sigma_c, bool demodulate, const float* frame,
@@ -397,9 +457,9 @@ hipError_t denoise_guided_enqueue(const DenoiseLaunch& l, float sigma_c, bool de
   for (uint32_t i = 0; i < l.iterations; ++i) {
     const int step = 1 << i;
     const bool last = i + 1 == l.iterations;
-    e = step == 1   ? launch_guided<1>(last, grid, st, cur, feat, nxt, out, out_var, l, step, sigma_c, demod)
-        : step == 2 ? launch_guided<2>(last, grid, st, cur, feat, nxt, out, out_var, l, step, sigma_c, demod)
-                    : launch_guided<0>(last, grid, st, cur, feat, nxt, out, out_var, l, step, sigma_c, demod);
+    e = step == 1   ? launch_guided<1, false>(last, grid, st, cur, feat, nxt, out, out_var, l, step, sigma_c, demod, kNoRect)
+        : step == 2 ? launch_guided<2, false>(last, grid, st, cur, feat, nxt, out, out_var, l, step, sigma_c, demod, kNoRect)
+                    : launch_guided<0, false>(last, grid, st, cur, feat, nxt, out, out_var, l, step, sigma_c, demod, kNoRect);
     if (e != hipSuccess) return e;
     float4* t = cur;
     cur = nxt;
@@ -423,15 +483,60 @@ hipError_t denoise_enqueue(const DenoiseLaunch& l, const float* frame, const flo
     const int step = 1 << i;
     const float kc = l.inv_c * float(1 << i);  // sigma_color halves every iteration
     const bool last = i + 1 == l.iterations;
-    e = step == 1   ? launch_iter<1>(last, grid, st, cur, feat, nxt, out, l, step, kc)
-        : step == 2 ? launch_iter<2>(last, grid, st, cur, feat, nxt, out, l, step, kc)
-                    : launch_iter<0>(last, grid, st, cur, feat, nxt, out, l, step, kc);
+    e = step == 1   ? launch_iter<1, false>(last, grid, st, cur, feat, nxt, out, l, step, kc, kNoRect)
+        : step == 2 ? launch_iter<2, false>(last, grid, st, cur, feat, nxt, out, l, step, kc, kNoRect)
+                    : launch_iter<0, false>(last, grid, st, cur, feat, nxt, out, l, step, kc, kNoRect);
     if (e != hipSuccess) return e;
     float4* t = cur;
     cur = nxt;
     nxt = t;
   }
   return hipSuccess;
+}
+
+hipError_t denoise_rect_enqueue(const DenoiseLaunch& l, const DenoiseRect& r, uint32_t height, float sigma_c,
+                                bool demodulate, const float* frame, const float4* feat, const float* var, float* out,
+                                float* out_var, float4* buf0, float4* buf1, hipStream_t st) {
+  if (r.w == 0 || r.h == 0 || r.x0 >= l.width || r.w > l.width - r.x0 || r.y0 >= height || r.h > height - r.y0 ||
+      l.iterations == 0 || l.iterations > 8)
+    return hipErrorInvalidValue;
+  const size_t pixels = size_t(l.width) * height;
+  const uint32_t demod = var && demodulate ? 1u : 0u;
+  hipLaunchKernelGGL(dn_pack_rect_kernel, dim3(uint32_t((pixels + 255) / 256)), dim3(256), 0, st, frame, feat, var, buf0,
+                     out, var ? out_var : nullptr, l.width, height, r, demod);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  const dim3 grid((r.w + kDnBX - 1) / kDnBX, (r.h + kDnBY - 1) / kDnBY);
+  float4* cur = buf0;
+  float4* nxt = buf1;
+  for (uint32_t i = 0; i < l.iterations; ++i) {
+    const int step = 1 << i;
+    const bool last = i + 1 == l.iterations;
+    if (var) {
+      e = step == 1   ? launch_guided<1, true>(last, grid, st, cur, feat, nxt, out, out_var, l, step, sigma_c, demod, r)
+          : step == 2 ? launch_guided<2, true>(last, grid, st, cur, feat, nxt, out, out_var, l, step, sigma_c, demod, r)
+                      : launch_guided<0, true>(last, grid, st, cur, feat, nxt, out, out_var, l, step, sigma_c, demod, r);
+    } else {
+      const float kc = l.inv_c * float(1 << i);  // sigma_color halves every iteration
+      e = step == 1   ? launch_iter<1, true>(last, grid, st, cur, feat, nxt, out, l, step, kc, r)
+          : step == 2 ? launch_iter<2, true>(last, grid, st, cur, feat, nxt, out, l, step, kc, r)
+                      : launch_iter<0, true>(last, grid, st, cur, feat, nxt, out, l, step, kc, r);
+    }
+    if (e != hipSuccess) return e;
+    float4* t = cur;
+    cur = nxt;
+    nxt = t;
+  }
+  return hipSuccess;
+}
+
+hipError_t camera_variance_enqueue(const DenoiseRect& r, uint32_t width, float ik, float sc, const float4* sum,
+                                   float* var, hipStream_t st) {
+  const size_t pixels = size_t(r.w) * r.h;
+  if (pixels == 0) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(camera_variance_kernel, dim3(uint32_t((pixels + 255) / 256)), dim3(256), 0, st, sum, var, width, r,
+                     ik, sc);
+  return hipGetLastError();
 }
 
 }  // namespace zrt

@@ -33,4 +33,23 @@ hipError_t denoise_guided_enqueue(const DenoiseLaunch& l, float sigma_c, bool de
                                   const float4* feat, const float* var, float* out, float* out_var, float4* buf0,
                                   float4* buf1, hipStream_t st);
 
+// A pixel rectangle of the frame (zrt_rect): the domain of denoise_rect_enqueue.
+struct DenoiseRect {
+  uint32_t x0, y0, w, h;
+};
+
+// Both filters with D = r (zrt_ctx_denoise_rect).  l: width, iterations, terms and the
+// inverse sigmas (l.n is not read); height: the frame's.  var == nullptr: the plain filter
+// (sigma_c, demodulate and out_var are not read); else the guided one.  frame / out: width *
+// height * 3 floats, feat: width * height * 2 float4, var / out_var: width * height floats;
+// buf0 / buf1: r.w * r.h float4 each.  Pixels outside r are copied to out (and out_var).
+hipError_t denoise_rect_enqueue(const DenoiseLaunch& l, const DenoiseRect& r, uint32_t height, float sigma_c,
+                                bool demodulate, const float* frame, const float4* feat, const float* var, float* out,
+                                float* out_var, float4* buf0, float4* buf1, hipStream_t st);
+
+// The variance plane of a camera query's sums over r (zrt_ctx_camera_variance): sum: width *
+// height float4 {r, g, b, Q}; var: width * height floats, written inside r only.
+hipError_t camera_variance_enqueue(const DenoiseRect& r, uint32_t width, float ik, float sc, const float4* sum,
+                                   float* var, hipStream_t st);
+
 }  // namespace zrt

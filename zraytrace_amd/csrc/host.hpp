@@ -135,6 +135,9 @@ int plan_pass(const zrt_params* p, uint32_t done, uint32_t n_samples, zrt_pass_p
 int plan_adapt(const zrt_params* p, const zrt_adaptive* ad, std::vector<uint32_t>* levels);
 int plan_variance(const zrt_params* p, uint32_t n, zrt_variance_plan* out);
 int plan_denoise(const zrt_params* p, const zrt_denoise* dn, DenoiseLaunch* out);
+int check_rect(const zrt_params* p, const zrt_rect* r);
+int plan_denoise_rect(const zrt_params* p, const zrt_denoise* dn, const zrt_rect* r, DenoiseLaunch* out);
+int plan_camera_variance(const zrt_params* p, const zrt_rect* r, uint32_t n_total, zrt_variance_plan* out);
 int plan_reproject(const zrt_camera* prev, const zrt_params* p, zrt_reproject_plan* out);
 int plan_temporal(const zrt_params* p, const zrt_temporal* tp, TemporalLaunch* out);
 

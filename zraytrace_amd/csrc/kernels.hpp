@@ -271,9 +271,16 @@ hipError_t launch_radiance_finish(hipStream_t st, const float4* partial, uint32_
                                   const unsigned long long* error_flag);
 // zrt_ctx_camera's: launch_radiance_finish over the slots of g (n_items is not read), slot -> pixel; only the
 // rectangle's pixels of sum and rgb (whole-frame buffers indexed by R) are read or written
+// moments (zrt_ctx_camera_moments): sum.w carries Q over the first q_chunks of the round's parked sums
 hipError_t launch_camera_finish(hipStream_t st, const float4* partial, const CameraArgs& g, uint32_t n_chunks,
                                 uint32_t zero_first, float4* sum, float* rgb, float scale, uint32_t final,
-                                const unsigned long long* error_flag);
+                                const unsigned long long* error_flag, uint32_t moments, uint32_t q_chunks);
+// lens_features_kernel<mode, stack width> (zrt_ctx_camera_features): anyhit_kernel's modes; g: the rectangle, its
+// slots (n, tiles_w) and the lens (the sample fields are not read)
+void* lens_features_kernel_ptr(int mode, bool stk16);
+// zrt_ctx_camera_features': NaN in the rectangle's floats behind a launch that set *error_flag
+hipError_t launch_lens_features_error(hipStream_t st, float4* out, const CameraArgs& g,
+                                      const unsigned long long* error_flag);
 hipError_t launch_debug_math(int fn, const float* x, const float* y, float* out, uint32_t n);
 hipError_t launch_debug_division(uint64_t n, unsigned long long* counts);
 hipError_t launch_debug_rng(uint32_t prng, uint64_t key, unsigned long long* out, uint32_t n);

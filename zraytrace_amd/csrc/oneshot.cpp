@@ -488,3 +488,87 @@ int zrt_render_lens(const zrt_scene* scene, const zrt_params* params, const zrt_
   }
   ZRT_CATCH_ALL
 }
+
+// A lens frame through the post chain (zrt.h "denoising lens frames"): the camera query (with
+// moments for the guided filter), lens features, the variance plane and the filter over the
+// query's rectangle, on one context; every device buffer starts zeroed.
+int zrt_render_lens_denoised(const zrt_scene* scene, const zrt_params* params, const zrt_lens* lens,
+                             const zrt_camera_query* query, const zrt_denoise* dn, uint32_t guided, uint32_t flags,
+                             float* out_rgb, float* out_noisy, float* out_features, float* out_variance,
+                             zrt_radiance_info* info, double* denoise_ms) {
+  zrt_camera_plan plan;
+  int rc = zrt::plan_camera(params, query, 1, 0, &plan);  // (refused before any device work)
+  if (rc) return rc;
+  rc = zrt::check_lens(lens);
+  if (rc) return rc;
+  const zrt_rect rect{query->x0, query->y0, query->w, query->h};
+  zrt_denoise d;
+  uint32_t default_flags = 0;
+  if (dn) d = *dn;
+  else if (guided) zrt_denoise_guided_defaults(&d, &default_flags);
+  else zrt_denoise_defaults(&d);
+  zrt::DenoiseLaunch l{};
+  rc = zrt::plan_denoise_rect(params, &d, &rect, &l);
+  if (rc) return rc;
+  if (flags & ~uint32_t(ZRT_DN_DEMODULATE)) return fail(ZRT_E_INVALID, "denoise: unknown flag");
+  if (!guided && flags) return fail(ZRT_E_INVALID, "denoise: flags need the guided filter");
+  if (guided) {
+    zrt_variance_plan vp{};
+    rc = zrt::plan_camera_variance(params, &rect, query->n_samples, &vp);
+    if (rc) return rc;
+  }
+  if (!out_rgb) return fail(ZRT_E_INVALID, "null argument");
+  rc = zrt::validate_scene(scene);
+  if (rc) return rc;
+  rc = zrt::check_device(int(params->device));
+  if (rc) return rc;
+  try {
+    const bool use_bvh = params->bounded_volume_hierarchy != 0 && scene->n_prims > 10;
+    zrt::HostScene h;
+    zrt::flatten_for_device(&h, scene, use_bvh, int(params->device));
+    std::unique_ptr<zrt_ctx> ctx = zrt::ctx_on_device(h, int(params->device));
+    zrt_ctx* c = ctx.get();
+    const uint64_t n = uint64_t(params->width) * params->height;  // whole-frame buffers
+    zrt::DevBuf<float> d_rgb, d_feat, d_var, d_out;
+    zrt::DevBuf<float4> d_sum;
+    d_sum.alloc(n);
+    d_rgb.alloc(3ull * n);
+    d_feat.alloc(8ull * n);
+    d_out.alloc(3ull * n);
+    HIPCHK(hipMemset(d_sum.p, 0, sizeof(float4) * n));
+    HIPCHK(hipMemset(d_rgb.p, 0, sizeof(float) * 3ull * n));
+    HIPCHK(hipMemset(d_feat.p, 0, sizeof(float) * 8ull * n));
+    if (guided) {
+      d_var.alloc(n);
+      HIPCHK(hipMemset(d_var.p, 0, sizeof(float) * n));
+    }
+    float* sum = reinterpret_cast<float*>(d_sum.p);
+    rc = guided ? zrt_ctx_camera_moments(c, params, lens, query, sum, d_rgb.p, nullptr)
+                : zrt_ctx_camera(c, params, lens, query, sum, d_rgb.p, nullptr);
+    if (rc) return rc;
+    rc = zrt_ctx_sync(c);  // (a device error of the query; one query is in flight per context)
+    if (rc) return rc;
+    if (info) {
+      rc = zrt_ctx_camera_info(c, info);
+      if (rc) return rc;
+    }
+    rc = zrt_ctx_camera_features(c, params, lens, &rect, d_feat.p, nullptr);
+    if (rc) return rc;
+    if (guided) {
+      rc = zrt_ctx_camera_variance(c, params, &rect, query->n_samples, sum, d_var.p, nullptr);
+      if (rc) return rc;
+    }
+    rc = zrt_ctx_denoise_rect(c, params, &d, flags, &rect, d_rgb.p, d_feat.p, guided ? d_var.p : nullptr, d_out.p,
+                              nullptr, nullptr);
+    if (rc) return rc;
+    HIPCHK(hipStreamSynchronize(c->stream));
+    rc = zrt_ctx_sync(c);  // (the feature launch's device error)
+    if (rc) return rc;
+    HIPCHK(hipMemcpy(out_rgb, d_out.p, sizeof(float) * 3ull * n, hipMemcpyDeviceToHost));
+    if (out_noisy) HIPCHK(hipMemcpy(out_noisy, d_rgb.p, sizeof(float) * 3ull * n, hipMemcpyDeviceToHost));
+    if (out_features) HIPCHK(hipMemcpy(out_features, d_feat.p, sizeof(float) * 8ull * n, hipMemcpyDeviceToHost));
+    if (guided && out_variance) HIPCHK(hipMemcpy(out_variance, d_var.p, sizeof(float) * n, hipMemcpyDeviceToHost));
+    return denoise_ms ? zrt_ctx_denoise_ms(c, denoise_ms) : ZRT_OK;
+  }
+  ZRT_CATCH_ALL
+}

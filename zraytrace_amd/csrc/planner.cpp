@@ -458,11 +458,8 @@ int plan_variance(const zrt_params* p, uint32_t n, zrt_variance_plan* out) {
   return ZRT_OK;
 }
 
-// What zrt_ctx_denoise refuses of a zrt_denoise, and the launch it asks for otherwise.
-int plan_denoise(const zrt_params* p, const zrt_denoise* dn, DenoiseLaunch* out) {
-  if (!dn) return fail(ZRT_E_INVALID, "denoise is null");
-  int rc = validate_params(p);
-  if (rc) return rc;
+// What the filters refuse of a zrt_denoise (after their params), and the launch's settings otherwise.
+static int denoise_settings(const zrt_denoise* dn, DenoiseLaunch* out) {
   if (dn->iterations > 8) return fail(ZRT_E_INVALID, "denoise iterations must be <= 8");
   const float sg[4] = {dn->sigma_color, dn->sigma_normal, dn->sigma_albedo, dn->sigma_depth};
   const char* names[4] = {"sigma_color", "sigma_normal", "sigma_albedo", "sigma_depth"};
@@ -476,8 +473,6 @@ int plan_denoise(const zrt_params* p, const zrt_denoise* dn, DenoiseLaunch* out)
       inv[k] = 1.0f / sg[k];
     }
   }
-  out->width = p->width;
-  out->n = p->height;
   out->iterations = dn->iterations ? dn->iterations : ZRT_DEFAULT_DENOISE_ITERATIONS;
   out->terms = terms;
   out->inv_c = inv[0];
@@ -485,6 +480,55 @@ int plan_denoise(const zrt_params* p, const zrt_denoise* dn, DenoiseLaunch* out)
   out->inv_a = inv[2];
   out->inv_z = inv[3];
   return ZRT_OK;
+}
+
+// What zrt_ctx_denoise refuses of a zrt_denoise, and the launch it asks for otherwise.
+int plan_denoise(const zrt_params* p, const zrt_denoise* dn, DenoiseLaunch* out) {
+  if (!dn) return fail(ZRT_E_INVALID, "denoise is null");
+  int rc = validate_params(p);
+  if (rc) return rc;
+  rc = denoise_settings(dn, out);
+  if (rc) return rc;
+  out->width = p->width;
+  out->n = p->height;
+  return ZRT_OK;
+}
+
+// zrt_rect_check (zrt.h "denoising lens frames"): the frame as the camera query takes it - the
+// whole width, height > width allowed - and a rectangle inside it.
+int check_rect(const zrt_params* p, const zrt_rect* r) {
+  if (!p || !r) return fail(ZRT_E_INVALID, "null argument");
+  if (p->width == 0 || p->height == 0 || p->width > 65535 || p->height > 65535)
+    return fail(ZRT_E_INVALID, "camera: width and height must be 1 .. 65535");
+  if (p->traversal > ZRT_TRAVERSAL_BINARY) return fail(ZRT_E_INVALID, "unknown traversal");
+  if (p->prng > ZRT_PRNG_XOSHIRO256) return fail(ZRT_E_INVALID, "unknown prng");
+  if (r->w == 0 || r->h == 0) return fail(ZRT_E_INVALID, "camera: the rectangle is empty");
+  if (r->x0 >= p->width || r->w > p->width - r->x0 || r->y0 >= p->height || r->h > p->height - r->y0)
+    return fail(ZRT_E_INVALID, "camera: the rectangle leaves the frame");
+  return ZRT_OK;
+}
+
+// zrt_ctx_denoise_rect's refusals that need no context, and its launch: plan_denoise without
+// raytrace.zig:168's square (l->n is not used; the rectangle is the domain).
+int plan_denoise_rect(const zrt_params* p, const zrt_denoise* dn, const zrt_rect* r, DenoiseLaunch* out) {
+  if (!dn) return fail(ZRT_E_INVALID, "denoise is null");
+  int rc = check_rect(p, r);
+  if (rc) return rc;
+  rc = denoise_settings(dn, out);
+  if (rc) return rc;
+  out->width = p->width;
+  out->n = 0;
+  return ZRT_OK;
+}
+
+// zrt_ctx_camera_variance's plan: plan_variance's (k, ik, sc) and refusals of (sample_chunk,
+// n_total); the frame's extents are check_rect's business (a lens frame may be taller than wide).
+int plan_camera_variance(const zrt_params* p, const zrt_rect* r, uint32_t n_total, zrt_variance_plan* out) {
+  int rc = check_rect(p, r);
+  if (rc) return rc;
+  zrt_params q = *p;
+  q.width = q.height = q.samples_per_pixel = 1;
+  return plan_variance(&q, n_total, out);
 }
 
 // The reprojection plan of a previous camera (zrt.h "temporal accumulation";
@@ -553,3 +597,5 @@ int plan_temporal(const zrt_params* p, const zrt_temporal* tp, TemporalLaunch* o
   return ZRT_OK;
 }
 }  // namespace zrt
+
+int zrt_rect_check(const zrt_params* params, const zrt_rect* rect) { return zrt::check_rect(params, rect); }

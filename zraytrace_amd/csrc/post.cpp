@@ -1,6 +1,7 @@
 // post.cpp - what a context does with a rendered frame: the first-hit feature
 // buffers (zrt_ctx_features), the two denoisers and the temporal step, with their
-// default values.  The kernels: render.hip, denoise.hip, temporal.hip.
+// default values; for lens frames the variance plane of a camera query's sums and both
+// denoisers on a rectangle.  The kernels: render.hip, denoise.hip, temporal.hip.
 #include <cstring>
 
 #include "context.hpp"
@@ -161,6 +162,59 @@ int zrt_ctx_denoise_guided(zrt_ctx* c, const zrt_params* p, const zrt_denoise* d
                                        reinterpret_cast<const float4*>(dev_features), dev_variance, dev_out,
                                        dev_out_variance, b0, b1, st));
   });
+}
+
+// ---- lens frames (zrt.h "denoising lens frames"): the variance plane of a camera query's
+// sums, and both filters with a rectangle as their domain ----
+int zrt_ctx_camera_variance(zrt_ctx* c, const zrt_params* p, const zrt_rect* rect, uint32_t n_total,
+                            const float* dev_sum, float* dev_variance, void* hip_stream) {
+  zrt_variance_plan vp{};
+  int rc = zrt::plan_camera_variance(p, rect, n_total, &vp);  // (the refusals that need no context come first)
+  if (rc) return rc;
+  if (!c || !dev_sum || !dev_variance) return fail(ZRT_E_INVALID, "null argument");
+  if (reinterpret_cast<uintptr_t>(dev_sum) & 15u)
+    return fail(ZRT_E_INVALID, "camera variance: dev_sum must be 16-byte aligned");
+  if (reinterpret_cast<uintptr_t>(dev_variance) & 3u)
+    return fail(ZRT_E_INVALID, "camera variance: dev_variance must be 4-byte aligned");
+  if (int(p->device) != c->device)
+    return fail(ZRT_E_INVALID, "params->device differs from the device the context was created on");
+  try {
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t st = zrt::stream_of(c, hip_stream);
+    const zrt::DenoiseRect r{rect->x0, rect->y0, rect->w, rect->h};
+    HIPCHK(zrt::camera_variance_enqueue(r, p->width, vp.ik, vp.sc, reinterpret_cast<const float4*>(dev_sum),
+                                        dev_variance, st));
+    return ZRT_OK;
+  }
+  ZRT_CATCH_ALL
+}
+
+int zrt_ctx_denoise_rect(zrt_ctx* c, const zrt_params* p, const zrt_denoise* dn, uint32_t flags, const zrt_rect* rect,
+                         const float* dev_frame, const float* dev_features, const float* dev_variance, float* dev_out,
+                         float* dev_out_variance, void* hip_stream) {
+  zrt::DenoiseLaunch l{};
+  int rc = zrt::plan_denoise_rect(p, dn, rect, &l);  // (the refusals that need no context come first)
+  if (rc) return rc;
+  const bool guided = dev_variance != nullptr;
+  if (flags & ~uint32_t(ZRT_DN_DEMODULATE)) return fail(ZRT_E_INVALID, "denoise: unknown flag");
+  if (!guided && flags) return fail(ZRT_E_INVALID, "denoise: flags need a variance plane (dev_variance is null)");
+  if (!guided && dev_out_variance)
+    return fail(ZRT_E_INVALID, "denoise: dev_out_variance needs a variance plane (dev_variance is null)");
+  rc = check_post_args("denoise", c, p, dev_frame, dev_features, dev_out, guided, dev_variance, dev_out_variance);
+  if (rc) return rc;
+  try {
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t st = zrt::stream_of(c, hip_stream);
+    const zrt::DenoiseRect r{rect->x0, rect->y0, rect->w, rect->h};
+    for (zrt::DevBuf<float4>& b : c->dn.buf) b.grow(size_t(r.w) * r.h);
+    timed_step(c->dn.timer, st, [&] {
+      HIPCHK(zrt::denoise_rect_enqueue(l, r, p->height, dn->sigma_color, (flags & ZRT_DN_DEMODULATE) != 0, dev_frame,
+                                       reinterpret_cast<const float4*>(dev_features), dev_variance, dev_out,
+                                       dev_out_variance, c->dn.buf[0].p, c->dn.buf[1].p, st));
+    });
+    return ZRT_OK;
+  }
+  ZRT_CATCH_ALL
 }
 
 int zrt_ctx_denoise_ms(zrt_ctx* c, double* ms) {

@@ -3816,6 +3816,100 @@ __global__ void features_error_kernel(float4* __restrict__ out, uint64_t n_f4,
     out[i] = make_float4(q, q, q, q);
 }
 
+// First-hit feature buffers along lens rays (zrt_ctx_camera_features): features_kernel's hit
+// and outputs for the centre ray of a camera query's lens model, one lane per slot of the
+// rectangle (camera_kernel's slots: 8 x 8 tiles anchored at (x0, y0)).  The centre ray is the
+// query's sample ray at r1 = r2 = 0.5, where ((float)x + 0.5f) - 0.5f = (float)x exactly; the
+// thin lens is taken at its centre.  g.kind is a kernel argument: the switch is a scalar branch.
+// Pixels outside the rectangle are not touched.
+template <int MODE, class StackT>
+__global__ void __launch_bounds__(kBlock) lens_features_kernel(const KArgs a, const CameraArgs g,
+                                                               const uint32_t* __restrict__ slot_prim,
+                                                               float4* __restrict__ out) {
+  extern __shared__ __attribute__((aligned(16))) char lds_raw[];
+  StackT* stk = reinterpret_cast<StackT*>(lds_raw) + threadIdx.x;
+  float4* lds_top = reinterpret_cast<float4*>(lds_raw + a.lds_top_off);
+  if (MODE == 3 && !layout_ok(a)) return;
+  if (MODE == 3) fill_lds_top(a, lds_top);
+  const uint32_t gl = blockIdx.x * kBlock + threadIdx.x;
+  if (gl >= g.n) return;
+  const uint32_t tile = gl >> 6, p = gl & 63u;
+  const uint32_t ty = tile / g.tiles_w, tx = tile - ty * g.tiles_w;
+  const uint32_t lx = tx * 8u + (p & 7u), ly = ty * 8u + (p >> 3);
+  if (lx >= g.w || ly >= g.h) return;  // a slot outside the rectangle
+  const uint32_t px = g.x0 + lx, py = g.y0 + ly;
+  float4* dst = out + 2ull * ((uint64_t)py * g.width + px);
+  const float u = (float)px / g.f_width;  // IEEE `/`, as features_kernel
+  const float v = (float)py / g.f_height;
+  const V3 org = mk(g.org[0], g.org[1], g.org[2]);
+  const V3 aw = mk(g.aw[0], g.aw[1], g.aw[2]);
+  V3 o = org, tgt;
+  if (g.kind == ZRT_LENS_EQUIRECT) {
+    float sp, cp, st, ct;
+    dev::sincos_z(kTwoPi * u, &sp, &cp);
+    dev::sincos_z(3.1415927f * v, &st, &ct);
+    tgt = add(o, mk(st * cp, -ct, st * sp));
+  } else if (g.kind == ZRT_LENS_FISHEYE) {
+    const V3 au = mk(g.au[0], g.au[1], g.au[2]);
+    const V3 av = mk(g.av[0], g.av[1], g.av[2]);
+    const float qx = 2.0f * u - 1.0f, qy = 2.0f * v - 1.0f;
+    const float r = dev::sqrt_rn(qx * qx + qy * qy);
+    V3 dd = aw;
+    if (r != 0.0f) {
+      float sn, cs;
+      dev::sincos_z(r * g.half_fov, &sn, &cs);
+      const float k = dev::div_rn(sn, r);
+      dd = add(add(scale(au, qx * k), scale(av, qy * k)), scale(aw, cs));
+    }
+    tgt = add(o, dd);
+  } else {  // the view plane: Camera.getRay's point (camera.zig:47-49)
+    const V3 llc = mk(g.llc[0], g.llc[1], g.llc[2]);
+    const V3 hor = mk(g.hor[0], g.hor[1], g.hor[2]);
+    const V3 ver = mk(g.ver[0], g.ver[1], g.ver[2]);
+    const V3 P = add(add(llc, scale(hor, u)), scale(ver, v));
+    if (g.kind == ZRT_LENS_ORTHO) {
+      o = P;
+      tgt = add(o, aw);
+    } else {  // pinhole; the thin lens at its centre
+      tgt = P;
+    }
+  }
+  const V3 d = unit(sub(tgt, o));
+  float best_t;
+  int best;
+  closest_hit<MODE, StackT>(a, o, d, stk, lds_top, gl, best_t, best);
+  if (best < 0) {
+    const V3 bg = background(d);
+    dst[0] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    dst[1] = make_float4(bg.x, bg.y, bg.z, 0.0f);
+    return;
+  }
+  uint32_t c_shade = 0, c_tex = 0;
+  Coh coh;
+  HitRec h;
+  hit_record<false, false>(a, a.mats, best, best_t, o, d, c_shade, c_tex, coh, h);
+  const uint32_t code = h.mkind == ZRT_MAT_DIELECTRIC ? kAttOne : albedo_code<false>(h.mat, h.tag & 0x7fffffffu, h.tu, h.tv);
+  const V3 alb = att_value<false>(a, a.mats, code);
+  dst[0] = make_float4(h.normal.x, h.normal.y, h.normal.z, best_t);
+  dst[1] = make_float4(alb.x, alb.y, alb.z, __uint_as_float(slot_prim[best] + 1u));
+}
+
+// Behind lens_features_kernel: a launch that set its error flag leaves NaN in the rectangle.
+__global__ void lens_features_error_kernel(float4* __restrict__ out, const CameraArgs g,
+                                           const unsigned long long* __restrict__ error_flag) {
+  if (*error_flag == 0ull) return;
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= g.n) return;
+  const uint32_t tile = i >> 6, l = i & 63u;
+  const uint32_t ty = tile / g.tiles_w, tx = tile - ty * g.tiles_w;
+  const uint32_t lx = tx * 8u + (l & 7u), ly = ty * 8u + (l >> 3);
+  if (lx >= g.w || ly >= g.h) return;
+  const float q = __builtin_nanf("");
+  float4* dst = out + 2ull * ((uint64_t)(g.y0 + ly) * g.width + (g.x0 + lx));
+  dst[0] = make_float4(q, q, q, q);
+  dst[1] = make_float4(q, q, q, q);
+}
+
 // Per-pixel sum of the chunk sums in chunk order, times 1/spp
 // (raytrace.zig:182), into the rank's tile-major output.  A launch that set the
 // device error flag (a traversal stack overflow) leaves NaN in every pixel, so
@@ -4524,9 +4618,14 @@ __global__ void __launch_bounds__(kBlock, MODE == 3 ? 4 : 1) camera_kernel(const
 // Behind camera_kernel, one lane per slot: radiance_finish_kernel with the slot mapped to
 // its pixel.  sum and rgb are whole-frame buffers indexed by R = y * width + x; a slot
 // outside the rectangle reads and writes nothing, so the frame's other pixels stay.
+// moments (zrt_ctx_camera_moments; block-uniform): sum[R].w is Q, accumulate_kernel's second
+// moment - per parked sum S_j of the round's first q_chunks (all but a ragged last one), l =
+// (S_j.r + S_j.g) + S_j.b, Q = Q + l * l, in chunk order, from 0 where zero_first, else from
+// sum[R].w; NaN after a device error.  Without it .w is written 0, as before.
 __global__ void camera_finish_kernel(const float4* __restrict__ partial, const CameraArgs g, uint32_t n_chunks,
                                      uint32_t zero_first, float4* __restrict__ sum, float* __restrict__ rgb,
-                                     float scale, uint32_t final, const unsigned long long* __restrict__ error_flag) {
+                                     float scale, uint32_t final, const unsigned long long* __restrict__ error_flag,
+                                     uint32_t moments, uint32_t q_chunks) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= g.n) return;
   const uint32_t tile = i >> 6, l = i & 63u;
@@ -4535,14 +4634,22 @@ __global__ void camera_finish_kernel(const float4* __restrict__ partial, const C
   if (lx >= g.w || ly >= g.h) return;
   const uint64_t R = (uint64_t)(g.y0 + ly) * g.width + (g.x0 + lx);
   float4 s = zero_first ? make_float4(0.0f, 0.0f, 0.0f, 0.0f) : sum[R];
+  float q = moments ? s.w : 0.0f;
   for (uint32_t j = 0; j < n_chunks; ++j) {
     const float4 p = partial[(uint64_t)j * g.n + i];
     s.x += p.x;
     s.y += p.y;
     s.z += p.z;
+    if (moments && j < q_chunks) {  // (a ragged last chunk is left out of the second moment)
+      const float lum = (p.x + p.y) + p.z;
+      q = q + lum * lum;
+    }
   }
-  if (final && *error_flag != 0ull) s.x = s.y = s.z = __builtin_nanf("");
-  sum[R] = make_float4(s.x, s.y, s.z, 0.0f);
+  if (final && *error_flag != 0ull) {
+    s.x = s.y = s.z = __builtin_nanf("");
+    if (moments) q = __builtin_nanf("");
+  }
+  sum[R] = make_float4(s.x, s.y, s.z, q);
   if (final && rgb) {
     rgb[3ull * R + 0] = s.x * scale;
     rgb[3ull * R + 1] = s.y * scale;
@@ -4780,9 +4887,25 @@ void* camera_kernel_ptr(int mode, uint32_t prng, bool stk16) {
 }
 hipError_t launch_camera_finish(hipStream_t st, const float4* partial, const CameraArgs& g, uint32_t n_chunks,
                                 uint32_t zero_first, float4* sum, float* rgb, float scale, uint32_t final,
-                                const unsigned long long* error_flag) {
+                                const unsigned long long* error_flag, uint32_t moments, uint32_t q_chunks) {
   return launch(camera_finish_kernel, uint32_t((uint64_t(g.n) + 255) / 256), 256, st, partial, g, n_chunks, zero_first,
-                sum, rgb, scale, final, error_flag);
+                sum, rgb, scale, final, error_flag, moments, q_chunks);
+}
+// Lens features (camera_query.cpp), after the camera query's: lens_features_kernel by anyhit_kernel's modes.
+void* lens_features_kernel_ptr(int mode, bool stk16) {
+#ifdef ZRT_ISA_KERNEL
+  (void)mode; (void)stk16;
+  return nullptr;
+#else
+#define ZRT_LF(M) (stk16 ? reinterpret_cast<void*>(&lens_features_kernel<M, uint16_t>) \
+                         : reinterpret_cast<void*>(&lens_features_kernel<M, uint32_t>))
+  return mode == 0 ? ZRT_LF(0) : mode == 1 ? ZRT_LF(1) : mode == 2 ? ZRT_LF(2) : ZRT_LF(3);
+#undef ZRT_LF
+#endif
+}
+hipError_t launch_lens_features_error(hipStream_t st, float4* out, const CameraArgs& g,
+                                      const unsigned long long* error_flag) {
+  return launch(lens_features_error_kernel, uint32_t((uint64_t(g.n) + 255) / 256), 256, st, out, g, error_flag);
 }
 
 const KernelConfig& kernel_config() {
