@@ -195,7 +195,18 @@ enum { ZRT_DEFAULT_SAMPLE_CHUNK = 32u };
  * primary ray can hit anything in (zrt_debug_tile_classes) render in a kernel of
  * their own without traversal; the frame and the counters are the same bit for bit.
  * The classes are kept under the same key as the order; classifying counts into
- * schedule_ms of a launch that probes.  ZRT_SKY_TILES=0 turns the split off (A/B). */
+ * schedule_ms of a launch that probes.  ZRT_SKY_TILES=0 turns the split off (A/B).
+ * One-sphere tiles (the same launches, where the scene and the params also allow the
+ * lean kernel - solid-colour Lambertian and metal materials, no ZRT_FLAG_SCANLINES;
+ * with or without ZRT_FLAG_STATS): the tiles the host proves no primary ray can hit
+ * anything in but one sphere whose leaf is a child of the wide tree's root render in
+ * an instance of the lockstep kernel whose camera rays test that sphere alone instead
+ * of walking the tree; every later ray of a path is traced as before, and the frame
+ * and the counters are the same bit for bit (STATS counts such a ray as one ray and one
+ * sphere test, no node visit).  Where a frame has such tiles for several spheres, those of
+ * the sphere with the most are taken.  ZRT_SPHERE_TILES=0 leaves them general (A/B);
+ * ZRT_SPHERE_TILES=2 sends their list through a launch of the unchanged render kernel (what
+ * they cost there); either needs the all-sky split on. */
 
 /* ZRT_FLAG_GUARD (FAST traversal): the grazing-triangle guard (DESIGN.md
  * section 3 "Triangles"): every box is widened by the reach of the rounded
@@ -1581,14 +1592,29 @@ int zrt_debug_octant_offsets(uint32_t stride_f4, uint32_t n_top, uint32_t node_f
  * lockstep FAST loop with max_depth >= 1, without ZRT_FLAG_SCANLINES and
  * ZRT_FLAG_GUARD, from a camera inside the scene's ray-origin bound, over a scene
  * with no non-finite plane; and when the environment says ZRT_SKY_TILES=0.
+ * ZRT_TILE_ONE_SPHERE | s for a tile no primary ray of which can return a hit from any
+ * primitive but the sphere in device primitive slot s (a ray of the tile may hit s or
+ * nothing); every one-sphere tile of a call carries the same s.  Only where, besides
+ * the conditions above, the launch is lean-eligible (zrt_debug_lean_kernel's conditions
+ * but for ZRT_FLAG_STATS), the sphere's leaf is a child of the wide tree's root, and the
+ * environment does not say ZRT_SPHERE_TILES=0.  Test (word & ZRT_TILE_SKY) == 0 &&
+ * (word & ZRT_TILE_ONE_SPHERE) != 0.
  * margins (4 doubles, or NULL): the largest distance past a sphere's surface and past
  * a triangle at which the classifier still counts a ray as a possible hit, and the
  * triangles' two coefficients (reach = k_ao |ao| + k_c).  n_sky: the rank's sky tiles.
- * zrt_ctx_debug_counters slot 47 of a context's last launch holds the same count.
+ * zrt_ctx_debug_counters slot 47 of a context's last launch holds the same count,
+ * slot 46 the tiles it rendered as one-sphere.
  * (tests only) */
 #define ZRT_TILE_SKY 0x80000000u
+#define ZRT_TILE_ONE_SPHERE 0x40000000u
 int zrt_debug_tile_classes(const zrt_scene* scene, const zrt_camera* camera, const zrt_params* params,
                            uint32_t* classes, uint32_t cap, uint32_t* n_tiles, uint32_t* n_sky, double* margins);
+/* The list index (zrt_scene::prims) of the primitive in each device primitive slot, as
+ * zrt_ctx_create flattens the scene under these params, with no device: prims[slot] for
+ * slot < *n_slots (at most cap words are written).  The slot in a ZRT_TILE_ONE_SPHERE class
+ * word is such a slot.  (tests only) */
+int zrt_debug_slot_prims(const zrt_scene* scene, const zrt_params* params, uint32_t* prims, uint32_t cap,
+                         uint32_t* n_slots);
 
 #ifdef __cplusplus
 }

@@ -4,7 +4,9 @@ usage: python tools/pmc_summary.py <gpurun_out/TAG>   (prints the entry as JSON)
 
 Reads <dir>/pmcN/run_counter_collection.csv (one rocprofv3 --pmc pass each),
 keeps the timed kernel flavour (render_kernel<MODE, PRNG, false, ...>: no
-diagnostic counters; the one-step run launches it once), and writes per launch:
+diagnostic counters; the one-step run launches it once - or twice, the one-sphere
+instance <..., true, true> over its tiles and the general one over the rest: their
+counts and durations are summed), and writes per launch:
   hbm_bytes_per_launch = (2 * FETCH_SIZE + WRITE_SIZE) * 1 KiB (gfx950 FETCH_SIZE
       counts half the bytes of wide reads: MI355X_MICROARCH.md §HBM),
   sq    - the SQ instruction counters and valu_lane_util
@@ -32,13 +34,18 @@ def main():
     for csvp in sorted(glob.glob(os.path.join(d, "pmc*", "run_counter_collection.csv"))):
         for r in rows(csvp):
             name = r["Kernel_Name"]
-            if "zrt::render_kernel<" not in name or ", false," not in name:
-                continue  # the timed flavour only (the STATS flavour has `true`)
+            if "zrt::render_kernel<" not in name:
+                continue
+            targs = [x.strip() for x in name.split("<", 1)[1].split(">")[0].split(",")]
+            if targs[2] != "false":
+                continue  # the timed flavour only (the STATS flavour's third argument is `true`)
             names.add(name.split("(")[0])
             c = r["Counter_Name"]
             counters[c] = counters.get(c, 0.0) + float(r["Counter_Value"])
-            durations.setdefault(os.path.dirname(csvp), int(r["End_Timestamp"]) - int(r["Start_Timestamp"]))
-    assert len(names) == 1, names
+            durations.setdefault(os.path.dirname(csvp), {})[r["Dispatch_Id"]] = int(r["End_Timestamp"]) - int(r["Start_Timestamp"])
+    durations = {k: sum(v.values()) for k, v in durations.items()}
+    # one kernel, or the general one and its one-sphere sibling
+    assert len(names) == 1 or (len(names) == 2 and any(n.endswith("true, true>") for n in names)), names
     with open(os.path.join(d, "pmc1.json")) as f:
         bench = json.loads(f.read().strip().splitlines()[-1])
     cfg = {k: bench["config"][k] for k in ("scene", "width", "height", "spp", "max_depth", "traversal", "sample_chunk")}
@@ -46,7 +53,7 @@ def main():
     if sq.get("SQ_ACTIVE_INST_VALU"):
         sq["valu_lane_util"] = round(sq["SQ_THREAD_CYCLES_VALU"] / (64.0 * sq["SQ_ACTIVE_INST_VALU"]), 4)
     cache = {k: v for k, v in counters.items() if k.startswith(("TCP_", "TCC_", "TA_", "TD_", "GRBM_"))}
-    entry = {"config": cfg, "build_id": bench.get("build_id"), "kernel": names.pop(),
+    entry = {"config": cfg, "build_id": bench.get("build_id"), "kernel": " + ".join(sorted(names)),
              "hbm_bytes_per_launch": int((2 * counters["FETCH_SIZE"] + counters["WRITE_SIZE"]) * 1024),
              "fetch_size_kb": counters["FETCH_SIZE"], "write_size_kb": counters["WRITE_SIZE"],
              "duration_ns_per_pass": sorted(durations.values()),

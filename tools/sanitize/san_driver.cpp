@@ -197,6 +197,17 @@ static void one_scene(uint32_t index, const std::string& assets, const std::stri
           double margins[4];
           rc = zrt_debug_tile_classes(s, &cam, &q, cls.data(), uint32_t(cls.size()), &n_tiles, &n_sky, margins);
           CHECK(rc == ZRT_OK && n_sky <= n_tiles, "scene %u tile classes: %s", index, zrt_last_error());
+          // the one-sphere class: one sphere per call, never on a sky tile, none where the launch is not eligible
+          uint32_t n_one = 0, word = 0;
+          for (uint32_t i = 0; i < n_tiles && i < cls.size(); ++i) {
+            if (cls[i] == ZRT_TILE_SKY || !(cls[i] & ZRT_TILE_ONE_SPHERE)) continue;
+            CHECK(!(cls[i] & ZRT_TILE_SKY) && (n_one == 0 || cls[i] == word), "scene %u: class word %08x beside %08x",
+                  index, cls[i], word);
+            word = cls[i];
+            ++n_one;
+          }
+          CHECK(n_one + n_sky <= n_tiles && (n_one == 0 || (lean && depth >= 1 && trav == ZRT_TRAVERSAL_FAST)),
+                "scene %u: %u one-sphere tiles (lean %u depth %u traversal %u)", index, n_one, lean, depth, trav);
         }
       }
   {  // ... and a frame large enough for its threads (1024 x 1024: 16 squares of 32 x 32 tiles)
@@ -205,6 +216,36 @@ static void one_scene(uint32_t index, const std::string& assets, const std::stri
     rc = zrt_debug_tile_classes(s, &cam, &q, nullptr, 0, &n_tiles, &n_sky, nullptr);
     CHECK(rc == ZRT_OK && n_tiles == 16384 && n_sky <= n_tiles, "scene %u tile classes at 1024 x 1024: %s", index,
           zrt_last_error());
+    // ... its one-sphere tiles (the threads' counts merged, one sphere kept), and the class switched off
+    std::vector<uint32_t> big(n_tiles), off(n_tiles);
+    uint32_t n_sky_off = 0;
+    rc = zrt_debug_tile_classes(s, &cam, &q, big.data(), n_tiles, &n_tiles, &n_sky, nullptr);
+    setenv("ZRT_SPHERE_TILES", "0", 1);
+    const int rc_off = zrt_debug_tile_classes(s, &cam, &q, off.data(), n_tiles, &n_tiles, &n_sky_off, nullptr);
+    unsetenv("ZRT_SPHERE_TILES");
+    CHECK(rc == ZRT_OK && rc_off == ZRT_OK && n_sky == n_sky_off, "scene %u: sky tiles %u / %u with the one-sphere class on / off",
+          index, n_sky, n_sky_off);
+    uint32_t n_one = 0;
+    for (uint32_t i = 0; i < n_tiles; ++i) {
+      const bool one = big[i] != ZRT_TILE_SKY && (big[i] & ZRT_TILE_ONE_SPHERE);
+      n_one += one;
+      CHECK(off[i] == (one ? 0u : big[i]), "scene %u tile %u: class %08x, %08x with ZRT_SPHERE_TILES=0", index, i, big[i],
+            off[i]);
+    }
+    if (index == 2) CHECK(n_one > n_tiles / 4, "scene 2: %u one-sphere tiles of %u", n_one, n_tiles);
+    // the slot a class word names is a sphere's (zrt_debug_slot_prims)
+    uint32_t n_slots = 0;
+    rc = zrt_debug_slot_prims(s, &q, nullptr, 0, &n_slots);
+    std::vector<uint32_t> slot_prim(n_slots);
+    if (!rc) rc = zrt_debug_slot_prims(s, &q, slot_prim.data(), n_slots, &n_slots);
+    CHECK(rc == ZRT_OK && n_slots == s->n_prims, "scene %u slot prims: %s", index, zrt_last_error());
+    for (uint32_t i = 0; i < n_tiles && !rc; ++i)
+      if (big[i] != ZRT_TILE_SKY && (big[i] & ZRT_TILE_ONE_SPHERE)) {
+        const uint32_t slot = big[i] & (ZRT_TILE_ONE_SPHERE - 1u);
+        CHECK(slot < n_slots && s->prims[slot_prim[slot]].kind == ZRT_PRIM_SPHERE, "scene %u tile %u: slot %u is no sphere",
+              index, i, slot);
+        break;
+      }
   }
   if (s->n_prims > 10) {
     uint64_t n_slots = 0;

@@ -1109,14 +1109,17 @@ def debug_lean_kernel(scene, camera, params) -> bool:
 
 
 ZRT_TILE_SKY = 0x80000000
+ZRT_TILE_ONE_SPHERE = 0x40000000  # | the sphere's device primitive slot
 
 
-def debug_tile_classes(scene, camera, params):
+def debug_tile_classes(scene, camera, params, one_sphere=False):
     """The class word of each of this rank's 8x8 tiles as a render of this scene from
     this camera with these params would split them (zrt_debug_tile_classes; no device),
     under the environment knobs a real launch reads (ZRT_SKY_TILES among them): a
-    uint32 array (0 general, ZRT_TILE_SKY all sky) and a dict of the classifier's
-    margins (sphere_reach, tri_reach, k_ao, k_c)."""
+    uint32 array (0 general, ZRT_TILE_SKY all sky, ZRT_TILE_ONE_SPHERE | slot for a tile
+    whose primary rays can hit that one sphere alone) and a dict of the classifier's
+    margins (sphere_reach, tri_reach, k_ao, k_c).  one_sphere=False (the default, what
+    callers that know the sky class alone expect) reports a one-sphere tile as general."""
     view = scene.view if isinstance(scene, LoadedScene) else scene
     p = params.abi()
     n, n_sky = C.c_uint32(), C.c_uint32()
@@ -1127,7 +1130,21 @@ def debug_tile_classes(scene, camera, params):
                                        n.value, C.byref(n), C.byref(n_sky), m))
     out = out[:n.value]
     assert int((out == ZRT_TILE_SKY).sum()) == n_sky.value
+    if not one_sphere:
+        out[(out & ZRT_TILE_SKY) == 0] = 0
     return out, dict(sphere_reach=m[0], tri_reach=m[1], k_ao=m[2], k_c=m[3])
+
+
+def debug_slot_prims(scene, params):
+    """The list index of the primitive in each device primitive slot (zrt_debug_slot_prims; no
+    device): a uint32 array indexed by slot, e.g. by the slot bits of a one-sphere class word."""
+    view = scene.view if isinstance(scene, LoadedScene) else scene
+    p = params.abi()
+    n = C.c_uint32()
+    check(lib().zrt_debug_slot_prims(view, C.byref(p), None, 0, C.byref(n)))
+    out = np.zeros(max(1, n.value), dtype=np.uint32)
+    check(lib().zrt_debug_slot_prims(view, C.byref(p), out.ctypes.data_as(C.POINTER(C.c_uint32)), n.value, C.byref(n)))
+    return out[:n.value]
 
 
 def debug_qnodes(scene) -> int:

@@ -423,6 +423,8 @@ SIGNATURES = [
                                          C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(C.c_uint32),
                                          C.POINTER(C.c_uint32), C.POINTER(C.c_double)]),
     ("zrt_debug_octant_offsets", C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32]),
+    ("zrt_debug_slot_prims", C.c_int, [C.POINTER(Scene), C.POINTER(Params), C.POINTER(C.c_uint32), C.c_uint32,
+                                       C.POINTER(C.c_uint32)]),
 ]
 
 _lib = None

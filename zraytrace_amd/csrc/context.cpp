@@ -401,6 +401,8 @@ struct LaunchEnv {
   bool auto_sync = true;      // ZRT_SYNC or ZRT_AUTO_SYNC=0: the fixed interval, A/B
   bool sky_tiles = true;      // ZRT_SKY_TILES=0: A/B, every tile through the render kernel
   bool sky_by_render = false; // ZRT_SKY_TILES=2: measurement, the sky list through a second launch of the render kernel
+  bool sphere_tiles = true;   // ZRT_SPHERE_TILES=0: A/B, the one-sphere tiles stay general
+  bool sphere_by_render = false;  // ZRT_SPHERE_TILES=2: measurement, the one-sphere list through a launch of the render kernel
   bool cap_rows = false;      // ZRT_DEBUG_ROW_CAP: tests, the STATS device check reports a smaller buffer
   double row_cap = 1.0;
 };
@@ -415,6 +417,8 @@ LaunchEnv read_launch_env() {
   v.auto_sync = !v.sync && !(as && std::atoi(as) == 0);
   v.sky_tiles = sky_tiles_wanted();
   if (const char* e = std::getenv("ZRT_SKY_TILES")) v.sky_by_render = std::atoi(e) == 2;
+  v.sphere_tiles = sphere_tiles_wanted();
+  if (const char* e = std::getenv("ZRT_SPHERE_TILES")) v.sphere_by_render = std::atoi(e) == 2;
   if (const char* e = std::getenv("ZRT_DEBUG_ROW_CAP")) {
     v.cap_rows = true;
     v.row_cap = std::atof(e);
@@ -619,33 +623,51 @@ bool choose_order(zrt_ctx* c, const Frame& f, const FrameSize& z, const LaunchEn
 // pass takes its first pass's.  Classification runs here, behind the enqueued probe and
 // before e0, so a scheduled launch's schedule_ms covers it.  An adaptive level does not
 // take the split (its active list changes from level to level on the device).
-// Returns the sky tiles (0: no split; a.tile_order and a.total_work are as they were).
-uint32_t split_sky(zrt_ctx* c, const Frame& f, const LaunchEnv& env, KArgs& a) {
+// The one-sphere tiles (their camera rays can hit one sphere alone: the ONE_SPHERE
+// kernels test it without walking the tree) are split off the same way, into a third
+// list in the same order, where sphere_split_allowed and ZRT_SPHERE_TILES say so.
+// Returns the sky and one-sphere tiles (0, 0: no split; a.tile_order and a.total_work are
+// as they were) and where the one-sphere launch reads its list.
+struct TileSplit {
+  uint32_t n_sky = 0, n_one = 0;
+  const uint32_t* one_order = nullptr;
+};
+TileSplit split_sky(zrt_ctx* c, const Frame& f, const LaunchEnv& env, KArgs& a) {
   const zrt_params* p = f.p;
   SkySplit& sp = c->sky;
   if (!env.sky_tiles || f.adapt || f.my_tiles == 0 || !sp.scene.ok || !sky_split_allowed(f.plan, p, f.cam_inside))
-    return 0;
+    return {};
+  const bool want_one = env.sphere_tiles && sphere_split_allowed(f.plan, p, f.cam_inside);
   const OrderKey key{*f.cam, p->width, p->height, p->max_depth, p->rank, p->world_size, p->traversal,
                      f.plan.guard_on ? 1u : 0u, f.my_tiles};
-  const bool hit = sp.valid && std::memcmp(&key, &sp.key, sizeof(key)) == 0 && (env.order_cache || !f.first);
+  const bool hit = sp.valid && std::memcmp(&key, &sp.key, sizeof(key)) == 0 && sp.key_sphere == want_one &&
+                   (env.order_cache || !f.first);
   if (!hit) {
     sp.valid = false;
     const double t0 = now_ms();
-    classify_tiles(sp.scene, f.cam, p, &sp.cls, &sp.n_sky);
+    OneSphere one;
+    one.want = want_one;
+    classify_tiles(sp.scene, f.cam, p, &sp.cls, &sp.n_sky, nullptr, &one);
+    sp.n_one = one.n_tiles;
+    sp.one_sphere = one.sphere;
     if (env.debug)
-      std::fprintf(stderr, "zrt launch: %u of %u tiles all sky, classified in %.2f ms\n", sp.n_sky, f.my_tiles,
-                   now_ms() - t0);
+      std::fprintf(stderr, "zrt launch: %u of %u tiles all sky, %u one-sphere, classified in %.2f ms\n", sp.n_sky,
+                   f.my_tiles, sp.n_one, now_ms() - t0);
     sp.sky_host.clear();
     sp.gen_host.clear();
-    for (uint32_t lt = 0; lt < f.my_tiles; ++lt) (sp.cls[lt] == kTileSky ? sp.sky_host : sp.gen_host).push_back(lt);
-    if (sp.n_sky) {
+    sp.one_host.clear();
+    for (uint32_t lt = 0; lt < f.my_tiles; ++lt)
+      (sp.cls[lt] == kTileSky ? sp.sky_host : sp.cls[lt] == kTileGeneral ? sp.gen_host : sp.one_host).push_back(lt);
+    if (sp.n_sky || sp.n_one) {
       // (stream-ordered behind the previous launch, which may still read the old lists)
       if (sp.cls_dev.n < f.my_tiles) {
         HIPCHK(hipStreamSynchronize(f.st));
         sp.cls_dev.alloc(f.my_tiles);
         sp.sky_list.alloc(f.my_tiles);
         sp.gen_list.alloc(f.my_tiles);
+        sp.one_list.alloc(f.my_tiles);
         sp.gen_sorted.alloc(f.my_tiles);
+        sp.one_sorted.alloc(f.my_tiles);
         sp.count.alloc(1);
       }
       const auto up = [&](DevBuf<uint32_t>& d, const std::vector<uint32_t>& h) {
@@ -654,26 +676,40 @@ uint32_t split_sky(zrt_ctx* c, const Frame& f, const LaunchEnv& env, KArgs& a) {
       up(sp.cls_dev, sp.cls);
       up(sp.sky_list, sp.sky_host);
       up(sp.gen_list, sp.gen_host);
+      up(sp.one_list, sp.one_host);
       HIPCHK(hipStreamSynchronize(f.st));  // (the host vectors are rewritten by the next classification)
     }
     sp.sorted_valid = false;
     sp.key = key;
+    sp.key_sphere = want_one;
     sp.valid = true;
   }
-  if (sp.n_sky == 0) return 0;
-  const uint32_t n_gen = f.my_tiles - sp.n_sky;
-  if (a.tile_order) {  // the probe's cost order, without the sky tiles
+  if (sp.n_sky == 0 && sp.n_one == 0) return {};
+  TileSplit ts;
+  ts.n_sky = sp.n_sky;
+  ts.n_one = sp.n_one;
+  const uint32_t n_gen = f.my_tiles - sp.n_sky - sp.n_one;
+  if (a.tile_order) {  // the probe's cost order, each class's tiles of it
     if (!sp.sorted_valid || sp.sorted_gen != c->probe.order_gen) {
-      HIPCHK(launch_compact(f.st, c->probe.tile_order.p, f.my_tiles, sp.cls_dev.p, sp.gen_sorted.p, sp.count.p));
+      if (sp.n_one) {
+        HIPCHK(launch_compact_class(f.st, c->probe.tile_order.p, f.my_tiles, sp.cls_dev.p, kTileGeneral, sp.gen_sorted.p,
+                                    sp.count.p));
+        HIPCHK(launch_compact_class(f.st, c->probe.tile_order.p, f.my_tiles, sp.cls_dev.p, sp.cls[sp.one_host[0]],
+                                    sp.one_sorted.p, sp.count.p));
+      } else {
+        HIPCHK(launch_compact(f.st, c->probe.tile_order.p, f.my_tiles, sp.cls_dev.p, sp.gen_sorted.p, sp.count.p));
+      }
       sp.sorted_gen = c->probe.order_gen;
       sp.sorted_valid = true;
     }
     a.tile_order = sp.gen_sorted.p;
+    ts.one_order = sp.one_sorted.p;
   } else {
     a.tile_order = sp.gen_list.p;
+    ts.one_order = sp.one_list.p;
   }
   a.total_work = uint32_t(uint64_t(n_gen) * f.pass.pass_chunks);
-  return sp.n_sky;
+  return ts;
 }
 
 // 7. The lockstep interval's probe, the scanline and wave-time outputs, and - the
@@ -706,7 +742,8 @@ void optional_outputs(zrt_ctx* c, const Frame& f, const FrameSize& z, const Laun
 
 // 8. The kernel between its events, and what resolves its chunk sums into dev_tiles:
 // finalize (a frame), accumulate (a pass), or resolve and compact (an adaptive level).
-void enqueue(zrt_ctx* c, const Frame& f, const FrameSize& z, const LaunchEnv& env, KArgs& a, uint32_t n_sky) {
+void enqueue(zrt_ctx* c, const Frame& f, const FrameSize& z, const LaunchEnv& env, KArgs& a, const TileSplit& ts) {
+  const uint32_t n_sky = ts.n_sky;
   const zrt_params* p = f.p;
   const Geometry& g = f.g;
   const uint32_t n_chunks = f.pass.pass_chunks, n_slots = f.my_tiles * 64u;
@@ -724,6 +761,23 @@ void enqueue(zrt_ctx* c, const Frame& f, const FrameSize& z, const LaunchEnv& en
     } else {
       HIPCHK(hipLaunchKernel(sky_kernel_ptr(p->prng, f.diag), dim3(grid), dim3(kBlock), args, 0, f.st));
     }
+  }
+  if (ts.n_one > 0) {  // the one-sphere tiles: the same loop, its camera rays' step without the tree
+    const SkySplit& sp = c->sky;
+    KArgs oa = a;
+    oa.tile_order = ts.one_order;
+    oa.total_work = uint32_t(uint64_t(ts.n_one) * n_chunks);
+    const SphereArgs& sa = sp.scene.sphere_args[size_t(sp.one_sphere)];
+    std::memcpy(oa.one_lo, sa.lo, sizeof(sa.lo));
+    std::memcpy(oa.one_hi, sa.hi, sizeof(sa.hi));
+    std::memcpy(oa.one_rec, sa.rec, sizeof(sa.rec));
+    oa.one_slot = sp.scene.spheres[size_t(sp.one_sphere)];
+    // (ZRT_SPHERE_TILES=2: what these tiles cost in the render kernel)
+    void* kfn = env.sphere_by_render ? f.kfn : one_sphere_kernel(p->prng, f.diag, f.plan.stk16);
+    const uint32_t grid = std::max(1u, std::min(z.grid, (oa.total_work + kBlock / 64 - 1) / (kBlock / 64)));
+    void* args[] = {&oa};
+    HIPCHK(hipLaunchKernel(kfn, dim3(grid), dim3(kBlock), args, f.plan.lp.bytes, f.st));
+    HIPCHK(hipMemsetAsync(c->scratch.p + kWorkSlot, 0, sizeof(unsigned long long), f.st));  // its own work counter
   }
   if (a.total_work > 0) {
     void* args[] = {&a};
@@ -764,7 +818,7 @@ void enqueue(zrt_ctx* c, const Frame& f, const FrameSize& z, const LaunchEnv& en
 }
 
 // 9. The error flag copied back behind the done event; the launch recorded; the run advanced.
-void finish(zrt_ctx* c, const Frame& f, const FrameSize& z, const KArgs& a, bool schedule, uint32_t n_sky) {
+void finish(zrt_ctx* c, const Frame& f, const FrameSize& z, const KArgs& a, bool schedule, const TileSplit& ts) {
   HIPCHK(hipMemcpyAsync(c->render.err.get(), c->scratch.p + kErrorSlot, sizeof(unsigned long long), hipMemcpyDeviceToHost,
                         f.st));
   HIPCHK(hipEventRecord(c->render.done, f.st));
@@ -791,7 +845,8 @@ void finish(zrt_ctx* c, const Frame& f, const FrameSize& z, const KArgs& a, bool
   l.guard = a.guard;
   l.scanline_rows = (f.p->flags & ZRT_FLAG_SCANLINES) ? f.p->height : 0u;
   l.n_waves = K.profile ? z.grid * (kBlock / 64) : 0u;
-  l.sky_tiles = n_sky;
+  l.sky_tiles = ts.n_sky;
+  l.sphere_tiles = ts.n_one;
   c->last = l;
   if (f.run_pass) {
     c->run.done = f.pass.samples_after;
@@ -821,10 +876,10 @@ int launch_frame(zrt_ctx* c, const zrt_camera* cam, const zrt_params* p, float* 
     if (run_pass && !f.first) rotate_events(c);
     KArgs a = fill_args(c, f, z, env);
     const bool schedule = choose_order(c, f, z, env, a);
-    const uint32_t n_sky = split_sky(c, f, env, a);
+    const TileSplit ts = split_sky(c, f, env, a);
     optional_outputs(c, f, z, env, schedule, a);
-    enqueue(c, f, z, env, a, n_sky);
-    finish(c, f, z, a, schedule, n_sky);
+    enqueue(c, f, z, env, a, ts);
+    finish(c, f, z, a, schedule, ts);
     return ZRT_OK;
   }
   ZRT_CATCH_ALL

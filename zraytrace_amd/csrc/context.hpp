@@ -177,11 +177,15 @@ struct SkySplit {
   OrderKey key{};
   bool valid = false;  // cls / the lists are `key`'s
   uint32_t n_sky = 0;
-  std::vector<uint32_t> cls, sky_host, gen_host;  // per local tile; the sky / general tiles in tile order
-  DevBuf<uint32_t> cls_dev, sky_list, gen_list;
-  // the general tiles in the probe's cost order: Probe::tile_order without the sky tiles
-  // (compact_kernel), valid while sorted_gen == Probe::order_gen and sorted_valid
-  DevBuf<uint32_t> gen_sorted, count;
+  // the one-sphere tiles (classified where key_sphere says so: part of what the lists are valid for)
+  bool key_sphere = false;
+  uint32_t n_one = 0;
+  int32_t one_sphere = -1;  // their sphere's index in scene.spheres
+  std::vector<uint32_t> cls, sky_host, gen_host, one_host;  // per local tile; the sky / general / one-sphere tiles in tile order
+  DevBuf<uint32_t> cls_dev, sky_list, gen_list, one_list;
+  // the general and the one-sphere tiles in the probe's cost order: Probe::tile_order's tiles
+  // of each class (compact_kernel), valid while sorted_gen == Probe::order_gen and sorted_valid
+  DevBuf<uint32_t> gen_sorted, one_sorted, count;
   uint64_t sorted_gen = 0;
   bool sorted_valid = false;
 };
@@ -198,6 +202,7 @@ struct LastLaunch {
   uint32_t scanline_rows = 0;  // rows it counted (0: not flagged)
   uint32_t n_waves = 0;        // ZRT_PROFILE builds
   uint32_t sky_tiles = 0;      // tiles the launch rendered in sky_kernel (zrt_ctx_debug_counters slot kSkyTilesSlot)
+  uint32_t sphere_tiles = 0;   // ... in the one-sphere kernel (slot kSphereTilesSlot)
 };
 
 // ---- the accumulation run (zrt_ctx_accum_*): at most one per context ----

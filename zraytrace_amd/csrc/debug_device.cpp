@@ -17,6 +17,7 @@ int zrt_ctx_debug_counters(zrt_ctx* c, uint64_t* out, uint32_t n) {
     unsigned long long h[zrt::kScratchSlots] = {0};
     HIPCHK(hipMemcpy(h, c->scratch.p, sizeof(h), hipMemcpyDeviceToHost));
     h[zrt::kSkyTilesSlot] = c->last.sky_tiles;
+    h[zrt::kSphereTilesSlot] = c->last.sphere_tiles;
     for (uint32_t i = 0; i < n && i < uint32_t(zrt::kScratchSlots); ++i) out[i] = h[i];
     return ZRT_OK;
   }

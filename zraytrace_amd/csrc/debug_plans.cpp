@@ -233,12 +233,35 @@ int zrt_debug_tile_classes(const zrt_scene* scene, const zrt_camera* camera, con
       zrt::SkyScene sky;
       zrt::build_sky_scene(&sky, h);
       const double t0 = zrt::now_ms();
-      zrt::classify_tiles(sky, camera, params, &cls, n_sky, margins);
+      zrt::OneSphere one;
+      one.want = zrt::sphere_tiles_wanted() &&
+                 zrt::sphere_split_allowed(P, params, zrt::camera_inside(camera, h.root_c, h.origin_bound));
+      zrt::classify_tiles(sky, camera, params, &cls, n_sky, margins, &one);
       if (std::getenv("ZRT_DEBUG_LAUNCH"))
-        std::fprintf(stderr, "zrt tile classes: %u of %zu tiles sky in %.2f ms\n", *n_sky, cls.size(), zrt::now_ms() - t0);
+        std::fprintf(stderr, "zrt tile classes: %u sky, %u one-sphere of %zu tiles in %.2f ms\n", *n_sky, one.n_tiles,
+                     cls.size(), zrt::now_ms() - t0);
     }
     *n_tiles = uint32_t(cls.size());
     for (uint32_t i = 0; i < cap && i < cls.size(); ++i) classes[i] = cls[i];
+    return ZRT_OK;
+  }
+  ZRT_CATCH_HOST
+}
+
+int zrt_debug_slot_prims(const zrt_scene* scene, const zrt_params* params, uint32_t* prims, uint32_t cap,
+                         uint32_t* n_slots) {
+  if (!n_slots || (cap && !prims)) return fail(ZRT_E_INVALID, "null argument");
+  *n_slots = 0;
+  int rc = zrt::validate_scene(scene);
+  if (rc) return rc;
+  rc = zrt::validate_params(params);
+  if (rc) return rc;
+  try {
+    const bool use_bvh = params->bounded_volume_hierarchy != 0 && scene->n_prims > 10;  // (zrt_ctx_create)
+    zrt::HostScene h;
+    zrt::flatten_scene(&h, scene, use_bvh, -1);
+    *n_slots = uint32_t(h.slot_to_prim.size());
+    for (uint32_t i = 0; i < cap && i < h.slot_to_prim.size(); ++i) prims[i] = h.slot_to_prim[i];
     return ZRT_OK;
   }
   ZRT_CATCH_HOST

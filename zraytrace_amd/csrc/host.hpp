@@ -158,6 +158,9 @@ int check_lens(const zrt_lens* lens);
 // from a tile order) marks a tile no primary ray of which can hit anything; the low
 // bits are free for later classes.
 constexpr uint32_t kTileGeneral = 0u, kTileSky = kTileFrozen;
+// One-sphere tiles (DESIGN.md §3 "One-sphere tiles"): bit 30, with the device slot of the
+// one sphere a primary ray of the tile can hit in the low bits.
+constexpr uint32_t kTileOneSphere = 0x40000000u;
 struct SkyNode {  // a reference-tree node: its box's bounding sphere and its children (KArgs::nodes refs)
   double c[3], r;
   int32_t left, right;
@@ -165,6 +168,9 @@ struct SkyNode {  // a reference-tree node: its box's bounding sphere and its ch
 struct SkyPrim {  // a primitive slot's bounding sphere; sphere_index >= 0: a sphere (r: its radius)
   double c[3], r;
   int32_t sphere_index;
+};
+struct SphereArgs {  // a sphere's reference leaf box and its record {center.xyz, radius^2} (KArgs::one_*)
+  float lo[3], hi[3], rec[4];
 };
 // What the classifier keeps of a flattened scene (a context keeps it past the upload).
 struct SkyScene {
@@ -175,12 +181,25 @@ struct SkyScene {
   std::vector<uint32_t> spheres;  // the slots that hold spheres
   double k_ao = 0, k_c = 0;       // the triangles' reach k_ao |ao| + k_c (tools/tri_reach_bound.py, doubled)
   double tri_c[3] = {0, 0, 0}, tri_r = 0;  // the triangles' bounding sphere
+  // per sphere (`spheres` order): its reference leaf is a slot of the root wide node (the
+  // one-sphere path may stand in for its traversal), and what that path reads of it
+  std::vector<uint8_t> sphere_root;
+  std::vector<SphereArgs> sphere_args;
 };
-bool sky_tiles_wanted();  // ZRT_SKY_TILES (default on)
+// classify_tiles' one-sphere class: want (in): mark it; n_tiles, sphere (out): the tiles
+// marked and their sphere's index in SkyScene::spheres (-1: none)
+struct OneSphere {
+  bool want = false;
+  uint32_t n_tiles = 0;
+  int32_t sphere = -1;
+};
+bool sky_tiles_wanted();     // ZRT_SKY_TILES (default on)
+bool sphere_tiles_wanted();  // ZRT_SPHERE_TILES (default on)
 bool sky_split_allowed(const LaunchPlan& P, const zrt_params* p, bool cam_inside);
+bool sphere_split_allowed(const LaunchPlan& P, const zrt_params* p, bool cam_inside);
 void build_sky_scene(SkyScene* s, const HostScene& h);
 void classify_tiles(const SkyScene& s, const zrt_camera* cam, const zrt_params* p, std::vector<uint32_t>* cls,
-                    uint32_t* n_sky, double* margins = nullptr);
+                    uint32_t* n_sky, double* margins = nullptr, OneSphere* one = nullptr);
 
 // ---- flatten.cpp ----
 // `device` >= 0: the GPU that may build the reference BVH (bvh_gpu.hip); a failed

@@ -97,6 +97,13 @@ struct KArgs {
   float graze_leaf;        // (no kernel reads it: leaf slots share graze_m; the host still fills it)
   float guard;             // the grazing-triangle guard (RayT::gk, wide_iter; 0: off)
   uint64_t att_cap, ovf_cap;  // elements of `att` and of `stack_ovf` (StackT): row_ok's bounds
+  // The one-sphere kernels alone (render_loop ONE_SPHERE; DESIGN.md §3 "One-sphere tiles"):
+  // the one sphere a camera ray of the launch's tiles can hit - its reference leaf's box,
+  // its record {center.xyz, radius^2} and its primitive slot.  (Last, so that every other
+  // field keeps its offset: the other kernels' code changes in nothing but the kernarg
+  // offsets of what follows KArgs in their argument lists, hidden arguments included.)
+  float one_lo[3], one_hi[3], one_rec[4];
+  uint32_t one_slot;
 };
 
 // ao_kernel / ao_finish_kernel's own arguments (zrt_ctx_ao; zrt::plan_ao fills the counts)
@@ -144,6 +151,8 @@ constexpr uint32_t kErrLayout = 2u;    // the wide tree's encoding is not the on
 constexpr uint32_t kErrBounds = 4u;    // STATS flavour: a global row index past its buffer (row_ok)
 
 // counters[]: progress counters of raytrace.zig:20-34 + traffic diagnostics
+// (kSphereTests: the one-sphere kernels count one per short-path camera ray, before the leaf
+// box's loose test: also for the rays that box rejects, the sky rays of a horizon tile)
 enum { kDepthHits, kReflections, kBackground, kRays, kNodes, kTriTests, kSphereTests, kShades, kTexels,
        kLeaves, kReplays, kExcessTri, kExcessSph, kExcessHits, kNumCounters };
 constexpr int kWorkSlot = 14, kErrorSlot = 15, kProfSlot = 16, kScratchSlots = 48;
@@ -186,6 +195,8 @@ constexpr int kVNodeTrips = 32, kVNodeLines = 33, kSNodeTrips = 34, kRbTrips = 3
 
 // zrt_ctx_debug_counters: the tiles the last launch rendered in sky_kernel (filled in on the host)
 constexpr int kSkyTilesSlot = 47;
+// ... and the tiles it rendered in the one-sphere kernel (render_kernel's ONE_SPHERE instantiation)
+constexpr int kSphereTilesSlot = 46;
 // radiance_kernel (the query's own counters): the most attenuation rows any path of the call pushed
 constexpr int kRqDeepestSlot = 44;
 
@@ -216,6 +227,12 @@ const KernelConfig& kernel_config();
 // The kernel of a launch (hipLaunchKernel takes it).  select_kernel: render_kernel<kmode, prng,
 // stats, stack width, lean>; the others by traversal mode (8: FAST over compressed nodes).
 void* select_kernel(int kmode, uint32_t prng, bool stats, bool stk16, bool lean);
+// render_kernel<3, prng, stats, stack width, !stats, true>: the lockstep FAST loop whose camera
+// rays test one sphere alone (tile_class.cpp proves the tiles), lean when timed, general under STATS
+void* one_sphere_kernel(uint32_t prng, bool stats, bool stk16);
+// compact_kernel's scheme with another predicate: the tiles of `in` whose class word equals `word`
+hipError_t launch_compact_class(hipStream_t st, const uint32_t* in, uint32_t n, const uint32_t* cls, uint32_t word,
+                                uint32_t* out, uint32_t* count);
 void* probe_kernel(uint32_t prng, bool stk16);
 void* sky_kernel_ptr(uint32_t prng, bool stats);  // the all-sky tiles' kernel (tile_class.cpp proves them)
 void* trace_kernel_ptr(int mode, bool stk16);

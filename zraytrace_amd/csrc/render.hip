@@ -1636,6 +1636,21 @@ __device__ __forceinline__ void traverse_wide_q(const KArgs& a, const RayT& r, S
   wide_finish<STATS, StackT>(a, r, stk, gl, best_t, best, c_replays);
 }
 
+// The closest hit of a ray that can hit one sphere alone (render_loop ONE_SPHERE; DESIGN.md
+// §3 "One-sphere tiles"): the reference reaches that sphere's test exactly when its leaf's
+// box passes the loose test against t_max = +inf (§3 "Spheres"; static_ok on the planes in
+// the ray's octant, as wide_iter's static_ok_slot applies it to a sphere slot), and with one
+// candidate there is nothing to order.  Not for a degenerate ray (its octant is not defined).
+__device__ __forceinline__ void one_sphere_hit(const KArgs& a, const RayT& r, float& best_t, int& best) {
+  const OctSigns os(r);
+  float entry;
+  if (static_ok_planes(os.sx ? a.one_hi[0] : a.one_lo[0], os.sy ? a.one_hi[1] : a.one_lo[1],
+                       os.sz ? a.one_hi[2] : a.one_lo[2], os.sx ? a.one_lo[0] : a.one_hi[0],
+                       os.sy ? a.one_lo[1] : a.one_hi[1], os.sz ? a.one_lo[2] : a.one_hi[2], r, entry))
+    sphere_test<false>(make_float4(a.one_rec[0], a.one_rec[1], a.one_rec[2], a.one_rec[3]), (int)a.one_slot, r, best_t,
+                       best);
+}
+
 template <bool STATS, class StackT, bool PAXIS = false, bool LEAN = false>
 __device__ __forceinline__ void traverse_wide(const KArgs& a, const RayT& r, StackT* __restrict__ stk,
                                               const float4* __restrict__ lds_top, uint32_t gl, float& best_t,
@@ -2115,10 +2130,16 @@ __device__ __forceinline__ uint32_t auto_sync(const KArgs& a) {
 // units - one per tile, 65 536 on C4 - are dealt to the waves round-robin instead of
 // through the global counter, whose one atomic per unit serialised the probe
 // (the render launch's units are 32 samples and keep the counter)
+// ONE_SPHERE: the instance for the tiles the host proved one-sphere (tile_class.cpp: no
+// camera ray of theirs can return a hit from any primitive but the launch's one sphere,
+// KArgs::one_*): a camera ray's step tests that sphere alone (one_sphere_hit) instead
+// of walking the tree; every later step of the path is the loop's own.
 template <int MODE /*0 list, 1 BVH binary, 2 BVH reference, 3 wide (FAST)*/, int PRNG, bool STATS, class StackT,
-          bool PROBE = false, bool LEAN = false /* MODE 3, timed flavour: the lean kernel (struct Lean) */>
+          bool PROBE = false, bool LEAN = false /* MODE 3, timed flavour: the lean kernel (struct Lean) */,
+          bool ONE_SPHERE = false>
 __device__ __forceinline__ void render_loop(const KArgs& a) {
   static_assert(!LEAN || (MODE == 3 && !STATS && !PROBE), "the lean kernel is the timed lockstep FAST loop's");
+  static_assert(!ONE_SPHERE || (MODE == 3 && !PROBE), "the one-sphere step is the lockstep FAST loop's");
   extern __shared__ __attribute__((aligned(16))) char lds_raw[];
   StackT* stk = reinterpret_cast<StackT*>(lds_raw) + threadIdx.x;  // LDS: the traversal stack
   float4* lds_top = reinterpret_cast<float4*>(lds_raw + a.lds_top_off);
@@ -2289,13 +2310,21 @@ __device__ __forceinline__ void render_loop(const KArgs& a) {
           }
         }
       } else if (MODE == 3) {
-        if (kLaneLds) {
-          LaneState<PRNG>::park(st_l, rng, acc_r, acc_g, acc_b, sample, depth_left);
-        }
-        traverse_wide<STATS, StackT, false, LEAN>(a, r, stk, lds_top, gl, best_t, best, c_nodes, c_leaves, c_tri, c_sph,
-                                                  c_replays, coh);
-        if (kLaneLds) {
-          LaneState<PRNG>::unpark(st_l, rng, acc_r, acc_g, acc_b, sample, depth_left);
+        // (ONE_SPHERE: the camera ray, unless FAST would hand it to the replay - a rare lane-level branch)
+        const bool walk = !ONE_SPHERE || depth_left != a.max_depth || ray_degenerate(r) ||
+                          (!Lean<LEAN>::origin && !ray_origin_ok(a, r));
+        if (walk) {
+          if (kLaneLds) {
+            LaneState<PRNG>::park(st_l, rng, acc_r, acc_g, acc_b, sample, depth_left);
+          }
+          traverse_wide<STATS, StackT, false, LEAN>(a, r, stk, lds_top, gl, best_t, best, c_nodes, c_leaves, c_tri, c_sph,
+                                                    c_replays, coh);
+          if (kLaneLds) {
+            LaneState<PRNG>::unpark(st_l, rng, acc_r, acc_g, acc_b, sample, depth_left);
+          }
+        } else {
+          if (STATS) ++c_sph;  // (per short-path ray, whether or not the leaf box lets the test run)
+          one_sphere_hit(a, r, best_t, best);
         }
       } else {
         traverse_bvh<MODE == 1, STATS>(a, r, stk, best_t, best, c_nodes, c_tri, c_sph, &excess);
@@ -3257,20 +3286,21 @@ __device__ __forceinline__ void render_loop_list(const KArgs& a) {
 #define ZRT_ATT_ROWS_POOL 3  // path-pool loop: attenuation rows kept in LDS per path (2 KiB per row per block)
 #endif
 
-template <int MODE, int PRNG, bool STATS, class StackT, bool LEAN = false>
+template <int MODE, int PRNG, bool STATS, class StackT, bool LEAN = false, bool ONE_SPHERE = false>
 __global__ void __launch_bounds__(kBlock, MODE == 5 || MODE == 7 || MODE == 8 || MODE == 9 ? ZRT_WAVES_POOL
                                           : MODE == 4 ? ZRT_WAVES_WF
                                           : MODE == 3 ? ZRT_WAVES_WIDE
                                           : MODE == 0 || MODE == 6 ? ZRT_WAVES_LIST
                                                       : ZRT_WAVES_PER_SIMD)
     render_kernel(const KArgs a) {
+  static_assert(!ONE_SPHERE || MODE == 3, "the one-sphere kernels are the lockstep FAST loop's");
   if constexpr (MODE == 6) render_loop_list<PRNG, STATS>(a);
   else if constexpr (MODE == 5) render_loop_pool<PRNG, STATS, StackT, false>(a);
   else if constexpr (MODE == 7) render_loop_pool<PRNG, STATS, StackT, true>(a);  // with the grazing-triangle guard
   else if constexpr (MODE == 8) render_loop_pool<PRNG, STATS, StackT, false, true>(a);  // compressed nodes
   else if constexpr (MODE == 9) render_loop_pool<PRNG, STATS, StackT, true, true>(a);   // compressed, guarded
   else if constexpr (MODE == 4) render_loop_wf<PRNG, STATS, StackT>(a);
-  else render_loop<MODE, PRNG, STATS, StackT, false, LEAN>(a);
+  else render_loop<MODE, PRNG, STATS, StackT, false, LEAN, ONE_SPHERE>(a);
 }
 
 // The scheduling probe (FAST traversal): the same loop over a few samples per
@@ -4132,38 +4162,51 @@ __global__ void resolve_kernel(const float4* __restrict__ partial, float4* __res
 // One block: per round of blockDim.x list entries a ballot and the lanes' mbcnt ranks
 // within each wave, the waves' counts scanned through LDS, a running base across rounds.
 // out[base + ...] stays below the number of entries read, so within n.
+// (One body for both predicates, as text: as a template over the predicate the first
+// kernel's sums came out reassociated, and it is compared with its earlier assembly.)
 constexpr uint32_t kCompactBlock = 1024;
+#define ZRT_COMPACT_BODY(KEEP)                                                                                      \
+  __shared__ uint32_t wave_count[kCompactBlock / 64];                                                               \
+  const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;                                                   \
+  uint32_t base = 0;                                                                                                \
+  for (uint32_t start = 0; start < n; start += kCompactBlock) {                                                     \
+    const uint32_t pos = start + threadIdx.x;                                                                       \
+    uint32_t lt = 0;                                                                                                \
+    bool keep = false;                                                                                              \
+    if (pos < n) {                                                                                                  \
+      lt = in[pos];                                                                                                 \
+      keep = KEEP;                                                                                                  \
+    }                                                                                                               \
+    const unsigned long long b = __ballot(keep);                                                                    \
+    const uint32_t below = __builtin_amdgcn_mbcnt_hi(uint32_t(b >> 32), __builtin_amdgcn_mbcnt_lo(uint32_t(b), 0u)); \
+    if (lane == 0u) wave_count[wv] = uint32_t(__popcll(b));                                                         \
+    __syncthreads();                                                                                                \
+    uint32_t off = 0, total = 0;                                                                                    \
+    for (uint32_t k = 0; k < kCompactBlock / 64; ++k) {                                                             \
+      const uint32_t v = wave_count[k];                                                                             \
+      off += k < wv ? v : 0u;                                                                                       \
+      total += v;                                                                                                   \
+    }                                                                                                               \
+    if (keep) out[base + off + below] = lt;                                                                         \
+    base += total;                                                                                                  \
+    __syncthreads();                                                                                                \
+  }                                                                                                                 \
+  if (threadIdx.x == 0u) *count = base;
 __global__ void __launch_bounds__(kCompactBlock) compact_kernel(const uint32_t* __restrict__ in, uint32_t n,
                                                                 const uint32_t* __restrict__ tile_done,
                                                                 uint32_t* __restrict__ out,
                                                                 uint32_t* __restrict__ count) {
-  __shared__ uint32_t wave_count[kCompactBlock / 64];
-  const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
-  uint32_t base = 0;
-  for (uint32_t start = 0; start < n; start += kCompactBlock) {
-    const uint32_t pos = start + threadIdx.x;
-    uint32_t lt = 0;
-    bool keep = false;
-    if (pos < n) {
-      lt = in[pos];
-      keep = (tile_done[lt] & kTileFrozen) == 0u;
-    }
-    const unsigned long long b = __ballot(keep);
-    const uint32_t below = __builtin_amdgcn_mbcnt_hi(uint32_t(b >> 32), __builtin_amdgcn_mbcnt_lo(uint32_t(b), 0u));
-    if (lane == 0u) wave_count[wv] = uint32_t(__popcll(b));
-    __syncthreads();
-    uint32_t off = 0, total = 0;
-    for (uint32_t k = 0; k < kCompactBlock / 64; ++k) {
-      const uint32_t v = wave_count[k];
-      off += k < wv ? v : 0u;
-      total += v;
-    }
-    if (keep) out[base + off + below] = lt;
-    base += total;
-    __syncthreads();
-  }
-  if (threadIdx.x == 0u) *count = base;
+  ZRT_COMPACT_BODY((tile_done[lt] & kTileFrozen) == 0u)
 }
+// ... and the tiles whose class word is `word` (the general and the one-sphere tiles of a
+// classified frame, each in the probe's order)
+__global__ void __launch_bounds__(kCompactBlock) compact_class_kernel(const uint32_t* __restrict__ in, uint32_t n,
+                                                                      const uint32_t* __restrict__ cls, uint32_t word,
+                                                                      uint32_t* __restrict__ out,
+                                                                      uint32_t* __restrict__ count) {
+  ZRT_COMPACT_BODY(cls[lt] == word)
+}
+#undef ZRT_COMPACT_BODY
 
 // Scatter gathered rank tiles into the framebuffer (raytrace.zig:182 layout).
 // Packed (stride_px == 0): rank r's tiles start at rank_base[r].  Padded: rank r
@@ -4661,9 +4704,9 @@ __global__ void camera_finish_kernel(const float4* __restrict__ partial, const C
 // host side (kernels.hpp): what must see a kernel symbol or a device template
 // ---------------------------------------------------------------------------
 namespace {
-template <int MODE, int PRNG, bool STATS, class StackT, bool LEAN = false>
+template <int MODE, int PRNG, bool STATS, class StackT, bool LEAN = false, bool ONE_SPHERE = false>
 void* kernel_ptr() {
-  return reinterpret_cast<void*>(&render_kernel<MODE, PRNG, STATS, StackT, LEAN>);
+  return reinterpret_cast<void*>(&render_kernel<MODE, PRNG, STATS, StackT, LEAN, ONE_SPHERE>);
 }
 
 template <int PRNG, bool STATS>
@@ -4682,7 +4725,8 @@ void* select_kernel_ps(int mode, bool stk16) {
 }  // namespace
 #ifdef ZRT_ISA_KERNEL
 // tools/isa.sh: device assembly of ONE render kernel (register / spill probes in
-// seconds instead of minutes); ZRT_ISA_KERNEL = MODE, PRNG, STATS, StackT[, true: the lean kernel]
+// seconds instead of minutes); ZRT_ISA_KERNEL = MODE, PRNG, STATS, StackT[, true: the lean kernel[, true: its
+// one-sphere sibling]]
 void* select_kernel(int, uint32_t, bool, bool, bool) { return kernel_ptr<ZRT_ISA_KERNEL>(); }
 #else
 // lean: the lean kernel of the timed lockstep FAST loop (plan_launch decides; four kernels)
@@ -4726,6 +4770,26 @@ void* sky_kernel_ptr(uint32_t prng, bool stats) {
                  : reinterpret_cast<void*>(&sky_kernel<ZRT_PRNG_XOSHIRO256, false>);
   return stats ? reinterpret_cast<void*>(&sky_kernel<ZRT_PRNG_XOROSHIRO128, true>)
                : reinterpret_cast<void*>(&sky_kernel<ZRT_PRNG_XOROSHIRO128, false>);
+#endif
+}
+// the one-sphere kernels: the lean timed flavour and the (general) STATS flavour, both
+// generators, both stack widths - eight
+void* one_sphere_kernel(uint32_t prng, bool stats, bool stk16) {
+#ifdef ZRT_ISA_KERNEL
+  return nullptr;
+#else
+  if (prng == ZRT_PRNG_XOSHIRO256) {
+    if (stats)
+      return stk16 ? kernel_ptr<3, ZRT_PRNG_XOSHIRO256, true, uint16_t, false, true>()
+                   : kernel_ptr<3, ZRT_PRNG_XOSHIRO256, true, uint32_t, false, true>();
+    return stk16 ? kernel_ptr<3, ZRT_PRNG_XOSHIRO256, false, uint16_t, true, true>()
+                 : kernel_ptr<3, ZRT_PRNG_XOSHIRO256, false, uint32_t, true, true>();
+  }
+  if (stats)
+    return stk16 ? kernel_ptr<3, ZRT_PRNG_XOROSHIRO128, true, uint16_t, false, true>()
+                 : kernel_ptr<3, ZRT_PRNG_XOROSHIRO128, true, uint32_t, false, true>();
+  return stk16 ? kernel_ptr<3, ZRT_PRNG_XOROSHIRO128, false, uint16_t, true, true>()
+               : kernel_ptr<3, ZRT_PRNG_XOROSHIRO128, false, uint32_t, true, true>();
 #endif
 }
 hipError_t sort_tiles(void* temp, size_t* temp_bytes, const uint32_t* cost, uint32_t* cost_sorted, const uint32_t* ids,
@@ -4775,6 +4839,10 @@ hipError_t launch_resolve(hipStream_t st, const float4* partial, float4* accum, 
 hipError_t launch_compact(hipStream_t st, const uint32_t* in, uint32_t n, const uint32_t* tile_done, uint32_t* out,
                           uint32_t* count) {
   return launch(compact_kernel, 1, kCompactBlock, st, in, n, tile_done, out, count);
+}
+hipError_t launch_compact_class(hipStream_t st, const uint32_t* in, uint32_t n, const uint32_t* cls, uint32_t word,
+                                uint32_t* out, uint32_t* count) {
+  return launch(compact_class_kernel, 1, kCompactBlock, st, in, n, cls, word, out, count);
 }
 hipError_t launch_assemble(hipStream_t st, const float* gathered, float* frame, const uint32_t* rank_base,
                            uint32_t world, uint32_t tiles_x, uint32_t xbound, uint32_t height, uint32_t width,

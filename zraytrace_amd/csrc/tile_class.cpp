@@ -1,7 +1,10 @@
 // tile_class.cpp - the conservative tile classifier: which 8x8 tiles of a frame are
 // all sky, i.e. no primary ray the kernels can generate for any of their pixels can
 // return a hit from the reference's closest-hit query (DESIGN.md §3 "All-sky tiles").
-// Such tiles render in sky_kernel (render.hip) with no traversal.  Pure host C++:
+// Such tiles render in sky_kernel (render.hip) with no traversal.  And which are
+// one-sphere(s): no such ray can return a hit from any primitive but the sphere s
+// (DESIGN.md §3 "One-sphere tiles"); their camera rays test s alone, without walking the
+// tree (render.hip render_loop ONE_SPHERE).  Pure host C++:
 // no HIP call; the host sanitizer program links and drives it (tools/sanitize).
 //
 // The proof, per block of tiles: every ray of the block leaves the camera origin
@@ -20,6 +23,7 @@
 #include "host.hpp"
 
 namespace zrt {
+static_assert(kTileSky == ZRT_TILE_SKY && kTileOneSphere == ZRT_TILE_ONE_SPHERE, "zrt.h names the class words");
 namespace {
 constexpr double kU = 0x1p-24;
 constexpr uint32_t kMaxSkyNodes = 1u << 21;  // larger trees are not kept for classification (all general)
@@ -55,6 +59,8 @@ struct Classifier {
   std::vector<double> sphere_r;   // per sphere (S.spheres order): its radius grown by its reach
   std::vector<uint32_t>* cls;
   uint32_t n_sky = 0;
+  bool want_one = false;          // mark one-sphere tiles too
+  std::vector<uint32_t> n_one;    // per sphere (S.spheres order): the tiles marked one-sphere(it)
   std::vector<std::vector<int32_t>> frontier;  // per recursion depth
   std::vector<int32_t> stack;
 
@@ -97,17 +103,31 @@ struct Classifier {
   // Does every ray of the cone run into one sphere (shrunk a little)?  Then the block is
   // general whatever else it sees: no need to split it further.  (A shortcut only:
   // general is always a safe answer.)
-  bool inside_a_sphere(const Cone& k) const {
-    if (S.spheres.size() > 16) return false;
-    for (const uint32_t slot : S.spheres) {
-      const SkyPrim& q = S.prims[slot];
+  // Returns that sphere's index (S.spheres order), or -1.
+  int32_t inside_a_sphere(const Cone& k) const {
+    if (S.spheres.size() > 16) return -1;
+    for (size_t i = 0; i < S.spheres.size(); ++i) {
+      const SkyPrim& q = S.prims[S.spheres[i]];
       const V w = V{q.c[0], q.c[1], q.c[2]} - o;
       const double dist = len(w), r = 0.999 * q.r;
       if (!(dist > r)) continue;
       const double sa = r / dist, ca = std::sqrt(1.0 - sa * sa);
-      if (sa > k.s && dot(k.axis, w) / dist > ca * k.c + sa * k.s) return true;
+      if (sa > k.s && dot(k.axis, w) / dist > ca * k.c + sa * k.s) return int32_t(i);
     }
-    return false;
+    return -1;
+  }
+  // The one sphere (its index) a frontier of touched boxes and primitives reduces to:
+  // every entry is that sphere's primitive, and its leaf is one the one-sphere path can
+  // stand in for (SkyScene::sphere_root).  -1: anything else.
+  int32_t sole_sphere(const std::vector<int32_t>& f) const {
+    int32_t one = -1;
+    for (const int32_t n : f) {
+      if (n >= 0) return -1;
+      const int32_t si = S.prims[uint32_t(-n - 1) >> 1].sphere_index;
+      if (si < 0 || !S.sphere_root[size_t(si)] || (one >= 0 && one != si)) return -1;
+      one = si;
+    }
+    return one;
   }
   bool prim_touches(const Cone& k, int32_t ref) const {
     const SkyPrim& p = S.prims[uint32_t(-ref - 1) >> 1];
@@ -116,13 +136,19 @@ struct Classifier {
     return touches(k, V{p.c[0], p.c[1], p.c[2]}, p.r + reach_tri);
   }
 
-  void mark(uint32_t tx0, uint32_t ty0, uint32_t tx1, uint32_t ty1) {
+  // one < 0: sky; else one-sphere(sphere index `one`)
+  void mark(uint32_t tx0, uint32_t ty0, uint32_t tx1, uint32_t ty1, int32_t one = -1) {
     for (uint32_t ty = ty0; ty < ty1; ++ty)
       for (uint32_t tx = tx0; tx < tx1; ++tx) {
         const uint32_t t = ty * tiles_x + tx;
         if (t % world != rank) continue;
-        (*cls)[t / world] = kTileSky;
-        ++n_sky;
+        if (one < 0) {
+          (*cls)[t / world] = kTileSky;
+          ++n_sky;
+        } else {
+          (*cls)[t / world] = kTileOneSphere | S.spheres[size_t(one)];
+          ++n_one[size_t(one)];
+        }
       }
   }
   bool owns_any(uint32_t tx0, uint32_t ty0, uint32_t tx1, uint32_t ty1) const {
@@ -141,10 +167,11 @@ struct Classifier {
     const std::vector<int32_t>& in = frontier[depth];
     std::vector<int32_t>& out = frontier[depth + 1];
     out.clear();
+    int32_t inside = -1;  // the sphere every ray of the cone runs into
     if (!k.ok) {
       if (single) return;  // general
       out = in;
-    } else if (inside_a_sphere(k)) {
+    } else if ((inside = inside_a_sphere(k)) >= 0 && !(want_one && S.sphere_root[size_t(inside)])) {
       return;  // general, all of it
     } else {
       uint32_t tests = 0;
@@ -161,8 +188,9 @@ struct Classifier {
         ++tests;
         if (n < 0) {
           if (!prim_touches(k, n)) continue;
-          if (single) return;  // a primitive within reach of some ray: general
           out.push_back(n);
+          // a primitive within reach of some ray: general, unless all of them are one sphere
+          if (single && !(want_one && sole_sphere(out) >= 0)) return;
           continue;
         }
         const SkyNode& nd = S.nodes[size_t(n)];
@@ -184,6 +212,17 @@ struct Classifier {
       mark(tx0, ty0, tx1, ty1);
       return;
     }
+    // what is left is one sphere's primitive alone: a tile is one-sphere; so is a block no
+    // tile of which can be sky (every ray runs into that sphere); any other block goes on
+    // to its quarters with that one entry (some of them may be sky)
+    const int32_t one = want_one ? sole_sphere(out) : -1;
+    if (one >= 0) {
+      out.resize(1);
+      if (single || inside == one) {
+        mark(tx0, ty0, tx1, ty1, one);
+        return;
+      }
+    }
     if (single) return;
     const uint32_t mx = tx1 - tx0 > 1 ? tx0 + (tx1 - tx0) / 2 : tx1, my = ty1 - ty0 > 1 ? ty0 + (ty1 - ty0) / 2 : ty1;
     block(tx0, ty0, mx, my, depth + 1);
@@ -199,6 +238,11 @@ bool sky_tiles_wanted() {
   const char* e = std::getenv("ZRT_SKY_TILES");
   return !(e && std::atoi(e) == 0);
 }
+// ZRT_SPHERE_TILES=0 turns the one-sphere class off (default: on; 2: context.cpp).
+bool sphere_tiles_wanted() {
+  const char* e = std::getenv("ZRT_SPHERE_TILES");
+  return !(e && std::atoi(e) == 0);
+}
 
 // A launch may split its all-sky tiles off only where the proof above holds and the
 // sky kernel computes what the render kernel would: the lockstep FAST loop (general
@@ -206,6 +250,12 @@ bool sky_tiles_wanted() {
 // camera inside the origin bound (so FAST == reference for its rays).
 bool sky_split_allowed(const LaunchPlan& P, const zrt_params* p, bool cam_inside) {
   return P.kmode == 3 && p->max_depth >= 1 && (p->flags & (ZRT_FLAG_SCANLINES | ZRT_FLAG_GUARD)) == 0 && cam_inside;
+}
+// ... and its one-sphere tiles where, besides, the plan is lean-eligible (plan_launch's
+// facts, before the STATS exclusion: the timed and the STATS launch of a frame split
+// alike): the one-sphere kernels are instantiated for those two flavours only.
+bool sphere_split_allowed(const LaunchPlan& P, const zrt_params* p, bool cam_inside) {
+  return sky_split_allowed(P, p, cam_inside) && P.lean;
 }
 
 // What the classifier keeps of a flattened scene: per reference-tree node its box's
@@ -289,14 +339,44 @@ void build_sky_scene(SkyScene* s, const HostScene& h) {
       return;
     }
   }
+  // the spheres the one-sphere path can stand in for: their reference leaf is a slot of the
+  // root wide node (in LDS; every ray's traversal begins there), in the full-node tree
+  s->sphere_root.assign(s->spheres.size(), 0);
+  s->sphere_args.assign(s->spheres.size(), SphereArgs{});
+  if (h.wn.size() >= 8 && h.leaf_of_slot.size() >= n_slots) {
+    int32_t ra[4], rb[4];
+    std::memcpy(ra, &h.wn[6], 16);
+    std::memcpy(rb, &h.wn[7], 16);
+    for (size_t i = 0; i < s->spheres.size(); ++i) {
+      const uint32_t slot = s->spheres[i], leaf = h.leaf_of_slot[slot];
+      if (leaf >= h.n_nodes) continue;
+      const int32_t ref = -int32_t(2u * slot) - 1;
+      for (int k = 0; k < 4; ++k) {
+        if (ra[k] >= 0 || ra[k] == INT32_MIN) continue;  // an inner child, an empty slot
+        const int32_t a = ra[k] < -(int32_t(1) << 30) ? ra[k] + (int32_t(1) << 30) : ra[k];
+        if (a == ref || rb[k] == ref) s->sphere_root[i] = 1;
+      }
+      SphereArgs& g = s->sphere_args[i];
+      const float4 lo = h.nodes[2 * leaf], hi = h.nodes[2 * leaf + 1], rec = h.prims[3 * slot];
+      g.lo[0] = lo.x; g.lo[1] = lo.y; g.lo[2] = lo.z;
+      g.hi[0] = hi.x; g.hi[1] = hi.y; g.hi[2] = hi.z;
+      g.rec[0] = rec.x; g.rec[1] = rec.y; g.rec[2] = rec.z; g.rec[3] = rec.w;
+    }
+  }
   s->ok = true;
 }
 
 // The class word of each of this rank's tiles (kTileGeneral / kTileSky), their sky count,
 // and (m, 4 doubles, optional) the margins: the largest sphere reach, the triangles'
-// reach, and its two coefficients.
+// reach, and its two coefficients.  one (optional, one->want set): the one-sphere tiles
+// too (kTileOneSphere | slot), of one sphere only - the one with the most tiles, the
+// others' tiles stay general - so that sphere is a constant of the launch.
 void classify_tiles(const SkyScene& s, const zrt_camera* cam, const zrt_params* p, std::vector<uint32_t>* cls,
-                    uint32_t* n_sky, double* m) {
+                    uint32_t* n_sky, double* m, OneSphere* one) {
+  if (one) {
+    one->n_tiles = 0;
+    one->sphere = -1;
+  }
   const Geometry g = geometry(p);
   const uint32_t mine = rank_tiles(g, p->rank, p->world_size);
   cls->assign(mine, kTileGeneral);
@@ -318,6 +398,8 @@ void classify_tiles(const SkyScene& s, const zrt_camera* cam, const zrt_params* 
   C.rank = p->rank;
   C.world = p->world_size;
   C.cls = cls;
+  C.want_one = one && one->want && !s.spheres.empty();
+  C.n_one.assign(s.spheres.size(), 0);
   // Camera.getRay in f32: u, v (two roundings and a correctly rounded quotient), two
   // scalings and three sums - each within 2^-24 of a value no larger than the sum S of
   // the four vectors' lengths, so the direction errs by < 2^-21 S (taken: 2^-20 S)
@@ -378,23 +460,43 @@ void classify_tiles(const SkyScene& s, const zrt_camera* cam, const zrt_params* 
   const uint32_t sq_x = (g.tiles_x + kSquare - 1) / kSquare, sq_y = (g.tiles_y + kSquare - 1) / kSquare;
   const uint32_t n_strips = sq_x * sq_y;
   const uint32_t n_thr = std::min({8u, std::max(1u, std::thread::hardware_concurrency()), n_strips / 4u});
+  // the one-sphere tiles of every sphere but the one with the most (the lowest index among equals) go back to general
+  const auto keep_one = [&](const std::vector<uint32_t>& n_one) {
+    if (!C.want_one) return;
+    size_t best = 0;
+    for (size_t i = 1; i < n_one.size(); ++i)
+      if (n_one[i] > n_one[best]) best = i;
+    if (n_one[best] == 0) return;
+    const uint32_t word = kTileOneSphere | s.spheres[best];
+    for (uint32_t& w : *cls)
+      if ((w & kTileOneSphere) && !(w & kTileSky) && w != word) w = kTileGeneral;
+    one->n_tiles = n_one[best];
+    one->sphere = int32_t(best);
+  };
   if (n_thr <= 1) {
     C.block(0, 0, g.tiles_x, g.tiles_y, 0);
     *n_sky = C.n_sky;
+    keep_one(C.n_one);
     return;
   }
   std::atomic<uint32_t> next{0}, total{0};
+  std::vector<std::atomic<uint32_t>> total_one(s.spheres.size());
+  for (auto& t : total_one) t.store(0);
   const auto work = [&]() {
     Classifier W = C;
     for (uint32_t i = next.fetch_add(1); i < n_strips; i = next.fetch_add(1))
       W.block((i % sq_x) * kSquare, (i / sq_x) * kSquare, std::min(g.tiles_x, (i % sq_x + 1) * kSquare),
               std::min(g.tiles_y, (i / sq_x + 1) * kSquare), 0);
     total.fetch_add(W.n_sky);
+    for (size_t i = 0; i < W.n_one.size(); ++i) total_one[i].fetch_add(W.n_one[i]);
   };
   std::vector<std::thread> pool;
   for (uint32_t t = 1; t < n_thr; ++t) pool.emplace_back(work);
   work();
   for (std::thread& t : pool) t.join();
   *n_sky = total.load();
+  std::vector<uint32_t> n_one(total_one.size());
+  for (size_t i = 0; i < n_one.size(); ++i) n_one[i] = total_one[i].load();
+  keep_one(n_one);
 }
 }  // namespace zrt
